@@ -5,8 +5,11 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it
 torch.distributed.run, one rank per GPU.  Rank 0 prints ONE JSON line.
 
 N = 1 (the default): `value` is BASELINE config 2 -- one 64 MiB pseudo-random-English buffer, level 6, resident in HBM
-when the timed region starts; a step is one pass of the hot path (zs_deflate_batch_device) over it.  The same run
-also measures the other BASELINE configs and the caller-visible paths and reports them under `secondary`:
+when the timed region starts; a step is one pass of the hot path (zs_deflate_batch_device) over it.  A plain run does
+only that: set-up, warm-up, the timed steps and the line.  `--dump-outputs DIR` writes what the last timed step computed
+(see dump_outputs).  `--full` adds the CPU baseline of the headline buffer (`cpu_baseline`, `bit_identical_to_cpu`), the
+round trip of the headline's streams through zlib, and measures the other BASELINE configs and the caller-visible paths,
+reported under `secondary` (the full report goes to bench_secondary.json):
     sparse64_L1 / _L6 / _L9   config 3: 4096 x 4096 RGBA of the reference's GetImageBytes (DeflateSparseBenchmark.cs:53-99)
     batch1024_L6              config 4 on one GPU: 1024 x 1 MiB buffers (the N = 1 point of the scaling workload)
     inflate1g                 config 5: 16 x 64 MiB level-6 streams (seeds 0..15) -> 1 GiB, compared on the device
@@ -15,7 +18,7 @@ also measures the other BASELINE configs and the caller-visible paths and report
     corpus_L1 / _L3 / _L6     config 1: the 11 Canterbury files as one batch, sizes against the reference's published ones, the CPU
                               path file by file beside them (and the reference's own published MB/s)
 N > 1: the same headline -- one 64 MiB buffer per GPU (weak scaling: `value` is N buffers / max-over-ranks time, so the
-values of N = 1, 2, 4, 8 are one curve) -- and, in the same line under `sharded_batch1024`, BASELINE config 4: the
+values of N = 1, 2, 4, 8 are one curve) -- and, with `--full`, in the same line under `sharded_batch1024`, BASELINE config 4: the
 1024 x 1 MiB batch partitioned over the ranks (zs_partition, the library's own; no collective in the data path), total
 input bytes / max-over-ranks time (strong scaling), with the same batch timed on rank 0's GPU alone beside it
 (`n1_same_workload`).  `--workload batch` makes config 4 the headline at any N.
@@ -264,6 +267,34 @@ class DeviceBatch:
             assert zlib.decompress(self.stream_bytes(i)) == self.datas[i], "device output %d does not inflate to its input" % i
 
 
+DUMP_BYTES = 1 << 22  # stream bytes --dump-outputs keeps: 16 MiB as float32 + 32 MiB of float64 positions, under 64 MB in all
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, batch):
+    """--dump-outputs: what a caller of zs_deflate_batch_device holds after the last timed step, as .npy files --
+    stream_lengths / stream_crc32 (float64, one per buffer: every byte of every stream is behind its CRC-32) and
+    stream_bytes (float32) at stream_byte_positions (float64, offsets into the streams laid end to end): all the bytes when
+    there are at most DUMP_BYTES of them, else DUMP_BYTES positions drawn with a fixed seed."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    lens = [int(x) for x in batch.out_lens]
+    flat = torch.cat([o[:n] for o, n in zip(batch.d_outs, lens)]).cpu().numpy()
+    crcs, off = [], 0
+    for n in lens:
+        crcs.append(zlib.crc32(flat[off:off + n]))
+        off += n
+    if len(flat) <= DUMP_BYTES:
+        pos = np.arange(len(flat), dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(len(flat), DUMP_BYTES, replace=False))
+    np.save(os.path.join(out_dir, "stream_lengths.npy"), np.array(lens, dtype=np.float64))
+    np.save(os.path.join(out_dir, "stream_crc32.npy"), np.array(crcs, dtype=np.float64))
+    np.save(os.path.join(out_dir, "stream_bytes.npy"), flat[pos].astype(np.float32))
+    np.save(os.path.join(out_dir, "stream_byte_positions.npy"), pos.astype(np.float64))
+
+
 # stages of an inflate call that are several launches: the kernels whose time and HBM traffic the stage's figures sum
 INFLATE_STAGE_KERNELS = {"inf_decode": ["zs_inf_expand_kernel", "zs_inf_decode_lane_kernel", "zs_inf_cellflat_kernel", "zs_inf_decode_kernel"],
                          "inf_find": ["zs_inf_prefilter_kernel", "zs_inf_check_kernel", "zs_inf_flatten_kernel"],
@@ -494,13 +525,19 @@ def main():
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--size", type=int, default=64 << 20)
     ap.add_argument("--workload", default=None, choices=["english64", "sparse64", "batch"],
-                    help="default: english64 (one 64 MiB buffer per GPU; at --gpus N > 1 the sharded 1024 x 1 MiB batch is measured beside it)")
+                    help="default: english64 (one 64 MiB buffer per GPU; at --gpus N > 1 --full the sharded 1024 x 1 MiB batch is measured beside it)")
     ap.add_argument("--buffers", type=int, default=BATCH_BUFFERS, help="--workload batch: buffers in the whole job")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the round-trip check and the secondary configs (the full report: bench_secondary.json)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (rank 0's buffers)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU legs")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: without the secondary configs")
     ap.add_argument("--secondary-steps", type=int, default=3)
     ap.add_argument("--inflight", type=int, default=1, help="> 1: also report the `pipelined` figure with that many contexts in flight")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -541,6 +578,8 @@ def main():
     main_batch = DeviceBatch(eng, dev, datas)
     n = main_batch.n
     dt, stage_ms = main_batch.timed(args.level, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main_batch)
     total_n, total_out = n, sum(main_batch.out_lens)
     per_rank_bytes = [n]
     if world > 1:
@@ -555,12 +594,13 @@ def main():
         o = torch.tensor([total_out], dtype=torch.int64, device=red_dev)
         dist.all_reduce(o)
         total_out = int(o.item())
-    main_batch.check_roundtrip(max(1, len(datas) // 8))
+    if args.full:
+        main_batch.check_roundtrip(max(1, len(datas) // 8))
 
-    # N > 1, default workload: BASELINE config 4 beside the headline -- the 1024 x 1 MiB batch partitioned over the ranks, and the
-    # same batch on rank 0's GPU alone (the N = 1 point of that workload, measured in this very run)
+    # N > 1, default workload, --full: BASELINE config 4 beside the headline -- the 1024 x 1 MiB batch partitioned over the ranks,
+    # and the same batch on rank 0's GPU alone (the N = 1 point of that workload, measured in this very run)
     sharded = None
-    if world > 1 and workload == "english64" and not args.no_secondary:
+    if world > 1 and workload == "english64" and args.full and not args.no_secondary:
         ssteps = max(2, min(args.steps, 5))
         n1 = None
         if rank == 0:
@@ -649,7 +689,7 @@ def main():
             line["pipelined"] = pipelined
         if sharded:
             line["sharded_batch1024"] = sharded
-        if world == 1:
+        if world == 1 and args.full:
             data = datas[0]
             if not args.no_cpu_baseline:  # the CPU leg runs on rank 0 of the single-GPU run only
                 cb, ref, sample_len = cpu_baseline(data, args.level, name=workload)
@@ -715,7 +755,10 @@ def main():
                 eng.close()  # the stream-API tool is its own process with its own context
                 sec["stream_api"] = secondary_stream_api(data, args.level)
                 line["secondary"] = sec
-        emit_report(line)
+        if args.full:
+            emit_report(line)
+        else:
+            print(compact_line(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
