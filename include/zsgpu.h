@@ -156,8 +156,18 @@ ZS_API int zs_png_filter_device(zs_ctx *ctx, const void *pixels, int64_t row_byt
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took
  * over its chunks (0: one workgroup per stream); "fast_fallbacks", "round_runs", "cut_rounds", "lit_fallbacks" -- batches that took
  * one of the slower paths since the context was made; "lit_engine_bytes" -- input bytes the one-wave literal engine parsed
- * beyond the streams' last 261. */
+ * beyond the streams' last 261; "spec_streams", "spec_fallbacks", "spec_wrong_chunks" -- the last deflate call's speculative
+ * chunk walk (levels 4-9): streams that tried it, those of them that took the transfer maps after all, chunks whose guessed
+ * entry was wrong; "spec_periodic" -- those of the fallbacks that were never walked (periodic by the match kernel's count). */
 ZS_API int64_t zs_ctx_counter(const zs_ctx *ctx, const char *name);
+/* (A test hook, not part of the product's surface: declared only where ZS_TESTING is defined.)
+ * For the tests: what the parse stage of the last deflate call left for its first stream, copied from the device -- "state"
+ * (int32 x 6: tail_p, tail_kind, tail_pend, k_done, preins, body_syms), "blk_end" / "blk_top" (int32 per finished block of the
+ * body), "symbase" (uint32 per 2048-position chunk, the map path) or "spec_base" (uint32 per chunk of the speculative grid).
+ * Returns the bytes written, -1 for an unknown name or too small a buffer. */
+#if defined(ZS_TESTING) || defined(ZS_BUILDING_LIBRARY)
+ZS_API int64_t zs_ctx_debug_read(zs_ctx *ctx, const char *name, void *out, int64_t cap);
+#endif
 ZS_API void zs_ctx_set_profiling(zs_ctx *ctx, int enable);
 ZS_API int zs_ctx_stage_count(const zs_ctx *ctx);
 ZS_API const char *zs_ctx_stage_name(const zs_ctx *ctx, int stage);

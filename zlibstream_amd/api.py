@@ -109,7 +109,8 @@ class Engine:
         self._lib.zs_ctx_set_profiling(self._h, 1 if on else 0)
 
     def counter(self, name):
-        """zs_ctx_counter: "fast_rounds", "fast_fallbacks", "round_runs", "cut_rounds", "lit_fallbacks", "lit_engine_bytes"."""
+        """zs_ctx_counter: "fast_rounds", "fast_fallbacks", "round_runs", "cut_rounds", "lit_fallbacks", "lit_engine_bytes",
+        "spec_streams", "spec_fallbacks", "spec_periodic", "spec_wrong_chunks"."""
         return int(self._lib.zs_ctx_counter(self._h, name.encode()))
 
     def stage_ms(self):

@@ -103,6 +103,10 @@ struct StreamDesc {
     // DeflateFast as rounds over the chunks of the stream (zs_fast_sweep.h "Rounds"): the stream's chunks in the batch's list (fr_n == 0: the
     // stream is one workgroup's, from its first position to fv_end)
     int32_t fr_first, fr_n;
+    // the speculative chunk walk in place of the transfer maps (zs_spec_walk: levels 4-9, one Write, long enough): spec != 0 --
+    // the stream is tried; its chunks on the speculative grid (chunk j >= 1 begins at j * len - 261) and where their records
+    // begin in spec_rec / spec_base
+    int32_t spec, spec_n, spec_off;
 };
 
 // where each kernel's work items start in the work array (zs_worklist_kernel): 9 lists, then the total
@@ -169,6 +173,29 @@ struct StreamState {
     // the true path met a read whose pre-insert hashes bytes behind the data (zs_core.h kMapPoisonBit): the host runs the
     // stream on the literal engine
     int32_t poison;
+    // the speculative chunk walk: match tiles of the stream that took the RUNS walk (periodic data: the stream is not tried),
+    // whether every chunk's guessed entry was its predecessor's exit (the kernels of the map path then skip the stream), and
+    // the chunks whose guess was wrong
+    int32_t spec_run_tiles, spec_ok, spec_wrong;
+};
+// A speculative chunk's record: bits 0..8 the guessed entry slot, 9..17 the exit slot (relative to the next chunk's start, as
+// map_exit is), 18..29 the symbols of the chunk from the guess, bit 30: an event on the path is K4's business (kMapEqualBit /
+// kMapPoisonBit).
+constexpr uint32_t kSpecBail = 1u << 30;
+ZS_HD uint32_t spec_pack(int guess, int exit_slot, int count, bool bail) {
+    return (uint32_t)guess | ((uint32_t)exit_slot << 9) | ((uint32_t)count << 18) | (bail ? kSpecBail : 0u);
+}
+ZS_HD int spec_guess(uint32_t r) { return (int)(r & 0x1FF); }
+ZS_HD int spec_exit(uint32_t r) { return (int)((r >> 9) & 0x1FF); }
+ZS_HD int spec_count(uint32_t r) { return (int)((r >> 18) & 0xFFF); }
+constexpr int kSpecMinInput = 1 << 20;  // shorter streams keep the maps (the attempt is a launch and a look at the flags)
+constexpr int kSpecLenBits = 10;        // positions per speculative chunk: 1024 (DESIGN.md section 6 has the table)
+constexpr int kSpecWarm = 128;          // positions walked in front of a chunk before its entry is guessed
+constexpr int kSpecRunsDen = 8;         // a stream with more than 1 / 8 of its match tiles on the RUNS walk is periodic: not tried
+struct K5Spec {  // the symbol kernel's arguments on the speculative grid
+    uint32_t *rec;
+    uint32_t *base;
+    int len_bits, warm, corrupt;  // corrupt: the chunk whose recorded guess is spoiled (a test's switch; -1: none)
 };
 constexpr int kDeferBudget = 8;   // cuts with positions to walk again that a stream may repair on its one CU before it is given up
 constexpr int kCutBudget = 12;    // ... and cuts of any kind (a cut without such positions is a scan of 32 Ki records on one CU)

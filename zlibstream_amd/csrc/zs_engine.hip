@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#define ZS_BUILDING_LIBRARY  // (the test hooks of the header are declared for the library itself)
 #include "../../include/zsgpu.h"
 #include "zs_kernels.hip"
 #include "zs_inflate_par.hip"
@@ -27,10 +28,10 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
-                                           "emit_syms", "tail", "trees", "offsets", "emit_bits"};
+                                           "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify"};
 
 }  // namespace
 
@@ -39,6 +40,7 @@ struct zs_ctx {
     hipStream_t stream = nullptr;
     hipStream_t aux = nullptr;  // second stream: tree building of the finished blocks runs beside the tail engine
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pre0 = nullptr, ev_pre = nullptr;
+    hipEvent_t ev_spec[2] = {};           // the speculative walk and its verdict (profiling)
     hipEvent_t ev_part[16] = {};          // one long stream run part by part: part k's maps are ready
     std::vector<hipEvent_t> ev_pool;      // timing pairs of the part-wise launches (profiling)
     std::string err;
@@ -47,6 +49,12 @@ struct zs_ctx {
     int round_runs = 0;      // batches with streams in the batched cut rounds (their cuts were not one CU's job)
     int cut_rounds = 0;      // rounds of those
     int lit_fallbacks = 0;   // batches run again with a stream on the literal engine (zs_core.h kMapPoisonBit)
+    // the last call's speculative chunk walk (levels 4-9): streams that tried it, those of them that went to the maps after
+    // all, and chunks whose guessed entry was wrong
+    int spec_streams = 0, spec_fallbacks = 0, spec_wrong_chunks = 0;
+    int spec_periodic = 0;  // ... and those of the fallbacks that were never walked: the match kernel's tile count said "periodic"
+    // where the first stream of the last deflate call has its parse results (zs_ctx_debug_read)
+    int64_t dbg_blk_off = 0, dbg_chunk_off = 0, dbg_nchunks = 0, dbg_spec_n = 0, dbg_n_spec = 0;
     int64_t lit_engine_bytes = 0;  // input bytes parsed by the one-wave literal engine beyond the streams' last 261 (zs_ctx_counter)
     // inflate: compressed bytes each stream of the last call used, trailer included (0: unknown / not ended); and, for a
     // probing call (zs_inflate asking whether the stream's end has arrived), where the block chain ended
@@ -60,7 +68,7 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags;
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -141,6 +149,8 @@ struct Plan {
     WorkList w_clear, w_adler, w_links, w_match, w_chunks, w_segs, w_sups, w_blocks, w_runs;
     int64_t n_pos = 0, n_syms = 0;
     int64_t n_chunks = 0, n_segs = 0, n_sups = 0, n_blocks = 0, n_pieces = 0, n_runs = 0;
+    int64_t n_spec = 0;  // chunks of the speculative grid, all streams that try the speculative walk
+    int max_spec_n = 0, n_spec_streams = 0;
     bool any_fv = false, any_rle = false;
     bool any_dual = false;  // levels 1-3, a few streams below 4 MiB: planned for the sweeps and for the speculative runs, the links decide (zs_fast_probe_kernel)
     int64_t n_rle_tiles = 0;
@@ -244,6 +254,15 @@ bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len
                       !getenv("ZS_FAST_NO_ROUNDS");
     for (int i = 0; i < n && allow_dual; i++) allow_dual = in_len[i] >= fast_min_input && in_len[i] < kFastMinInput;
     bool dual_broken = false;
+    // The speculative chunk walk.  ZS_NO_SPEC: every stream through the maps; ZS_SPEC_LEN / ZS_SPEC_WARM /
+    // ZS_SPEC_MIN: the chunk length (512, 1024 or 2048), the warm-up and the shortest stream that tries it; ZS_SPEC_CORRUPT=j:
+    // chunk j's recorded guess is spoiled (the tests' way to a failed verification)
+    const bool spec_on = !getenv("ZS_NO_SPEC") && !getenv("ZS_PIPE_PARTS");
+    const int spec_len_env = getenv("ZS_SPEC_LEN") ? atoi(getenv("ZS_SPEC_LEN")) : 0;
+    const int spec_bits = spec_len_env == 512 ? 9 : spec_len_env == 2048 ? 11 : spec_len_env == 1024 ? 10 : kSpecLenBits;
+    const int spec_warm = getenv("ZS_SPEC_WARM") ? std::max(0, std::min(4096, atoi(getenv("ZS_SPEC_WARM")))) : kSpecWarm;
+    const int64_t spec_min = getenv("ZS_SPEC_MIN") ? std::max<int64_t>(kWindowSize, atoll(getenv("ZS_SPEC_MIN"))) : kSpecMinInput;
+    const int spec_corrupt = getenv("ZS_SPEC_CORRUPT") ? atoi(getenv("ZS_SPEC_CORRUPT")) : -1;
 plan_again:
     Plan pl;
     pl.sd.resize((size_t)n);
@@ -394,6 +413,25 @@ plan_again:
         pl.n_segs += s.nsegs;
         s.sup_off = (int32_t)pl.n_sups;
         pl.n_sups += (s.nsegs + kSupSegs - 1) / kSupSegs;
+        // the speculative chunk walk in place of the maps: the slow levels' single Write from a minimum length on (a stream that
+        // does not verify, or whose match tiles say it is periodic, goes to the maps as it always did)
+        s.spec = 0, s.spec_n = 0, s.spec_off = (int32_t)pl.n_spec;
+        bool spec_geo = s.body_end >= 0 && geo.body_end == len - kMinLookahead;
+        if (spec_geo) {
+            // the speculative grid's own closed form (spec_chunk_ctx): segment k >= 1 is the one window end 65536 + 32768 (k - 1),
+            // whatever the 2048-position chunks of the map path look like
+            const int64_t want = 1 + (len > kWindowSize ? (len - kWindowSize - 1) / kWSize + 1 : 0);
+            spec_geo = (int64_t)geo.nsegs() == want && geo.seg_cl.size() == (size_t)want + 1 && geo.seg_cl[0] == 0 && geo.seg_cl[1] == 0;
+            for (int64_t k = 1; k < want && spec_geo; k++)
+                spec_geo = geo.seg_cl[(size_t)k + 1] - geo.seg_cl[(size_t)k] == 1 &&
+                           geo.cl[(size_t)geo.seg_cl[(size_t)k]] == ((uint32_t)(kWindowSize + kWSize * (k - 1)) | kClWindowBit);
+        }
+        if (spec_on && lv.func == 2 && (strategy == kDefault || strategy == kFiltered) && !writes && !ro && !lit_forced && spec_geo && len >= spec_min &&
+            n <= 65535) {
+            s.spec = 1, s.spec_n = (int32_t)((((int64_t)s.body_end + kMinLookahead - 1) >> spec_bits) + 1);
+            pl.n_spec += s.spec_n, pl.n_spec_streams++;
+            pl.max_spec_n = std::max(pl.max_spec_n, (int)s.spec_n);
+        }
         // levels 1-3, one Write, large enough: speculative chunk runs instead of one sequential engine
         s.run_chunk = run_chunk;
         s.fast_runs = fast_par ? (force_seq == 2 ? 1 : (int32_t)((len + run_chunk - 1) / run_chunk)) : 0;
@@ -445,6 +483,16 @@ plan_again:
         if (s.body_end < 0 && s.fv_end < 0 && s.rle_end < 0 && s.fast_runs == 0 && s.plan_nblk == 0 && !(level == 0 && strategy != kRle && !ro)) {
             const int64_t from = resume ? ro->p0 : ro ? ro->hist : 0;
             pl.lit_bytes += std::max<int64_t>(0, len - from - (kMinLookahead - 1));
+        }
+    }
+    {
+        // the walk's grids are (most chunks of a stream / 64) x streams: one long stream among thousands of short ones would make
+        // them mostly workgroups that return at once, twice per call -- such a batch keeps the maps
+        int64_t need = 0;
+        for (int i = 0; i < n; i++) need += (pl.sd[(size_t)i].spec_n + 63) / 64;
+        if (pl.n_spec && (int64_t)((pl.max_spec_n + 63) / 64) * n > 4 * need + 4096) {
+            for (int i = 0; i < n; i++) pl.sd[(size_t)i].spec = 0, pl.sd[(size_t)i].spec_n = 0, pl.sd[(size_t)i].spec_off = 0;
+            pl.n_spec = 0, pl.max_spec_n = 0, pl.n_spec_streams = 0;
         }
     }
     if (allow_dual && dual_broken) {  // (a stream the fast forms do not take after all: the batch as it always was planned)
@@ -535,7 +583,8 @@ plan_again:
         !ensure(c, c->blk_top, 4 * (size_t)pl.n_blocks + 64) || !ensure(c, c->blocks, sizeof(BlockRec) * (size_t)pl.n_blocks) ||
         !ensure(c, c->trees, sizeof(TreeWork) * (size_t)pl.n_blocks) || !ensure(c, c->info, sizeof(BlockInfo) * (size_t)pl.n_blocks) ||
         !ensure(c, c->pieces, 4 * (size_t)pl.n_pieces + 64) || !ensure(c, c->scratch, (size_t)kScratchBytes * (size_t)n) ||
-        !ensure(c, c->cut_pos, 8 * (size_t)pl.n_cuts + 64) || !ensure(c, c->cut_bkt, 8 * (size_t)pl.n_cuts + 64))
+        !ensure(c, c->cut_pos, 8 * (size_t)pl.n_cuts + 64) || !ensure(c, c->cut_bkt, 8 * (size_t)pl.n_cuts + 64) ||
+        (pl.n_spec && (!ensure(c, c->spec_rec, 8 * (size_t)pl.n_spec + 64) || !ensure(c, c->spec_flags, 4 * (size_t)n + 64))))
         return false;
     // parse-segment tables: [seg_c0 | seg_after | seg_base | seg_S : int32 x n_segs each][seg_cl : int32 x (n_segs + n)]
     // [cstart : int32 x (n_chunks + n)][head : int32 x n_chunks][cl : u32 x n_cl]
@@ -665,6 +714,12 @@ plan_again:
     const uint2 *d_work = dev<uint2>(c->work);
     const bool prof = c->profiling;
     const int k5_ahead = getenv("ZS_K5_AHEAD") ? atoi(getenv("ZS_K5_AHEAD")) : 1;  // lines the symbol kernel's helper wave asks for ahead of a lane
+    c->dbg_blk_off = pl.sd[0].blk_off, c->dbg_chunk_off = pl.sd[0].chunk_off, c->dbg_nchunks = pl.sd[0].nchunks;
+    c->dbg_spec_n = pl.sd[0].spec_n, c->dbg_n_spec = pl.n_spec;
+    const K5Spec k5s{dev<uint32_t>(c->spec_rec), dev<uint32_t>(c->spec_rec) + pl.n_spec, spec_bits, spec_warm, spec_corrupt};
+    int spec_ok_streams = 0;  // streams whose speculative walk verified: the map kernels skip them (all of them: not launched)
+    bool need_maps = true, spec_ran = false;
+    if (!rounds) c->spec_streams = c->spec_fallbacks = c->spec_wrong_chunks = c->spec_periodic = 0;
     auto mark = [&](int i) {
         if (prof) (void)hipEventRecord(c->ev[i], stream);
     };
@@ -849,7 +904,7 @@ plan_again:
             if (tiles_end > tiles_done)
                 timed(kStMatch, stream, [&] {
                     hipLaunchKernelGGL(zs_match_kernel, dim3((unsigned)(tiles_end - tiles_done)), dim3(1024), kMatchLds + 16, stream, d_sd,
-                                       d_work + o_match + tiles_done, dev<uint16_t>(c->link), dev<uint2>(c->mm), lv, strategy);
+                                       d_work + o_match + tiles_done, dev<uint16_t>(c->link), dev<uint2>(c->mm), lv, strategy, d_st);
                 });
             spans_done = spans_end > spans_done ? spans_end : spans_done, tiles_done = tiles_end > tiles_done ? tiles_end : tiles_done;
             timed(kStChunkMap, stream, [&] {
@@ -887,10 +942,10 @@ plan_again:
                                    c->crc_tab, lv, strategy, hash_variant);
             });
             timed(kStEmitSyms, c->aux, [&] {
-                hipLaunchKernelGGL(zs_emit_syms_lane_kernel<4>, dim3((unsigned)((cb - ca + 63) / 64)), dim3(kK5Threads), 0, c->aux, d_sd, d_st,
+                hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 0>), dim3((unsigned)((cb - ca + 63) / 64)), dim3(kK5Threads), 0, c->aux, d_sd, d_st,
                                    d_work + o_chunks + ca, cb - ca, dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint16_t>(c->entry), dev<uint32_t>(c->symbase),
                                    dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), c->crc_tab, lv, strategy,
-                                   hash_variant, k5_ahead);
+                                   hash_variant, k5_ahead, k5s);
             });
         }
         ZS_HIP(c, hipEventRecord(c->ev_join, c->aux));
@@ -932,21 +987,55 @@ plan_again:
         ZS_HIP(c, hipMemsetAsync(c->mm.p, 0, 8 * (size_t)pl.n_pos + 64, stream));
     } else if (!pl.w_match.empty())
         hipLaunchKernelGGL(zs_match_kernel, dim3((unsigned)pl.w_match.size()), dim3(1024), kMatchLds + 16, stream, d_sd, d_work + o_match,
-                           dev<uint16_t>(c->link), dev<uint2>(c->mm), lv, strategy);
+                           dev<uint16_t>(c->link), dev<uint2>(c->mm), lv, strategy, d_st);
     mark(4);
     if (!side_work()) return false;
-    if (!pl.w_chunks.empty())
+    // The speculative chunk walk: every chunk of the streams that qualify walked from a guessed entry, the guesses checked
+    // against the exits, one look at the verdicts.  A stream that verified has its chunks' entries and first symbols and what
+    // the resolve kernel would leave; the others -- and the streams that never qualified, with no look at anything -- take the maps.
+    if (pl.n_spec) {
+        spec_ran = true;
+        hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 1>), dim3((unsigned)((pl.max_spec_n + 63) / 64), (unsigned)n), dim3(kK5Threads), 0, stream, d_sd, d_st,
+                           (const uint2 *)nullptr, 0, dev<uint2>(c->mm), dev<uint16_t>(c->link), (const uint16_t *)nullptr, (const uint32_t *)nullptr,
+                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
+        if (prof) (void)hipEventRecord(c->ev_spec[0], stream);
+        hipLaunchKernelGGL(zs_spec_verify_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, dev<uint2>(c->mm), dev<uint16_t>(c->link), c->crc_tab, lv,
+                           strategy, hash_variant, k5s, dev<int32_t>(c->spec_flags));
+        int32_t *hf = (int32_t *)c->pinned;  // (the staging copy's uploads are through by the time the verdicts arrive: same stream)
+        ZS_HIP(c, hipMemcpyAsync(hf, c->spec_flags.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+        ZS_HIP(c, hipStreamSynchronize(stream));
+        if (prof) (void)hipEventRecord(c->ev_spec[1], stream);
+        for (int i = 0; i < n; i++) {
+            if (hf[i] == 0) continue;
+            c->spec_streams++;
+            if (hf[i] == 1) spec_ok_streams++;
+            else c->spec_fallbacks++;
+            if (hf[i] == 2) c->spec_periodic++;  // (the verdicts: 1 verified, 2 periodic -- never walked, 3 an event bailed, 4 wrong guesses)
+        }
+        if (spec_ok_streams < c->spec_streams) {  // how many guesses were wrong: the streams' states (a failed attempt is rare)
+            StreamState *hs = (StreamState *)c->pinned;
+            ZS_HIP(c, hipMemcpyAsync(hs, d_st, sizeof(StreamState) * (size_t)n, hipMemcpyDeviceToHost, stream));
+            ZS_HIP(c, hipStreamSynchronize(stream));
+            for (int i = 0; i < n; i++) c->spec_wrong_chunks += hs[i].spec_wrong;
+        }
+        if (getenv("ZS_DEBUG"))
+            fprintf(stderr, "zs: speculative walk: %d streams tried, %d verified, %d wrong guesses (chunks of %d, warm-up %d)\n", c->spec_streams, spec_ok_streams,
+                    c->spec_wrong_chunks, 1 << spec_bits, spec_warm);
+    }
+    need_maps = spec_ok_streams < n;
+    const StreamState *spec_st = spec_ok_streams ? (const StreamState *)d_st : nullptr;
+    if (!pl.w_chunks.empty() && need_maps)
         hipLaunchKernelGGL(zs_chunkmap_kernel, dim3((unsigned)pl.w_chunks.size()), dim3(512), 0, stream, d_sd, d_work + o_chunks,
                            dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint32_t>(c->maps), c->crc_tab, lv, strategy,
-                           hash_variant, dev<uint16_t>(c->chunk_far));
+                           hash_variant, dev<uint16_t>(c->chunk_far), (uint8_t *)nullptr, (const StreamState *)nullptr, spec_st);
     mark(5);
-    if (!pl.w_segs.empty())
+    if (!pl.w_segs.empty() && need_maps)
         hipLaunchKernelGGL(zs_segmap_kernel, dim3((unsigned)pl.w_segs.size()), dim3(320), 0, stream, d_sd, d_work + o_segs,
-                           dev<uint32_t>(c->maps), dev<uint2>(c->segmap));
+                           dev<uint32_t>(c->maps), dev<uint2>(c->segmap), spec_st);
     // the segment maps composed 16 at a time, for the resolve kernel's short way through a long stream (ZS_NO_SUPMAP: without)
-    if (use_sup)
+    if (use_sup && need_maps)
         hipLaunchKernelGGL(zs_supmap_kernel, dim3((unsigned)pl.w_sups.size()), dim3(320), 0, stream, d_sd, d_work + o_sups,
-                           dev<uint2>(c->segmap), dev<uint8_t>(c->seg_stale), dev<uint2>(c->supmap));
+                           dev<uint2>(c->segmap), dev<uint8_t>(c->seg_stale), dev<uint2>(c->supmap), spec_st);
     mark(6);
     // A stream whose refills are equal-bucket ones with positions to walk again by the thousand (zero pages, runs) is not
     // one CU's job: the resolve kernel gives it up after kDeferBudget such cuts (the kernels behind it skip the stream) and the
@@ -956,7 +1045,7 @@ plan_again:
     // synchronisation, which is what a cut's repair takes on one CU at level 6.  64 MiB of short runs: level 9 7.3 s -> 2.0 s,
     // level 6 175 ms inline against 237 in rounds.)
     // (ZS_DEFER_ALL: at every level, for the tests)
-    launch_resolve(defer_mode, 0);
+    if (need_maps) launch_resolve(defer_mode, 0);
     }
     mark(7);
     // fork: the tail engine (sequential, one workgroup per stream) needs only what the resolve kernel left, so it runs
@@ -1083,18 +1172,28 @@ plan_again:
                            dev<uint8_t>(c->scratch), c->crc_tab, lv, strategy, hash_variant, level);
         ZS_HIP(c, hipEventRecord(c->ev_join, c->aux));
     }
-    if (!pl.w_segs.empty())
+    if (!pl.w_segs.empty() && need_maps)
         hipLaunchKernelGGL(zs_expand_kernel, dim3((unsigned)((pl.w_segs.size() + 63) / 64)), dim3(64), 0, stream, d_sd, d_st,
                            d_work + o_segs, (int)pl.w_segs.size(), dev<uint2>(c->mm), dev<uint16_t>(c->link),
                            dev<uint32_t>(c->maps), dev<uint16_t>(c->seg_entry), dev<uint32_t>(c->seg_symbase),
                            dev<uint8_t>(c->stale), dev<uint16_t>(c->entry), dev<uint32_t>(c->symbase), c->crc_tab, lv, strategy,
                            hash_variant);
     mark(8);
-    if (!pl.w_chunks.empty())
-        hipLaunchKernelGGL(zs_emit_syms_lane_kernel<4>, dim3((unsigned)((pl.w_chunks.size() + 63) / 64)), dim3(kK5Threads), 0, stream, d_sd, d_st,
+    if (!pl.w_chunks.empty() && need_maps)
+        hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 0>), dim3((unsigned)((pl.w_chunks.size() + 63) / 64)), dim3(kK5Threads), 0, stream, d_sd, d_st,
                            d_work + o_chunks, (int)pl.w_chunks.size(), dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint16_t>(c->entry),
                            dev<uint32_t>(c->symbase), dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top),
-                           c->crc_tab, lv, strategy, hash_variant, k5_ahead);
+                           c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
+    // the streams whose speculative walk verified: their symbols, from the entries that walk found.
+    // (In the re-entry behind the batched cut rounds -- `rounds` -- nothing of the speculative path is launched: the verified
+    // streams' symbols and block cuts are those of the call's first pass, which ran to its end for them; the rounds touch only
+    // the records and maps of the streams that were given up, nothing zeroes syms / blk_end / blk_top in between, and the map
+    // kernels skip the verified streams by StreamState::spec_ok, which the re-entry does not reset either.
+    // tests/test_gpu_spec.py test_a_verified_stream_beside_one_in_the_cut_rounds.)
+    if (spec_ok_streams)
+        hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 2>), dim3((unsigned)((pl.max_spec_n + 63) / 64), (unsigned)n), dim3(kK5Threads), 0, stream, d_sd, d_st,
+                           (const uint2 *)nullptr, 0, dev<uint2>(c->mm), dev<uint16_t>(c->link), (const uint16_t *)nullptr, (const uint32_t *)nullptr,
+                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
     mark(9);
     if (tail_serial)
         hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
@@ -1231,8 +1330,15 @@ plan_again:
     if (prof) {
         for (int i = 0; i < kStCount; i++) {
             float ms = 0;
-            if (i >= kStLinks) (void)hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]);  // clear / adler: beside the others, unmarked
+            if (i >= kStLinks && i <= kStEmitBits) (void)hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]);  // clear / adler: beside the others, unmarked
             c->stage_ms[i] = ms;
+        }
+        if (spec_ran) {  // the speculative walk and its verdict sit between the match kernel and the maps
+            float a = 0, b = 0, m = 0;
+            (void)hipEventElapsedTime(&a, c->ev[kStChunkMap], c->ev_spec[0]);
+            (void)hipEventElapsedTime(&b, c->ev_spec[0], c->ev_spec[1]);
+            (void)hipEventElapsedTime(&m, c->ev_spec[1], c->ev[kStChunkMap + 1]);
+            c->stage_ms[kStSpecWalk] = a, c->stage_ms[kStSpecVerify] = b, c->stage_ms[kStChunkMap] = m;
         }
         if (n_parts) {  // part-wise launches: every launch has its own pair of events, a stage is the sum of its launches
             for (int i = kStLinks; i <= kStTail; i++) c->stage_ms[i] = 0;
@@ -1388,6 +1494,7 @@ int zs_ctx_create(int device, zs_ctx **out) {
         return ZS_MEM_ERROR;
     }
     for (auto &e : c->ev) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_spec) (void)hipEventCreate(&e);
     {
         // the link kernel relies on the LDS applying the lanes of one DS_MSKOR_RTN_B32 in lane order: check it here
         int *d_ok = nullptr, ok = 0;
@@ -1457,7 +1564,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -1467,6 +1574,8 @@ void zs_ctx_destroy(zs_ctx *c) {
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_part)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_spec)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_pool)
         if (e) (void)hipEventDestroy(e);
@@ -1496,7 +1605,37 @@ int64_t zs_ctx_counter(const zs_ctx *c, const char *name) {
     if (k == "cut_rounds") return c->cut_rounds;
     if (k == "lit_fallbacks") return c->lit_fallbacks;    // batches run again with a stream on the literal engine
     if (k == "lit_engine_bytes") return c->lit_engine_bytes;  // input bytes the one-wave literal engine has parsed (all calls)
+    // the last deflate call's speculative chunk walk (levels 4-9): streams that tried it, those of them that took the maps
+    // after all, chunks whose guessed entry was wrong
+    if (k == "spec_streams") return c->spec_streams;
+    if (k == "spec_fallbacks") return c->spec_fallbacks;
+    if (k == "spec_periodic") return c->spec_periodic;  // ... fallbacks that were never walked (the match kernel's count of RUNS tiles)
+    if (k == "spec_wrong_chunks") return c->spec_wrong_chunks;
     return -1;
+}
+
+int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
+    if (!c || !name || !out || !c->st.p) return -1;
+    const std::string k(name);
+    (void)hipSetDevice(c->device);
+    StreamState ss;
+    if (hipMemcpy(&ss, c->st.p, sizeof ss, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const void *src = nullptr;
+    int64_t bytes = 0;
+    const int32_t state[6] = {ss.tail_p, ss.tail_kind, (int32_t)ss.tail_pend, ss.k_done, ss.preins, (int32_t)ss.body_syms};
+    if (k == "state") {
+        if (cap < (int64_t)sizeof state) return -1;
+        memcpy(out, state, sizeof state);
+        return sizeof state;
+    }
+    if (k == "blk_end") src = dev<int32_t>(c->blk_end) + c->dbg_blk_off, bytes = 4 * (int64_t)(ss.body_syms / kBlockSyms);
+    else if (k == "blk_top") src = dev<int32_t>(c->blk_top) + c->dbg_blk_off, bytes = 4 * (int64_t)(ss.body_syms / kBlockSyms);
+    else if (k == "symbase") src = dev<uint32_t>(c->symbase) + c->dbg_chunk_off, bytes = 4 * c->dbg_nchunks;
+    else if (k == "spec_base") src = dev<uint32_t>(c->spec_rec) + c->dbg_n_spec, bytes = 4 * c->dbg_spec_n;  // (the first stream's spec_off is 0)
+    else return -1;
+    if (bytes > cap || (bytes > 0 && !src)) return -1;
+    if (bytes > 0 && hipMemcpy(out, src, (size_t)bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return bytes;
 }
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {

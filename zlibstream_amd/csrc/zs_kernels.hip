@@ -552,7 +552,7 @@ __global__ __launch_bounds__(1024) void zs_resume_check_kernel(const LitPersist 
 // Per main-loop iteration a lane does one unit of work: test a candidate and
 // compare its first 8 bytes, or compare 8 more bytes of a long match.
 __global__ __launch_bounds__(1024) void zs_match_kernel(const StreamDesc *sd, const uint2 *work, const uint16_t *link,
-                                                        uint2 *mm, LevelCfg lv, int strategy) {
+                                                        uint2 *mm, LevelCfg lv, int strategy, StreamState *st) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *wb = smem;
     uint16_t *wl = (uint16_t *)(smem + kMatchLdsBytes);
@@ -645,8 +645,11 @@ __global__ __launch_bounds__(1024) void zs_match_kernel(const StreamDesc *sd, co
     // neighbours too: their LDS reads fall into the same words -- unless the tile is mostly the inside of long matches
     // (image rows, runs): then in runs per lane, for the sake of the hint.  Two instances of the walk, so that a text tile
     // pays nothing for the other kind.
-    if (wg_same * 4 > kMatchLdsLinks / 8) match_walk<true>(wb, wl, om, lo, wendi, &wg_cursor, K, K4, nice, lane);
-    else match_walk<false>(wb, wl, om, lo, wendi, &wg_cursor, K, K4, nice, lane);
+    if (wg_same * 4 > kMatchLdsLinks / 8) {
+        // (periodic data: a speculative parse does not re-converge on it -- the stream's count keeps it off that path)
+        if (threadIdx.x == 0 && s.spec) atomicAdd(&st[w.x].spec_run_tiles, 1);
+        match_walk<true>(wb, wl, om, lo, wendi, &wg_cursor, K, K4, nice, lane);
+    } else match_walk<false>(wb, wl, om, lo, wendi, &wg_cursor, K, K4, nice, lane);
 }
 
 // ------------------------------------------------------------------ parse-segment tables (StreamDesc)
@@ -684,6 +687,27 @@ __device__ __forceinline__ ChunkCtx chunk_ctx(const StreamDesc &s, int c) {
         cx.cl = s.cl + o, cx.m = s.seg_cl[k + 1] - o, cx.S = s.seg_S[k], cx.after = s.seg_after[k];
     }
     return cx;
+}
+// chunk j of the speculative grid of a single Write (zs_device.h K5Spec): j >= 1 begins at j * len - 261, len a power of two
+// that divides kChunk, so every window end's trigger (65536 + 32768 k - 261) is the beginning of a chunk
+__device__ __forceinline__ ChunkCtx spec_chunk_ctx(const StreamDesc &s, int j, int len_bits) {
+    ChunkCtx cx;
+    cx.cs = j ? ((int64_t)j << len_bits) - (kMinLookahead - 1) : 0;
+    cx.ce = ((int64_t)(j + 1) << len_bits) - (kMinLookahead - 1);
+    if (cx.ce > (int64_t)s.body_end + 1) cx.ce = (int64_t)s.body_end + 1;
+    cx.cl = nullptr, cx.m = 0, cx.S = 0, cx.after = 0;
+    constexpr int64_t seg1 = kWindowSize - (kMinLookahead - 1);
+    if (cx.cs >= seg1 && ((cx.cs - seg1) & (kWSize - 1)) == 0) {
+        const int k = (int)((cx.cs - seg1) >> 15) + 1;  // (a window end below the stream's end: its segment exists)
+        if (k < s.nsegs) {
+            const int o = s.seg_cl[k];
+            cx.cl = s.cl + o, cx.m = s.seg_cl[k + 1] - o, cx.S = s.seg_S[k], cx.after = s.seg_after[k];
+        }
+    }
+    return cx;
+}
+__device__ __forceinline__ bool spec_periodic(const StreamDesc &s, const StreamState &ss) {
+    return (int64_t)ss.spec_run_tiles * kSpecRunsDen > (int64_t)s.body_end / kMatchTile + 1;
 }
 __device__ __forceinline__ int chunk_of(const StreamDesc &s, int64_t p) {  // last chunk whose first position is <= p
     // a single Write's chunks are on the grid 2048 c - 261; otherwise from a guess by proportion, a few steps either way (every
@@ -892,7 +916,9 @@ __device__ __forceinline__ void chunkmap_compute(const StreamDesc &s, int c, con
 __global__ __launch_bounds__(512) void zs_chunkmap_kernel(const StreamDesc *sd, const uint2 *work, const uint2 *mm, const uint16_t *link,
                                                           uint32_t *maps, const uint32_t *crc_tab_g,
                                                           LevelCfg lv, int strategy, int hash_variant, uint16_t *chunk_far,
-                                                          uint8_t *only_stale = nullptr, const StreamState *st = nullptr) {
+                                                          uint8_t *only_stale = nullptr, const StreamState *st = nullptr,
+                                                          const StreamState *spec_st = nullptr) {
+    if (spec_st && spec_st[work[blockIdx.x].x].spec_ok) return;  // the speculative walk verified: the stream needs no maps
     __shared__ uint32_t fk[kChunk + 1], fk4[kChunk + 1];
     __shared__ uint32_t tbl[kNodeExit3];
     __shared__ uint32_t tab[1024];
@@ -911,8 +937,9 @@ __global__ __launch_bounds__(512) void zs_chunkmap_kernel(const StreamDesc *sd, 
 // Compose the chunk maps of one parse segment (16 chunks; 32 for segment 0) for every
 // entry slot: 260 lanes, one dependent lookup per chunk.
 __global__ __launch_bounds__(320) void zs_segmap_kernel(const StreamDesc *sd, const uint2 *work, const uint32_t *maps,
-                                                        uint2 *segmap) {
+                                                        uint2 *segmap, const StreamState *spec_st = nullptr) {
     uint2 w = work[blockIdx.x];
+    if (spec_st && spec_st[w.x].spec_ok) return;
     const StreamDesc s = sd[w.x];
     const int seg = (int)w.y;
     int slot = threadIdx.x;
@@ -945,8 +972,9 @@ __device__ __forceinline__ uint32_t seg_row_meta(const StreamDesc &s, int seg, c
     return m | ((uint32_t)(lim < 0 ? 0 : lim) << 2);
 }
 __global__ __launch_bounds__(320) void zs_supmap_kernel(const StreamDesc *sd, const uint2 *work, const uint2 *segmap,
-                                                        const uint8_t *seg_stale, uint2 *supmap) {
+                                                        const uint8_t *seg_stale, uint2 *supmap, const StreamState *spec_st = nullptr) {
     const uint2 w = work[blockIdx.x];
+    if (spec_st && spec_st[w.x].spec_ok) return;
     const StreamDesc s = sd[w.x];
     const int g = (int)w.y;
     if ((int)threadIdx.x >= kSlots) return;
@@ -1226,6 +1254,7 @@ __global__ __launch_bounds__(1024) void zs_resolve_kernel(const StreamDesc *sd, 
         sh_cut_e = -1, sh_nc = 0, sh_diff = 0x7FFFFFFF;
     __syncthreads();
     if (dry && ss.deferred != 1) return;  // only the streams that were given up take part in the rounds
+    if (ss.spec_ok) return;  // the speculative walk verified: zs_spec_verify_kernel has left what this kernel would
     // a run that took the stream over in the middle (StreamDesc::resume) starts in the node and with the symbols it was handed
     if (s.resume && threadIdx.x == 0 && sh_seg == 0 && sh_slot == 0 && sh_total == 0) sh_slot = s.start_slot, sh_total = s.start_syms;
     __syncthreads();
@@ -1848,7 +1877,7 @@ __global__ __launch_bounds__(64) void zs_expand_kernel(const StreamDesc *sd, con
     int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= nwork) return;
     uint2 w = work[i];
-    if (st[w.x].deferred) return;  // the resolve kernel gave the stream up: the batch is run again in rounds
+    if (st[w.x].deferred || st[w.x].spec_ok) return;  // the resolve kernel gave the stream up: the batch is run again in rounds
     const StreamDesc s = sd[w.x];
     const int seg = (int)w.y;
     GlobalAcc acc{as_global(s.in), mm + s.pos_off, crc_tab_g, strategy, hash_variant, link + s.pos_off};
@@ -1915,11 +1944,16 @@ __device__ __forceinline__ void k5_publish(lds_u32p slot, uint32_t v) {
 // (reads the compiler knows about: it places the waits; volatile keeps them in program order among themselves)
 __device__ __forceinline__ uint32_t k5_peek(lds_u32p slot) { return *(volatile __attribute__((address_space(3))) uint32_t *)slot; }
 __device__ __forceinline__ uint64_t k5_peek64(uint32_t addr) { return *(volatile __attribute__((address_space(3))) uint64_t *)(uintptr_t)addr; }
-template <int kK5Ring>
+// MODE 0: the chunks of the work list from the entries the maps gave (K4b).  On the speculative grid (blockIdx.y = the stream,
+// K5Spec): MODE 1 -- the walk without symbols: a lane starts sp.warm positions in front of its chunk in state R with nothing
+// pending, takes the node at the first loop-top at or behind the chunk's start for its entry (the guess) and leaves guess, exit
+// and symbol count; MODE 2 -- the streams whose guesses verified (zs_spec_verify_kernel) once more from those entries, with
+// their symbols' places known: what MODE 0 does.
+template <int kK5Ring, int MODE>
 __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const StreamDesc *sd, const StreamState *st, const uint2 *work, int nwork, const uint2 *mm,
                                                                const uint16_t *link, const uint16_t *entry, const uint32_t *symbase, uint32_t *syms,
                                                                int32_t *blk_end, int32_t *blk_top, const uint32_t *crc_tab_g,
-                                                               LevelCfg lv, int strategy, int hash_variant, int ahead) {
+                                                               LevelCfg lv, int strategy, int hash_variant, int ahead, K5Spec sp) {
     // Wave 0 walks (one lane per chunk), wave 1 feeds it.  A lane's records come 8 bytes a step out of its own 128-byte
     // lines: as loads of the walking wave they are 64 different lines per instruction (the texture path takes them one
     // lane at a time), two instructions a step, and a wave's loads return in order, so it cannot ask ahead for itself.
@@ -2001,23 +2035,37 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
         __device__ ~Done() { k5_publish(slot, kK5Done); }
     } done{sh_line};
     const int i = blockIdx.x * 64 + lane;
-    if (i >= nwork) return;
-    const uint2 w = work[i];
-    if (st[w.x].deferred) return;
-    const StreamDesc s = sd[w.x];
-    const int c = (int)w.y;
+    int si, c;
+    if constexpr (MODE == 0) {
+        if (i >= nwork) return;
+        const uint2 w = work[i];
+        if (st[w.x].deferred || st[w.x].spec_ok) return;
+        si = (int)w.x, c = (int)w.y;
+    } else {
+        si = (int)blockIdx.y, c = i;
+        if (!sd[si].spec || c >= sd[si].spec_n) return;
+        if (MODE == 1 ? spec_periodic(sd[si], st[si]) : !st[si].spec_ok) return;
+    }
+    const StreamDesc s = sd[si];
     GlobalAcc acc{as_global(s.in), mm + s.pos_off, crc_tab_g, strategy, hash_variant, link + s.pos_off};
-    const uint32_t base = symbase[s.chunk_off + c];
+    const uint32_t base = MODE == 0 ? symbase[s.chunk_off + c] : MODE == 2 ? sp.base[s.spec_off + c] : 0u;
     GlobalSymSink sink(syms + s.sym_off + base, base, blk_end + s.blk_off, blk_top + s.blk_off);
     // the refill-rule prefix (first chunks of segments) by the shared code, then plain automaton steps
     int kind, ns;
     int64_t p;
-    uint32_t pflags;
+    uint32_t pflags = 0;
     NullEv nev;
-    const ChunkCtx cx = chunk_ctx(s, c);
-    chunk_special_prefix(acc, sink, cx, (int)entry[s.chunk_off + c], lv, strategy, kind, p, ns, pflags, nev);
+    const ChunkCtx cx = MODE == 0 ? chunk_ctx(s, c) : spec_chunk_ctx(s, c, sp.len_bits);
+    if constexpr (MODE == 1) {
+        // (chunk 0 starts in the stream's initial state, which is slot 0)
+        kind = kR, ns = 0, p = cx.cs - sp.warm;
+        p = (c == 0 || p < 0) ? 0 : p;
+    } else {
+        chunk_special_prefix(acc, sink, cx, MODE == 0 ? (int)entry[s.chunk_off + c] : spec_guess(sp.rec[s.spec_off + c]), lv, strategy, kind, p, ns,
+                             pflags, nev);
+    }
     const int64_t ce = cx.ce;
-    if (p >= ce) return;
+    if (MODE != 1 && p >= ce) return;
     // A step's successor is p+1 or, when the pending match is emitted, p-1+len(pend): both records (the literal byte a
     // step at p+1 may emit rides in bits 24..31 of the first) are requested before the step is worked out.
     const uint2 *a = acc.mm;
@@ -2032,7 +2080,7 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
     // filter_match on a record: gone if len - 3 <= klm and dist > kdm (TOO_FAR: 3 / 4096; Filtered: <= 5 / any)
     static_assert(kNoMatch == 0 && kMinMatch == 3, "record arithmetic below");
     const uint32_t klm = strategy == kFiltered ? 2u : 0u, kdm = strategy == kFiltered ? 0u : (uint32_t)kTooFar;
-    const int q_end = (int)ce, q_last = s.n - 1, lazy = lv.lazy, good = lv.good;
+    const int q_last = s.n - 1, lazy = lv.lazy, good = lv.good;
     int q = (int)p;
     // line 0 = the line of the first loop-top's record; q0 = the position its first record would have
     const int64_t gi0 = s.pos_off + q;
@@ -2042,7 +2090,7 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
     k5_publish(sh_last, (uint32_t)(q_last - q0) >> 4);
     // the loop in two copies: with one, the literal's register is the target of a load in one case and of a shift in the
     // other, and the compiler guards the shift with a wait for everything in flight -- the loads just issued
-    auto steps = [&](auto rl_tag, auto ring_tag) {
+    auto steps = [&](auto rl_tag, auto ring_tag, const int q_end) {
         constexpr bool kRecLits = decltype(rl_tag)::value, kRing = decltype(ring_tag)::value;
         // a step's symbol is stored at the top of the next step, ahead of that step's loads (the wave's memory operations
         // complete in order: behind the loads, its acknowledgement would be waited for with them in the same step)
@@ -2053,7 +2101,8 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
         int k5steps = 0, k5miss = 0, k5lanemiss = 0, k5mysteps = 0;
 #endif
         while (q < q_end) {
-            if (dns >= 0) sink(dns, dsym, dend, dtop);
+            if constexpr (MODE != 1)
+                if (dns >= 0) sink(dns, dsym, dend, dtop);
             const int m = pend ? (int)(pend >> 16) + 3 : 2;
             int qa = q + 1, qb = q - 1 + m;
             qa = qa > q_last ? q_last : qa;
@@ -2115,16 +2164,159 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
             lit = nlit;
             q = npos;
         }
-        if (dns >= 0) sink(dns, dsym, dend, dtop);
+        if constexpr (MODE != 1)
+            if (dns >= 0) sink(dns, dsym, dend, dtop);
 #ifdef ZS_FV_PROF
         if (kRing && (blockIdx.x & 63) == 7 && (lane == 0 || lane == 37))
             printf("K5PROF block %d lane %d: my steps %d, my misses %d; steps with a miss in the wave %d; ticks (100 MHz) %lld\n", (int)blockIdx.x, lane,
                    k5mysteps, k5lanemiss, k5miss, wall_clock64() - k5t0);
 #endif
     };
-    if (!rec_lits) steps(std::false_type{}, std::false_type{});
-    else if (ahead > 0) steps(std::true_type{}, std::true_type{});
-    else steps(std::true_type{}, std::false_type{});
+    auto run_to = [&](const int q_end) {
+        if (!rec_lits) steps(std::false_type{}, std::false_type{}, q_end);
+        else if (ahead > 0) steps(std::true_type{}, std::true_type{}, q_end);
+        else steps(std::true_type{}, std::false_type{}, q_end);
+    };
+    if constexpr (MODE != 1) {
+        run_to((int)ce);
+    } else {
+        // the warm-up: up to the first loop-top at or behind the chunk's start; that node is one of the chunk's entry slots
+        // (R at cs + i, i <= 256, or L / XK / XK4 at cs itself, the pending match being the record of cs - 1)
+        const int cs = (int)cx.cs;
+        run_to(cs);
+        const int guess = kind == kR ? q - cs : 256 + kind;
+        ns = 0;
+        if (cx.m != 0) {
+            // a segment's first chunk: its events by the shared code from the guessed slot, then on from where that leaves
+            NullSink nsk;
+            chunk_special_prefix(acc, nsk, cx, guess, lv, strategy, kind, p, ns, pflags, nev);
+            q = (int)p;
+            pend = kind == kXK ? acc.mK(p - 1) : kind == kXK4 ? acc.mK4(p - 1) : kNoMatch;
+            lit = gin[p - 1];
+            cur = a[p];
+        }
+        run_to((int)ce);
+        const int exit_slot = kind == kR ? q - (int)ce : 256 + kind;
+        const int told = c == sp.corrupt ? (guess + 1) % kSlots : guess;
+        sp.rec[s.spec_off + c] = spec_pack(told, exit_slot, ns, (pflags & (kMapEqualBit | kMapPoisonBit)) != 0);
+    }
+}
+
+// ------------------------------------------------------------------ KSv
+// The speculative walk's verdict, one workgroup per stream: the stream is the reference's iff no chunk met an event that is
+// K4's business and every chunk's guessed entry is its predecessor's exit -- chunk 0 starts in the true state, so by induction
+// every walk was the true one.  Then: the chunks' first symbols (prefix sum of the counts) and what the resolve kernel leaves
+// in StreamState for the tail engine and the block kernels.  Otherwise the stream goes to the maps as it would have.
+__global__ __launch_bounds__(1024) void zs_spec_verify_kernel(const StreamDesc *sd, StreamState *st, const uint2 *mm, const uint16_t *link,
+                                                             const uint32_t *crc_tab_g, LevelCfg lv, int strategy, int hash_variant, K5Spec sp,
+                                                             int32_t *flags) {
+    // tiles of 8192 records through LDS: read and written along the lanes, eight consecutive chunks to a thread in between
+    constexpr int kTile = 8192, kPer = kTile / 1024;
+    __shared__ uint32_t sh_rec[kTile];
+    __shared__ uint32_t sh_wave[16];
+    __shared__ int sh_bad, sh_wrong;
+    __shared__ uint32_t sh_carry, sh_prev;
+    const int si = (int)blockIdx.x, t = (int)threadIdx.x;
+    const StreamDesc s = sd[si];
+    StreamState &ss = st[si];
+    if (!s.spec) {
+        if (t == 0) flags[si] = 0;
+        return;
+    }
+    if (spec_periodic(s, ss)) {  // no lane walked
+        if (t == 0) flags[si] = 2, ss.spec_ok = 0, ss.spec_wrong = 0;
+        return;
+    }
+    if (t == 0) sh_bad = 0, sh_wrong = 0, sh_carry = 0, sh_prev = 0;
+    const int n = s.spec_n;
+    const uint32_t *rec = sp.rec + s.spec_off;
+    uint32_t *base = sp.base + s.spec_off;
+    int bad = 0, wrong = 0;
+    for (int T = 0; T < n; T += kTile) {
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kPer; k++) sh_rec[t + 1024 * k] = T + t + 1024 * k < n ? rec[T + t + 1024 * k] : 0u;
+        __syncthreads();
+        uint32_t r[kPer], sum = 0;
+        uint32_t prev = t ? sh_rec[kPer * t - 1] : sh_prev;
+#pragma unroll
+        for (int e = 0; e < kPer; e++) {
+            r[e] = sh_rec[kPer * t + e];
+            const int c = T + kPer * t + e;
+            if (c < n) {
+                bad |= (r[e] & kSpecBail) != 0;
+                wrong += c > 0 && spec_guess(r[e]) != spec_exit(prev);
+                sum += (uint32_t)spec_count(r[e]);
+            }
+            prev = r[e];
+        }
+        uint32_t inc = sum;  // inclusive scan of the threads' sums: along the wave, then over the 16 waves
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t v = __shfl_up(inc, d, 64);
+            if ((t & 63) >= d) inc += v;
+        }
+        if ((t & 63) == 63) sh_wave[t >> 6] = inc;
+        __syncthreads();
+        uint32_t at = sh_carry + inc - sum;
+        for (int w = 0; w < (t >> 6); w++) at += sh_wave[w];
+#pragma unroll
+        for (int e = 0; e < kPer; e++) {
+            sh_rec[kPer * t + e] = at;
+            at += T + kPer * t + e < n ? (uint32_t)spec_count(r[e]) : 0u;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kPer; k++)
+            if (T + t + 1024 * k < n) base[T + t + 1024 * k] = sh_rec[t + 1024 * k];
+        if (t == 1023) sh_carry = at, sh_prev = r[kPer - 1];
+    }
+    if (bad) atomicOr(&sh_bad, 1);
+    if (wrong) atomicAdd(&sh_wrong, wrong);
+    __syncthreads();
+    const bool ok = !sh_bad && sh_wrong == 0;
+    if (!ok) {
+        if (t == 0) flags[si] = sh_bad ? 3 : 4, ss.spec_ok = 0, ss.spec_wrong = sh_wrong;
+        return;
+    }
+    if (t != 0) return;
+    GlobalAcc acc{as_global(s.in), mm + s.pos_off, crc_tab_g, strategy, hash_variant, link + s.pos_off};
+    const int slot = spec_exit(rec[n - 1]);
+    const int64_t ce = (int64_t)s.body_end + 1;
+    const int kind = slot <= 256 ? (int)kR : slot - 256;
+    const int64_t p = slot <= 256 ? ce + slot : ce;
+    ss.tail_p = (int32_t)p;
+    ss.tail_kind = kind;
+    ss.tail_pend = kind == kXK ? acc.mK(p - 1) : kind == kXK4 ? acc.mK4(p - 1) : 0;
+    // the last parse segment whose event fired in the body (its entry loop-top is one of the body's) and the position that event
+    // pre-inserted, as the resolve kernel finds them
+    int k_done = 0;
+    int64_t preins = -1;
+    for (int k = s.nsegs - 1; k >= 1; k--) {
+        const int j = (int)(((int64_t)kWindowSize + (int64_t)kWSize * (k - 1)) >> sp.len_bits);
+        if (j >= n) continue;
+        const ChunkCtx cx = spec_chunk_ctx(s, j, sp.len_bits);
+        const int g = spec_guess(rec[j]);
+        if ((g <= 256 ? cx.cs + g : cx.cs) > (int64_t)s.body_end) continue;
+        struct LastEv {
+            int64_t pos;
+            __device__ void operator()(int64_t q, bool) { pos = q; }
+        } lev{-1};
+        NullSink nsk;
+        int k2, n2;
+        int64_t p2;
+        uint32_t f2;
+        chunk_special_prefix(acc, nsk, cx, g, lv, strategy, k2, p2, n2, f2, lev);
+        k_done = k;
+        preins = lev.pos >= 0 ? lev.pos + 1 : -1;
+        break;
+    }
+    ss.k_done = k_done;
+    ss.preins = (int32_t)preins;
+    ss.body_syms = sh_carry;
+    ss.deferred = 0;
+    ss.spec_ok = 1, ss.spec_wrong = 0;
+    flags[si] = 1;
 }
 
 // ------------------------------------------------------------------ K5b
