@@ -186,7 +186,7 @@ int main(int argc, char **argv) {
         guess[(size_t)j] = j == corrupt ? (g + 1) % kSlots : g, exit_slot[(size_t)j] = ex, count[(size_t)j] = cnt;
     }
     // ---- 2. verify + scan ----
-    int wrong = 0;
+    int wrong = guess[0] != 0;  // (chunk 0's entry is the stream's initial state, slot 0: the induction's base is checked too)
     for (int j = 1; j < nsc; j++) wrong += guess[(size_t)j] != exit_slot[(size_t)j - 1];
     if (bail || wrong) {
         // the stream is the maps' (tests/model/zs_model.cpp mode chunk is their model): nothing of this walk is used

@@ -40,12 +40,42 @@ def test_corpus_matches_committed_digests(engine, name):
         assert hashlib.sha256(z).hexdigest() == sha, (name, lvl)
 
 
-@pytest.mark.parametrize("name", [n for n in CORPUS if n in oracle_binding.CRLF_FILES or n in ("cp.html", "sum", "ptt5")])
-def test_published_sizes_on_device(engine, name):
+@pytest.mark.parametrize("name", sorted(k for k in KAT if k != "sparse3500"))
+def test_published_sizes_on_device(engine, oracle, name):
+    """The sizes the reference publishes (benchmarks.md, levels 1 / 3 / 6 of the canonical corpus files) on the HIP path: the
+    oracle is pinned to the reference by them (tests/test_oracle.py), the device here -- and to the oracle's bytes."""
     d = oracle_binding.corpus(name, canonical=True)
-    z = engine.deflate_batch([d], level=6)[0]
-    assert len(z) == KAT[name][2]  # benchmarks.md level-6 column
+    for lvl, want in zip((1, 3, 6), KAT[name]):
+        z = engine.deflate_batch([d], level=lvl)[0]
+        assert len(z) == want, (name, lvl)
+        assert z == oracle.compress(d, lvl), (name, lvl)
+        assert zlib.decompress(z) == d, (name, lvl)
+
+
+@pytest.mark.parametrize("lvl", [1, 3, 6])
+def test_published_sizes_sparse_on_device(engine, oracle, lvl):
+    """The reference's own sparse image, 3500 x 3500: rows of 14 000 bytes, the only image here whose rows are not a power of two
+    wide.  At level 6 it is a stream the speculative walk is offered and declines (periodic by the match kernel's count)."""
+    import time
+    d = datagen.sparse(3500, 3500)
+    assert hashlib.sha256(d).hexdigest() == "c61198fa31667adcc50bac51215b120527ad93767cc7662df60163517909fbb9"
+    t0 = time.perf_counter()
+    z = engine.deflate_batch([d], level=lvl)[0]
+    print("sparse(3500, 3500) level %d: %.3f s on the device (host call, first run)" % (lvl, time.perf_counter() - t0))
+    if lvl == 6:
+        cnt = {k: engine.counter(k) for k in ("spec_streams", "spec_periodic", "spec_fallbacks", "spec_wrong_chunks")}
+        assert cnt == {"spec_streams": 1, "spec_periodic": 1, "spec_fallbacks": 1, "spec_wrong_chunks": 0}, cnt
+    assert len(z) == KAT["sparse3500"][(1, 3, 6).index(lvl)]
+    assert z == oracle.compress(d, lvl)
     assert zlib.decompress(z) == d
+    if lvl == 6:
+        os.environ["ZS_NO_SPEC"] = "1"
+        try:
+            z0 = engine.deflate_batch([d], level=6)[0]
+            assert engine.counter("spec_streams") == 0
+        finally:
+            del os.environ["ZS_NO_SPEC"]
+        assert z0 == z
 
 
 def _edge_inputs():

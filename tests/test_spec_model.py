@@ -16,25 +16,68 @@ CORPUS = os.path.join(ROOT, "tests", "golden", "corpus")
 LENS = "512,1024,2048"
 
 
-@pytest.fixture(scope="module")
-def exe():
+def build_model():
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     subprocess.run(["g++", "-O2", "-std=c++17", "-o", EXE, os.path.join(ROOT, "tests/model/zs_spec_model.cpp"),
                     os.path.join(ROOT, "oracle/zs_oracle.c"), os.path.join(ROOT, "oracle/zs_inflate_oracle.c")], check=True)
     return EXE
 
 
-def _run(exe, path, level, strategy=0, lens=LENS, warm=128, corrupt=None):
+@pytest.fixture(scope="module")
+def exe():
+    return build_model()
+
+
+def run_model(exe, path, level, strategy=0, lens=LENS, warm=128, corrupt=None):
+    """{chunk length: {"path": "spec" | "maps", "wrong": wrong guesses, "bail": 0 | 1}} -- every line must be a PASS: what the
+    model emits on the speculative path is the oracle's"""
     cmd = [exe, path, str(level), str(strategy), lens, str(warm)] + ([str(corrupt)] if corrupt is not None else [])
     r = subprocess.run(cmd, capture_output=True, text=True)
     lines = [l for l in r.stdout.splitlines() if l.startswith(("PASS", "FAIL"))]
     assert r.returncode == 0 and lines and all(l.startswith("PASS") for l in lines), (cmd, r.stdout[-800:])
-    return {int(m.group(1)): m.group(2) for m in (re.search(r"len=(\d+) .*path=(\w+)", l) for l in lines) if m}
+    out = {}
+    for l in lines:
+        f = dict(kv.split("=", 1) for kv in l.split() if "=" in kv)
+        if "len" in f:
+            out[int(f["len"])] = {"path": f["path"], "wrong": int(f.get("wrong", 0)), "bail": int(f.get("bail", 0))}
+    return out
 
 
-def _all(jobs):
+def _run(exe, path, level, strategy=0, lens=LENS, warm=128, corrupt=None):
+    return {n: v["path"] for n, v in run_model(exe, path, level, strategy, lens, warm, corrupt).items()}
+
+
+# ---- stream lengths on the structure of the speculative grid (single Write of n bytes, chunks of L) ----
+# body_end = n - 262; chunk j >= 1 is [j L - 261, (j + 1) L - 261) cut at n - 261, so n = j L + 1 makes the last chunk one
+# position long and n = j L removes it; window end k fires at 65536 + 32768 k - 261, the first position of a chunk.
+GRID_D = (-262, -261, -260, -1, 0, 1, 260, 261, 262, 263)
+GRID_B = {2048: (35, 51, 70), 1024: (71, 101, 141), 512: (143, 203, 287)}      # j L in 70-145 KB
+GRID_B_BIG = {1024: (1024, 1025, 1027), 512: (2049, 2051)}                      # j L from 1 MiB on
+
+
+def family_a(ks):
+    """a window end one byte either side of the stream's end, of the body's end, of the last chunk's"""
+    return sorted({65536 + 32768 * k + d for k in ks for d in GRID_D if 65536 + 32768 * k + d >= 65536})
+
+
+def family_b(js):
+    """the last chunk absent, one position long, two positions long"""
+    return sorted({j * L + d for L, jl in js.items() for j in jl for d in (0, 1, 2)})
+
+
+def grid_lengths(big=False):
+    return sorted(set(family_a((31, 32, 33)) + family_b(GRID_B_BIG))) if big else sorted(set(family_a((0, 1, 2, 3)) + family_b(GRID_B)))
+
+
+def alice_of(n):
+    """alice29.txt as committed, repeated and cut to n bytes (the repeat distance is far beyond the window)"""
+    d = open(os.path.join(CORPUS, "alice29.txt"), "rb").read()
+    return (d * (n // len(d) + 1))[:n]
+
+
+def _all(jobs, fn=None):
     with ThreadPoolExecutor(max_workers=max(1, min(8, len(os.sched_getaffinity(0))))) as pool:
-        return [f.result() for f in [pool.submit(_run, *j) for j in jobs]]
+        return [f.result() for f in [pool.submit(fn or _run, *j) for j in jobs]]
 
 
 def test_corpus_at_every_chunk_length(exe):
@@ -88,3 +131,19 @@ def test_filtered_warmups_and_a_spoiled_guess(exe):
     assert _run(exe, p, 6, 0, LENS, 256) == {512: "spec", 1024: "spec", 2048: "spec"}
     _run(exe, p, 6, 0, LENS, 64)
     assert _run(exe, p, 6, 0, LENS, 128, corrupt=7) == {512: "maps", 1024: "maps", 2048: "maps"}
+    # (chunk 0's recorded entry is checked against the initial state: the walk that emits starts from the record)
+    assert run_model(exe, p, 6, 0, LENS, 128, corrupt=0) == {n: {"path": "maps", "wrong": 1, "bail": 0} for n in (512, 1024, 2048)}
+
+
+def test_lengths_on_the_speculative_grid(exe, tmp_path):
+    """Window ends one byte from the stream's end and last chunks of zero, one and two positions (grid_lengths), levels 6 and 9,
+    chunks of 512 / 1024 / 2048: every stream verifies and is the oracle's -- the expectation tests/test_gpu_spec.py holds the
+    device to (there with ZS_SPEC_MIN=65536)."""
+    jobs = []
+    for n in grid_lengths():
+        (tmp_path / ("alice_%d" % n)).write_bytes(alice_of(n))
+        jobs += [(exe, str(tmp_path / ("alice_%d" % n)), lvl) for lvl in (6, 9)]
+    assert len(jobs) == 2 * 63
+    res = _all(jobs)
+    notspec = [(os.path.basename(j[1]), j[2], r) for j, r in zip(jobs, res) if r != {512: "spec", 1024: "spec", 2048: "spec"}]
+    assert not notspec, notspec

@@ -2204,8 +2204,8 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
 
 // ------------------------------------------------------------------ KSv
 // The speculative walk's verdict, one workgroup per stream: the stream is the reference's iff no chunk met an event that is
-// K4's business and every chunk's guessed entry is its predecessor's exit -- chunk 0 starts in the true state, so by induction
-// every walk was the true one.  Then: the chunks' first symbols (prefix sum of the counts) and what the resolve kernel leaves
+// K4's business and every chunk's guessed entry is its predecessor's exit -- chunk 0's recorded entry is checked against the
+// stream's initial state (slot 0: the second walk starts from the record), so by induction every walk was the true one.  Then: the chunks' first symbols (prefix sum of the counts) and what the resolve kernel leaves
 // in StreamState for the tail engine and the block kernels.  Otherwise the stream goes to the maps as it would have.
 __global__ __launch_bounds__(1024) void zs_spec_verify_kernel(const StreamDesc *sd, StreamState *st, const uint2 *mm, const uint16_t *link,
                                                              const uint32_t *crc_tab_g, LevelCfg lv, int strategy, int hash_variant, K5Spec sp,
@@ -2245,7 +2245,7 @@ __global__ __launch_bounds__(1024) void zs_spec_verify_kernel(const StreamDesc *
             const int c = T + kPer * t + e;
             if (c < n) {
                 bad |= (r[e] & kSpecBail) != 0;
-                wrong += c > 0 && spec_guess(r[e]) != spec_exit(prev);
+                wrong += spec_guess(r[e]) != (c > 0 ? spec_exit(prev) : 0);  // (chunk 0: the stream's initial state is slot 0)
                 sum += (uint32_t)spec_count(r[e]);
             }
             prev = r[e];
