@@ -65,6 +65,14 @@ namespace SixLabors.ZlibStream
                                                                                 int strategy, int hashVariant);
         [DllImport(Lib)] public static extern int zs_inflate_batch_multi_device(IntPtr* ctxs, int nCtx, int n, IntPtr* input, long* inLen, IntPtr* output,
                                                                                 long* outCap, long* outLen, int* status, int* partOf);
+        // ---- the PNG caller path on the device: scanline filtering of an image in HBM (the IDAT payload before compression), and
+        //      its inverse over what zs_inflate_batch_device left there (n images, or the Adam7 passes of one, per call)
+        [DllImport(Lib)] public static extern int zs_png_filter_device(IntPtr ctx, IntPtr pixels, long rowBytes, long height, int bpp, int filter,
+                                                                       IntPtr output, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_unfilter_batch_device(IntPtr ctx, int n, IntPtr* input, long* rowBytes, long* height, int* bpp,
+                                                                               IntPtr* output, int* status, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_unfilter_device(IntPtr ctx, IntPtr input, long rowBytes, long height, int bpp, IntPtr output,
+                                                                         IntPtr hipStream);
         // bytes fed behind a stream's trailer before its end was seen (the engine looks for the end now and then)
         [DllImport(Lib)] public static extern long zs_inflate_surplus(IntPtr s, IntPtr* p);
     }

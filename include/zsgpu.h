@@ -151,6 +151,25 @@ ZS_API int zs_inflate_batch_multi_device(zs_ctx *const *ctxs, int n_ctx, int n, 
 ZS_API int zs_png_filter_device(zs_ctx *ctx, const void *pixels, int64_t row_bytes, int64_t height, int bpp, int filter,
                                 void *out, void *hip_stream);
 
+/* Inverse of zs_png_filter_device: n independent filtered images (what zs_inflate_batch_device leaves for a PNG's
+ * IDAT payload, or for one Adam7 pass), each height[i] rows of 1 + row_bytes[i] bytes (filter type 0..4, then the
+ * filtered bytes), reconstructed per PNG specification 9.2 into height[i] * row_bytes[i] bytes of pixels.
+ * in[i] / out[i]: DEVICE pointers on ctx's GPU, must not overlap.  bpp[i]: bytes per complete pixel, 1..8.
+ * row_bytes / height / bpp / status are HOST arrays.  Work is ordered on hip_stream (NULL = the context's stream);
+ * the call synchronises that stream once and returns after the results are known, like zs_inflate_batch_device.
+ * status[i] (may be NULL): ZS_OK, or ZS_DATA_ERROR when a row's filter-type byte is > 4 (zs_ctx_last_error names the
+ * image and the first such row; that image's output is unspecified, the others are unaffected).
+ * Returns ZS_OK, the first failing image's code, or ZS_STREAM_ERROR for bad arguments (also: more than 2^31 - 1 rows in
+ * one call), or ZS_MEM_ERROR when the call's workspace (16 bytes per row) does not fit the device.
+ * zs_ctx_counter(ctx, "png_segments"): the independent runs of rows the last call found -- a run starts at
+ * row 0 and at every None or Sub row, and one run is one workgroup's job (KU). */
+ZS_API int zs_png_unfilter_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *row_bytes,
+                                        const int64_t *height, const int *bpp, void *const *out, int *status,
+                                        void *hip_stream);
+/* One image: the batch call with n = 1. */
+ZS_API int zs_png_unfilter_device(zs_ctx *ctx, const void *in, int64_t row_bytes, int64_t height, int bpp, void *out,
+                                  void *hip_stream);
+
 /* Stage timing of the last *_batch_device call, measured with hipEvents on
  * the stream the kernels ran on.  Enable before the call. */
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took

@@ -57,6 +57,15 @@ private:
     zs_ctx *ctx_ = nullptr;
 };
 
+// The decode half of the PNG caller path for an image that stays on the GPU: what zs_inflate_batch_device left for an IDAT
+// payload (device pointer, height rows of 1 + rowBytes bytes) -> height * rowBytes bytes of pixels (device pointer).
+inline void PngUnfilterDevice(const void *filtered, int64_t rowBytes, int64_t height, int bytesPerPixel, void *pixels, zs_ctx *ctx = nullptr,
+                              void *hipStream = nullptr) {
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    const int rc = zs_png_unfilter_device(c, filtered, rowBytes, height, bytesPerPixel, pixels, hipStream);
+    if (rc != ZS_OK) throw ZlibStreamException(rc == ZS_DATA_ERROR ? std::string("png: ") + zs_ctx_last_error(c) : std::string("png: bad arguments"));
+}
+
 // ZlibOutputStream.cs: write-only stream that deflates into BaseStream.
 class ZlibOutputStream {
 public:

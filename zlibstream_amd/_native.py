@@ -14,6 +14,7 @@ SYMBOLS = [
     "zs_deflate_init", "zs_deflate", "zs_deflate_end", "zs_last_message", "zs_adler32_device",
     "zs_inflate_batch_device", "zs_inflate_batch", "zs_inflate_init", "zs_inflate", "zs_inflate_end", "zs_inflate_message", "zs_inflate_surplus",
     "zs_device_count", "zs_partition", "zs_deflate_batch_multi", "zs_inflate_batch_multi", "zs_png_filter_device", "zs_deflate_writes_device", "zs_deflate_batch_multi_device", "zs_inflate_batch_multi_device",
+    "zs_png_unfilter_batch_device", "zs_png_unfilter_device",
 ]
 
 _lib = None
@@ -107,5 +108,9 @@ def lib():
     L.zs_inflate_batch_multi.argtypes = [P(vp), i32, i32, P(vp), P(i64), P(vp), P(i64), P(i64), P(i32)]
     L.zs_png_filter_device.restype = i32
     L.zs_png_filter_device.argtypes = [vp, vp, i64, i64, i32, i32, vp, vp]
+    L.zs_png_unfilter_batch_device.restype = i32
+    L.zs_png_unfilter_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(vp), P(i32), vp]
+    L.zs_png_unfilter_device.restype = i32
+    L.zs_png_unfilter_device.argtypes = [vp, vp, i64, i64, i32, vp, vp]
     _lib = L
     return L

@@ -110,7 +110,7 @@ class Engine:
 
     def counter(self, name):
         """zs_ctx_counter: "fast_rounds", "fast_fallbacks", "round_runs", "cut_rounds", "lit_fallbacks", "lit_engine_bytes",
-        "spec_streams", "spec_fallbacks", "spec_periodic", "spec_wrong_chunks"."""
+        "spec_streams", "spec_fallbacks", "spec_periodic", "spec_wrong_chunks", "png_segments"."""
         return int(self._lib.zs_ctx_counter(self._h, name.encode()))
 
     def stage_ms(self):
@@ -304,6 +304,45 @@ def png_filter_device(engine, pixels_ptr, row_bytes, height, bpp, filter_type, o
                                             int(filter_type), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0))
     if rc != 0:
         raise ValueError("zs_png_filter_device rejected the arguments (%d)" % rc)
+
+
+def _png_unfilter_check(in_ptr, row_bytes, height, bpp, out_ptr):
+    if not in_ptr or not out_ptr or int(row_bytes) < 1 or not 1 <= int(height) <= 0x7FFFFFFF or not 1 <= int(bpp) <= 8:
+        raise ValueError("png_unfilter: row_bytes >= 1, 1 <= height <= 2^31 - 1, bpp 1..8 and non-null device pointers are required")
+
+
+def png_unfilter_device(engine, in_ptr, row_bytes, height, bpp, out_ptr, stream=None):
+    """PNG scanline reconstruction (the inverse of png_filter_device) of a device-resident filtered image -- height rows of
+    1 + row_bytes bytes, what inflate_batch_device leaves for an IDAT payload -- into height * row_bytes bytes of pixels in
+    a device buffer.  Returns when the pixels are written.  A filter-type byte above 4 raises ZlibStreamException."""
+    _png_unfilter_check(in_ptr, row_bytes, height, bpp, out_ptr)
+    rc = _native.lib().zs_png_unfilter_device(engine.handle, ctypes.c_void_p(in_ptr), int(row_bytes), int(height), int(bpp),
+                                              ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0))
+    if rc == -3:
+        raise ZlibStreamException("png: " + engine.last_error())
+    if rc != 0:
+        raise ValueError("zs_png_unfilter_device failed (%d): %s" % (rc, engine.last_error()))
+
+
+def png_unfilter_batch_device(engine, in_ptrs, row_bytes, heights, bpps, out_ptrs, stream=None):
+    """Many independent filtered images (the images of a batch, the Adam7 passes of one) in one call -> a status per image:
+    0, or -3 (ZS_DATA_ERROR) for an image with a filter-type byte above 4 (engine.last_error() names the first such image
+    and row; the other images are reconstructed all the same)."""
+    n = len(in_ptrs)
+    if not (len(row_bytes) == len(heights) == len(bpps) == len(out_ptrs) == n):
+        raise ValueError("png_unfilter_batch_device: the argument lists differ in length")
+    if n == 0:
+        return []
+    for a in zip(in_ptrs, row_bytes, heights, bpps, out_ptrs):
+        _png_unfilter_check(*a)
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    status = I32()
+    rc = _native.lib().zs_png_unfilter_batch_device(engine.handle, n, VP(*[int(p) for p in in_ptrs]), I64(*[int(x) for x in row_bytes]),
+                                                    I64(*[int(x) for x in heights]), I32(*[int(x) for x in bpps]),
+                                                    VP(*[int(p) for p in out_ptrs]), status, ctypes.c_void_p(stream or 0))
+    if rc not in (0, -3):
+        raise ValueError("zs_png_unfilter_batch_device failed (%d): %s" % (rc, engine.last_error()))
+    return list(status)
 
 
 _default_engine = None

@@ -16,6 +16,7 @@
 #include "zs_kernels.hip"
 #include "zs_inflate_par.hip"
 #include "zs_inflate_tok.hip"
+#include "zs_png.hip"
 
 using namespace zs;
 
@@ -60,6 +61,7 @@ struct zs_ctx {
     // probing call (zs_inflate asking whether the stream's end has arrived), where the block chain ended
     std::vector<int64_t> inf_used;
     int64_t *inf_probe = nullptr;
+    int64_t png_segments = 0;  // independent runs of rows the last unfilter call found (zs_png.h png_row_cuts)
     int fast_rounds = 0;  // rounds the last call's DeflateFast took over its chunks (0: one workgroup per stream)
     bool no_rounds_once = false;  // the next plan takes one workgroup per stream (set when the rounds gave up)
     int last_op = 0;  // 0: deflate stages, 1: block-parallel inflate stages, 2: deflate at levels 1-3 (for zs_ctx_stage_name)
@@ -68,7 +70,7 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, png_img, png_seg, png_ctr;
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1543,6 +1545,7 @@ int zs_ctx_create(int device, zs_ctx **out) {
         hipFuncSetAttribute((const void *)zs_cuts_repair_kernel<256, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kRepairLds) != hipSuccess ||
         hipFuncSetAttribute((const void *)zs_cuts_repair_kernel<256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kRepairLds) != hipSuccess ||
         hipFuncSetAttribute((const void *)zs_cuts_repair_kernel<1024, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, kRepairLds) != hipSuccess ||
+        hipFuncSetAttribute((const void *)zs_png_unfilter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kPngMaxLds) != hipSuccess ||
         hipFuncSetAttribute((const void *)zs_inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kInfLds) != hipSuccess) {
         zs_ctx_destroy(c);
         return ZS_MEM_ERROR;
@@ -1564,7 +1567,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->png_img, &c->png_seg, &c->png_ctr};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -1611,6 +1614,7 @@ int64_t zs_ctx_counter(const zs_ctx *c, const char *name) {
     if (k == "spec_fallbacks") return c->spec_fallbacks;
     if (k == "spec_periodic") return c->spec_periodic;  // ... fallbacks that were never walked (the match kernel's count of RUNS tiles)
     if (k == "spec_wrong_chunks") return c->spec_wrong_chunks;
+    if (k == "png_segments") return c->png_segments;  // segments the last zs_png_unfilter_batch_device call found
     return -1;
 }
 
@@ -2263,6 +2267,85 @@ extern "C" int zs_png_filter_device(zs_ctx *c, const void *pixels, int64_t row_b
                        (uint8_t *)out);
     if (hipGetLastError() != hipSuccess) return ZS_STREAM_ERROR;
     return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
+}
+
+// ------------------------------------------------------------------ PNG scanline reconstruction (KU, zs_png.hip): inflate -> pixels in HBM
+namespace {
+constexpr int kPngGrid = 1024;  // workgroups that loop over the segments: four per CU where the tiles allow it
+
+bool run_png_unfilter(zs_ctx *c, int n, const void *const *in, const int64_t *row_bytes, const int64_t *height, const int *bpp, void *const *out,
+                      int64_t total_rows, int max_bpp, int *st, hipStream_t s, bool *no_memory) {
+    const size_t b_img = sizeof(PngImg) * (size_t)n, b_ctr = sizeof(int32_t) * ((size_t)n + 1);
+    if (!ensure(c, c->png_img, b_img) || !ensure(c, c->png_seg, sizeof(PngSeg) * (size_t)total_rows) || !ensure(c, c->png_ctr, b_ctr) ||
+        !ensure_pinned(c, std::max(b_img, b_ctr))) {
+        *no_memory = true;
+        return false;
+    }
+    PngImg *hi = (PngImg *)c->pinned;
+    for (int i = 0; i < n; i++) hi[i] = PngImg{(const uint8_t *)in[i], (uint8_t *)out[i], row_bytes[i], (int32_t)height[i], bpp[i]};
+    ZS_HIP(c, hipMemcpyAsync(c->png_img.p, c->pinned, b_img, hipMemcpyHostToDevice, s));
+    ZS_HIP(c, hipMemsetAsync(c->png_ctr.p, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(zs_png_scan_kernel, dim3((unsigned)n), dim3(256), 0, s, (const PngImg *)c->png_img.p, (PngSeg *)c->png_seg.p, (int32_t *)c->png_ctr.p);
+    ZS_HIP(c, hipGetLastError());
+    const int waves = png_waves(max_bpp);
+    const int tiles = waves * kPngRows * png_tile_stride(max_bpp);
+    hipLaunchKernelGGL(zs_png_unfilter_kernel, dim3((unsigned)std::min<int64_t>(total_rows, kPngGrid)), dim3(64 * (unsigned)waves),
+                       (size_t)png_lds_bytes(max_bpp, waves), s, (const PngImg *)c->png_img.p, (const PngSeg *)c->png_seg.p, (const int32_t *)c->png_ctr.p, tiles);
+    ZS_HIP(c, hipGetLastError());
+    ZS_HIP(c, hipMemcpyAsync(c->pinned, c->png_ctr.p, b_ctr, hipMemcpyDeviceToHost, s));  // (the descriptors' upload is through by then: same stream)
+    ZS_HIP(c, hipStreamSynchronize(s));
+    const int32_t *hc = (const int32_t *)c->pinned;
+    c->png_segments = hc[0];
+    bool ok = true;
+    for (int i = n - 1; i >= 0; i--) {
+        st[i] = hc[1 + i] == kPngNoBadRow ? ZS_OK : ZS_DATA_ERROR;
+        if (st[i] != ZS_OK) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "data error: image %d: row %d has a filter type above 4", i, (int)hc[1 + i]);
+            c->err = msg;  // (the loop runs downwards: the first failing image's message stays)
+            ok = false;
+        }
+    }
+    return ok;
+}
+}  // namespace
+
+extern "C" int zs_png_unfilter_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *row_bytes, const int64_t *height, const int *bpp,
+                                            void *const *out, int *status, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!in || !row_bytes || !height || !bpp || !out) return ZS_STREAM_ERROR;
+    if (status)
+        for (int i = 0; i < n; i++) status[i] = ZS_STREAM_ERROR;
+    int64_t total_rows = 0;
+    int max_bpp = 1;
+    for (int i = 0; i < n; i++) {
+        if (!in[i] || !out[i] || row_bytes[i] <= 0 || height[i] <= 0 || height[i] > 0x7FFFFFFF || bpp[i] < 1 || bpp[i] > 8) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        total_rows += height[i];
+        max_bpp = std::max(max_bpp, bpp[i]);
+    }
+    if (total_rows > 0x7FFFFFFF) {  // (the segment list is indexed with 32 bits)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    std::vector<int> st((size_t)n, ZS_STREAM_ERROR);
+    bool no_memory = false;
+    const bool ok = run_png_unfilter(c, n, in, row_bytes, height, bpp, out, total_rows, max_bpp, st.data(), s, &no_memory);
+    if (no_memory) std::fill(st.begin(), st.end(), (int)ZS_MEM_ERROR);  // (the workspace or the staging buffer did not fit: not the caller's arguments)
+    if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
+    if (ok) return ZS_OK;
+    for (int v : st)
+        if (v != ZS_OK) return v;
+    return ZS_STREAM_ERROR;
+}
+
+extern "C" int zs_png_unfilter_device(zs_ctx *c, const void *in, int64_t row_bytes, int64_t height, int bpp, void *out, void *hip_stream) {
+    return zs_png_unfilter_batch_device(c, 1, &in, &row_bytes, &height, &bpp, &out, nullptr, hip_stream);
 }
 
 // ------------------------------------------------------------------ multi-GPU batch entry points

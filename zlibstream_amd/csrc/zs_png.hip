@@ -1,0 +1,264 @@
+// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip).  What inflate leaves for
+// an IDAT payload is, per row, a filter-type byte and the filtered bytes; reconstruction reads reconstructed neighbours
+// (left, above, above-left), so it is serial along a row and across rows.  Two kernels:
+//   zs_png_scan_kernel      one workgroup per image over its type bytes: the first invalid one, and the segments
+//                           (zs_png.h png_row_cuts) appended to one list for the whole batch
+//   zs_png_unfilter_kernel  a fixed grid over that list, one workgroup per segment at a time, the skewed wavefront of
+//                           zs_png.h inside it.  No workgroup waits for another.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "zs_png.h"
+
+namespace zs {
+
+struct PngImg {
+    const uint8_t *in;
+    uint8_t *out;
+    int64_t row_bytes;
+    int32_t height, bpp;
+};
+struct PngSeg {
+    int32_t img, row0, row1, pad;
+};
+
+constexpr int kPngNoBadRow = 0x7FFFFFFF;
+constexpr int kPngMaxLds = png_lds_bytes(4, png_waves(4)) > png_lds_bytes(8, png_waves(8)) ? png_lds_bytes(4, png_waves(4)) : png_lds_bytes(8, png_waves(8));
+
+// counters[0]: segments of the batch (zeroed before the launch); counters[1 + i]: image i's first row with a type > 4
+__global__ __launch_bounds__(256) void zs_png_scan_kernel(const PngImg *imgs, PngSeg *segs, int32_t *counters) {
+    __shared__ int s_cnt[4], s_base, s_prev, s_bad;
+    const int img = (int)blockIdx.x, tid = (int)threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const PngImg im = imgs[img];
+    const int64_t pitch = im.row_bytes + 1;
+    if (tid == 0) s_prev = -1, s_bad = kPngNoBadRow;
+    __syncthreads();
+    for (int64_t r0 = 0; r0 < im.height; r0 += 256) {
+        const int64_t r = r0 + tid;
+        const bool valid = r < im.height;
+        const int ft = valid ? im.in[r * pitch] : 2;
+        const bool cut = valid && (r == 0 || png_row_cuts(ft));
+        if (valid && ft > 4) atomicMin(&s_bad, (int)r);
+        const unsigned long long m = __ballot(cut);
+        if (lane == 0) s_cnt[w] = __popcll(m);
+        __syncthreads();
+        const int tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        int before = __popcll(m & ((1ull << lane) - 1));
+        for (int i = 0; i < w; i++) before += s_cnt[i];
+        if (tid == 0 && tot > 0) s_base = atomicAdd(&counters[0], tot);
+        __syncthreads();
+        if (cut) {
+            const int slot = s_base + before;
+            segs[slot].img = img;
+            segs[slot].row0 = (int)r;
+            const int prev = before > 0 ? slot - 1 : s_prev;  // the segment that ends where this one starts
+            if (prev >= 0) segs[prev].row1 = (int)r;
+        }
+        __syncthreads();
+        if (tid == 0 && tot > 0) s_prev = s_base + tot - 1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        segs[s_prev].row1 = im.height;  // (row 0 always starts a segment)
+        counters[1 + img] = s_bad;
+    }
+}
+
+template <int BPP>
+__device__ __forceinline__ uint64_t png_lds_px(const uint8_t *p) {
+    if constexpr (BPP == 8) return *(const uint64_t *)p;
+    else if constexpr (BPP == 4) return *(const uint32_t *)p;
+    else if constexpr (BPP == 2) return *(const uint16_t *)p;
+    else {
+        uint64_t v = 0;
+#pragma unroll
+        for (int j = 0; j < BPP; j++) v |= (uint64_t)p[j] << (8 * j);
+        return v;
+    }
+}
+template <int BPP>
+__device__ __forceinline__ void png_lds_put(uint8_t *p, uint64_t v) {
+    if constexpr (BPP == 8) *(uint64_t *)p = v;
+    else if constexpr (BPP == 4) *(uint32_t *)p = (uint32_t)v;
+    else if constexpr (BPP == 2) *(uint16_t *)p = (uint16_t)v;
+    else {
+#pragma unroll
+        for (int j = 0; j < BPP; j++) p[j] = (uint8_t)(v >> (8 * j));
+    }
+}
+
+// what lane L-1 holds, in lane L; lane 0 gets `first` (DPP wave_shr:1, nothing goes through memory)
+template <int BPP>
+__device__ __forceinline__ uint64_t png_from_lane_above(uint64_t v, uint64_t first) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)first, (int)(uint32_t)v, 0x138, 0xf, 0xf, false);
+    if constexpr (BPP <= 4) return lo;
+    else {
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(first >> 32), (int)(uint32_t)(v >> 32), 0x138, 0xf, 0xf, false);
+        return ((uint64_t)hi << 32) | lo;
+    }
+}
+
+// lane `from`'s value in every lane (`from` is the same for the whole wave)
+template <int BPP>
+__device__ __forceinline__ uint64_t png_lane_value(uint64_t v, int from) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, from);
+    if constexpr (BPP <= 4) return lo;
+    else return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), from) << 32) | lo;
+}
+
+// `rows` rows of `nbytes` bytes each, row i at g + i * gpitch (any alignment) and at l + i * lpitch (4-aligned): whole
+// dwords over the 64 lanes, row after row, and the last bytes of a row one by one -- nothing outside a row is touched
+template <bool TO_LDS>
+__device__ __forceinline__ void png_copy_rows(uint8_t *l, int lpitch, uint8_t *g, int64_t gpitch, int rows, int nbytes, int dw_per_row, int lane) {
+    const int total = rows * dw_per_row;
+    if (nbytes == 4 * dw_per_row) {  // whole dwords only (all but a row's last tile column): sixteen loads on their way, then their stores
+        for (int base = 0; base < total; base += 64 * 16) {
+            uint32_t v[16];
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                if (base + 64 * j >= total) break;  // (the same for the whole wave: a band of few rows issues few loads)
+                const int at = base + 64 * j + lane, idx = at < total ? at : total - 1;  // (past the end: the last dword again, not stored)
+                const int i = idx / dw_per_row, off = 4 * (idx - i * dw_per_row);
+                if (TO_LDS) __builtin_memcpy(&v[j], g + i * gpitch + off, 4);
+                else v[j] = *(const uint32_t *)(l + i * lpitch + off);
+            }
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const int idx = base + 64 * j + lane;
+                const int i = idx / dw_per_row, off = 4 * (idx - i * dw_per_row);
+                if (idx < total) {
+                    if (TO_LDS) *(uint32_t *)(l + i * lpitch + off) = v[j];
+                    else __builtin_memcpy(g + i * gpitch + off, &v[j], 4);
+                }
+            }
+        }
+        return;
+    }
+    for (int idx = lane; idx < total; idx += 64) {
+        const int i = idx / dw_per_row, off = 4 * (idx - i * dw_per_row);
+        uint8_t *gp = g + i * gpitch + off, *lp = l + i * lpitch + off;
+        if (off + 4 <= nbytes) {
+            uint32_t v;
+            if (TO_LDS) {
+                __builtin_memcpy(&v, gp, 4);
+                *(uint32_t *)lp = v;
+            } else {
+                v = *(const uint32_t *)lp;
+                __builtin_memcpy(gp, &v, 4);
+            }
+        } else {
+            for (int b = off; b < nbytes; b++) {
+                if (TO_LDS) lp[b - off] = gp[b - off];
+                else gp[b - off] = lp[b - off];
+            }
+        }
+    }
+}
+
+// One segment, rows [row0, row1) of image `im`, by the `waves` waves of the workgroup (zs_png.h for the schedule).
+// lds: waves x tile (64 rows of png_tile_stride(BPP) bytes), then at bnd_off waves x kPngBndBytes.
+template <int BPP>
+__device__ void png_segment(const PngImg &im, int row0, int row1, uint8_t *lds, int bnd_off, int waves) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    constexpr int stride = png_tile_stride(BPP), col_bytes = kPngChunk * BPP, dw_per_col = col_bytes / 4;
+    uint8_t *tile = lds + w * (kPngRows * stride), *bnd = lds + bnd_off + w * kPngBndBytes;
+    uint8_t *my = tile + lane * stride;
+    const int64_t rb = im.row_bytes, npx = png_npx(rb, BPP), nq = png_nq(npx);
+    const int64_t nbands = ((int64_t)(row1 - row0) + kPngRows - 1) / kPngRows;
+    const int64_t steps = png_total_steps(nbands, waves, nq), period = png_period(nq, waves);
+    int64_t k = w, q = -2 * (int64_t)w;  // this wave's band, and the chunk step of that band
+    uint64_t a = 0, cprev = 0, pout = 0;
+    PngSel sel = png_sel(0);
+    bool rowvalid = false;
+    for (int64_t T = 0; T < steps; T++) {
+        const bool active = q >= 0 && q < nq && k < nbands;
+        const int64_t y0 = row0 + k * kPngRows;
+        const int rows = active ? (int)((int64_t)row1 - y0 < kPngRows ? (int64_t)row1 - y0 : kPngRows) : 0;
+        const int slot = (int)(q & 1);
+        if (active) {
+            if (q == 0) {
+                a = cprev = pout = 0;
+                rowvalid = lane < rows;
+                const int ft = rowvalid ? im.in[(y0 + lane) * (rb + 1)] : 0;
+                sel = png_sel(ft);  // (a type above 4 selects nothing: None)
+            }
+            const int64_t byte0 = q * col_bytes;  // tile column q of the rows
+            const int nbytes = (int)(rb - byte0 < col_bytes ? rb - byte0 : col_bytes);
+            if (nbytes > 0) {
+                png_copy_rows<true>(tile + slot * col_bytes, stride, const_cast<uint8_t *>(im.in) + y0 * (rb + 1) + 1 + byte0, rb + 1, rows, nbytes,
+                                    dw_per_col, lane);
+                // the row above the band: zeros above a segment, else what another wave of this workgroup stored at least two
+                // chunk steps ago.  That store is visible here because of the barriers in between: __syncthreads() orders global
+                // memory at workgroup scope, and the waves of a workgroup share their CU's L1.  (Not so in tgsplit mode, where a
+                // workgroup may span CUs: this kernel is not built for it.)
+                if (w == 0) {
+                    if (k == 0) {
+                        for (int i = lane; i < dw_per_col; i += 64) *(uint32_t *)(bnd + slot * col_bytes + 4 * i) = 0;
+                    } else
+                        png_copy_rows<true>(bnd + slot * col_bytes, 0, im.out + (y0 - 1) * rb + byte0, 0, 1, nbytes, dw_per_col, lane);
+                }
+            }
+        }
+        __syncthreads();
+        if (active) {
+            // the row above lane 0, tile column q: pixel s in lane s, handed to lane 0 at inner step s
+            const uint64_t above = png_lds_px<BPP>(bnd + slot * col_bytes + lane * BPP);
+            const int64_t x0 = q * kPngChunk - lane;
+            for (int g = 0; g < kPngChunk; g += 8) {
+                uint64_t f[8];
+                bool act[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int64_t x = x0 + g + u;
+                    act[u] = rowvalid && x >= 0 && x < npx;
+                    f[u] = png_lds_px<BPP>(my + (int)(x & (kPngRing - 1)) * BPP);  // (inside the tile whatever x is)
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) asm volatile("" : "+v"(f[u]));  // all eight reads are on their way before the first is used
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint64_t b = png_from_lane_above<BPP>(pout, png_lane_value<BPP>(above, g + u));
+                    const uint64_t rec = png_recon_px<BPP>(sel, act[u] ? f[u] : 0, a, b, cprev);
+                    pout = act[u] ? rec : 0;
+                    a = act[u] ? rec : a;
+                    cprev = b;
+                    if (act[u]) png_lds_put<BPP>(my + (int)((x0 + g + u) & (kPngRing - 1)) * BPP, rec);
+                }
+            }
+        }
+        if (active && q >= 1) {  // tile column q-1 is complete in every row of the band (the slot no wave reads in this chunk step)
+            const int64_t byte0 = (q - 1) * col_bytes;
+            const int nbytes = (int)(rb - byte0 < col_bytes ? rb - byte0 : col_bytes);
+            const int pslot = slot ^ 1;
+            png_copy_rows<false>(tile + pslot * col_bytes, stride, im.out + y0 * rb + byte0, rb, rows, nbytes, dw_per_col, lane);
+            if (w + 1 < waves)  // its last row is the row above the next band, which is two chunk steps behind
+                for (int i = lane; i < dw_per_col; i += 64)
+                    *(uint32_t *)(bnd + kPngBndBytes + pslot * col_bytes + 4 * i) = *(const uint32_t *)(tile + (kPngRows - 1) * stride + pslot * col_bytes + 4 * i);
+        }
+        __syncthreads();  // what was stored and handed on is there for the next chunk step's loads
+        if (++q == period) q = 0, k += waves;
+    }
+}
+
+__global__ __launch_bounds__(256) void zs_png_unfilter_kernel(const PngImg *imgs, const PngSeg *segs, const int32_t *counters, int bnd_off) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t png_lds[];
+    const int total = counters[0], waves = (int)blockDim.x >> 6;
+    for (int item = (int)blockIdx.x; item < total; item += (int)gridDim.x) {
+        const PngSeg sg = segs[item];
+        const PngImg im = imgs[sg.img];
+        switch (im.bpp) {
+        case 1: png_segment<1>(im, sg.row0, sg.row1, png_lds, bnd_off, waves); break;
+        case 2: png_segment<2>(im, sg.row0, sg.row1, png_lds, bnd_off, waves); break;
+        case 3: png_segment<3>(im, sg.row0, sg.row1, png_lds, bnd_off, waves); break;
+        case 4: png_segment<4>(im, sg.row0, sg.row1, png_lds, bnd_off, waves); break;
+        case 5: png_segment<5>(im, sg.row0, sg.row1, png_lds, bnd_off, waves); break;
+        case 6: png_segment<6>(im, sg.row0, sg.row1, png_lds, bnd_off, waves); break;
+        case 7: png_segment<7>(im, sg.row0, sg.row1, png_lds, bnd_off, waves); break;
+        default: png_segment<8>(im, sg.row0, sg.row1, png_lds, bnd_off, waves); break;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace zs
