@@ -73,6 +73,17 @@ namespace SixLabors.ZlibStream
                                                                                IntPtr* output, int* status, IntPtr hipStream);
         [DllImport(Lib)] public static extern int zs_png_unfilter_device(IntPtr ctx, IntPtr input, long rowBytes, long height, int bpp, IntPtr output,
                                                                          IntPtr hipStream);
+        // ---- the encoder for a batch: n streams each in its own NoFlush Writes (writeEnds[i]: stream i's cumulative ends, or null), the
+        //      filter for n images in one launch, and the two together -- pixels in HBM to IDAT payloads in HBM, rowsPerWrite rows a Write.
+        //      A stream takes the path it takes alone: scanline Writes at levels 1-3 often mean the one-wave literal engine.
+        [DllImport(Lib)] public static extern int zs_deflate_writes_batch_device(IntPtr ctx, int n, IntPtr* input, long* inLen, long** writeEnds, long* nWrites,
+                                                                                 IntPtr* output, long* outCap, long* outLen, int* status, int level,
+                                                                                 int strategy, int hashVariant, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_filter_batch_device(IntPtr ctx, int n, IntPtr* pixels, long* rowBytes, long* height, int* bpp,
+                                                                             int* filter, IntPtr* output, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_idat_batch_device(IntPtr ctx, int n, IntPtr* pixels, long* rowBytes, long* height, int* bpp,
+                                                                           int* filter, long rowsPerWrite, IntPtr* output, long* outCap, long* outLen,
+                                                                           int* status, int level, int strategy, int hashVariant, IntPtr hipStream);
         // bytes fed behind a stream's trailer before its end was seen (the engine looks for the end now and then)
         [DllImport(Lib)] public static extern long zs_inflate_surplus(IntPtr s, IntPtr* p);
     }

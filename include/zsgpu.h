@@ -98,6 +98,25 @@ ZS_API int zs_deflate_writes_device(zs_ctx *ctx, const void *in, int64_t in_len,
                                     void *out, int64_t out_cap, int64_t *out_len, int level, int strategy, int hash_variant,
                                     void *hip_stream);
 
+/* n independent streams, each written in its own NoFlush Writes: zs_deflate_writes_device for a batch, one call.
+ * write_ends / n_writes are HOST arrays of n entries; write_ends[i] holds stream i's n_writes[i] cumulative Write ends
+ * (non-decreasing, the last one = in_len[i]; an empty Write is dropped, as ZlibOutputStream drops it).
+ * write_ends[i] == NULL, n_writes[i] <= 0 or a list that leaves one distinct end: the stream is one Write (a list of one
+ * end is still checked against in_len[i]; zs_deflate_writes_device, which has no "no list", rejects n_writes == 0 for a
+ * non-empty input).
+ * write_ends == NULL: the call is zs_deflate_batch_device.  A malformed list anywhere is ZS_STREAM_ERROR for the whole
+ * call, before any device work.  out_len / status / sub-batches / the one synchronisation at the end: as
+ * zs_deflate_batch_device (ZS_BUF_ERROR for a stream whose out_cap is too small, the others unaffected).
+ * One exception that leaves the bytes alone: at levels 1-3 a list-less stream of 256 KiB .. 4 MiB in a batch of at most 16
+ * is not probed for the speculative runs (periodic data) once any stream of the call has a list; it takes the sweeps.
+ * Every stream takes the path it takes alone through zs_deflate_writes_device -- also the slow one: a stream written
+ * a few bytes at a time, and at levels 1-3 a stream with a Write end within 261 bytes below a window end (scanline
+ * Writes often have one), runs on the one-wave literal engine whatever its neighbours are. */
+ZS_API int zs_deflate_writes_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *in_len,
+                                          const int64_t *const *write_ends, const int64_t *n_writes, void *const *out,
+                                          const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy,
+                                          int hash_variant, void *hip_stream);
+
 /* Host-pointer form: copies in over PCIe, runs the device path, copies out. */
 ZS_API int zs_deflate_batch(zs_ctx *ctx, int n, const void *const *in, const int64_t *in_len, void *const *out,
                             const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy,
@@ -151,6 +170,25 @@ ZS_API int zs_inflate_batch_multi_device(zs_ctx *const *ctxs, int n_ctx, int n, 
 ZS_API int zs_png_filter_device(zs_ctx *ctx, const void *pixels, int64_t row_bytes, int64_t height, int bpp, int filter,
                                 void *out, void *hip_stream);
 
+/* zs_png_filter_device for n images in one launch: pixels / out are HOST arrays of DEVICE pointers, row_bytes / height /
+ * bpp / filter HOST arrays; the rules per image are those above and the bytes those of n single calls (the tie rule of
+ * filter 5 included).  n == 0 is ZS_OK; n < 0, a null array, a bad image or more than 2^31 - 1 rows in one call is
+ * ZS_STREAM_ERROR.  The call waits for hip_stream once (its descriptors go through the context's staging buffer);
+ * with hip_stream == NULL it returns when the rows are written, otherwise the launch is ordered on that stream. */
+ZS_API int zs_png_filter_batch_device(zs_ctx *ctx, int n, const void *const *pixels, const int64_t *row_bytes,
+                                      const int64_t *height, const int *bpp, const int *filter, void *const *out,
+                                      void *hip_stream);
+
+/* Pixels to IDAT payloads, n images a call, nothing leaving HBM: zs_png_filter_batch_device into a buffer the context
+ * owns (height * (row_bytes + 1) bytes per image, kept until zs_ctx_destroy), then zs_deflate_writes_batch_device with
+ * one Write per rows_per_write rows -- 1: the scanline-by-scanline encoder, 0: one Write per image.  out[i] receives
+ * the zlib stream of image i; out_cap / out_len / status / level / strategy / hash_variant as for the deflate call,
+ * whose remarks on the literal engine apply (rows_per_write = 1 at levels 1-3). */
+ZS_API int zs_png_idat_batch_device(zs_ctx *ctx, int n, const void *const *pixels, const int64_t *row_bytes,
+                                    const int64_t *height, const int *bpp, const int *filter, int64_t rows_per_write,
+                                    void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level,
+                                    int strategy, int hash_variant, void *hip_stream);
+
 /* Inverse of zs_png_filter_device: n independent filtered images (what zs_inflate_batch_device leaves for a PNG's
  * IDAT payload, or for one Adam7 pass), each height[i] rows of 1 + row_bytes[i] bytes (filter type 0..4, then the
  * filtered bytes), reconstructed per PNG specification 9.2 into height[i] * row_bytes[i] bytes of pixels.
@@ -175,7 +213,7 @@ ZS_API int zs_png_unfilter_device(zs_ctx *ctx, const void *in, int64_t row_bytes
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took
  * over its chunks (0: one workgroup per stream); "fast_fallbacks", "round_runs", "cut_rounds", "lit_fallbacks" -- batches that took
  * one of the slower paths since the context was made; "lit_engine_bytes" -- input bytes the one-wave literal engine parsed
- * beyond the streams' last 261; "spec_streams", "spec_fallbacks", "spec_wrong_chunks" -- the last deflate call's speculative
+ * beyond the streams' last 261 (a call that runs its batch again counts the plan it ends with); "spec_streams", "spec_fallbacks", "spec_wrong_chunks" -- the last deflate call's speculative
  * chunk walk (levels 4-9): streams that tried it, those of them that took the transfer maps after all, chunks whose guessed
  * entry was wrong; "spec_periodic" -- those of the fallbacks that were never walked (periodic by the match kernel's count). */
 ZS_API int64_t zs_ctx_counter(const zs_ctx *ctx, const char *name);

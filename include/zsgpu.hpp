@@ -66,6 +66,63 @@ inline void PngUnfilterDevice(const void *filtered, int64_t rowBytes, int64_t he
     if (rc != ZS_OK) throw ZlibStreamException(rc == ZS_DATA_ERROR ? std::string("png: ") + zs_ctx_last_error(c) : std::string("png: bad arguments"));
 }
 
+// The encode half for images that stay on the GPU, n a call: pixels[i] (device pointer, height[i] rows of rowBytes[i] bytes)
+// -> the zlib stream of image i's IDAT payload in out[i] (device pointer, outCap[i] bytes), rows filtered with filter[i]
+// (0-4, 5 adaptive) and written rowsPerWrite rows a Write, as a scanline encoder writes to ZlibOutputStream (1; 0: one Write
+// per image).  Returns the streams' lengths.  (The two halves follow.
+// At levels 1-3 scanline Writes often put a stream on the one-wave literal engine, as they do one image at a time.)
+inline std::vector<int64_t> PngIdatBatchDevice(const std::vector<const void *> &pixels, const std::vector<int64_t> &rowBytes,
+                                               const std::vector<int64_t> &height, const std::vector<int> &bytesPerPixel, const std::vector<int> &filter,
+                                               int64_t rowsPerWrite, const std::vector<void *> &out, const std::vector<int64_t> &outCap,
+                                               CompressionLevel level = CompressionLevel::DefaultCompression,
+                                               CompressionStrategy strategy = CompressionStrategy::DefaultStrategy, zs_ctx *ctx = nullptr,
+                                               void *hipStream = nullptr) {
+    const size_t n = pixels.size();
+    if (rowBytes.size() != n || height.size() != n || bytesPerPixel.size() != n || filter.size() != n || out.size() != n || outCap.size() != n)
+        throw ZlibStreamException("png: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    std::vector<int64_t> outLen(n, 0);
+    std::vector<int> status(n, 0);
+    const int rc = zs_png_idat_batch_device(c, (int)n, pixels.data(), rowBytes.data(), height.data(), bytesPerPixel.data(), filter.data(), rowsPerWrite,
+                                            out.data(), outCap.data(), outLen.data(), status.data(), (int)level, (int)strategy, 0, hipStream);
+    if (rc != ZS_OK) throw ZlibStreamException(std::string("deflating: ") + zs_ctx_last_error(c));
+    return outLen;
+}
+
+// The two halves of PngIdatBatchDevice for a caller that wants the filtered rows, or has them: all rows of n images filtered
+// in one launch (filtered[i]: height[i] * (rowBytes[i] + 1) bytes on the device) ...
+inline void PngFilterBatchDevice(const std::vector<const void *> &pixels, const std::vector<int64_t> &rowBytes, const std::vector<int64_t> &height,
+                                 const std::vector<int> &bytesPerPixel, const std::vector<int> &filter, const std::vector<void *> &filtered,
+                                 zs_ctx *ctx = nullptr, void *hipStream = nullptr) {
+    const size_t n = pixels.size();
+    if (rowBytes.size() != n || height.size() != n || bytesPerPixel.size() != n || filter.size() != n || filtered.size() != n)
+        throw ZlibStreamException("png: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    if (zs_png_filter_batch_device(c, (int)n, pixels.data(), rowBytes.data(), height.data(), bytesPerPixel.data(), filter.data(), filtered.data(),
+                                   hipStream) != ZS_OK)
+        throw ZlibStreamException("png: bad arguments");
+}
+// ... and n device-resident streams deflated in one call, stream i written in the NoFlush Writes whose cumulative ends are
+// writeEnds[i] (empty: one Write).  Returns the streams' lengths.
+inline std::vector<int64_t> DeflateWritesBatchDevice(const std::vector<const void *> &in, const std::vector<int64_t> &inLen,
+                                                     const std::vector<std::vector<int64_t>> &writeEnds, const std::vector<void *> &out,
+                                                     const std::vector<int64_t> &outCap, CompressionLevel level = CompressionLevel::DefaultCompression,
+                                                     CompressionStrategy strategy = CompressionStrategy::DefaultStrategy, zs_ctx *ctx = nullptr,
+                                                     void *hipStream = nullptr) {
+    const size_t n = in.size();
+    if (inLen.size() != n || writeEnds.size() != n || out.size() != n || outCap.size() != n)
+        throw ZlibStreamException("deflating: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    std::vector<const int64_t *> lists(n, nullptr);
+    std::vector<int64_t> counts(n, 0), outLen(n, 0);
+    for (size_t i = 0; i < n; i++)
+        if (!writeEnds[i].empty()) lists[i] = writeEnds[i].data(), counts[i] = (int64_t)writeEnds[i].size();
+    const int rc = zs_deflate_writes_batch_device(c, (int)n, in.data(), inLen.data(), lists.data(), counts.data(), out.data(), outCap.data(), outLen.data(),
+                                                  nullptr, (int)level, (int)strategy, 0, hipStream);
+    if (rc != ZS_OK) throw ZlibStreamException(std::string("deflating: ") + zs_ctx_last_error(c));
+    return outLen;
+}
+
 // ZlibOutputStream.cs: write-only stream that deflates into BaseStream.
 class ZlibOutputStream {
 public:

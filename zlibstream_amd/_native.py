@@ -15,6 +15,7 @@ SYMBOLS = [
     "zs_inflate_batch_device", "zs_inflate_batch", "zs_inflate_init", "zs_inflate", "zs_inflate_end", "zs_inflate_message", "zs_inflate_surplus",
     "zs_device_count", "zs_partition", "zs_deflate_batch_multi", "zs_inflate_batch_multi", "zs_png_filter_device", "zs_deflate_writes_device", "zs_deflate_batch_multi_device", "zs_inflate_batch_multi_device",
     "zs_png_unfilter_batch_device", "zs_png_unfilter_device",
+    "zs_deflate_writes_batch_device", "zs_png_filter_batch_device", "zs_png_idat_batch_device",
 ]
 
 _lib = None
@@ -112,5 +113,12 @@ def lib():
     L.zs_png_unfilter_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(vp), P(i32), vp]
     L.zs_png_unfilter_device.restype = i32
     L.zs_png_unfilter_device.argtypes = [vp, vp, i64, i64, i32, vp, vp]
+    if hasattr(L, "zs_deflate_writes_batch_device"):  # (an older build selected with ZS_LIB for an A/B run lacks the batch encoder)
+        L.zs_deflate_writes_batch_device.restype = i32
+        L.zs_deflate_writes_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(P(i64)), P(i64), P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
+        L.zs_png_filter_batch_device.restype = i32
+        L.zs_png_filter_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), P(vp), vp]
+        L.zs_png_idat_batch_device.restype = i32
+        L.zs_png_idat_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), i64, P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
     _lib = L
     return L

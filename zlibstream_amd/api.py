@@ -172,6 +172,49 @@ class Engine:
             raise ZlibStreamException("deflating: " + self.last_error())
         return olen.value
 
+    def deflate_writes_batch_device(self, in_ptrs, in_lens, write_ends, out_ptrs, out_caps, level=6, strategy=0, hash_variant=0, stream=None,
+                                    return_status=False):
+        """n device-resident streams, each written in its own NoFlush Writes (zs_deflate_writes_batch_device).  write_ends: None
+        (every stream one Write: deflate_batch_device), or per stream None (one Write) or its cumulative Write ends -- a
+        sequence of ints or a ctypes int64 array, non-decreasing, the last one = in_lens[i].  Returns the output lengths; with
+        return_status=True nothing is raised for a failing stream and (code, lengths, per-stream codes) comes back (-5,
+        ZS_BUF_ERROR, for a stream whose capacity was too small; the other streams are complete).  A stream takes the path it
+        takes alone through deflate_writes_device: scanline Writes at levels 1-3 often mean the one-wave literal engine."""
+        n = len(in_ptrs)
+        if not (len(in_lens) == len(out_ptrs) == len(out_caps) == n) or (write_ends is not None and len(write_ends) != n):
+            raise ValueError("deflate_writes_batch_device: the argument lists differ in length")
+        arrays = []
+        for i in range(n):
+            we = write_ends[i] if write_ends is not None else None
+            if we is None:
+                arrays.append(None)
+                continue
+            prev = 0
+            for e in we:
+                if int(e) < prev:
+                    raise ValueError("deflate_writes_batch_device: the Write ends of stream %d decrease" % i)
+                prev = int(e)
+            if len(we) and prev != int(in_lens[i]):
+                raise ValueError("deflate_writes_batch_device: the last Write end of stream %d is not its length" % i)
+            arrays.append(we if isinstance(we, ctypes.Array) else (ctypes.c_int64 * len(we))(*[int(e) for e in we]))
+        if n == 0:
+            return (0, [], []) if return_status else []
+        P64 = ctypes.POINTER(ctypes.c_int64)
+        ends = None
+        if write_ends is not None:
+            ends = (P64 * n)(*[ctypes.cast(a, P64) if a is not None and len(a) else P64() for a in arrays])
+        counts = (ctypes.c_int64 * n)(*[len(a) if a is not None else 0 for a in arrays])
+        VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+        out_len, status = I64(), I32()
+        rc = self._lib.zs_deflate_writes_batch_device(self._h, n, VP(*[int(p) for p in in_ptrs]), I64(*[int(x) for x in in_lens]), ends, counts,
+                                                      VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, status,
+                                                      int(level), int(strategy), int(hash_variant), ctypes.c_void_p(stream or 0))
+        if return_status:
+            return rc, list(out_len), list(status)
+        if rc != 0:
+            raise ZlibStreamException("deflating: " + self.last_error())
+        return list(out_len)
+
     def deflate_batch(self, buffers, level=6, strategy=0, hash_variant=0):
         """Host buffers (bytes-like) -> list of zlib streams (bytes)."""
         bufs = [bytes(b) for b in buffers]
@@ -304,6 +347,59 @@ def png_filter_device(engine, pixels_ptr, row_bytes, height, bpp, filter_type, o
                                             int(filter_type), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0))
     if rc != 0:
         raise ValueError("zs_png_filter_device rejected the arguments (%d)" % rc)
+
+
+def _png_filter_check(name, ptrs, row_bytes, heights, bpps, filters, out_ptrs):
+    n = len(ptrs)
+    if not (len(row_bytes) == len(heights) == len(bpps) == len(filters) == len(out_ptrs) == n):
+        raise ValueError(name + ": the argument lists differ in length")
+    for p, rb, h, b, f, o in zip(ptrs, row_bytes, heights, bpps, filters, out_ptrs):
+        if not p or not o or int(rb) < 1 or not 1 <= int(h) <= 0x7FFFFFFF or not 1 <= int(b) <= 8 or not 0 <= int(f) <= 5:
+            raise ValueError(name + ": row_bytes >= 1, 1 <= height <= 2^31 - 1, bpp 1..8, filter 0..5 and non-null device pointers are required")
+    if sum(int(h) for h in heights) > 0x7FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 rows in one call")
+    return n
+
+
+def png_filter_batch_device(engine, pixel_ptrs, row_bytes, heights, bpps, filters, out_ptrs, stream=None):
+    """png_filter_device for many device-resident images in one launch: image i's height * (row_bytes + 1) filtered bytes
+    go to out_ptrs[i], byte for byte what the single call writes (filters[i] 0..5, 5 = adaptive)."""
+    n = _png_filter_check("png_filter_batch_device", pixel_ptrs, row_bytes, heights, bpps, filters, out_ptrs)
+    if n == 0:
+        return
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    rc = _native.lib().zs_png_filter_batch_device(engine.handle, n, VP(*[int(p) for p in pixel_ptrs]), I64(*[int(x) for x in row_bytes]),
+                                                  I64(*[int(x) for x in heights]), I32(*[int(x) for x in bpps]), I32(*[int(x) for x in filters]),
+                                                  VP(*[int(p) for p in out_ptrs]), ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_filter_batch_device failed (%d): %s" % (rc, engine.last_error()))
+
+
+def png_idat_batch_device(engine, pixel_ptrs, row_bytes, heights, bpps, filters, out_ptrs, out_caps, rows_per_write=1, level=6, strategy=0,
+                          hash_variant=0, stream=None, return_status=False):
+    """Pixels -> IDAT payloads for many device-resident images in one call (zs_png_idat_batch_device): the batch filter into
+    a buffer the engine keeps, then every image's rows as the Writes of its own zlib stream -- rows_per_write rows a Write
+    (1: the scanline-by-scanline encoder; 0: one Write per image).  Returns the stream lengths; return_status as
+    Engine.deflate_writes_batch_device.  At levels 1-3 scanline Writes often put a stream on the one-wave literal engine,
+    as they do one image at a time."""
+    if len(out_caps) != len(pixel_ptrs):
+        raise ValueError("png_idat_batch_device: the argument lists differ in length")
+    n = _png_filter_check("png_idat_batch_device", pixel_ptrs, row_bytes, heights, bpps, filters, out_ptrs)
+    if int(rows_per_write) < 0:
+        raise ValueError("png_idat_batch_device: rows_per_write is negative")
+    if n == 0:
+        return (0, [], []) if return_status else []
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    rc = _native.lib().zs_png_idat_batch_device(engine.handle, n, VP(*[int(p) for p in pixel_ptrs]), I64(*[int(x) for x in row_bytes]),
+                                                I64(*[int(x) for x in heights]), I32(*[int(x) for x in bpps]), I32(*[int(x) for x in filters]),
+                                                int(rows_per_write), VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len,
+                                                status, int(level), int(strategy), int(hash_variant), ctypes.c_void_p(stream or 0))
+    if return_status:
+        return rc, list(out_len), list(status)
+    if rc != 0:
+        raise ZlibStreamException("deflating: " + engine.last_error())
+    return list(out_len)
 
 
 def _png_unfilter_check(in_ptr, row_bytes, height, bpp, out_ptr):

@@ -70,7 +70,7 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, png_img, png_seg, png_ctr;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, png_img, png_seg, png_ctr, png_fimg, png_scratch;
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -213,10 +213,11 @@ struct RunOpts {
     uint32_t start_syms = 0;
 };
 
-// `writes` (optional, one stream only): the Writes of a multi-Write stream, or of one whose Writes carry a flush mode
+// `writes` (optional): one entry per stream, the Writes of a multi-Write stream (null: the stream is one Write).  A spec whose
+// Writes carry a flush mode, and `ro`, are the Stream API's and come with one stream only.
 bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out, const int64_t *out_cap,
                   int64_t *out_len, int *status, int level, int strategy, int hash_variant, hipStream_t stream,
-                  const WriteSpec *writes = nullptr, int force_seq = 0, RunOpts *ro = nullptr, bool rounds = false,
+                  const WriteSpec *const *writes = nullptr, int force_seq = 0, RunOpts *ro = nullptr, bool rounds = false,
                   const std::vector<uint8_t> *force_lit = nullptr) {
     if (level == -1) level = 6;
     LevelCfg lv = level_cfg(level);
@@ -228,31 +229,48 @@ bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len
         out_len[i] = 0;
         if (status) status[i] = ZS_STREAM_ERROR;
     }
+    bool any_writes = false;
+    for (int i = 0; i < n && writes; i++) any_writes = any_writes || writes[i] != nullptr;
+    if (any_writes && n > 1)
+        for (int i = 0; i < n; i++)
+            if (ro || (writes[i] && writes[i]->flushing())) {
+                c->err = "flush modes and incremental runs take one stream a call";
+                return false;
+            }
     // CompressionStrategy.Rle does not look at Write ends: Deflate.Rle.cs leaves a Deflate call as soon as fewer than MAX_MATCH bytes
     // are ahead under NoFlush (:24-38), so every match is measured with a full lookahead whatever the Writes are, and nothing is
     // inserted anywhere.  What a Write end can move is the loop-top at which the window slides -- when it lies within 262 bytes
     // below a window end -- and with it a block's permission to be stored.  Any other NoFlush schedule is the single Write's
     // stream (checked against the oracle on random data and schedules, tests/test_oracle.py) and runs as one.
-    WriteSpec rle_one;
-    if (writes && writes->ends.size() > 1 && strategy == kRle && level >= 1 && !writes->flushing() && !ro && n == 1 && !getenv("ZS_NO_RLE_MULTI")) {
-        bool safe = true;
-        for (size_t k = 0; k + 1 < writes->ends.size() && safe; k++) {
-            const int64_t E = writes->ends[k];
-            safe = !(E >= kWindowSize - kMinLookahead && (E % kWSize) >= kWSize - kMinLookahead);
+    std::vector<WriteSpec> rle_one;
+    std::vector<const WriteSpec *> rle_writes;
+    if (any_writes && strategy == kRle && level >= 1 && !ro && !getenv("ZS_NO_RLE_MULTI")) {
+        rle_one.resize((size_t)n);
+        rle_writes.assign(writes, writes + n);
+        for (int i = 0; i < n; i++) {
+            const WriteSpec *wr = writes[i];
+            if (!wr || wr->ends.size() <= 1 || wr->flushing()) continue;
+            bool safe = true;
+            for (size_t k = 0; k + 1 < wr->ends.size() && safe; k++) {
+                const int64_t E = wr->ends[k];
+                safe = !(E >= kWindowSize - kMinLookahead && (E % kWSize) >= kWSize - kMinLookahead);
+            }
+            if (safe) {
+                rle_one[(size_t)i] = *wr;
+                rle_one[(size_t)i].ends.assign(1, in_len[i]);
+                rle_one[(size_t)i].flush.assign(1, 0);
+                rle_writes[(size_t)i] = &rle_one[(size_t)i];
+            }
         }
-        if (safe) {
-            rle_one = *writes;
-            rle_one.ends.assign(1, in_len[0]);
-            rle_one.flush.assign(1, 0);
-            writes = &rle_one;
-        }
+        writes = rle_writes.data();
     }
     // Levels 1-3, a few streams of 256 KiB .. 4 MiB: data that is all period (zeros, image rows, a short period) takes the sweeps'
     // rounds one range a round -- 1 MiB of zeros 57 ms -- and the speculative runs' engine 7; anything else is better off with
     // the sweeps, and which it is the links tell (zs_fast_probe_kernel).  Such a batch is planned for both; the kernels behind
     // the link kernel see the one the probe chose.
     static const int64_t fast_min_input = getenv("ZS_FAST_MIN_INPUT") ? atoll(getenv("ZS_FAST_MIN_INPUT")) : kFastMinPeriodic;
-    bool allow_dual = lv.func == 1 && strategy != kRle && strategy != kHuffmanOnly && !writes && !ro && !rounds && force_seq == 0 && !force_lit && n <= 16 && !getenv("ZS_NO_FAST_VEC") &&
+    // (a batch with a Write list anywhere is not planned for both: its list-less streams take the sweeps -- the same bytes)
+    bool allow_dual = lv.func == 1 && strategy != kRle && strategy != kHuffmanOnly && !any_writes && !ro && !rounds && force_seq == 0 && !force_lit && n <= 16 && !getenv("ZS_NO_FAST_VEC") &&
                       !getenv("ZS_FAST_NO_ROUNDS");
     for (int i = 0; i < n && allow_dual; i++) allow_dual = in_len[i] >= fast_min_input && in_len[i] < kFastMinInput;
     bool dual_broken = false;
@@ -280,13 +298,14 @@ plan_again:
     for (int i = 0; i < n; i++) {
         StreamDesc &s = pl.sd[(size_t)i];
         int64_t len = in_len[i];
+        const WriteSpec *const wr = writes ? writes[i] : nullptr;  // this stream's own Writes
         s.in = (const uint8_t *)in[i];
         s.out = (uint8_t *)out[i];
         s.out_cap = out_cap[i];
         s.n = (int32_t)len;
-        const bool multi = writes && writes->ends.size() > 1;
+        const bool multi = wr && wr->ends.size() > 1;
         // an incremental run always takes the block-by-block output accounting (its state is carried from run to run)
-        const bool flushing = writes && (writes->flushing() || ro);
+        const bool flushing = wr && (wr->flushing() || ro);
         const bool resume = ro && ro->resume;
         const bool cont = ro && ro->cont && !resume, final_run = !ro || ro->final_run;
         // the bulk pipeline takes the NoFlush schedules build_geometry accepts (zs_core.h: any Write sizes but streams written
@@ -295,22 +314,22 @@ plan_again:
         std::vector<ReadEvent> rev;
         Geometry geo;
         const int64_t one_write[1] = {len};
-        const bool real_flush = writes && writes->flushing();
+        const bool real_flush = wr && wr->flushing();
         const bool lit_forced = force_lit && (*force_lit)[(size_t)i];
         const std::vector<int64_t> no_ends_;
         GeoStart gs;
         if (resume) gs.resume = true, gs.at_read = ro->at_read, gs.p0 = ro->p0, gs.E0 = ro->E0, gs.base0 = ro->base0;
         // (a flush mode on the run's last Write alone is the tail engine's business: it closes the block there)
         bool inner_flush = false;
-        if (writes)
-            for (size_t k = 0; k + 1 < writes->flush.size(); k++) inner_flush = inner_flush || writes->flush[k] != 0;
+        if (wr)
+            for (size_t k = 0; k + 1 < wr->flush.size(); k++) inner_flush = inner_flush || wr->flush[k] != 0;
         const bool slow_ok = lv.func == 2 && strategy != kRle && !cont && !lit_forced && !(multi && inner_flush) &&
-                             build_geometry(len, multi ? writes->ends : no_ends_, geo, gs);
+                             build_geometry(len, multi ? wr->ends : no_ends_, geo, gs);
         // levels 1-3 take several NoFlush Writes too when every read brings a full lookahead and no Write ends where its loop-top
         // may or may not slide the window (zs_core.h build_read_events: Stream.CopyTo's 81 920-byte Writes do; a Write every few
         // bytes does not)
         const bool fast_multi = multi && !inner_flush && !cont && !resume && lv.func == 1 && strategy != kRle && !getenv("ZS_NO_FAST_MULTI") &&
-                                build_read_events(len, writes->ends, rev, true);
+                                build_read_events(len, wr->ends, rev, true);
         // levels 1-3 behind a flush (round 5): the run goes on from the suspended engine's chains too -- zs_import_chains_kernel's
         // links ARE DeflateFast's chains for the history (prev[] names inserted positions only), so with "inserted" for every
         // position the chains reach, the sweeps start at p0 as they start at 0; one Write, the engine standing at the flush
@@ -318,7 +337,7 @@ plan_again:
         // full lookahead, no Write ends where its loop-top may or may not slide the window)
         const bool fast_resume = resume && ro->at_read && lv.func == 1 && strategy != kRle && !inner_flush && !lit_forced && !getenv("ZS_NO_FAST_RESUME") &&
                                  len - ro->p0 >= 2 * kMinLookahead &&
-                                 (multi ? build_read_events(len, writes->ends, rev, true, ro->p0, ro->base0)
+                                 (multi ? build_read_events(len, wr->ends, rev, true, ro->p0, ro->base0)
                                         : build_read_events(len, std::vector<int64_t>(one_write, one_write + 1), rev, true, ro->p0, ro->base0));
         const bool regular = fast_resume ? true : cont ? false : multi ? fast_multi : build_read_events(len, std::vector<int64_t>(one_write, one_write + 1), rev);
         s.body_end = slow_ok ? (int32_t)geo.body_end : -1;
@@ -351,9 +370,9 @@ plan_again:
                 pl.n_rle_tiles += (s.rle_end + kMaxMatch + 1 + 4095) / 4096;
             }
         }
-        s.n_wr = (multi || flushing) ? (int32_t)writes->ends.size() : 1;  // 0: a run without input (Finish alone)
+        s.n_wr = (multi || flushing) ? (int32_t)wr->ends.size() : 1;  // 0: a run without input (Finish alone)
         s.wr_end = nullptr;
-        s.wr_flush = nullptr, s.wr_blk = nullptr, s.out_chunk = writes ? writes->chunk : 512, s.raw = writes && writes->raw;
+        s.wr_flush = nullptr, s.wr_blk = nullptr, s.out_chunk = wr ? wr->chunk : 512, s.raw = wr && wr->raw;
         s.kl = num_refills(len - (resume ? ro->base0 : 0));
         s.resume = resume && (slow_ok || fast_resume) ? 1 : 0, s.cont_bits = (cont || resume) ? 1 : 0, s.mid_write = (ro && (ro->mid_write || (resume && !ro->at_read))) ? 1 : 0;
         if (resume && !slow_ok && !fast_resume) {
@@ -428,7 +447,7 @@ plan_again:
                 spec_geo = geo.seg_cl[(size_t)k + 1] - geo.seg_cl[(size_t)k] == 1 &&
                            geo.cl[(size_t)geo.seg_cl[(size_t)k]] == ((uint32_t)(kWindowSize + kWSize * (k - 1)) | kClWindowBit);
         }
-        if (spec_on && lv.func == 2 && (strategy == kDefault || strategy == kFiltered) && !writes && !ro && !lit_forced && spec_geo && len >= spec_min &&
+        if (spec_on && lv.func == 2 && (strategy == kDefault || strategy == kFiltered) && !wr && !ro && !lit_forced && spec_geo && len >= spec_min &&
             n <= 65535) {
             s.spec = 1, s.spec_n = (int32_t)((((int64_t)s.body_end + kMinLookahead - 1) >> spec_bits) + 1);
             pl.n_spec += s.spec_n, pl.n_spec_streams++;
@@ -444,7 +463,7 @@ plan_again:
         s.blk_off = (int32_t)pl.n_blocks;
         // level 0 runs with memLevel 7: a block is flushed every 8191 symbols (only Rle tallies symbols there)
         s.max_blocks = (int32_t)(level == 0 ? len / 8191 + len / 32506 + 4 : len / kBlockSyms + 2);
-        if (flushing) s.max_blocks += (int32_t)writes->ends.size() + 1;  // every Write under a flush mode closes a block
+        if (flushing) s.max_blocks += (int32_t)wr->ends.size() + 1;  // every Write under a flush mode closes a block
         s.plan_blk = nullptr, s.plan_nblk = 0;
         s.final_run = final_run ? 1 : 0, s.cont = cont ? 1 : 0, s.persist = ro ? ro->persist : nullptr;
         s.abs_off = (ro && !resume) ? ro->abs_off : 0, s.adler_stream = ro ? ro->adler_stream : 1, s.carry_byte = ro ? ro->carry_byte : 0;
@@ -454,8 +473,8 @@ plan_again:
             const size_t first = pl.plan_blk.size();
             const std::vector<int64_t> no_ends;
             const std::vector<uint8_t> no_flush;
-            if (flushing) pl.plan_wr_blk.assign(writes->ends.size(), 0);
-            plan_stored_blocks(len, (multi || flushing) ? writes->ends : no_ends, flushing ? writes->flush : no_flush,
+            if (flushing) pl.plan_wr_blk.assign(wr->ends.size(), 0);
+            plan_stored_blocks(len, (multi || flushing) ? wr->ends : no_ends, flushing ? wr->flush : no_flush,
                                [&](int64_t start, int32_t blen, int can_store, int eof) {
                                    pl.plan_blk.push_back(BlockRec{start, 0, blen, 0, can_store, eof});
                                },
@@ -503,6 +522,9 @@ plan_again:
     }
     pl.any_dual = allow_dual;
     c->lit_engine_bytes += pl.lit_bytes;
+    // (a call that runs its batch again -- below: the sweeps after runs that did not verify, a stream moved to the literal engine,
+    // the cut rounds -- counts the plan it ends with, so that a stream adds the same whatever its neighbours made the batch do)
+    auto plan_rerun = [&]() { c->lit_engine_bytes -= pl.lit_bytes; };
     c->fast_rounds = 0;
     const bool no_rounds_this_call = c->no_rounds_once;
     c->no_rounds_once = false;
@@ -622,22 +644,38 @@ plan_again:
          !ensure(c, c->run_fail, 4 * (size_t)n + 64)))
         return false;
     // rounds: the call goes on behind the batched cut rounds of the call that made it -- same plan, same workspace; nothing
-    // is uploaded or zeroed again and the kernels up to the resolve kernel are not run
-    if (!rounds && writes && (writes->ends.size() > 1 || writes->flushing() || ro)) {
+    // is uploaded or zeroed again and the kernels up to the resolve kernel are not run (the descriptors get the pointers
+    // into the Write table again: the table itself is on the device already)
+    if (any_writes) {
+        // every stream's block (zs_core.h write_block_bytes), back to back and 8-byte aligned:
         // [ends: int64 x nw][blocks before each Write: int32 x nw][flush modes: u8 x nw]
-        const size_t nw = writes->ends.size();
-        if (!ensure(c, c->wr, 13 * nw + 64)) return false;
-        ZS_HIP(c, hipMemsetAsync(c->wr.p, 0, 13 * nw + 64, stream));
-        if (nw) ZS_HIP(c, hipMemcpyAsync(c->wr.p, writes->ends.data(), sizeof(int64_t) * nw, hipMemcpyHostToDevice, stream));
-        pl.sd[0].wr_end = (const int64_t *)c->wr.p;
-        if (writes->flushing() || ro) {
-            if (nw) ZS_HIP(c, hipMemcpyAsync((uint8_t *)c->wr.p + 12 * nw, writes->flush.data(), nw, hipMemcpyHostToDevice, stream));
-            pl.sd[0].wr_blk = (int32_t *)((uint8_t *)c->wr.p + 8 * nw);
-            pl.sd[0].wr_flush = (const uint8_t *)c->wr.p + 12 * nw;
+        std::vector<size_t> nws((size_t)n, 0), offs;
+        for (int i = 0; i < n; i++) {
+            const WriteSpec *wr = writes[i];
+            if (wr && (wr->ends.size() > 1 || wr->flushing() || ro)) nws[(size_t)i] = wr->ends.size();
         }
-        if (!pl.plan_wr_blk.empty())
-            ZS_HIP(c, hipMemcpyAsync((uint8_t *)c->wr.p + 8 * nw, pl.plan_wr_blk.data(), 4 * nw, hipMemcpyHostToDevice, stream));
-        ZS_HIP(c, hipStreamSynchronize(stream));  // `writes` is caller-owned pageable memory
+        const size_t wr_bytes = layout_write_blocks(nws, offs);
+        if (!ensure(c, c->wr, wr_bytes + 64)) return false;
+        std::vector<uint8_t> hw(rounds ? 0 : wr_bytes + 64, 0);
+        for (int i = 0; i < n; i++) {
+            const WriteSpec *wr = writes[i];
+            const size_t nw = nws[(size_t)i];
+            if (!wr || !(wr->ends.size() > 1 || wr->flushing() || ro)) continue;
+            uint8_t *blk = (uint8_t *)c->wr.p + offs[(size_t)i];
+            pl.sd[(size_t)i].wr_end = (const int64_t *)blk;
+            if (wr->flushing() || ro) {
+                pl.sd[(size_t)i].wr_blk = (int32_t *)(blk + 8 * nw);
+                pl.sd[(size_t)i].wr_flush = blk + 12 * nw;
+            }
+            if (rounds || !nw) continue;
+            memcpy(hw.data() + offs[(size_t)i], wr->ends.data(), sizeof(int64_t) * nw);
+            if (wr->flushing() || ro) memcpy(hw.data() + offs[(size_t)i] + 12 * nw, wr->flush.data(), nw);
+            if (!pl.plan_wr_blk.empty()) memcpy(hw.data() + offs[(size_t)i] + 8 * nw, pl.plan_wr_blk.data(), 4 * nw);  // (a flushing spec: one stream)
+        }
+        if (!rounds && wr_bytes) {
+            ZS_HIP(c, hipMemcpyAsync(c->wr.p, hw.data(), hw.size(), hipMemcpyHostToDevice, stream));
+            ZS_HIP(c, hipStreamSynchronize(stream));  // pageable source
+        }
     }
     if (!rounds && !pl.plan_blk.empty()) {
         ZS_HIP(c, hipMemcpyAsync(c->plan_blk.p, pl.plan_blk.data(), sizeof(BlockRec) * pl.plan_blk.size(), hipMemcpyHostToDevice, stream));
@@ -1072,7 +1110,7 @@ plan_again:
                 ZS_HIP(c, hipStreamSynchronize(c->aux));
                 ZS_HIP(c, hipStreamSynchronize(stream));
                 c->no_rounds_once = true;
-                return run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, force_lit);
+                return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, force_lit);
             }
             ZS_HIP(c, hipMemcpyAsync(c->fr_chunks.p, pl.fr_chunks.data(), nch * sizeof(FsChunk), hipMemcpyHostToDevice, stream));
             ZS_HIP(c, hipMemsetAsync(c->fr_counters.p, 0, 4 * ((size_t)max_rounds + 16), stream));
@@ -1123,7 +1161,7 @@ plan_again:
                 // workgroup per stream instead of failing the call)
                 ZS_HIP(c, hipStreamSynchronize(c->aux));
                 c->no_rounds_once = true;
-                return run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, force_lit);
+                return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, force_lit);
             }
             const FsMeta *mf = dev<FsMeta>(c->fr_meta) + (size_t)((r - 1) & 1) * nch;
             hipLaunchKernelGGL(zs_fast_commit_scan_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, mf, dev<int32_t>(c->fr_base));
@@ -1221,7 +1259,7 @@ plan_again:
             for (int i = 0; i < n; i++)
                 if (np[(size_t)i]) {
                     ZS_HIP(c, hipStreamSynchronize(c->aux));  // (the forked passes read the workspace that is about to be reused)
-                    return run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, 1, ro, false, force_lit);
+                    return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, 1, ro, false, force_lit);
                 }
         }
         ZS_HIP(c, hipMemsetAsync(c->run_fail.p, 0, 4 * (size_t)n + 64, stream));
@@ -1265,7 +1303,7 @@ plan_again:
                 }
                 const int mode = (force_seq == 0 && !getenv("ZS_NO_WHOLE_RUNS") && (getenv("ZS_WHOLE_RUNS") || t_engine < 0.7 * t_sweeps)) ? 2 : 1;
                 if (getenv("ZS_DEBUG")) fprintf(stderr, "zs: the runs did not verify: %s (engine %.1f ms, sweeps up to %.1f ms)\n", mode == 2 ? "one run per stream" : "the sweeps", t_engine * 1e3, t_sweeps * 1e3);
-                return run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, mode, ro, false, force_lit);
+                return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, mode, ro, false, force_lit);
             }
         hipLaunchKernelGGL(zs_fast_plan_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<FastRunOut>(c->run_outs), n);
         hipLaunchKernelGGL(zs_fast_stitch_kernel, dim3((unsigned)pl.w_runs.size()), dim3(256), 0, stream, d_sd, d_work + o_runs,
@@ -1320,13 +1358,14 @@ plan_again:
             fprintf(stderr, " ... %d hops, ends at %lld; position %lld is hop %d\n", hops, (long long)q, (long long)want, want_at);
         }
     }
-    if (getenv("ZS_DEBUG_FA") && writes && pl.sd[0].wr_blk) {  // the flush accounting's inputs: blocks flushed before each Write began
-        const size_t nw = writes->ends.size();
+    if (getenv("ZS_DEBUG_FA") && writes && writes[0] && pl.sd[0].wr_blk) {  // the flush accounting's inputs: blocks flushed before each Write began
+        const WriteSpec *wr = writes[0];
+        const size_t nw = wr->ends.size();
         std::vector<int32_t> wb(nw);
         (void)hipMemcpy(wb.data(), pl.sd[0].wr_blk, 4 * nw, hipMemcpyDeviceToHost);
         fprintf(stderr, "[zs] run of %lld bytes, %zu Writes, %d blocks, body ends at %d, resume %d; blocks before each Write:", (long long)in_len[0], nw, hst[0].nblocks,
                 pl.sd[0].body_end, pl.sd[0].resume);
-        for (size_t k = 0; k < nw && k < 24; k++) fprintf(stderr, " %d(end %lld, flush %d)", wb[k], (long long)writes->ends[k], writes->flush.empty() ? 0 : writes->flush[k]);
+        for (size_t k = 0; k < nw && k < 24; k++) fprintf(stderr, " %d(end %lld, flush %d)", wb[k], (long long)wr->ends[k], wr->flush.empty() ? 0 : wr->flush[k]);
         fprintf(stderr, "\n");
     }
     if (prof) {
@@ -1366,7 +1405,7 @@ plan_again:
                 return false;
             }
             c->lit_fallbacks++;
-            return run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, &fl);
+            return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, &fl);
         }
     }
     if (!ro && !rounds) {
@@ -1378,7 +1417,7 @@ plan_again:
             ZS_HIP(c, hipStreamSynchronize(c->aux));
             c->round_runs++;
             if (!run_cut_rounds()) return false;
-            return run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, true, force_lit);
+            return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, true, force_lit);
         }
     }
     if (ro) ro->end_bits = hst[0].end_bits;
@@ -1567,7 +1606,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->png_img, &c->png_seg, &c->png_ctr};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -1673,28 +1712,52 @@ int zs_deflate_batch_device(zs_ctx *c, int n, const void *const *in, const int64
     return rc;
 }
 
+int zs_deflate_writes_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, const int64_t *const *write_ends,
+                                   const int64_t *n_writes, void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level,
+                                   int strategy, int hash_variant, void *hip_stream) {
+    if (!write_ends) return zs_deflate_batch_device(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, hip_stream);
+    if (!check_args(c, n, in_len, level, strategy)) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    // every list is checked before any device work: a malformed one anywhere fails the call (zs_core.h write_list_ends)
+    std::vector<WriteSpec> specs((size_t)n);
+    std::vector<const WriteSpec *> ptrs((size_t)n, nullptr);
+    for (int i = 0; i < n; i++) {
+        if (!write_ends[i] || (n_writes && n_writes[i] <= 0)) continue;  // one Write
+        if (!n_writes || !write_list_ends(write_ends[i], n_writes[i], in_len[i], specs[(size_t)i].ends)) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        if (specs[(size_t)i].ends.empty()) continue;  // at most one distinct end
+        specs[(size_t)i].flush.assign(specs[(size_t)i].ends.size(), 0);
+        ptrs[(size_t)i] = &specs[(size_t)i];
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    int rc = ZS_OK;
+    for (int lo = 0; lo < n;) {  // sub-batches, as zs_deflate_batch_device
+        const int hi = batch_prefix_that_fits(c, n, in_len, out_cap, lo, 19);
+        if (!run_pipeline(c, hi - lo, in + lo, in_len + lo, out + lo, out_cap + lo, out_len + lo, status ? status + lo : nullptr, level, strategy,
+                          hash_variant, s, ptrs.data() + lo) && rc == ZS_OK)
+            rc = c->err == "buffer error" ? ZS_BUF_ERROR : ZS_STREAM_ERROR;
+        lo = hi;
+    }
+    return rc;
+}
+
 int zs_deflate_writes_device(zs_ctx *c, const void *in, int64_t in_len, const int64_t *write_ends, int64_t n_writes, void *out,
                              int64_t out_cap, int64_t *out_len, int level, int strategy, int hash_variant, void *hip_stream) {
     if (!check_args(c, 1, &in_len, level, strategy)) return ZS_STREAM_ERROR;
     if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
     WriteSpec ws;
-    int64_t prev = 0;
-    for (int64_t i = 0; i < n_writes; i++) {
-        if (write_ends[i] < prev || write_ends[i] > in_len) {
-            c->err = "stream error";
-            return ZS_STREAM_ERROR;
-        }
-        if (write_ends[i] > prev) ws.ends.push_back(write_ends[i]);  // an empty Write never reaches Deflate (ZlibOutputStream.cs:127-130)
-        prev = write_ends[i];
-    }
-    if (prev != in_len) {
+    if (!write_list_ends(write_ends, n_writes, in_len, ws.ends)) {
         c->err = "stream error";
         return ZS_STREAM_ERROR;
     }
     ws.flush.assign(ws.ends.size(), 0);
+    const WriteSpec *const one = &ws;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     int st = 0;
-    if (!run_pipeline(c, 1, &in, &in_len, &out, &out_cap, out_len, &st, level, strategy, hash_variant, s, ws.ends.size() > 1 ? &ws : nullptr))
+    if (!run_pipeline(c, 1, &in, &in_len, &out, &out_cap, out_len, &st, level, strategy, hash_variant, s, ws.ends.size() > 1 ? &one : nullptr))
         return c->err == "buffer error" ? ZS_BUF_ERROR : ZS_STREAM_ERROR;
     return ZS_OK;
 }
@@ -2267,6 +2330,118 @@ extern "C" int zs_png_filter_device(zs_ctx *c, const void *pixels, int64_t row_b
                        (uint8_t *)out);
     if (hipGetLastError() != hipSuccess) return ZS_STREAM_ERROR;
     return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
+}
+
+// ... for a batch: one launch over the flat list of all images' rows (zs_kernels.hip zs_png_filter_batch_kernel)
+namespace {
+bool png_filter_args(zs_ctx *c, int n, const void *const *pixels, const int64_t *row_bytes, const int64_t *height, const int *bpp, const int *filter,
+                     void *const *out, int64_t *total_rows) {
+    *total_rows = 0;
+    for (int i = 0; i < n; i++) {
+        if (!pixels[i] || (out && !out[i]) || row_bytes[i] <= 0 || height[i] <= 0 || height[i] > 0x7FFFFFFF || bpp[i] < 1 || bpp[i] > 8 || filter[i] < 0 ||
+            filter[i] > 5) {
+            c->err = "stream error";
+            return false;
+        }
+        *total_rows += height[i];
+    }
+    if (*total_rows > 0x7FFFFFFF) {  // (the grid is the row list)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return false;
+    }
+    return true;
+}
+
+constexpr int64_t kPngFilterSlice = 1 << 23;  // rows a launch, chosen: 2^31 threads, half of what a grid may hold
+
+// the launch is left in flight on `s`; the descriptors have left the pinned staging buffer when this returns
+bool run_png_filter_batch(zs_ctx *c, int n, const void *const *pixels, const int64_t *row_bytes, const int64_t *height, const int *bpp, const int *filter,
+                          void *const *out, int64_t total_rows, hipStream_t s) {
+    const size_t b_img = sizeof(PngFiltImg) * (size_t)n, b_off = sizeof(int32_t) * ((size_t)n + 1);
+    if (!ensure(c, c->png_fimg, b_img + b_off) || !ensure_pinned(c, b_img + b_off)) return false;
+    PngFiltImg *hi = (PngFiltImg *)c->pinned;
+    int32_t *ho = (int32_t *)((uint8_t *)c->pinned + b_img);
+    int64_t at = 0;
+    for (int i = 0; i < n; i++) {
+        hi[i] = PngFiltImg{(const uint8_t *)pixels[i], (uint8_t *)out[i], row_bytes[i], bpp[i], filter[i]};
+        ho[i] = (int32_t)at;
+        at += height[i];
+    }
+    ho[n] = (int32_t)at;
+    ZS_HIP(c, hipMemcpyAsync(c->png_fimg.p, c->pinned, b_img + b_off, hipMemcpyHostToDevice, s));
+    ZS_HIP(c, hipStreamSynchronize(s));  // (the staging buffer is the next call's too)
+    const int stage = getenv("ZS_PNG_NO_STAGE") ? 0 : 1;
+    // (a grid holds fewer than 2^32 threads: a call of more than kPngFilterSlice rows is several launches, each with its first row)
+    for (int64_t row0 = 0; row0 < total_rows; row0 += kPngFilterSlice) {
+        const int64_t rows = std::min<int64_t>(kPngFilterSlice, total_rows - row0);
+        hipLaunchKernelGGL(zs_png_filter_batch_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const PngFiltImg *)c->png_fimg.p,
+                           (const int32_t *)((const uint8_t *)c->png_fimg.p + b_img), n, stage, row0);
+        ZS_HIP(c, hipGetLastError());
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int zs_png_filter_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *row_bytes, const int64_t *height, const int *bpp,
+                                          const int *filter, void *const *out, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!pixels || !row_bytes || !height || !bpp || !filter || !out) return ZS_STREAM_ERROR;
+    int64_t total_rows = 0;
+    if (!png_filter_args(c, n, pixels, row_bytes, height, bpp, filter, out, &total_rows)) return ZS_STREAM_ERROR;
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (!run_png_filter_batch(c, n, pixels, row_bytes, height, bpp, filter, out, total_rows, s)) return ZS_STREAM_ERROR;
+    return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
+}
+
+// Pixels -> IDAT payloads: the batch filter into the context's scratch buffer, then every image's rows as the Writes of its
+// own stream (rows_per_write rows a Write; 0: one Write).  Nothing leaves the device in between.
+extern "C" int zs_png_idat_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *row_bytes, const int64_t *height, const int *bpp,
+                                        const int *filter, int64_t rows_per_write, void *const *out, const int64_t *out_cap, int64_t *out_len,
+                                        int *status, int level, int strategy, int hash_variant, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!pixels || !row_bytes || !height || !bpp || !filter || !out || !out_cap || !out_len || rows_per_write < 0) return ZS_STREAM_ERROR;
+    for (int i = 0; i < n; i++) {
+        out_len[i] = 0;
+        if (status) status[i] = ZS_STREAM_ERROR;
+    }
+    int64_t total_rows = 0;
+    if (!png_filter_args(c, n, pixels, row_bytes, height, bpp, filter, nullptr, &total_rows)) return ZS_STREAM_ERROR;
+    std::vector<int64_t> len((size_t)n);
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (row_bytes[i] > 0x7FFFFFFF || height[i] * (row_bytes[i] + 1) > 0x7FFFFFFF - 1024) {  // (a stream's input is indexed with 32 bits)
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        len[(size_t)i] = height[i] * (row_bytes[i] + 1);
+        total += ((size_t)len[(size_t)i] + 255) & ~(size_t)255;
+    }
+    if (!check_args(c, n, len.data(), level, strategy)) return ZS_STREAM_ERROR;
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (!ensure(c, c->png_scratch, total + 256)) return ZS_MEM_ERROR;
+    std::vector<void *> rows((size_t)n);
+    std::vector<const void *> rows_in((size_t)n);
+    std::vector<std::vector<int64_t>> ends((size_t)n);
+    std::vector<const int64_t *> ends_p((size_t)n, nullptr);
+    std::vector<int64_t> n_ends((size_t)n, 0);
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        rows[(size_t)i] = (uint8_t *)c->png_scratch.p + at;
+        rows_in[(size_t)i] = rows[(size_t)i];
+        at += ((size_t)len[(size_t)i] + 255) & ~(size_t)255;
+        if (rows_per_write > 0 && rows_per_write < height[i]) {
+            for (int64_t r = rows_per_write; r < height[i]; r += rows_per_write) ends[(size_t)i].push_back(r * (row_bytes[i] + 1));
+            ends[(size_t)i].push_back(len[(size_t)i]);
+            ends_p[(size_t)i] = ends[(size_t)i].data(), n_ends[(size_t)i] = (int64_t)ends[(size_t)i].size();
+        }
+    }
+    if (!run_png_filter_batch(c, n, pixels, row_bytes, height, bpp, filter, rows.data(), total_rows, s)) return ZS_STREAM_ERROR;
+    return zs_deflate_writes_batch_device(c, n, rows_in.data(), len.data(), ends_p.data(), n_ends.data(), out, out_cap, out_len, status, level, strategy,
+                                          hash_variant, hip_stream);
 }
 
 // ------------------------------------------------------------------ PNG scanline reconstruction (KU, zs_png.hip): inflate -> pixels in HBM

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "zs_device.h"
+#include "zs_png.h"
 
 namespace zs {
 
@@ -3749,6 +3750,119 @@ __global__ __launch_bounds__(256) void zs_png_filter_kernel(const uint8_t *pix, 
     for (int64_t i = threadIdx.x; i < row_bytes; i += 256) {
         const int x = cur[i], a = i >= bpp ? cur[i - bpp] : 0, b = has_up ? up[i] : 0, c = (has_up && i >= bpp) ? up[i - bpp] : 0;
         o[1 + i] = png_apply(f, x, a, b, c);
+    }
+}
+
+// ---- KP for a batch: one launch over the rows of all images ----
+// The grid is the flat row list; a workgroup finds its image by the uniform search of zs_png.h (png_row_image) and filters its
+// row with that image's row_bytes, bpp and filter -- png_apply and the sums of zs_png_filter_kernel, so the bytes are those of
+// n single launches (integer sums do not depend on the order they are added in; ties go to the first filter as there).
+// A row of up to kPngStageRow bytes and the row above it are staged in LDS with 16-byte loads: every byte is then read from
+// LDS (x, a, b, c, twice under the adaptive filter) instead of byte by byte from memory.  A row keeps its misalignment
+// (row byte i of a row at global address g lies at lds[16 + (g & 15) + i]), so the 16-byte loads are aligned on both sides,
+// and the 8 bytes in front of it are zero: `a` and `c` of the first pixel need no branch.  Longer rows take the loads of
+// the single-image kernel.
+struct PngFiltImg {
+    const uint8_t *pix;
+    uint8_t *out;
+    int64_t row_bytes;
+    int32_t bpp, filter;
+};
+constexpr int kPngStageRow = 16384;
+constexpr int kPngStageLds = kPngStageRow + 48;  // 16 in front (the zero bytes), up to 15 of misalignment, whole 16-byte stores
+
+// returns where row byte 0 lies in `lds`
+__device__ __forceinline__ int png_stage_row(uint8_t *lds, const uint8_t *g, int nbytes, int tid) {
+    const int mis = (int)((uintptr_t)g & 15), at0 = 16 + mis;
+    const int head = nbytes < ((16 - mis) & 15) ? nbytes : ((16 - mis) & 15);  // bytes in front of the first aligned 16
+    const int nvec = (nbytes - head) >> 4;
+    const gcbytes gg = as_global(g);
+    if (tid < 8) lds[at0 - 8 + tid] = 0;
+    if (tid < head) lds[at0 + tid] = gg[tid];
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const __attribute__((address_space(1))) u32x4 *gv = (const __attribute__((address_space(1))) u32x4 *)(uintptr_t)(g + head);  // (global, as the byte loads)
+    u32x4 *lv = (u32x4 *)(lds + at0 + head);
+    for (int k = tid; k < nvec; k += 256) lv[k] = gv[k];
+    for (int k = head + 16 * nvec + tid; k < nbytes; k += 256) lds[at0 + k] = gg[k];
+    return at0;
+}
+
+// One row by the 256 threads of a workgroup; get(i, x, a, b, c) hands out byte i and its three neighbours.
+template <class Idx, class Get>
+__device__ __forceinline__ void png_filter_row(int filter, Idx rb, uint8_t *o, int tid, uint32_t (*s_sum)[5], Get get) {
+    int f = filter;
+    if (filter == 5) {
+        uint32_t acc[5] = {0, 0, 0, 0, 0};
+        for (Idx i = tid; i < rb; i += 256) {
+            int x, a, b, c;
+            get(i, x, a, b, c);
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                const int v = (int8_t)png_apply(k, x, a, b, c);  // the sum is over the bytes read as signed values
+                acc[k] += (uint32_t)(v < 0 ? -v : v);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            for (int off = 32; off > 0; off >>= 1) acc[k] += (uint32_t)__shfl_xor((int)acc[k], off);
+            if ((tid & 63) == 0) s_sum[tid >> 6][k] = acc[k];
+        }
+        __syncthreads();
+        int best = 0;
+        uint32_t best_sum = s_sum[0][0] + s_sum[1][0] + s_sum[2][0] + s_sum[3][0];
+        for (int k = 1; k < 5; k++) {
+            const uint32_t t = s_sum[0][k] + s_sum[1][k] + s_sum[2][k] + s_sum[3][k];
+            if (t < best_sum) best = k, best_sum = t;
+        }
+        f = best;
+    }
+    if (tid == 0) o[0] = (uint8_t)f;
+    auto one = [&](Idx i) -> uint32_t {
+        int x, a, b, c;
+        get(i, x, a, b, c);
+        return png_apply(f, x, a, b, c);
+    };
+    // the filtered bytes begin one past the type byte: single bytes up to the first aligned dword, dwords, the last bytes
+    const int lead = (int)((4 - ((uintptr_t)(o + 1) & 3)) & 3);
+    const Idx head = rb < (Idx)lead ? rb : (Idx)lead;
+    const Idx nd = (rb - head) >> 2;
+    if (tid < head) o[1 + tid] = (uint8_t)one((Idx)tid);
+    for (Idx j = tid; j < nd; j += 256) {
+        const Idx i = head + 4 * j;
+        const uint32_t w = one(i) | (one(i + 1) << 8) | (one(i + 2) << 16) | (one(i + 3) << 24);
+        *(uint32_t *)(o + 1 + i) = w;
+    }
+    for (Idx i = head + 4 * nd + tid; i < rb; i += 256) o[1 + i] = (uint8_t)one(i);
+}
+
+// row_off: n + 1 offsets into the flat row list (zs_png.h); stage: 0 = every row by the loads of the single-image kernel;
+// row0: the flat row of workgroup 0
+__global__ __launch_bounds__(256) void zs_png_filter_batch_kernel(const PngFiltImg *imgs, const int32_t *row_off, int n, int stage, int64_t row0) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_cur[kPngStageLds], s_up[kPngStageLds];
+    __shared__ uint32_t s_sum[4][5];
+    const int tid = (int)threadIdx.x;
+    const int64_t r = row0 + blockIdx.x;  // (row0: the first row of this launch)
+    const int img = png_row_image(row_off, n, r);
+    const PngFiltImg im = imgs[img];
+    const int64_t y = r - row_off[img], rb = im.row_bytes;
+    const int bpp = im.bpp;
+    const bool has_up = y > 0;
+    const uint8_t *cur = im.pix + y * rb, *up = has_up ? cur - rb : cur;
+    uint8_t *o = im.out + y * (rb + 1);
+    if (stage && rb <= kPngStageRow) {
+        const uint8_t *C = s_cur + png_stage_row(s_cur, cur, (int)rb, tid), *U = s_up + 16;
+        if (has_up) U = s_up + png_stage_row(s_up, up, (int)rb, tid);
+        else
+            for (int k = tid; k < ((int)rb + 31) >> 4; k += 256) ((uint4 *)s_up)[k] = make_uint4(0, 0, 0, 0);  // no row above: zeros
+        __syncthreads();
+        png_filter_row<int>(im.filter, (int)rb, o, tid, s_sum, [&](int i, int &x, int &a, int &b, int &c) {
+            x = C[i], a = C[i - bpp], b = U[i], c = U[i - bpp];
+        });
+    } else {
+        const gcbytes gc = as_global(cur), gu = as_global(up);
+        png_filter_row<int64_t>(im.filter, rb, o, tid, s_sum, [&](int64_t i, int &x, int &a, int &b, int &c) {
+            x = gc[i], a = i >= bpp ? gc[i - bpp] : 0, b = has_up ? gu[i] : 0, c = (has_up && i >= bpp) ? gu[i - bpp] : 0;
+        });
     }
 }
 

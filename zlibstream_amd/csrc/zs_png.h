@@ -78,4 +78,19 @@ ZS_HD constexpr int png_lds_bytes(int max_bpp, int waves) { return waves * (kPng
 // of a CU's 160 KiB
 ZS_HD constexpr int png_waves(int max_bpp) { return max_bpp <= 4 ? 4 : 2; }
 
+// ---- filtering a batch (zs_png_filter_batch_kernel, KP) ----
+// The grid is the flat list of all images' rows.  row_off[i] = rows of the images before i, row_off[n] = all rows; every
+// image has at least one row, so the offsets increase strictly.  The image of flat row r is the last i with
+// row_off[i] <= r (the same for every thread of a workgroup: a uniform search, no divergence).
+template <class Off>
+ZS_HD int png_row_image(const Off &row_off, int n, int64_t r) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int64_t)row_off[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
 }  // namespace zs

@@ -435,7 +435,8 @@ int zs_deflate(zs_deflate_stream *s, const uint8_t *next_in, int32_t *avail_in, 
             int64_t olen = 0;
             int st = 0;
             const auto t0 = std::chrono::steady_clock::now();
-            if (!run_pipeline(c, 1, &din, &n, &dout, &cap, &olen, &st, s->level, s->strategy, s->hash_variant, c->stream, &ws, !last, ro)) return false;
+            const WriteSpec *const wsp = &ws;
+            if (!run_pipeline(c, 1, &din, &n, &dout, &cap, &olen, &st, s->level, s->strategy, s->hash_variant, c->stream, &wsp, !last, ro)) return false;
             if (env_debug())
                 fprintf(stderr, "[zs] stream run: %lld bytes, %s, %.2f ms, %lld bytes out\n", (long long)n, !ro ? "whole stream" : ro->resume ? "resumed on the bulk path" : ro->stop_abs >= 0 ? "warm-up" : ro->cont ? "continued" : "first run",
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), (long long)olen);
