@@ -84,6 +84,15 @@ namespace SixLabors.ZlibStream
         [DllImport(Lib)] public static extern int zs_png_idat_batch_device(IntPtr ctx, int n, IntPtr* pixels, long* rowBytes, long* height, int* bpp,
                                                                            int* filter, long rowsPerWrite, IntPtr* output, long* outCap, long* outLen,
                                                                            int* status, int level, int strategy, int hashVariant, IntPtr hipStream);
+        // ---- the decoder for a batch: IDAT payloads -> raw scanline pixels in HBM, interlaced (Adam7) or not; the interleave alone; and
+        //      the geometry both go by (host code: the inflated size, the seven passes' row bytes and rows)
+        [DllImport(Lib)] public static extern int zs_png_decode_batch_device(IntPtr ctx, int n, IntPtr* idat, long* idatLen, long* width, long* height,
+                                                                             int* bitsPerPixel, int* interlace, IntPtr* output, int* status,
+                                                                             IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_adam7_merge_batch_device(IntPtr ctx, int n, IntPtr* passes, long* width, long* height,
+                                                                                  int* bitsPerPixel, IntPtr* output, IntPtr hipStream);
+        [DllImport(Lib)] public static extern long zs_png_idat_layout(long width, long height, int bitsPerPixel, int interlace, long* rowBytes7,
+                                                                      long* rows7);
         // bytes fed behind a stream's trailer before its end was seen (the engine looks for the end now and then)
         [DllImport(Lib)] public static extern long zs_inflate_surplus(IntPtr s, IntPtr* p);
     }

@@ -208,6 +208,43 @@ ZS_API int zs_png_unfilter_batch_device(zs_ctx *ctx, int n, const void *const *i
 ZS_API int zs_png_unfilter_device(zs_ctx *ctx, const void *in, int64_t row_bytes, int64_t height, int bpp, void *out,
                                   void *hip_stream);
 
+/* Inflated size of a PNG's IDAT payload and, for interlace = 1, the seven passes' row_bytes[7] / rows[7] (0 / 0 for an
+ * absent pass; interlace = 0: entry 0 is the image, the rest 0).  -1 for bad arguments.  Pure host code, no GPU needed.
+ * bits_per_pixel: 1, 2, 4, 8, 16, 24, 32, 48 or 64 (bit depth times channels); width and height 1 .. 2^31 - 1.  A pass of
+ * Adam7 (PNG specification 8.2) that has no pixels is absent from the stream: no rows, no filter bytes.  Either array may
+ * be NULL. */
+ZS_API int64_t zs_png_idat_layout(int64_t width, int64_t height, int bits_per_pixel, int interlace, int64_t *row_bytes7,
+                                  int64_t *rows7);
+
+/* The Adam7 interleave on the device, n images a call.
+ * passes[i]: image i's reconstructed passes back to back in pass order (no filter bytes; absent passes absent), device pointer;
+ * out[i]: height[i] rows of ceil(width[i] * bits_per_pixel[i] / 8) bytes, device pointer of any alignment, must not overlap
+ * passes[i].  At 1, 2 and 4 bits the unused low bits of a row's last byte are written as zero.  Ordered on hip_stream
+ * (NULL: the context's, and the call returns when the pixels are written), like zs_png_filter_batch_device: the call waits
+ * for the stream once, for its descriptors' upload.  ZS_STREAM_ERROR for bad arguments (as for zs_png_decode_batch_device),
+ * ZS_MEM_ERROR when the descriptors do not fit. */
+ZS_API int zs_png_adam7_merge_batch_device(zs_ctx *ctx, int n, const void *const *passes, const int64_t *width,
+                                           const int64_t *height, const int *bits_per_pixel, void *const *out, void *hip_stream);
+
+/* IDAT payloads to pixels, n images a call, nothing leaving HBM, interlaced or not: zs_inflate_batch_device into a buffer
+ * the context owns, zs_png_unfilter_batch_device's kernels over every image -- or every present Adam7 pass -- whose stream
+ * decoded to exactly the length zs_png_idat_layout gives, and the interleave of zs_png_adam7_merge_batch_device for the
+ * interlaced ones.
+ * idat[i] / idat_len[i]: image i's IDAT chunks' data concatenated = one zlib stream (device pointer); out[i]: height rows of
+ * ceil(width * bits_per_pixel / 8) bytes of raw PNG scanline data (device pointer, no bit-depth expansion, no palette).
+ * status[i] (may be NULL): ZS_OK or ZS_DATA_ERROR; a failing image leaves the others complete, its own out[i] is
+ * unspecified.  zs_ctx_last_error names the first failing image: inflate's message ("incorrect data check", ...; where
+ * several streams fail in inflate, the message inflate left for the call), "IDAT holds ... the image needs ..." for a
+ * stream of the wrong length, or the pass and row whose filter type is above 4.
+ * Returns ZS_OK, ZS_DATA_ERROR, ZS_MEM_ERROR (the workspace does not fit) or, before any device work and with status
+ * untouched, ZS_STREAM_ERROR: null context, n < 0, null arrays or pointers, width or height below 1, a bits_per_pixel
+ * outside the set, interlace other than 0 or 1, a payload above 2 GiB - 1 KiB, more than 2^31 - 1 rows (pass rows counted)
+ * in one call.  Work is ordered on hip_stream (NULL: the context's); the call waits for it twice (inflate's results decide
+ * what is reconstructed) and returns when the pixels are written.  The context keeps both buffers until zs_ctx_destroy. */
+ZS_API int zs_png_decode_batch_device(zs_ctx *ctx, int n, const void *const *idat, const int64_t *idat_len,
+                                      const int64_t *width, const int64_t *height, const int *bits_per_pixel,
+                                      const int *interlace, void *const *out, int *status, void *hip_stream);
+
 /* Stage timing of the last *_batch_device call, measured with hipEvents on
  * the stream the kernels ran on.  Enable before the call. */
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took

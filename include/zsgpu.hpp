@@ -66,6 +66,40 @@ inline void PngUnfilterDevice(const void *filtered, int64_t rowBytes, int64_t he
     if (rc != ZS_OK) throw ZlibStreamException(rc == ZS_DATA_ERROR ? std::string("png: ") + zs_ctx_last_error(c) : std::string("png: bad arguments"));
 }
 
+// The whole decode path for images that stay on the GPU, n a call: idat[i] (device pointer, idatLen[i] bytes: the image's IDAT
+// data concatenated, one zlib stream) -> pixels[i] (device pointer, height[i] rows of ceil(width[i] * bitsPerPixel[i] / 8)
+// bytes of raw scanline data), interlaced (Adam7) or not.  Returns a status per image: ZS_OK, or ZS_DATA_ERROR for an image
+// that does not decode (zs_ctx_last_error names the first one; the others are complete).
+inline std::vector<int> PngDecodeBatchDevice(const std::vector<const void *> &idat, const std::vector<int64_t> &idatLen, const std::vector<int64_t> &width,
+                                             const std::vector<int64_t> &height, const std::vector<int> &bitsPerPixel, const std::vector<int> &interlace,
+                                             const std::vector<void *> &pixels, zs_ctx *ctx = nullptr, void *hipStream = nullptr) {
+    const size_t n = idat.size();
+    if (idatLen.size() != n || width.size() != n || height.size() != n || bitsPerPixel.size() != n || interlace.size() != n || pixels.size() != n)
+        throw ZlibStreamException("png: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    std::vector<int> status(n, 0);
+    const int rc = zs_png_decode_batch_device(c, (int)n, idat.data(), idatLen.data(), width.data(), height.data(), bitsPerPixel.data(), interlace.data(),
+                                              pixels.data(), status.data(), hipStream);
+    if (rc != ZS_OK && rc != ZS_DATA_ERROR) throw ZlibStreamException(rc == ZS_MEM_ERROR ? std::string("png: out of device memory") : std::string("png: bad arguments"));
+    return status;
+}
+// ... its last step alone, for a caller that reconstructs the passes itself: passes[i] (device pointer, the seven passes back
+// to back without filter bytes, absent ones absent; zs_png_idat_layout gives their sizes) -> pixels[i]
+inline void PngAdam7MergeBatchDevice(const std::vector<const void *> &passes, const std::vector<int64_t> &width, const std::vector<int64_t> &height,
+                                     const std::vector<int> &bitsPerPixel, const std::vector<void *> &pixels, zs_ctx *ctx = nullptr,
+                                     void *hipStream = nullptr) {
+    const size_t n = passes.size();
+    if (width.size() != n || height.size() != n || bitsPerPixel.size() != n || pixels.size() != n)
+        throw ZlibStreamException("png: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    if (zs_png_adam7_merge_batch_device(c, (int)n, passes.data(), width.data(), height.data(), bitsPerPixel.data(), pixels.data(), hipStream) != ZS_OK)
+        throw ZlibStreamException("png: bad arguments");
+}
+// ... and the geometry both go by (host code): the inflated size of an image's IDAT payload, -1 for bad arguments
+inline int64_t PngIdatLayout(int64_t width, int64_t height, int bitsPerPixel, bool interlace, int64_t rowBytes[7] = nullptr, int64_t rows[7] = nullptr) {
+    return zs_png_idat_layout(width, height, bitsPerPixel, interlace ? 1 : 0, rowBytes, rows);
+}
+
 // The encode half for images that stay on the GPU, n a call: pixels[i] (device pointer, height[i] rows of rowBytes[i] bytes)
 // -> the zlib stream of image i's IDAT payload in out[i] (device pointer, outCap[i] bytes), rows filtered with filter[i]
 // (0-4, 5 adaptive) and written rowsPerWrite rows a Write, as a scanline encoder writes to ZlibOutputStream (1; 0: one Write

@@ -16,6 +16,7 @@ SYMBOLS = [
     "zs_device_count", "zs_partition", "zs_deflate_batch_multi", "zs_inflate_batch_multi", "zs_png_filter_device", "zs_deflate_writes_device", "zs_deflate_batch_multi_device", "zs_inflate_batch_multi_device",
     "zs_png_unfilter_batch_device", "zs_png_unfilter_device",
     "zs_deflate_writes_batch_device", "zs_png_filter_batch_device", "zs_png_idat_batch_device",
+    "zs_png_idat_layout", "zs_png_adam7_merge_batch_device", "zs_png_decode_batch_device",
 ]
 
 _lib = None
@@ -120,5 +121,12 @@ def lib():
         L.zs_png_filter_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), P(vp), vp]
         L.zs_png_idat_batch_device.restype = i32
         L.zs_png_idat_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), i64, P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
+    if hasattr(L, "zs_png_decode_batch_device"):  # (an older build selected with ZS_LIB for an A/B run lacks the decoder)
+        L.zs_png_idat_layout.restype = i64
+        L.zs_png_idat_layout.argtypes = [i64, i64, i32, i32, P(i64), P(i64)]
+        L.zs_png_adam7_merge_batch_device.restype = i32
+        L.zs_png_adam7_merge_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(vp), vp]
+        L.zs_png_decode_batch_device.restype = i32
+        L.zs_png_decode_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i64), P(i32), P(i32), P(vp), P(i32), vp]
     _lib = L
     return L

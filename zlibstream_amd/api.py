@@ -441,6 +441,76 @@ def png_unfilter_batch_device(engine, in_ptrs, row_bytes, heights, bpps, out_ptr
     return list(status)
 
 
+PNG_BITS_PER_PIXEL = (1, 2, 4, 8, 16, 24, 32, 48, 64)
+
+
+def png_idat_layout(width, height, bits_per_pixel, interlace):
+    """zs_png_idat_layout (host code, no GPU): (inflated size of the IDAT payload, row_bytes[7], rows[7]) -- for an interlaced
+    image the seven Adam7 passes, 0 / 0 for an absent one; otherwise entry 0 is the image.  ValueError for bad arguments."""
+    rb, rows = (ctypes.c_int64 * 7)(), (ctypes.c_int64 * 7)()
+    width, height, bits_per_pixel, interlace = int(width), int(height), int(bits_per_pixel), int(interlace)
+    ok = 1 <= width <= 0x7FFFFFFF and 1 <= height <= 0x7FFFFFFF and bits_per_pixel in PNG_BITS_PER_PIXEL and interlace in (0, 1)
+    total = _native.lib().zs_png_idat_layout(width, height, bits_per_pixel, interlace, rb, rows) if ok else -1
+    if total < 0:
+        raise ValueError("png_idat_layout: 1 <= width, height <= 2^31 - 1, bits_per_pixel in %r and interlace 0 or 1 are required" % (PNG_BITS_PER_PIXEL,))
+    return int(total), list(rb), list(rows)
+
+
+def _png_image_check(name, ptrs, widths, heights, bits, interlace, out_ptrs):
+    """-> the rows the call works on, pass rows counted"""
+    n = len(ptrs)
+    if not (len(widths) == len(heights) == len(bits) == len(interlace) == len(out_ptrs) == n):
+        raise ValueError(name + ": the argument lists differ in length")
+    total_rows = 0
+    for p, w, h, b, il, o in zip(ptrs, widths, heights, bits, interlace, out_ptrs):
+        if not p or not o or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF or int(b) not in PNG_BITS_PER_PIXEL or int(il) not in (0, 1):
+            raise ValueError(name + ": 1 <= width, height <= 2^31 - 1, bits_per_pixel in %r, interlace 0 or 1 and non-null device pointers "
+                             "are required" % (PNG_BITS_PER_PIXEL,))
+        total_rows += sum(png_idat_layout(int(w), int(h), int(b), 1)[2]) if int(il) else int(h)
+    if total_rows > 0x7FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 rows in one call")
+    return n
+
+
+def png_adam7_merge_batch_device(engine, pass_ptrs, widths, heights, bits_per_pixel, out_ptrs, stream=None):
+    """The Adam7 interleave of many device-resident images in one launch (zs_png_adam7_merge_batch_device): pass_ptrs[i] holds
+    image i's reconstructed passes back to back (png_idat_layout gives their sizes; no filter bytes), out_ptrs[i] receives
+    heights[i] rows of ceil(widths[i] * bits_per_pixel[i] / 8) bytes."""
+    n = _png_image_check("png_adam7_merge_batch_device", pass_ptrs, widths, heights, bits_per_pixel, [0] * len(pass_ptrs), out_ptrs)
+    if n == 0:
+        return
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    rc = _native.lib().zs_png_adam7_merge_batch_device(engine.handle, n, VP(*[int(p) for p in pass_ptrs]), I64(*[int(x) for x in widths]),
+                                                       I64(*[int(x) for x in heights]), I32(*[int(x) for x in bits_per_pixel]),
+                                                       VP(*[int(p) for p in out_ptrs]), ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_adam7_merge_batch_device failed (%d): %s" % (rc, engine.last_error()))
+
+
+def png_decode_batch_device(engine, idat_ptrs, idat_lens, widths, heights, bits_per_pixel, interlace, out_ptrs, stream=None):
+    """IDAT payloads -> raw scanline pixels for many device-resident PNG images in one call (zs_png_decode_batch_device):
+    inflate, reconstruction and, for interlace[i] = 1, the Adam7 interleave, nothing leaving the device.  idat_ptrs[i] /
+    idat_lens[i]: the image's IDAT data concatenated (one zlib stream).  Returns a status per image: 0, or -3
+    (ZS_DATA_ERROR) for an image whose stream does not inflate, has the wrong length or holds a filter type above 4
+    (engine.last_error() names the first such image; the others are decoded all the same)."""
+    if len(idat_lens) != len(idat_ptrs):
+        raise ValueError("png_decode_batch_device: the argument lists differ in length")
+    n = _png_image_check("png_decode_batch_device", idat_ptrs, widths, heights, bits_per_pixel, interlace, out_ptrs)
+    if any(not 0 <= int(x) <= 0x7FFFFFFF - 1024 for x in idat_lens):
+        raise ValueError("png_decode_batch_device: a stream's length is negative or above 2 GiB - 1 KiB")
+    if n == 0:
+        return []
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    status = I32()
+    rc = _native.lib().zs_png_decode_batch_device(engine.handle, n, VP(*[int(p) for p in idat_ptrs]), I64(*[int(x) for x in idat_lens]),
+                                                  I64(*[int(x) for x in widths]), I64(*[int(x) for x in heights]),
+                                                  I32(*[int(x) for x in bits_per_pixel]), I32(*[int(x) for x in interlace]),
+                                                  VP(*[int(p) for p in out_ptrs]), status, ctypes.c_void_p(stream or 0))
+    if rc not in (0, -3):
+        raise ValueError("zs_png_decode_batch_device failed (%d): %s" % (rc, engine.last_error()))
+    return list(status)
+
+
 _default_engine = None
 
 

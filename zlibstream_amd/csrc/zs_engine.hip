@@ -70,7 +70,7 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, png_img, png_seg, png_ctr, png_fimg, png_scratch;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes;
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1606,7 +1606,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -2448,14 +2448,19 @@ extern "C" int zs_png_idat_batch_device(zs_ctx *c, int n, const void *const *pix
 namespace {
 constexpr int kPngGrid = 1024;  // workgroups that loop over the segments: four per CU where the tiles allow it
 
-bool run_png_unfilter(zs_ctx *c, int n, const void *const *in, const int64_t *row_bytes, const int64_t *height, const int *bpp, void *const *out,
-                      int64_t total_rows, int max_bpp, int *st, hipStream_t s, bool *no_memory) {
+// Enqueue: the descriptors' upload, the scan, KU and the counters' way back to the staging buffer, all left in flight on `s`.
+// pinned_extra: bytes of the staging buffer the caller wants for itself behind this call's share, at *pinned_extra_at (the
+// buffer is sized once, here: growing it would move it under the copies in flight).
+bool png_unfilter_enqueue(zs_ctx *c, int n, const void *const *in, const int64_t *row_bytes, const int64_t *height, const int *bpp, void *const *out,
+                          int64_t total_rows, int max_bpp, hipStream_t s, bool *no_memory, size_t pinned_extra = 0, size_t *pinned_extra_at = nullptr) {
     const size_t b_img = sizeof(PngImg) * (size_t)n, b_ctr = sizeof(int32_t) * ((size_t)n + 1);
+    const size_t b_own = (std::max(b_img, b_ctr) + 255) & ~(size_t)255;
     if (!ensure(c, c->png_img, b_img) || !ensure(c, c->png_seg, sizeof(PngSeg) * (size_t)total_rows) || !ensure(c, c->png_ctr, b_ctr) ||
-        !ensure_pinned(c, std::max(b_img, b_ctr))) {
+        !ensure_pinned(c, pinned_extra ? b_own + pinned_extra : std::max(b_img, b_ctr))) {
         *no_memory = true;
         return false;
     }
+    if (pinned_extra_at) *pinned_extra_at = b_own;
     PngImg *hi = (PngImg *)c->pinned;
     for (int i = 0; i < n; i++) hi[i] = PngImg{(const uint8_t *)in[i], (uint8_t *)out[i], row_bytes[i], (int32_t)height[i], bpp[i]};
     ZS_HIP(c, hipMemcpyAsync(c->png_img.p, c->pinned, b_img, hipMemcpyHostToDevice, s));
@@ -2468,12 +2473,18 @@ bool run_png_unfilter(zs_ctx *c, int n, const void *const *in, const int64_t *ro
                        (size_t)png_lds_bytes(max_bpp, waves), s, (const PngImg *)c->png_img.p, (const PngSeg *)c->png_seg.p, (const int32_t *)c->png_ctr.p, tiles);
     ZS_HIP(c, hipGetLastError());
     ZS_HIP(c, hipMemcpyAsync(c->pinned, c->png_ctr.p, b_ctr, hipMemcpyDeviceToHost, s));  // (the descriptors' upload is through by then: same stream)
-    ZS_HIP(c, hipStreamSynchronize(s));
+    return true;
+}
+
+// Collect, once `s` has been waited for: the statuses, the first bad row of every image (bad_row, may be null;
+// kPngNoBadRow: none) and the first failing image's message.
+bool png_unfilter_collect(zs_ctx *c, int n, int *st, int32_t *bad_row = nullptr) {
     const int32_t *hc = (const int32_t *)c->pinned;
     c->png_segments = hc[0];
     bool ok = true;
     for (int i = n - 1; i >= 0; i--) {
         st[i] = hc[1 + i] == kPngNoBadRow ? ZS_OK : ZS_DATA_ERROR;
+        if (bad_row) bad_row[i] = hc[1 + i];
         if (st[i] != ZS_OK) {
             char msg[128];
             snprintf(msg, sizeof msg, "data error: image %d: row %d has a filter type above 4", i, (int)hc[1 + i]);
@@ -2482,6 +2493,13 @@ bool run_png_unfilter(zs_ctx *c, int n, const void *const *in, const int64_t *ro
         }
     }
     return ok;
+}
+
+bool run_png_unfilter(zs_ctx *c, int n, const void *const *in, const int64_t *row_bytes, const int64_t *height, const int *bpp, void *const *out,
+                      int64_t total_rows, int max_bpp, int *st, hipStream_t s, bool *no_memory) {
+    if (!png_unfilter_enqueue(c, n, in, row_bytes, height, bpp, out, total_rows, max_bpp, s, no_memory)) return false;
+    ZS_HIP(c, hipStreamSynchronize(s));
+    return png_unfilter_collect(c, n, st);
 }
 }  // namespace
 
@@ -2521,6 +2539,232 @@ extern "C" int zs_png_unfilter_batch_device(zs_ctx *c, int n, const void *const 
 
 extern "C" int zs_png_unfilter_device(zs_ctx *c, const void *in, int64_t row_bytes, int64_t height, int bpp, void *out, void *hip_stream) {
     return zs_png_unfilter_batch_device(c, 1, &in, &row_bytes, &height, &bpp, &out, nullptr, hip_stream);
+}
+
+// ------------------------------------------------------------------ Adam7 (KA, zs_png.hip) and the decode call: IDAT payloads -> pixels in HBM
+extern "C" int64_t zs_png_idat_layout(int64_t width, int64_t height, int bits_per_pixel, int interlace, int64_t *row_bytes7, int64_t *rows7) {
+    if (width < 1 || height < 1 || width > 0x7FFFFFFF || height > 0x7FFFFFFF || !png_bits_ok(bits_per_pixel) || (interlace != 0 && interlace != 1)) return -1;
+    int64_t total = 0;
+    for (int p = 0; p < kAdam7Passes; p++) {
+        int64_t pw = 0, ph = 0;
+        if (interlace) pw = adam7_pass_width(width, p), ph = adam7_pass_height(height, p);
+        else if (p == 0) pw = width, ph = height;
+        const bool present = pw > 0 && ph > 0;
+        const int64_t rb = present ? png_bits_row_bytes(pw, bits_per_pixel) : 0, rows = present ? ph : 0;
+        if (row_bytes7) row_bytes7[p] = rb;
+        if (rows7) rows7[p] = rows;
+        total += rows * (rb + 1);  // (below 2^31 * (2^34 + 1) a pass: seven of them fit 64 bits)
+    }
+    return total;
+}
+
+namespace {
+constexpr int64_t kAdam7Slice = 1 << 25;  // rows a launch: 64 threads a row, 2^31 threads, half of what a grid may hold
+
+// `staged`: m Adam7Img and then the m + 1 row offsets, in the context's staging buffer.  Left in flight on `s`.
+// wait_upload: the caller does not wait for `s` itself before the staging buffer is used again.
+bool png_adam7_enqueue(zs_ctx *c, int m, const void *staged, int64_t total_rows, hipStream_t s, bool wait_upload) {
+    const size_t b_img = sizeof(Adam7Img) * (size_t)m, b_off = sizeof(int32_t) * ((size_t)m + 1);
+    ZS_HIP(c, hipMemcpyAsync(c->png_a7img.p, staged, b_img + b_off, hipMemcpyHostToDevice, s));
+    if (wait_upload) ZS_HIP(c, hipStreamSynchronize(s));
+    static const int group = getenv("ZS_PNG_A7_GROUP") ? atoi(getenv("ZS_PNG_A7_GROUP")) : 16;  // (measurements: DESIGN.md section 4, KA)
+    const Adam7Img *d_img = (const Adam7Img *)c->png_a7img.p;
+    const int32_t *d_off = (const int32_t *)((const uint8_t *)c->png_a7img.p + b_img);
+    for (int64_t row0 = 0; row0 < total_rows; row0 += kAdam7Slice) {
+        const int64_t rows = std::min<int64_t>(kAdam7Slice, total_rows - row0);
+        const dim3 grid((unsigned)((rows + kAdam7RowsPerWg - 1) / kAdam7RowsPerWg)), block(64 * kAdam7RowsPerWg);
+        if (group == 4) hipLaunchKernelGGL(zs_png_adam7_kernel<4>, grid, block, 0, s, d_img, d_off, m, row0);
+        else if (group == 8) hipLaunchKernelGGL(zs_png_adam7_kernel<8>, grid, block, 0, s, d_img, d_off, m, row0);
+        else hipLaunchKernelGGL(zs_png_adam7_kernel<16>, grid, block, 0, s, d_img, d_off, m, row0);
+        ZS_HIP(c, hipGetLastError());
+    }
+    return true;
+}
+size_t png_adam7_staged_bytes(int m) { return sizeof(Adam7Img) * (size_t)m + sizeof(int32_t) * ((size_t)m + 1); }
+}  // namespace
+
+extern "C" int zs_png_adam7_merge_batch_device(zs_ctx *c, int n, const void *const *passes, const int64_t *width, const int64_t *height,
+                                               const int *bits_per_pixel, void *const *out, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!passes || !width || !height || !bits_per_pixel || !out) return ZS_STREAM_ERROR;
+    int64_t total_rows = 0;
+    for (int i = 0; i < n; i++) {
+        if (!passes[i] || !out[i] || width[i] < 1 || height[i] < 1 || width[i] > 0x7FFFFFFF || height[i] > 0x7FFFFFFF || !png_bits_ok(bits_per_pixel[i])) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        total_rows += height[i];
+    }
+    if (total_rows > 0x7FFFFFFF) {  // (the grid is the row list)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const size_t bytes = png_adam7_staged_bytes(n);
+    if (!ensure(c, c->png_a7img, bytes) || !ensure_pinned(c, bytes)) return ZS_MEM_ERROR;
+    Adam7Img *hi = (Adam7Img *)c->pinned;
+    int32_t *ho = (int32_t *)((uint8_t *)c->pinned + sizeof(Adam7Img) * (size_t)n);
+    int64_t at = 0;
+    for (int i = 0; i < n; i++) {
+        hi[i] = Adam7Img{(const uint8_t *)passes[i], (uint8_t *)out[i], {}, (int32_t)width[i], (int32_t)height[i], bits_per_pixel[i], 0};
+        adam7_layout(hi[i]);
+        ho[i] = (int32_t)at;
+        at += height[i];
+    }
+    ho[n] = (int32_t)at;
+    if (!png_adam7_enqueue(c, n, c->pinned, total_rows, s, true)) return ZS_STREAM_ERROR;
+    return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
+}
+
+// Inflate into a buffer of the context, KU over every image or present pass whose stream gave exactly what the IHDR needs,
+// KA behind it on the same stream for the interlaced ones.  Two waits: inflate's results decide what KU may touch.
+extern "C" int zs_png_decode_batch_device(zs_ctx *c, int n, const void *const *idat, const int64_t *idat_len, const int64_t *width, const int64_t *height,
+                                          const int *bits_per_pixel, const int *interlace, void *const *out, int *status, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!idat || !idat_len || !width || !height || !bits_per_pixel || !interlace || !out) return ZS_STREAM_ERROR;
+    constexpr int64_t kLim = 0x7FFFFFFF - 1024;  // what one inflate stream may take and give
+    std::vector<int64_t> need((size_t)n), inf_at((size_t)n), pass_at((size_t)n, 0);
+    int64_t total_rows = 0, n_items = 0, n_a7 = 0, a7_rows = 0;
+    size_t inf_total = 0, pass_total = 0;
+    for (int i = 0; i < n; i++) {
+        int64_t rb7[kAdam7Passes], rows7[kAdam7Passes];
+        need[(size_t)i] = !idat[i] || !out[i] || idat_len[i] < 0 || idat_len[i] > kLim
+                              ? -1
+                              : zs_png_idat_layout(width[i], height[i], bits_per_pixel[i], interlace[i], rb7, rows7);
+        if (need[(size_t)i] < 0 || need[(size_t)i] > kLim) {
+            c->err = need[(size_t)i] > kLim ? "stream error: an image's IDAT payload is above 2 GiB - 1 KiB" : "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        inf_at[(size_t)i] = (int64_t)inf_total;
+        inf_total += ((size_t)need[(size_t)i] + 255) & ~(size_t)255;
+        int64_t px = 0;
+        for (int p = 0; p < kAdam7Passes; p++) total_rows += rows7[p], n_items += rows7[p] > 0, px += rb7[p] * rows7[p];
+        if (interlace[i]) {
+            pass_at[(size_t)i] = (int64_t)pass_total;
+            pass_total += ((size_t)px + 255) & ~(size_t)255;
+            n_a7++, a7_rows += height[i];
+        }
+    }
+    if (total_rows > 0x7FFFFFFF) {  // (KU's segment list and KA's row list are indexed with 32 bits)
+        c->err = "stream error: more than 2^31 - 1 rows in one call, pass rows counted (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    std::vector<int> st((size_t)n, ZS_STREAM_ERROR);
+    auto finish = [&](int rc) {
+        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
+        return rc;
+    };
+    if (hipSetDevice(c->device) != hipSuccess) return finish(ZS_STREAM_ERROR);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (!ensure(c, c->png_inflated, inf_total + 256) || !ensure(c, c->png_passes, pass_total + 256) ||
+        (n_a7 && !ensure(c, c->png_a7img, png_adam7_staged_bytes((int)n_a7)))) {
+        std::fill(st.begin(), st.end(), (int)ZS_MEM_ERROR);
+        return finish(ZS_MEM_ERROR);
+    }
+    // ---- inflate: every stream against exactly the bytes its image needs
+    std::vector<void *> inf_out((size_t)n);
+    std::vector<int64_t> got((size_t)n, 0);
+    std::vector<int> ist((size_t)n, ZS_STREAM_ERROR);
+    for (int i = 0; i < n; i++) inf_out[(size_t)i] = (uint8_t *)c->png_inflated.p + inf_at[(size_t)i];
+    const int inf_rc = zs_inflate_batch_device(c, n, idat, idat_len, inf_out.data(), need.data(), got.data(), ist.data(), (void *)s);
+    const std::string inf_msg = inf_rc == ZS_OK ? std::string() : c->err;
+    for (int v : ist)
+        if (v == ZS_STREAM_ERROR || v == ZS_MEM_ERROR) return finish(v);  // (the device or the workspace failed, not a stream)
+    // what went wrong with image i, if anything did so far
+    std::vector<std::string> why((size_t)n);
+    char msg[192];
+    for (int i = 0; i < n; i++) {
+        const int64_t nd = need[(size_t)i];
+        if (ist[(size_t)i] == ZS_STREAM_END && got[(size_t)i] == nd) continue;
+        if (ist[(size_t)i] == ZS_STREAM_END)
+            snprintf(msg, sizeof msg, "data error: image %d: IDAT holds %lld bytes, the image needs %lld", i, (long long)got[(size_t)i], (long long)nd);
+        else if (ist[(size_t)i] == ZS_BUF_ERROR)
+            snprintf(msg, sizeof msg, "data error: image %d: IDAT holds more than the %lld bytes the image needs, or its stream is cut short (%lld bytes came out)", i,
+                     (long long)nd, (long long)got[(size_t)i]);
+        else snprintf(msg, sizeof msg, "data error: image %d: %s", i, inf_msg.c_str());
+        why[(size_t)i] = msg;
+    }
+    // ---- KU over the good images and their present passes, KA behind it
+    struct Item {
+        int img, pass;  // pass -1: a non-interlaced image
+    };
+    std::vector<Item> items;
+    std::vector<const void *> u_in;
+    std::vector<void *> u_out;
+    std::vector<int64_t> u_rb, u_h;
+    std::vector<int> u_bpp;
+    std::vector<Adam7Img> a7;
+    std::vector<int32_t> a7_off;
+    items.reserve((size_t)n_items);
+    int64_t u_rows = 0, a_rows = 0;
+    int max_bpp = 1;
+    for (int i = 0; i < n; i++) {
+        if (!why[(size_t)i].empty()) continue;
+        const int bpp = png_bits_bpp(bits_per_pixel[i]);
+        max_bpp = std::max(max_bpp, bpp);
+        const uint8_t *src = (const uint8_t *)inf_out[(size_t)i];
+        if (!interlace[i]) {
+            items.push_back(Item{i, -1});
+            u_in.push_back(src), u_out.push_back(out[i]), u_rb.push_back(png_bits_row_bytes(width[i], bits_per_pixel[i])), u_h.push_back(height[i]), u_bpp.push_back(bpp);
+            u_rows += height[i];
+            continue;
+        }
+        Adam7Img im{(const uint8_t *)c->png_passes.p + pass_at[(size_t)i], (uint8_t *)out[i], {}, (int32_t)width[i], (int32_t)height[i], bits_per_pixel[i], 0};
+        adam7_layout(im);
+        for (int p = 0; p < kAdam7Passes; p++) {
+            const int64_t pw = adam7_pass_width(width[i], p), ph = adam7_pass_height(height[i], p);
+            if (pw == 0 || ph == 0) continue;
+            const int64_t rb = png_bits_row_bytes(pw, bits_per_pixel[i]);
+            items.push_back(Item{i, p});
+            u_in.push_back(src), u_out.push_back(const_cast<uint8_t *>(im.passes) + im.off[p]), u_rb.push_back(rb), u_h.push_back(ph), u_bpp.push_back(bpp);
+            src += ph * (rb + 1);
+            u_rows += ph;
+        }
+        a7_off.push_back((int32_t)a_rows);
+        a7.push_back(im);
+        a_rows += height[i];
+    }
+    const int m = (int)items.size();
+    std::vector<int> ust((size_t)m, ZS_OK);
+    std::vector<int32_t> bad((size_t)m, kPngNoBadRow);
+    if (m > 0) {
+        bool no_memory = false;
+        size_t extra_at = 0;
+        const size_t a7_bytes = png_adam7_staged_bytes((int)a7.size());
+        if (!png_unfilter_enqueue(c, m, u_in.data(), u_rb.data(), u_h.data(), u_bpp.data(), u_out.data(), u_rows, max_bpp, s, &no_memory,
+                                  a7.empty() ? 0 : a7_bytes, &extra_at)) {
+            if (no_memory) std::fill(st.begin(), st.end(), (int)ZS_MEM_ERROR);
+            return finish(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+        }
+        if (!a7.empty()) {
+            a7_off.push_back((int32_t)a_rows);
+            uint8_t *staged = (uint8_t *)c->pinned + extra_at;  // (behind KU's share of the staging buffer, whose results are on their way into it)
+            memcpy(staged, a7.data(), sizeof(Adam7Img) * a7.size());
+            memcpy(staged + sizeof(Adam7Img) * a7.size(), a7_off.data(), sizeof(int32_t) * a7_off.size());
+            if (!png_adam7_enqueue(c, (int)a7.size(), staged, a_rows, s, false)) return finish(ZS_STREAM_ERROR);
+        }
+        if (hipStreamSynchronize(s) != hipSuccess) {
+            c->err = "hipStreamSynchronize failed";
+            return finish(ZS_STREAM_ERROR);
+        }
+        png_unfilter_collect(c, m, ust.data(), bad.data());
+    }
+    for (int k = m - 1; k >= 0; k--) {  // (downwards: an image's first bad pass stays)
+        if (ust[(size_t)k] == ZS_OK) continue;
+        const Item &it = items[(size_t)k];
+        if (it.pass < 0) snprintf(msg, sizeof msg, "data error: image %d: row %d has a filter type above 4", it.img, (int)bad[(size_t)k]);
+        else snprintf(msg, sizeof msg, "data error: image %d: pass %d: row %d has a filter type above 4", it.img, it.pass + 1, (int)bad[(size_t)k]);
+        why[(size_t)it.img] = msg;
+    }
+    int rc = ZS_OK;
+    for (int i = n - 1; i >= 0; i--) {
+        st[(size_t)i] = why[(size_t)i].empty() ? ZS_OK : ZS_DATA_ERROR;
+        if (st[(size_t)i] != ZS_OK) c->err = why[(size_t)i], rc = ZS_DATA_ERROR;  // (downwards: the first failing image's message stays)
+    }
+    return finish(rc);
 }
 
 // ------------------------------------------------------------------ multi-GPU batch entry points

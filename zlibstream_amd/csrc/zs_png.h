@@ -93,4 +93,136 @@ ZS_HD int png_row_image(const Off &row_off, int n, int64_t r) {
     return lo;
 }
 
+// ---- Adam7 (PNG specification 8.2): the pass geometry, and the gather that KA (zs_png.hip) and its host model
+// (tests/cpp/test_png_adam7.cpp) share ----
+// Pass p = 0..6 (the specification's 1..7) holds the pixels (xstart + k * xstep, ystart + j * ystep); the steps are powers
+// of two, kept as shifts.  One nibble per pass, pass 0 in the lowest.
+constexpr int kAdam7Passes = 7;
+ZS_HD int adam7_xstart(int p) { return (0x0102040 >> (4 * p)) & 15; }  // 0 4 0 2 0 1 0
+ZS_HD int adam7_ystart(int p) { return (0x1020400 >> (4 * p)) & 15; }  // 0 0 4 0 2 0 1
+ZS_HD int adam7_xshift(int p) { return (0x0112233 >> (4 * p)) & 15; }  // steps 8 8 4 4 2 2 1
+ZS_HD int adam7_yshift(int p) { return (0x1122333 >> (4 * p)) & 15; }  // steps 8 8 8 4 4 2 2
+ZS_HD int64_t adam7_span(int64_t n, int start, int shift) { return n > start ? (n - start + ((int64_t)1 << shift) - 1) >> shift : 0; }
+ZS_HD int64_t adam7_pass_width(int64_t w, int p) { return adam7_span(w, adam7_xstart(p), adam7_xshift(p)); }
+ZS_HD int64_t adam7_pass_height(int64_t h, int p) { return adam7_span(h, adam7_ystart(p), adam7_yshift(p)); }
+
+ZS_HD bool png_bits_ok(int bits) { return bits == 1 || bits == 2 || bits == 4 || (bits >= 8 && bits <= 64 && bits % 8 == 0 && bits != 40 && bits != 56); }
+ZS_HD int64_t png_bits_row_bytes(int64_t w, int bits) { return (w * bits + 7) >> 3; }
+ZS_HD int png_bits_bpp(int bits) { return bits < 8 ? 1 : bits >> 3; }  // what the filters call bpp
+
+// The inverse map: the pass of output pixel (x, y) and its place inside that pass.  Per output row the sources are few:
+// y % 8 == 0 draws on passes 0, 1, 3 and 5; y % 8 == 4 on 2, 3 and 5; y % 4 == 2 on 4 and 5; odd y on pass 6 alone.
+struct Adam7Src {
+    int pass;
+    int64_t col, row;
+};
+ZS_HD Adam7Src adam7_source(int64_t x, int64_t y) {
+    int p;
+    if (y & 1) p = 6;
+    else if (x & 1) p = 5;
+    else if (y & 2) p = 4;
+    else if (x & 2) p = 3;
+    else if (y & 4) p = 2;
+    else if (x & 4) p = 1;
+    else p = 0;
+    return Adam7Src{p, x >> adam7_xshift(p), y >> adam7_yshift(p)};  // (the start is below the step: the shift drops it)
+}
+
+// One interlaced image for KA.  passes: the reconstructed passes back to back (no filter bytes, absent passes absent);
+// off[p]: where pass p starts in it; out: height rows of png_bits_row_bytes(width, bits) bytes.
+struct Adam7Img {
+    const uint8_t *passes;
+    uint8_t *out;
+    int64_t off[kAdam7Passes];
+    int32_t width, height, bits, pad;
+};
+// ... filled in from the geometry; returns the bytes of all passes
+ZS_HD int64_t adam7_layout(Adam7Img &im) {
+    int64_t at = 0;
+    for (int p = 0; p < kAdam7Passes; p++) {
+        im.off[p] = at;
+        at += png_bits_row_bytes(adam7_pass_width(im.width, p), im.bits) * adam7_pass_height(im.height, p);
+    }
+    return at;
+}
+
+constexpr int kAdam7GroupBits = 4;  // output bytes a thread builds at 1, 2 and 4 bits a pixel (8 .. 32 pixels)
+
+ZS_HD const uint8_t *adam7_pass_row(const Adam7Img &im, int p, int64_t row) {
+    return im.passes + im.off[p] + row * png_bits_row_bytes(adam7_pass_width(im.width, p), im.bits);
+}
+
+// Output byte b of row y at 1, 2 or 4 bits a pixel: the 8 / 4 / 2 pixels that land in it, leftmost in the high bits, each
+// from its own pass row; pixels past the width leave zero bits.
+ZS_HD uint32_t adam7_bits_byte(const Adam7Img &im, int64_t y, int64_t b) {
+    const int bits = im.bits, ppb = 8 / bits;
+    uint32_t v = 0;
+    for (int j = 0; j < ppb; j++) {
+        const int64_t x = b * ppb + j;
+        if (x >= im.width) break;
+        const Adam7Src s = adam7_source(x, y);
+        const int64_t bit = s.col * bits;
+        const uint32_t byte = adam7_pass_row(im, s.pass, s.row)[bit >> 3];
+        v |= ((byte >> (8 - bits - (int)(bit & 7))) & ((1u << bits) - 1)) << (8 - bits - j * bits);
+    }
+    return v;
+}
+
+// Bytes [b0, b0 + G) of output row y (`dst` = the row's first byte, `rb` its length; dst + b0 is G-aligned, so the first
+// group of a row may begin in front of it and the last one end behind it: those two store byte by byte, every other group
+// is one aligned store of G bytes).  G = 4, 8 or 16.  No byte outside [0, rb) is touched, and none is touched twice.
+template <int G>
+ZS_HD void adam7_group(const Adam7Img &im, int64_t y, int64_t rb, uint8_t *dst, int64_t b0) {
+    static_assert(G == 4 || G == 8 || G == 16, "a group is one store");
+    uint64_t v[2] = {0, 0};  // byte k of the group in bits 8k.. of v[k / 8]
+    const int64_t lo = b0 < 0 ? 0 : b0, hi = b0 + G < rb ? b0 + G : rb;  // the group's bytes inside the row
+    const bool full = lo == b0 && hi == b0 + G;
+    if (y & 1) {
+        // an odd row is pass 6's row as it stands (its columns are the image's)
+        const uint8_t *src = adam7_pass_row(im, 6, y >> 1);
+        if (full) __builtin_memcpy(v, src + b0, G);
+        else
+            for (int64_t b = lo; b < hi; b++) v[(b - b0) >> 3] |= (uint64_t)src[b] << (8 * ((b - b0) & 7));
+        const int used = (int)(((int64_t)im.width * im.bits) & 7);  // bits of the row's last byte that hold pixels (0: all)
+        if (used && hi == rb) {
+            const int k = (int)(rb - 1 - b0);
+            v[k >> 3] &= ~((uint64_t)(0xFFu >> used) << (8 * (k & 7)));
+        }
+    } else if (im.bits < 8) {
+        for (int64_t b = lo; b < hi; b++) v[(b - b0) >> 3] |= (uint64_t)adam7_bits_byte(im, y, b) << (8 * ((b - b0) & 7));
+    } else {
+        // whole pixels of bpp bytes; the first and the last may lie partly in a neighbouring group
+        const int bpp = im.bits >> 3;
+        for (int64_t x = lo / bpp; x * bpp < hi; x++) {
+            const Adam7Src s = adam7_source(x, y);
+            const uint8_t *src = adam7_pass_row(im, s.pass, s.row) + s.col * bpp;
+            uint64_t px = 0;
+            switch (bpp) {
+            case 1: px = src[0]; break;
+            case 2: __builtin_memcpy(&px, src, 2); break;
+            case 3: __builtin_memcpy(&px, src, 3); break;
+            case 4: __builtin_memcpy(&px, src, 4); break;
+            case 6: __builtin_memcpy(&px, src, 6); break;
+            default: __builtin_memcpy(&px, src, 8); break;
+            }
+            int o = (int)(x * bpp - b0);  // the pixel's first byte in the group: -7 .. G - 1
+            if (o < 0) px >>= -8 * o, o = 0;
+            if (o < 8) {
+                v[0] |= px << (8 * o);
+                if (o > 0) v[1] |= px >> (8 * (8 - o));
+            } else
+                v[1] |= px << (8 * (o - 8));
+        }
+        // (bytes of the last pixel behind the group fell off v[1], or sit in it above byte G and are not stored)
+    }
+    if (full) {
+        __builtin_memcpy(__builtin_assume_aligned(dst + b0, G), v, G);
+    } else
+        for (int64_t b = lo; b < hi; b++) dst[b] = (uint8_t)(v[(b - b0) >> 3] >> (8 * ((b - b0) & 7)));
+}
+
+// groups of G bytes that cover a row of rb bytes beginning at address `row_addr`, and the first one's b0 (<= 0)
+ZS_HD int64_t adam7_row_groups(uint64_t row_addr, int64_t rb, int G) { return ((int64_t)(row_addr & (uint64_t)(G - 1)) + rb + G - 1) / G; }
+ZS_HD int64_t adam7_row_b0(uint64_t row_addr, int G) { return -(int64_t)(row_addr & (uint64_t)(G - 1)); }
+
 }  // namespace zs

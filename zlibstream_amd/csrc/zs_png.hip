@@ -261,4 +261,30 @@ __global__ __launch_bounds__(256) void zs_png_unfilter_kernel(const PngImg *imgs
     }
 }
 
+// KA: the Adam7 interleave, as a gather.  The grid is the flat list of all interlaced images' output rows (row_off as for
+// KP, zs_png.h png_row_image), four rows a workgroup: wave w takes row 4 * block + w, and its lanes the row's aligned groups
+// of G bytes (zs_png.h adam7_group), 64 at a time -- one full-width store per lane, contiguous over the wave.  Every pixel's
+// source is computed from (x, y); the reads are plain cached loads from the two to four pass rows that feed the output
+// row, each of them contiguous over the wave.  No atomics, no LDS: no output byte has two writers.
+constexpr int kAdam7RowsPerWg = 4;
+
+template <int G>
+__global__ __launch_bounds__(64 * kAdam7RowsPerWg) void zs_png_adam7_kernel(const Adam7Img *imgs, const int32_t *row_off, int n, int64_t row0) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    const int64_t r = row0 + (int64_t)blockIdx.x * kAdam7RowsPerWg + w;
+    if (r >= (int64_t)row_off[n]) return;
+    const int i = png_row_image(row_off, n, r);
+    const Adam7Img &im = imgs[i];  // (left in memory: off[] is indexed by a pass that differs from lane to lane)
+    const int64_t y = r - row_off[i], rb = png_bits_row_bytes(im.width, im.bits);
+    uint8_t *dst = im.out + y * rb;
+    const uint64_t addr = (uint64_t)(uintptr_t)dst;
+    if (im.bits < 8) {
+        const int64_t ng = adam7_row_groups(addr, rb, kAdam7GroupBits), b0 = adam7_row_b0(addr, kAdam7GroupBits);
+        for (int64_t g = lane; g < ng; g += 64) adam7_group<kAdam7GroupBits>(im, y, rb, dst, b0 + g * kAdam7GroupBits);
+    } else {
+        const int64_t ng = adam7_row_groups(addr, rb, G), b0 = adam7_row_b0(addr, G);
+        for (int64_t g = lane; g < ng; g += 64) adam7_group<G>(im, y, rb, dst, b0 + g * G);
+    }
+}
+
 }  // namespace zs
