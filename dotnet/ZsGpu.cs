@@ -93,6 +93,28 @@ namespace SixLabors.ZlibStream
                                                                                   int* bitsPerPixel, IntPtr* output, IntPtr hipStream);
         [DllImport(Lib)] public static extern long zs_png_idat_layout(long width, long height, int bitsPerPixel, int interlace, long* rowBytes7,
                                                                       long* rows7);
+        // ---- CRC-32 (zlib's crc32) of device-resident bytes, one span or n spans of any lengths in one launch (seed == null: all 0)
+        [DllImport(Lib)] public static extern int zs_crc32_device(IntPtr ctx, IntPtr buf, long len, uint seed, uint* crc, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_crc32_batch_device(IntPtr ctx, int n, IntPtr* buf, long* len, uint* seed, uint* crc, IntPtr hipStream);
+        // ---- whole PNG files: pixels in HBM -> files in HBM (signature, IHDR, the caller's chunks from host memory, IDAT chunks of at
+        //      most idatChunkBytes data bytes, IEND), the room such a file needs (host code), the chunk walk of one file in host memory
+        //      (host code; ancillary chunks are neither verified nor interpreted), and files in host memory -> pixels in HBM
+        [DllImport(Lib)] public static extern long zs_png_file_bound(long idatLen, long idatChunkBytes, long extraLen);
+        [DllImport(Lib)] public static extern int zs_png_encode_batch_device(IntPtr ctx, int n, IntPtr* pixels, long* width, long* height, int* bitDepth,
+                                                                             int* colorType, int* filter, IntPtr* extra, long* extraLen, long rowsPerWrite,
+                                                                             long idatChunkBytes, IntPtr* output, long* outCap, long* outLen, int* status,
+                                                                             int level, int strategy, int hashVariant, IntPtr hipStream);
+        [StructLayout(LayoutKind.Sequential)]
+        public struct PngInfo
+        {
+            public long Width, Height;
+            public int BitDepth, ColorType, Interlace, BitsPerPixel;
+            public long IdatBytes, PixelBytes, IdatChunks;
+        }
+
+        [DllImport(Lib)] public static extern int zs_png_file_info(IntPtr file, long len, PngInfo* info);
+        [DllImport(Lib)] public static extern int zs_png_decode_files_batch(IntPtr ctx, int n, IntPtr* file, long* fileLen, IntPtr* output, long* outCap,
+                                                                            PngInfo* info, int* status, IntPtr hipStream);
         // bytes fed behind a stream's trailer before its end was seen (the engine looks for the end now and then)
         [DllImport(Lib)] public static extern long zs_inflate_surplus(IntPtr s, IntPtr* p);
     }

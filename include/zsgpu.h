@@ -245,6 +245,87 @@ ZS_API int zs_png_decode_batch_device(zs_ctx *ctx, int n, const void *const *ida
                                       const int64_t *width, const int64_t *height, const int *bits_per_pixel,
                                       const int *interlace, void *const *out, int *status, void *hip_stream);
 
+/* ------------------------------------------------------------------ */
+/* CRC-32 (IEEE 802.3, reflected polynomial 0xEDB88320) of device-resident bytes: zlib's crc32(seed, buf, len), the pre- and
+ * post-inversion included -- seed 0 starts a CRC, a result fed back as the seed continues it.  The checksum that ends every
+ * chunk of a PNG file (and a gzip member); the engine's own streams carry Adler-32 (zs_adler32_device).
+ * d_buf: DEVICE pointer of any alignment (the kernel reads whole aligned 16-byte words, so up to 15 bytes in front of and
+ * behind the span are read and ignored; they lie in the same 16-byte granule as a byte of the span).  len: 0 .. 2 GiB - 1 KiB.
+ * _batch: n spans in one launch, whatever their lengths -- every span is cut into tiles of 8 KiB, the tiles of all spans
+ * share the launch (KC).  d_buf / len / seed / out are HOST arrays of n entries; seed == NULL: all 0;
+ * d_buf[i] may be NULL where len[i] is 0.  n == 0 is ZS_OK.  A null context, n < 0, a null array or pointer, a negative or
+ * oversized len: ZS_STREAM_ERROR before any device work.  Work is ordered on hip_stream (NULL: the context's); the call
+ * synchronises that stream once and returns when the results are known.  ZS_MEM_ERROR: the descriptors do not fit. */
+ZS_API int zs_crc32_device(zs_ctx *ctx, const void *d_buf, int64_t len, uint32_t seed, uint32_t *out, void *hip_stream);
+ZS_API int zs_crc32_batch_device(zs_ctx *ctx, int n, const void *const *d_buf, const int64_t *len, const uint32_t *seed,
+                                 uint32_t *out, void *hip_stream);
+
+/* Bytes of the PNG file that holds a zlib stream of idat_len bytes cut into IDAT chunks of at most idat_chunk_bytes data bytes
+ * (0: one chunk; 1 .. 2^31 - 1 otherwise) and extra_len bytes of caller-supplied chunks: signature, IHDR, the extra chunks,
+ * the IDAT chunks, IEND.  Exact for the stream length given; zs_png_file_bound(zs_deflate_bound(height * (row_bytes + 1)),
+ * idat_chunk_bytes, extra_len) is always enough room for zs_png_encode_batch_device.  -1 for bad arguments (negative values, a
+ * chunk size above 2^31 - 1, one chunk for more than 2^31 - 1 bytes).  Pure host code, no GPU needed. */
+ZS_API int64_t zs_png_file_bound(int64_t idat_len, int64_t idat_chunk_bytes, int64_t extra_len);
+
+/* Pixels to complete PNG files, n images a call, nothing leaving HBM: zs_png_idat_batch_device into a buffer the context owns
+ * (zs_deflate_bound of the filtered image per image, kept until zs_ctx_destroy), then one framing launch that reads every
+ * IDAT chunk's data once -- copying it into place, whatever the alignments of the two, and computing its CRC-32 -- and a
+ * small one that writes the chunks' length, type and CRC words.
+ * pixels[i]: raw PNG scanline data (device pointer): height[i] rows of ceil(width[i] * bits / 8) bytes, non-interlaced, bits =
+ * bit_depth[i] * channels(color_type[i]); only the (color type, bit depth) pairs of PNG specification table 11.1.  The filters
+ * take bpp = max(1, bits / 8).  filter / rows_per_write / level / strategy / hash_variant: as for zs_png_idat_batch_device,
+ * whose zlib stream the IDAT chunks hold byte for byte.
+ * extra (HOST array of HOST pointers, may be NULL; extra[i] may be NULL where extra_len[i] is 0): chunks the caller has
+ * framed already (PLTE, tRNS, gAMA, ...), written verbatim between IHDR and the first IDAT; only their length fields are
+ * looked at (they must add up to extra_len[i]), not their types, order or CRCs.
+ * idat_chunk_bytes: data bytes of an IDAT chunk at most (0: one chunk).
+ * out[i] (device pointer, any alignment) receives the file: signature, IHDR (compression 0, filter method 0, interlace 0),
+ * extra[i], the IDAT chunks, IEND.  out_len[i]: the file's length; status[i] (may be NULL): ZS_OK, ZS_BUF_ERROR when
+ * out_cap[i] is below that length (nothing is written for that image, the others complete), or the deflate call's code.
+ * Returns ZS_OK, the first failing image's code, ZS_MEM_ERROR, or -- before any device work, status and out_len untouched --
+ * ZS_STREAM_ERROR: null context, n < 0, a null array or pointer, width or height outside 1 .. 2^31 - 1, an illegal color
+ * type / bit depth pair, a filter outside 0..5, a filtered image above 2 GiB - 1 KiB, malformed extra chunks, a negative
+ * rows_per_write, an idat_chunk_bytes outside 0 .. 2^31 - 1, a level or strategy deflate rejects.
+ * Work is ordered on hip_stream (NULL: the context's); the call waits for it twice (the stream lengths decide the layout) and
+ * returns when the files are written.  zs_ctx_stage_ms shows the framing as "crc32_frame". */
+ZS_API int zs_png_encode_batch_device(zs_ctx *ctx, int n, const void *const *pixels, const int64_t *width, const int64_t *height,
+                                      const int *bit_depth, const int *color_type, const int *filter, const void *const *extra,
+                                      const int64_t *extra_len, int64_t rows_per_write, int64_t idat_chunk_bytes, void *const *out,
+                                      const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy,
+                                      int hash_variant, void *hip_stream);
+
+/* What a PNG file's IHDR and chunk chain say.  bits_per_pixel = bit depth times channels; idat_bytes: the IDAT chunks' data
+ * together (the zlib stream); pixel_bytes: height rows of ceil(width * bits_per_pixel / 8) bytes, what the decoder writes (2^63 - 1 where that is more);
+ * n_idat: IDAT chunks. */
+typedef struct zs_png_info {
+    int64_t width, height;
+    int bit_depth, color_type, interlace, bits_per_pixel;
+    int64_t idat_bytes, pixel_bytes;
+    int64_t n_idat;
+} zs_png_info;
+
+/* The chunk walk of one file in HOST memory, pure host code, no context and no GPU: ZS_OK and *info, or ZS_DATA_ERROR for a bad
+ * signature, a truncated chunk, a missing or late IHDR, an IHDR field outside the specification, no IDAT, IDAT chunks that
+ * are not consecutive, a missing IEND, or a wrong CRC in a critical chunk (IHDR, PLTE, IDAT, IEND; checked here on the host).
+ * Ancillary chunks are stepped over by their length fields: they are neither verified nor interpreted, here or in
+ * zs_png_decode_files_batch.  Bytes behind IEND are ignored.  ZS_STREAM_ERROR: null pointers or a negative len. */
+ZS_API int zs_png_file_info(const void *file, int64_t len, zs_png_info *info);
+
+/* PNG files to pixels, n files a call.  file[i] / file_len[i]: whole files in HOST memory.  The host walks every file's chunk
+ * chain (as zs_png_file_info, the CRCs aside); the files go to the device in one copy through the context's staging buffer;
+ * one CRC-32 launch checks the critical chunks (IHDR, PLTE, IDAT, IEND -- ancillary chunks are neither verified nor
+ * interpreted) and gathers every file's IDAT data into a buffer the context owns; zs_png_decode_batch_device's inflate,
+ * reconstruction and Adam7 interleave run on that.  out[i] (DEVICE pointer, out_cap[i] bytes): raw scanline data,
+ * info.pixel_bytes of it, no bit-depth expansion, no palette.  info (HOST, may be NULL): filled for every file whose chain
+ * could be walked.  status[i] (may be NULL): ZS_OK, ZS_BUF_ERROR (out_cap[i] < pixel_bytes), or ZS_DATA_ERROR -- a file fails
+ * for itself only, its out[i] is unspecified; zs_ctx_last_error names the first failing file and the reason: the walk's (see
+ * zs_png_file_info), "CRC error in <type> chunk at offset <o>", or what zs_png_decode_batch_device reports.
+ * Returns ZS_OK, the first failing file's code, ZS_MEM_ERROR, or, before any device work and with status untouched,
+ * ZS_STREAM_ERROR: null context, n < 0, null arrays or pointers, a negative length or capacity.  Work is ordered on
+ * hip_stream (NULL: the context's); the call waits for it three times.  The context keeps its buffers until zs_ctx_destroy. */
+ZS_API int zs_png_decode_files_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, void *const *out,
+                                     const int64_t *out_cap, zs_png_info *info, int *status, void *hip_stream);
+
 /* Stage timing of the last *_batch_device call, measured with hipEvents on
  * the stream the kernels ran on.  Enable before the call. */
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took

@@ -100,6 +100,76 @@ inline int64_t PngIdatLayout(int64_t width, int64_t height, int bitsPerPixel, bo
     return zs_png_idat_layout(width, height, bitsPerPixel, interlace ? 1 : 0, rowBytes, rows);
 }
 
+// zlib's crc32 of device-resident spans of any lengths and alignments, n a launch (zs_crc32_batch_device); seed: empty (all 0)
+// or one per span -- a result fed back as the seed continues a CRC.
+inline std::vector<uint32_t> Crc32BatchDevice(const std::vector<const void *> &buf, const std::vector<int64_t> &len, const std::vector<uint32_t> &seed = {},
+                                              zs_ctx *ctx = nullptr, void *hipStream = nullptr) {
+    const size_t n = buf.size();
+    if (len.size() != n || (!seed.empty() && seed.size() != n)) throw ZlibStreamException("crc32: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    std::vector<uint32_t> crc(n, 0);
+    const int rc = zs_crc32_batch_device(c, (int)n, buf.data(), len.data(), seed.empty() ? nullptr : seed.data(), crc.data(), hipStream);
+    if (rc != ZS_OK) throw ZlibStreamException(rc == ZS_MEM_ERROR ? std::string("crc32: out of device memory") : std::string("crc32: bad arguments"));
+    return crc;
+}
+inline uint32_t Crc32Device(const void *buf, int64_t len, uint32_t seed = 0, zs_ctx *ctx = nullptr, void *hipStream = nullptr) {
+    uint32_t crc = 0;
+    if (zs_crc32_device(ctx ? ctx : GpuContext::Shared(), buf, len, seed, &crc, hipStream) != ZS_OK) throw ZlibStreamException("crc32: bad arguments");
+    return crc;
+}
+
+// Whole PNG files.  Room for the file around a zlib stream of idatLen bytes (host code; -1 for bad arguments) ...
+inline int64_t PngFileBound(int64_t idatLen, int64_t idatChunkBytes = 0, int64_t extraLen = 0) { return zs_png_file_bound(idatLen, idatChunkBytes, extraLen); }
+// ... pixels on the GPU -> complete files on the GPU, n a call: pixels[i] (device pointer, height[i] rows of raw scanline data)
+// -> out[i] (device pointer, outCap[i] bytes): signature, IHDR, extra[i] (chunks the caller has framed, host bytes, verbatim; the
+// list may be empty), the stream of PngIdatBatchDevice in IDAT chunks of at most idatChunkBytes data bytes (0: one chunk), IEND.
+// Returns the files' lengths; status (optional) receives ZS_OK or ZS_BUF_ERROR per image.
+inline std::vector<int64_t> PngEncodeBatchDevice(const std::vector<const void *> &pixels, const std::vector<int64_t> &width, const std::vector<int64_t> &height,
+                                                 const std::vector<int> &bitDepth, const std::vector<int> &colorType, const std::vector<int> &filter,
+                                                 const std::vector<std::string> &extra, int64_t rowsPerWrite, int64_t idatChunkBytes,
+                                                 const std::vector<void *> &out, const std::vector<int64_t> &outCap, std::vector<int> *status = nullptr,
+                                                 CompressionLevel level = CompressionLevel::DefaultCompression,
+                                                 CompressionStrategy strategy = CompressionStrategy::DefaultStrategy, zs_ctx *ctx = nullptr,
+                                                 void *hipStream = nullptr) {
+    const size_t n = pixels.size();
+    if (width.size() != n || height.size() != n || bitDepth.size() != n || colorType.size() != n || filter.size() != n || out.size() != n || outCap.size() != n ||
+        (!extra.empty() && extra.size() != n))
+        throw ZlibStreamException("png: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    std::vector<const void *> xp(n, nullptr);
+    std::vector<int64_t> xl(n, 0), outLen(n, 0);
+    for (size_t i = 0; i < extra.size(); i++) xp[i] = extra[i].data(), xl[i] = (int64_t)extra[i].size();
+    std::vector<int> st(n, 0);
+    const int rc = zs_png_encode_batch_device(c, (int)n, pixels.data(), width.data(), height.data(), bitDepth.data(), colorType.data(), filter.data(),
+                                              extra.empty() ? nullptr : xp.data(), extra.empty() ? nullptr : xl.data(), rowsPerWrite, idatChunkBytes, out.data(),
+                                              outCap.data(), outLen.data(), st.data(), (int)level, (int)strategy, 0, hipStream);
+    if (status) *status = st;
+    if (rc != ZS_OK && !(rc == ZS_BUF_ERROR && status)) throw ZlibStreamException(std::string("png encode: ") + zs_ctx_last_error(c));
+    return outLen;
+}
+// ... the chunk walk of one file in host memory (host code; throws for a file that is not a whole PNG) ...
+inline zs_png_info PngFileInfo(const void *file, int64_t len) {
+    zs_png_info info{};
+    if (zs_png_file_info(file, len, &info) != ZS_OK) throw ZlibStreamException("png: not a whole PNG file");
+    return info;
+}
+// ... and files in host memory -> pixels on the GPU, n a call (zs_png_decode_files_batch): returns a status per file (ZS_OK,
+// ZS_BUF_ERROR, ZS_DATA_ERROR -- zs_ctx_last_error names the first failing file and the reason), info (optional) what each says.
+inline std::vector<int> PngDecodeFilesBatch(const std::vector<const void *> &file, const std::vector<int64_t> &fileLen, const std::vector<void *> &pixels,
+                                            const std::vector<int64_t> &pixelsCap, std::vector<zs_png_info> *info = nullptr, zs_ctx *ctx = nullptr,
+                                            void *hipStream = nullptr) {
+    const size_t n = file.size();
+    if (fileLen.size() != n || pixels.size() != n || pixelsCap.size() != n) throw ZlibStreamException("png: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    std::vector<int> status(n, 0);
+    if (info) info->assign(n, zs_png_info{});
+    const int rc = zs_png_decode_files_batch(c, (int)n, file.data(), fileLen.data(), pixels.data(), pixelsCap.data(), info ? info->data() : nullptr, status.data(),
+                                             hipStream);
+    if (rc != ZS_OK && rc != ZS_DATA_ERROR && rc != ZS_BUF_ERROR)
+        throw ZlibStreamException(rc == ZS_MEM_ERROR ? std::string("png: out of device memory") : std::string("png: bad arguments"));
+    return status;
+}
+
 // The encode half for images that stay on the GPU, n a call: pixels[i] (device pointer, height[i] rows of rowBytes[i] bytes)
 // -> the zlib stream of image i's IDAT payload in out[i] (device pointer, outCap[i] bytes), rows filtered with filter[i]
 // (0-4, 5 adaptive) and written rowsPerWrite rows a Write, as a scanline encoder writes to ZlibOutputStream (1; 0: one Write

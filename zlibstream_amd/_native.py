@@ -17,7 +17,15 @@ SYMBOLS = [
     "zs_png_unfilter_batch_device", "zs_png_unfilter_device",
     "zs_deflate_writes_batch_device", "zs_png_filter_batch_device", "zs_png_idat_batch_device",
     "zs_png_idat_layout", "zs_png_adam7_merge_batch_device", "zs_png_decode_batch_device",
+    "zs_crc32_device", "zs_crc32_batch_device", "zs_png_file_bound", "zs_png_encode_batch_device", "zs_png_file_info",
+    "zs_png_decode_files_batch",
 ]
+
+
+class PngInfo(ctypes.Structure):  # zs_png_info
+    _fields_ = [("width", ctypes.c_int64), ("height", ctypes.c_int64), ("bit_depth", ctypes.c_int), ("color_type", ctypes.c_int),
+                ("interlace", ctypes.c_int), ("bits_per_pixel", ctypes.c_int), ("idat_bytes", ctypes.c_int64),
+                ("pixel_bytes", ctypes.c_int64), ("n_idat", ctypes.c_int64)]
 
 _lib = None
 
@@ -128,5 +136,20 @@ def lib():
         L.zs_png_adam7_merge_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(vp), vp]
         L.zs_png_decode_batch_device.restype = i32
         L.zs_png_decode_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i64), P(i32), P(i32), P(vp), P(i32), vp]
+    if hasattr(L, "zs_crc32_batch_device"):  # (an older build selected with ZS_LIB for an A/B run lacks CRC-32 and the file calls)
+        u32 = ctypes.c_uint32
+        L.zs_crc32_device.restype = i32
+        L.zs_crc32_device.argtypes = [vp, vp, i64, u32, P(u32), vp]
+        L.zs_crc32_batch_device.restype = i32
+        L.zs_crc32_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(u32), P(u32), vp]
+        L.zs_png_file_bound.restype = i64
+        L.zs_png_file_bound.argtypes = [i64, i64, i64]
+        L.zs_png_encode_batch_device.restype = i32
+        L.zs_png_encode_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), P(i32), P(vp), P(i64), i64, i64, P(vp), P(i64),
+                                                 P(i64), P(i32), i32, i32, i32, vp]
+        L.zs_png_file_info.restype = i32
+        L.zs_png_file_info.argtypes = [vp, i64, P(PngInfo)]
+        L.zs_png_decode_files_batch.restype = i32
+        L.zs_png_decode_files_batch.argtypes = [vp, i32, P(vp), P(i64), P(vp), P(i64), P(PngInfo), P(i32), vp]
     _lib = L
     return L

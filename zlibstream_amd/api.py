@@ -511,6 +511,162 @@ def png_decode_batch_device(engine, idat_ptrs, idat_lens, widths, heights, bits_
     return list(status)
 
 
+CRC32_TILE = 8192          # bytes of a span one wave takes at a time (zs_crc32.h kCrcTile)
+CRC32_TILES_PER_WG = 4     # tiles a workgroup takes in one pass (kCrcWaves)
+_CRC_MAX_LEN = 0x7FFFFFFF - 1024
+# PNG specification table 11.1: color type -> (channels, bit depths)
+PNG_COLOR_TYPES = {0: (1, (1, 2, 4, 8, 16)), 2: (3, (8, 16)), 3: (1, (1, 2, 4, 8)), 4: (2, (8, 16)), 6: (4, (8, 16))}
+
+
+def crc32_device(engine, ptr, length, seed=0, stream=None):
+    """zlib.crc32(bytes, seed) of a device-resident buffer of any alignment (zs_crc32_device): seed 0 starts a CRC, a result
+    fed back as the seed continues it."""
+    length, seed = int(length), int(seed)
+    if not 0 <= length <= _CRC_MAX_LEN or not 0 <= seed <= 0xFFFFFFFF or (length > 0 and not ptr):
+        raise ValueError("crc32_device: 0 <= length <= 2 GiB - 1 KiB, a 32-bit seed and a non-null device pointer are required")
+    out = ctypes.c_uint32(0)
+    rc = _native.lib().zs_crc32_device(engine.handle, ctypes.c_void_p(ptr or 0), length, seed, ctypes.byref(out), ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_crc32_device failed (%d): %s" % (rc, engine.last_error()))
+    return int(out.value)
+
+
+def crc32_batch_device(engine, ptrs, lengths, seeds=None, stream=None):
+    """crc32_device for many spans of any lengths in one launch (zs_crc32_batch_device) -> the CRCs in input order.
+    seeds: None (all 0) or one per span."""
+    n = len(ptrs)
+    if len(lengths) != n or (seeds is not None and len(seeds) != n):
+        raise ValueError("crc32_batch_device: the argument lists differ in length")
+    for p, ln in zip(ptrs, lengths):
+        if not 0 <= int(ln) <= _CRC_MAX_LEN or (int(ln) > 0 and not p):
+            raise ValueError("crc32_batch_device: 0 <= length <= 2 GiB - 1 KiB and non-null device pointers are required")
+    if seeds is not None and any(not 0 <= int(s) <= 0xFFFFFFFF for s in seeds):
+        raise ValueError("crc32_batch_device: a seed is not a 32-bit value")
+    if n == 0:
+        return []
+    out = (ctypes.c_uint32 * n)()
+    rc = _native.lib().zs_crc32_batch_device(engine.handle, n, (ctypes.c_void_p * n)(*[int(p or 0) for p in ptrs]),
+                                             (ctypes.c_int64 * n)(*[int(x) for x in lengths]),
+                                             (ctypes.c_uint32 * n)(*[int(s) for s in seeds]) if seeds is not None else None, out,
+                                             ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_crc32_batch_device failed (%d): %s" % (rc, engine.last_error()))
+    return [int(v) for v in out]
+
+
+def png_file_bound(idat_len, idat_chunk_bytes=0, extra_len=0):
+    """zs_png_file_bound (host code, no GPU): bytes of the PNG file around a zlib stream of idat_len bytes in IDAT chunks of at
+    most idat_chunk_bytes data bytes (0: one chunk) with extra_len bytes of caller chunks.  ValueError for bad arguments."""
+    idat_len, idat_chunk_bytes, extra_len = int(idat_len), int(idat_chunk_bytes), int(extra_len)
+    ok = 0 <= idat_len < 1 << 60 and 0 <= extra_len < 1 << 60 and 0 <= idat_chunk_bytes <= 0x7FFFFFFF
+    v = _native.lib().zs_png_file_bound(idat_len, idat_chunk_bytes, extra_len) if ok else -1
+    if v < 0:
+        raise ValueError("png_file_bound: non-negative lengths and 0 <= idat_chunk_bytes <= 2^31 - 1 are required (one chunk holds 2^31 - 1 bytes)")
+    return int(v)
+
+
+def _png_chunks_well_formed(b):
+    at = 0
+    while at < len(b):
+        if len(b) - at < 12:
+            return False
+        n = int.from_bytes(b[at:at + 4], "big")
+        if n > 0x7FFFFFFF or n > len(b) - at - 12:
+            return False
+        at += 12 + n
+    return True
+
+
+def png_encode_batch_device(engine, pixel_ptrs, widths, heights, bit_depths, color_types, filters, out_ptrs, out_caps, extra=None,
+                            rows_per_write=1, idat_chunk_bytes=0, level=6, strategy=0, hash_variant=0, stream=None, return_status=False):
+    """Pixels -> complete PNG files for many device-resident images in one call (zs_png_encode_batch_device): the zlib stream
+    of png_idat_batch_device (same filters, rows_per_write, level, strategy) cut into IDAT chunks of at most idat_chunk_bytes
+    data bytes (0: one chunk), between signature + IHDR + extra[i] and IEND.  pixel_ptrs[i]: heights[i] rows of
+    ceil(widths[i] * bit_depths[i] * channels / 8) bytes; extra: None or one bytes object per image of chunks framed already
+    (PLTE, tRNS, ...), written verbatim behind IHDR.  Returns the file lengths; return_status: (rc, lengths, statuses), -5
+    (ZS_BUF_ERROR) for an image whose out_caps entry is below its file's length."""
+    n = len(pixel_ptrs)
+    if not (len(widths) == len(heights) == len(bit_depths) == len(color_types) == len(filters) == len(out_ptrs) == len(out_caps) == n) or \
+            (extra is not None and len(extra) != n):
+        raise ValueError("png_encode_batch_device: the argument lists differ in length")
+    if int(rows_per_write) < 0 or not 0 <= int(idat_chunk_bytes) <= 0x7FFFFFFF:
+        raise ValueError("png_encode_batch_device: rows_per_write >= 0 and 0 <= idat_chunk_bytes <= 2^31 - 1 are required")
+    if not -1 <= int(level) <= 9 or not 0 <= int(strategy) <= 4:
+        raise ValueError("png_encode_batch_device: level -1..9 and strategy 0..4 are required")
+    for p, w, h, bd, ct, f, o, cap in zip(pixel_ptrs, widths, heights, bit_depths, color_types, filters, out_ptrs, out_caps):
+        if not p or not o or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF or not 0 <= int(f) <= 5 or int(cap) < 0:
+            raise ValueError("png_encode_batch_device: 1 <= width, height <= 2^31 - 1, filter 0..5 and non-null device pointers are required")
+        if int(ct) not in PNG_COLOR_TYPES or int(bd) not in PNG_COLOR_TYPES[int(ct)][1]:
+            raise ValueError("png_encode_batch_device: color type %r with bit depth %r is not in PNG specification table 11.1" % (ct, bd))
+        if int(h) * ((int(w) * int(bd) * PNG_COLOR_TYPES[int(ct)][0] + 7) // 8 + 1) > _CRC_MAX_LEN:
+            raise ValueError("png_encode_batch_device: a filtered image is above 2 GiB - 1 KiB")
+    if sum(int(h) for h in heights) > 0x7FFFFFFF:
+        raise ValueError("png_encode_batch_device: more than 2^31 - 1 rows in one call")
+    if extra is not None:
+        extra = [bytes(x) if x is not None else b"" for x in extra]
+        if not all(_png_chunks_well_formed(x) for x in extra):
+            raise ValueError("png_encode_batch_device: an image's extra chunks are not a sequence of whole chunks")
+    if n == 0:
+        return (0, [], []) if return_status else []
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    # (the bytes objects are read in place: they outlive the call)
+    x_ptr = VP(*[ctypes.cast(ctypes.c_char_p(x), ctypes.c_void_p).value if x else None for x in extra]) if extra is not None else None
+    x_len = I64(*[len(x) for x in extra]) if extra is not None else None
+    rc = _native.lib().zs_png_encode_batch_device(engine.handle, n, VP(*[int(p) for p in pixel_ptrs]), I64(*[int(x) for x in widths]),
+                                                  I64(*[int(x) for x in heights]), I32(*[int(x) for x in bit_depths]),
+                                                  I32(*[int(x) for x in color_types]), I32(*[int(x) for x in filters]), x_ptr, x_len,
+                                                  int(rows_per_write), int(idat_chunk_bytes), VP(*[int(p) for p in out_ptrs]),
+                                                  I64(*[int(x) for x in out_caps]), out_len, status, int(level), int(strategy),
+                                                  int(hash_variant), ctypes.c_void_p(stream or 0))
+    if return_status:
+        return rc, list(out_len), list(status)
+    if rc != 0:
+        raise ZlibStreamException("png encode: " + engine.last_error())
+    return list(out_len)
+
+
+_PNG_INFO_FIELDS = ("width", "height", "bit_depth", "color_type", "interlace", "bits_per_pixel", "idat_bytes", "pixel_bytes", "n_idat")
+
+
+def png_file_info(data):
+    """zs_png_file_info (host code, no GPU, no engine): the chunk walk of one PNG file given as bytes -> a dict of width,
+    height, bit_depth, color_type, interlace, bits_per_pixel, idat_bytes, pixel_bytes, n_idat.  ZlibStreamException for a
+    file that is not a whole PNG: bad signature, truncated chunk, IHDR missing / not first / out of specification, no IDAT,
+    IDAT chunks not consecutive, missing IEND, a wrong CRC in IHDR, PLTE, IDAT or IEND (ancillary chunks are not verified)."""
+    data = bytes(data)
+    info = _native.PngInfo()
+    rc = _native.lib().zs_png_file_info(data, len(data), ctypes.byref(info))
+    if rc != 0:
+        raise ZlibStreamException("png_file_info: not a whole PNG file (%d)" % rc)
+    return {k: int(getattr(info, k)) for k in _PNG_INFO_FIELDS}
+
+
+def png_decode_files_batch(engine, files, out_ptrs, out_caps, stream=None):
+    """PNG files (bytes objects in host memory) -> raw scanline pixels in device buffers, many files a call
+    (zs_png_decode_files_batch): the chunk walk on the host, one upload, the critical chunks' CRC-32 and the gather of the
+    IDAT data on the device, then inflate, reconstruction and the Adam7 interleave.  Returns (statuses, infos): 0, -5
+    (ZS_BUF_ERROR: out_caps[i] below the image's pixel_bytes) or -3 (ZS_DATA_ERROR; engine.last_error() names the first
+    failing file and the reason; the other files are decoded all the same), and one png_file_info dict per file."""
+    n = len(files)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("png_decode_files_batch: the argument lists differ in length")
+    if any(not o or int(cap) < 0 for o, cap in zip(out_ptrs, out_caps)):
+        raise ValueError("png_decode_files_batch: non-null device pointers and non-negative capacities are required")
+    if n == 0:
+        return [], []
+    files = [bytes(f) for f in files]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    info, status = (_native.PngInfo * n)(), I32()
+    rc = _native.lib().zs_png_decode_files_batch(engine.handle, n, VP(*[ctypes.cast(ctypes.c_char_p(f), ctypes.c_void_p).value for f in files]),  # (read in place)
+                                                 I64(*[len(f) for f in files]),
+                                                 VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), info, status,
+                                                 ctypes.c_void_p(stream or 0))
+    if rc not in (0, -3, -5):
+        raise ValueError("zs_png_decode_files_batch failed (%d): %s" % (rc, engine.last_error()))
+    return list(status), [{k: int(getattr(i, k)) for k in _PNG_INFO_FIELDS} for i in info]
+
+
 _default_engine = None
 
 

@@ -1,0 +1,252 @@
+// zs_crc32.h -- CRC-32 (IEEE 802.3, reflected polynomial 0xEDB88320; zlib's crc32), the parts that the device kernels
+// (zs_crc32.hip) and the host (the engine's table set-up, the PNG chunk walk, tests/cpp/test_crc32.cpp) share: the byte
+// step, the table generator, x^n mod P, the GF(2) multiply and the combine; and the PNG chunk walk itself (host only).
+//
+// Representation.  A register value holds a polynomial over GF(2) of degree < 32, bit 31 the coefficient of x^0 (reflected).
+// Feeding a byte b to the register c is  c' = T0[(c ^ b) & 255] ^ (c >> 8);  feeding n zero bytes multiplies c by x^(8n)
+// mod P.  raw(m), the register after message m from a zero register, is linear in m, leading zero bytes leave it zero, and
+//     register(c0, a ++ b) = raw(a) * x^(8 |b|)  ^  raw(b)  ^  c0 * x^(8 (|a| + |b|))
+// which is all the kernels use: a span is cut into tiles, every tile's raw value is scaled by x^(8 * bytes behind it) and
+// the span's register is the XOR of them.  zlib's crc32(seed, buf, len) is ~register(~seed, buf).
+#pragma once
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "zs_core.h"
+
+namespace zs {
+
+constexpr uint32_t kCrc32Poly = 0xEDB88320u;
+constexpr uint32_t kCrc32One = 0x80000000u;  // x^0
+
+// eight steps of the register: entry i of the byte table T0 is crc32_byte_step(i)
+ZS_HD uint32_t crc32_byte_step(uint32_t c) {
+    for (int k = 0; k < 8; k++) c = (c >> 1) ^ (kCrc32Poly & (0u - (c & 1u)));
+    return c;
+}
+// table-free form of the byte step for cold paths
+ZS_HD uint32_t crc32_feed_byte(uint32_t c, uint32_t b) { return crc32_byte_step((c ^ b) & 0xFF) ^ (c >> 8); }
+// entry i of slice table t: the register after byte i and t zero bytes, from zero (t = 0: T0)
+ZS_HD uint32_t crc32_table_entry(int t, uint32_t i) {
+    uint32_t c = crc32_byte_step(i);
+    for (int k = 0; k < t; k++) c = crc32_byte_step(c & 0xFF) ^ (c >> 8);
+    return c;
+}
+
+// a * b mod P
+ZS_HD uint32_t crc32_mul(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 31; i >= 0; i--) {
+        p ^= b & (0u - ((a >> i) & 1u));
+        b = (b >> 1) ^ (kCrc32Poly & (0u - (b & 1u)));
+    }
+    return p;
+}
+
+// x2n[k] = x^(2^k) mod P, k = 0..31 (x^(2^32) = x: the table is used cyclically)
+ZS_HD void crc32_x2n_table(uint32_t *x2n) {
+    uint32_t p = kCrc32One >> 1;  // x^1
+    for (int k = 0; k < 32; k++) {
+        x2n[k] = p;
+        p = crc32_mul(p, p);
+    }
+}
+// x^(n * 2^k) mod P
+template <class Tab>
+ZS_HD uint32_t crc32_xpow(const Tab &x2n, uint64_t n, unsigned k) {
+    uint32_t p = kCrc32One;
+    for (; n; n >>= 1, k++)
+        if (n & 1) p = crc32_mul(x2n[k & 31], p);
+    return p;
+}
+// zlib's crc32_combine: the CRC of a ++ b from crc(a), crc(b) and |b|
+template <class Tab>
+ZS_HD uint32_t crc32_combine(const Tab &x2n, uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+    return crc32_mul(crc32_xpow(x2n, len_b, 3), crc_a) ^ crc_b;
+}
+
+// zlib's crc32(seed, buf, len) a byte at a time; t0: the 256 entries of T0
+template <class Tab>
+ZS_HD uint32_t crc32_bytes(const Tab &t0, uint32_t seed, const uint8_t *p, uint64_t len) {
+    uint32_t c = ~seed;
+    for (uint64_t i = 0; i < len; i++) c = t0[(c ^ p[i]) & 0xFF] ^ (c >> 8);
+    return ~c;
+}
+// ... and without a table (cold paths: a chunk type, IHDR, IEND)
+ZS_HD uint32_t crc32_bytes_slow(uint32_t seed, const uint8_t *p, uint64_t len) {
+    uint32_t c = ~seed;
+    for (uint64_t i = 0; i < len; i++) c = crc32_feed_byte(c, p[i]);
+    return ~c;
+}
+
+// ---- the tile kernel's geometry (zs_crc32.hip) ----
+constexpr int kCrcTile = 8192;      // bytes of a span one wave takes at a time
+constexpr int kCrcWaves = 4;        // waves of a workgroup = tiles it takes in one pass
+constexpr int kCrcStride = 64 * 16; // strided form: bytes between two words of a lane
+constexpr int kCrcPow128 = kCrcTile / 16 + 2;  // entries of the table x^(128 q): a tile and its head word
+// The tables the kernels read, in one device allocation (uint32 each):
+//   slice[16][256]   crc32_table_entry(t, i)
+//   shift[4][256]    byte j of a register moved kCrcStride bytes on: T0[i] * x^(8 (kCrcStride - 1 - j))
+//   pow128[kCrcPow128]  x^(128 q)      pow8[16]  x^(8 r)      x2n[32]
+constexpr int kCrcTabSlice = 0, kCrcTabShift = 16 * 256, kCrcTabPow128 = 20 * 256, kCrcTabPow8 = kCrcTabPow128 + kCrcPow128,
+              kCrcTabX2n = kCrcTabPow8 + 16, kCrcTabWords = kCrcTabX2n + 32;
+inline void crc32_fill_tables(uint32_t *t) {
+    uint32_t x2n[32];
+    crc32_x2n_table(x2n);
+    for (uint32_t i = 0; i < 256; i++) t[kCrcTabSlice + i] = crc32_byte_step(i);
+    for (int s = 1; s < 16; s++)
+        for (uint32_t i = 0; i < 256; i++) {
+            const uint32_t c = t[kCrcTabSlice + (s - 1) * 256 + i];
+            t[kCrcTabSlice + s * 256 + i] = t[kCrcTabSlice + (c & 0xFF)] ^ (c >> 8);
+        }
+    for (int j = 0; j < 4; j++) {
+        const uint32_t f = crc32_xpow(x2n, (uint64_t)(kCrcStride - 1 - j), 3);
+        for (uint32_t i = 0; i < 256; i++) t[kCrcTabShift + j * 256 + i] = crc32_mul(t[kCrcTabSlice + i], f);
+    }
+    for (int q = 0; q < kCrcPow128; q++) t[kCrcTabPow128 + q] = crc32_xpow(x2n, (uint64_t)q, 7);
+    for (int r = 0; r < 16; r++) t[kCrcTabPow8 + r] = crc32_xpow(x2n, (uint64_t)r, 3);
+    for (int k = 0; k < 32; k++) t[kCrcTabX2n + k] = x2n[k];
+}
+
+// One span of a batch.  src: `len` bytes on the device, any alignment; init: the register the span starts from (~seed).
+// dst (may be null): the span's bytes from byte `skip` on are also copied there, any alignment.  frame (may be null): a
+// PNG chunk is closed around the copy -- big-endian length and `type` at frame, the data at frame + 8 = dst, the
+// big-endian CRC behind it (the finishing launch writes the twelve bytes).
+struct Crc32Span {
+    const uint8_t *src;
+    uint8_t *dst, *frame;
+    int64_t len;
+    uint32_t init, skip, type, pad;
+};
+ZS_HD int64_t crc32_span_tiles(int64_t len) { return (len + kCrcTile - 1) / kCrcTile; }
+
+// the span of flat tile t: the last i with tile_off[i] <= t (spans without tiles share their successor's offset)
+template <class Off>
+ZS_HD int crc32_tile_span(const Off &tile_off, int n, uint32_t t) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tile_off[mid] <= t) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// ---- PNG files (PNG specification 5: signature, chunk layout; 11.2.2: IHDR) ----
+ZS_HD int png_channels(int color_type) { return color_type == 0 || color_type == 3 ? 1 : color_type == 2 ? 3 : color_type == 4 ? 2 : color_type == 6 ? 4 : 0; }
+// the (color type, bit depth) pairs of table 11.1
+ZS_HD bool png_color_ok(int color_type, int bit_depth) {
+    const bool d8_16 = bit_depth == 8 || bit_depth == 16, d1_8 = bit_depth == 1 || bit_depth == 2 || bit_depth == 4 || bit_depth == 8;
+    switch (color_type) {
+    case 0: return d1_8 || bit_depth == 16;
+    case 3: return d1_8;
+    case 2: case 4: case 6: return d8_16;
+    default: return false;
+    }
+}
+ZS_HD uint32_t png_be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+ZS_HD void png_put_be32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v; }
+constexpr uint32_t png_type(char a, char b, char c, char d) { return (uint32_t)(uint8_t)a | (uint32_t)(uint8_t)b << 8 | (uint32_t)(uint8_t)c << 16 | (uint32_t)(uint8_t)d << 24; }
+constexpr uint32_t kPngIHDR = png_type('I', 'H', 'D', 'R'), kPngPLTE = png_type('P', 'L', 'T', 'E'), kPngIDAT = png_type('I', 'D', 'A', 'T'),
+                   kPngIEND = png_type('I', 'E', 'N', 'D');
+constexpr int64_t kPngMaxChunk = 0x7FFFFFFF;  // a chunk's data length (PNG specification 5.3)
+
+// bytes of the file that holds a zlib stream of idat_len bytes in IDAT chunks of at most idat_chunk_bytes data bytes
+// (0: one chunk; an empty stream still gets one chunk) and extra_len bytes of caller chunks; -1 for bad arguments
+inline int64_t png_file_bound(int64_t idat_len, int64_t idat_chunk_bytes, int64_t extra_len) {
+    if (idat_len < 0 || extra_len < 0 || idat_chunk_bytes < 0 || idat_chunk_bytes > kPngMaxChunk) return -1;
+    if (idat_chunk_bytes == 0 && idat_len > kPngMaxChunk) return -1;
+    if (idat_len > (int64_t)1 << 60 || extra_len > (int64_t)1 << 60) return -1;
+    const int64_t chunks = idat_chunk_bytes == 0 || idat_len == 0 ? 1 : (idat_len + idat_chunk_bytes - 1) / idat_chunk_bytes;
+    return 8 + 25 + extra_len + idat_len + 12 * chunks + 12;
+}
+// a sequence of complete chunks by its length fields alone
+inline bool png_chunks_well_formed(const uint8_t *p, int64_t len) {
+    int64_t at = 0;
+    while (at < len) {
+        if (len - at < 12) return false;
+        const int64_t n = png_be32(p + at);
+        if (n > kPngMaxChunk || n > len - at - 12) return false;
+        at += 12 + n;
+    }
+    return true;
+}
+
+// What the chunk walk finds in one file.  Mirrors zs_png_info of the C ABI field for field (zs_engine.hip asserts it).
+struct PngFileInfo {
+    int64_t width, height;
+    int bit_depth, color_type, interlace, bits_per_pixel;
+    int64_t idat_bytes, pixel_bytes;
+    int64_t n_idat;
+};
+// one chunk the device is to check (critical chunks) or gather (IDAT): offsets into the file
+struct PngChunkRef {
+    uint32_t type;
+    int64_t at;    // of the chunk's length field
+    int64_t len;   // of its data
+};
+// Walks the chunk chain of a file in host memory: signature, IHDR first and valid, the IDAT run, IEND.  Ancillary chunks
+// are stepped over by their length fields (never interpreted, their CRCs never read).  Returns true and fills `info`, or
+// false with the reason in msg.  emit(ref) is called for every critical chunk (IHDR, PLTE, IDAT, IEND) in file order;
+// check_crc: critical chunks' CRCs are verified here on the host (zs_png_file_info) rather than left to the device.
+template <class Emit>
+inline bool png_walk_file(const uint8_t *f, int64_t len, PngFileInfo *info, char *msg, size_t msg_cap, bool check_crc, Emit emit) {
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+    memset(info, 0, sizeof *info);
+    if (len < 8 || memcmp(f, sig, 8) != 0) return snprintf(msg, msg_cap, "bad signature"), false;
+    int64_t at = 8;
+    bool first = true, in_idat = false, idat_done = false, ended = false;
+    while (at < len) {
+        if (len - at < 8) return snprintf(msg, msg_cap, "truncated chunk at offset %lld", (long long)at), false;
+        const int64_t n = png_be32(f + at);
+        uint32_t type;
+        memcpy(&type, f + at + 4, 4);
+        if (n > kPngMaxChunk || n > len - at - 12 || len - at < 12)
+            return snprintf(msg, msg_cap, "truncated chunk at offset %lld", (long long)at), false;
+        if (first != (type == kPngIHDR)) return snprintf(msg, msg_cap, first ? "IHDR is not the first chunk" : "a second IHDR at offset %lld", (long long)at), false;
+        const bool critical = type == kPngIHDR || type == kPngPLTE || type == kPngIDAT || type == kPngIEND;
+        if (critical && check_crc && crc32_bytes_slow(0, f + at + 4, (uint64_t)n + 4) != png_be32(f + at + 8 + n)) {
+            char t[5] = {(char)f[at + 4], (char)f[at + 5], (char)f[at + 6], (char)f[at + 7], 0};
+            return snprintf(msg, msg_cap, "CRC error in %s chunk at offset %lld", t, (long long)at), false;
+        }
+        if (first) {
+            first = false;
+            if (n != 13) return snprintf(msg, msg_cap, "IHDR holds %lld bytes, not 13", (long long)n), false;
+            const uint8_t *h = f + at + 8;
+            info->width = png_be32(h), info->height = png_be32(h + 4);
+            info->bit_depth = h[8], info->color_type = h[9], info->interlace = h[12];
+            if (info->width < 1 || info->width > 0x7FFFFFFF || info->height < 1 || info->height > 0x7FFFFFFF)
+                return snprintf(msg, msg_cap, "IHDR: width or height outside 1 .. 2^31 - 1"), false;
+            if (!png_color_ok(info->color_type, info->bit_depth))
+                return snprintf(msg, msg_cap, "IHDR: color type %d with bit depth %d", info->color_type, info->bit_depth), false;
+            if (h[10] != 0 || h[11] != 0 || h[12] > 1)
+                return snprintf(msg, msg_cap, "IHDR: compression %d, filter %d, interlace %d", h[10], h[11], h[12]), false;
+            info->bits_per_pixel = info->bit_depth * png_channels(info->color_type);
+            const int64_t rb = (info->width * info->bits_per_pixel + 7) >> 3;
+            info->pixel_bytes = rb > INT64_MAX / info->height ? INT64_MAX : info->height * rb;  // (saturates: 2^31 rows of 2^34 bytes)
+        }
+        if (type == kPngIDAT) {
+            if (idat_done) return snprintf(msg, msg_cap, "IDAT chunks are not consecutive (offset %lld)", (long long)at), false;
+            in_idat = true;
+            info->n_idat++, info->idat_bytes += n;
+        } else if (in_idat)
+            in_idat = false, idat_done = true;
+        if (critical) emit(PngChunkRef{type, at, n});
+        at += 12 + n;
+        if (type == kPngIEND) {
+            ended = true;
+            break;  // (bytes behind IEND are not the file's)
+        }
+    }
+    if (first) return snprintf(msg, msg_cap, "IHDR is missing"), false;
+    if (info->n_idat == 0) return snprintf(msg, msg_cap, "no IDAT chunk"), false;
+    if (!ended) return snprintf(msg, msg_cap, "IEND is missing"), false;
+    return true;
+}
+
+}  // namespace zs

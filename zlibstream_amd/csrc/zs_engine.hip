@@ -17,6 +17,7 @@
 #include "zs_inflate_par.hip"
 #include "zs_inflate_tok.hip"
 #include "zs_png.hip"
+#include "zs_crc32.hip"
 
 using namespace zs;
 
@@ -29,10 +30,10 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
-                                           "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify"};
+                                           "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame"};
 
 }  // namespace
 
@@ -70,7 +71,9 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather;
+    uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
+    hipEvent_t ev_crc[2] = {};            // KC and its finishing launch (profiling)
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1536,6 +1539,7 @@ int zs_ctx_create(int device, zs_ctx **out) {
     }
     for (auto &e : c->ev) (void)hipEventCreate(&e);
     for (auto &e : c->ev_spec) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_crc) (void)hipEventCreate(&e);
     {
         // the link kernel relies on the LDS applying the lanes of one DS_MSKOR_RTN_B32 in lane order: check it here
         int *d_ok = nullptr, ok = 0;
@@ -1606,10 +1610,13 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
+    if (c->crc32_tab) (void)hipFree(c->crc32_tab);
+    for (auto &e : c->ev_crc)
+        if (e) (void)hipEventDestroy(e);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pin_io) (void)hipHostFree(c->pin_io);
     if (c->pin_out) (void)hipHostFree(c->pin_out);
@@ -1683,6 +1690,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
+    if (s == kStCrc32) return kStageNames[s];  // KC: the CRC-32 calls, the framing of PNG files, the check and gather of their chunks
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine
@@ -2765,6 +2773,405 @@ extern "C" int zs_png_decode_batch_device(zs_ctx *c, int n, const void *const *i
         if (st[(size_t)i] != ZS_OK) c->err = why[(size_t)i], rc = ZS_DATA_ERROR;  // (downwards: the first failing image's message stays)
     }
     return finish(rc);
+}
+
+// ------------------------------------------------------------------ CRC-32 (KC, zs_crc32.hip), PNG files on top of it
+namespace {
+static_assert(sizeof(zs_png_info) == sizeof(PngFileInfo) && offsetof(zs_png_info, n_idat) == offsetof(PngFileInfo, n_idat), "zs_png_info mirrors PngFileInfo");
+
+// One KC job: m spans and `blob` bytes the caller's spans may read or frame (host bytes that travel with the descriptors),
+// laid out in the staging buffer as [spans][tile offsets][blob][results] and on the device, in crc_desc, as the first three.
+struct Crc32Job {
+    int m = 0;
+    size_t b_sp = 0, b_off = 0, b_blob = 0;
+    Crc32Span *spans = nullptr;     // staging: the caller fills these ...
+    uint8_t *blob = nullptr;        // ... and this,
+    uint8_t *d_blob = nullptr;      // which the device sees here
+    const uint32_t *crc = nullptr;  // staging: zlib's crc32 of every span, once the job has run
+    double ms = 0;                  // profiling: KC and its finishing launch
+};
+
+bool crc32_begin(zs_ctx *c, int m, size_t blob_bytes, Crc32Job *job, bool *no_memory) {
+    *no_memory = false;
+    if (!c->crc32_tab) {
+        std::vector<uint32_t> tab((size_t)kCrcTabWords);
+        crc32_fill_tables(tab.data());
+        if (hipMalloc((void **)&c->crc32_tab, 4 * tab.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            c->crc32_tab = nullptr;
+            c->err = "out of device memory";
+            *no_memory = true;
+            return false;
+        }
+        ZS_HIP(c, hipMemcpy(c->crc32_tab, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice));
+    }
+    job->m = m;
+    job->b_sp = sizeof(Crc32Span) * (size_t)m;
+    job->b_off = (sizeof(uint32_t) * ((size_t)m + 1) + 255) & ~(size_t)255;
+    job->b_blob = (blob_bytes + 255) & ~(size_t)255;
+    const size_t up = job->b_sp + job->b_off + job->b_blob;
+    if (!ensure(c, c->crc_desc, up) || !ensure(c, c->crc_res, 2 * sizeof(uint32_t) * (size_t)m) || !ensure_pinned(c, up + sizeof(uint32_t) * (size_t)m)) {
+        *no_memory = true;
+        return false;
+    }
+    uint8_t *hp = (uint8_t *)c->pinned;
+    job->spans = (Crc32Span *)hp;
+    job->blob = hp + job->b_sp + job->b_off;
+    job->d_blob = (uint8_t *)c->crc_desc.p + job->b_sp + job->b_off;
+    job->crc = (const uint32_t *)(hp + up);
+    return true;
+}
+
+// Uploads the job, runs KC and the finishing launch and waits for `s` once; the CRCs are in job->crc afterwards.
+bool crc32_run(zs_ctx *c, Crc32Job *job, hipStream_t s) {
+    const int m = job->m;
+    uint32_t *off = (uint32_t *)((uint8_t *)c->pinned + job->b_sp);
+    uint64_t tiles = 0;
+    for (int i = 0; i < m; i++) {
+        off[i] = (uint32_t)tiles;
+        tiles += (uint64_t)crc32_span_tiles(job->spans[i].len);
+        if (tiles > 0x7FFFFFFFu) {
+            c->err = "stream error: more than 2^31 - 1 tiles of 8 KiB in one call (split the batch)";
+            return false;
+        }
+    }
+    off[m] = (uint32_t)tiles;
+    const size_t up = job->b_sp + job->b_off + job->b_blob;
+    const Crc32Span *d_sp = (const Crc32Span *)c->crc_desc.p;
+    const uint32_t *d_off = (const uint32_t *)((const uint8_t *)c->crc_desc.p + job->b_sp);
+    uint32_t *d_res = (uint32_t *)c->crc_res.p, *d_crc = d_res + m;
+    ZS_HIP(c, hipMemcpyAsync(c->crc_desc.p, c->pinned, up, hipMemcpyHostToDevice, s));
+    const bool prof = c->profiling;
+    if (prof) (void)hipEventRecord(c->ev_crc[0], s);
+    ZS_HIP(c, hipMemsetAsync(d_res, 0, sizeof(uint32_t) * (size_t)m, s));
+    if (tiles) {
+        // (measurements of the two forms: DESIGN.md section 4, KC)
+        static const int form = getenv("ZS_CRC32_FORM") ? atoi(getenv("ZS_CRC32_FORM")) : 0;
+        const unsigned groups = (unsigned)((tiles + kCrcWaves - 1) / kCrcWaves);
+        const dim3 grid(std::min<unsigned>(groups, 2048)), block(64 * kCrcWaves);  // eight workgroups a CU keep their tables
+        if (form == 1) hipLaunchKernelGGL(zs_crc32_tile_kernel<false>, grid, block, 0, s, d_sp, d_off, m, (uint32_t)tiles, c->crc32_tab, d_res);
+        else hipLaunchKernelGGL(zs_crc32_tile_kernel<true>, grid, block, 0, s, d_sp, d_off, m, (uint32_t)tiles, c->crc32_tab, d_res);
+        ZS_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(zs_crc32_finish_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d_sp, m, (const uint32_t *)d_res, d_crc);
+    ZS_HIP(c, hipGetLastError());
+    if (prof) (void)hipEventRecord(c->ev_crc[1], s);
+    ZS_HIP(c, hipMemcpyAsync((void *)job->crc, d_crc, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
+    ZS_HIP(c, hipStreamSynchronize(s));
+    if (prof) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev_crc[0], c->ev_crc[1]);
+        job->ms = ms;
+    }
+    return true;
+}
+constexpr int64_t kCrcMaxLen = 0x7FFFFFFF - 1024;
+}  // namespace
+
+extern "C" int zs_crc32_batch_device(zs_ctx *c, int n, const void *const *d_buf, const int64_t *len, const uint32_t *seed, uint32_t *out, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!d_buf || !len || !out) return ZS_STREAM_ERROR;
+    for (int i = 0; i < n; i++)
+        if (len[i] < 0 || len[i] > kCrcMaxLen || (len[i] > 0 && !d_buf[i])) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    Crc32Job job;
+    bool no_memory = false;
+    if (!crc32_begin(c, n, 0, &job, &no_memory)) return no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+    for (int i = 0; i < n; i++) job.spans[i] = Crc32Span{(const uint8_t *)d_buf[i], nullptr, nullptr, len[i], ~(seed ? seed[i] : 0u), 0, 0, 0};
+    if (!crc32_run(c, &job, s)) return ZS_STREAM_ERROR;
+    memcpy(out, job.crc, sizeof(uint32_t) * (size_t)n);
+    if (c->profiling) {
+        for (double &v : c->stage_ms) v = 0;
+        c->stage_ms[kStCrc32] = job.ms;
+    }
+    return ZS_OK;
+}
+
+extern "C" int zs_crc32_device(zs_ctx *c, const void *d_buf, int64_t len, uint32_t seed, uint32_t *out, void *hip_stream) {
+    return zs_crc32_batch_device(c, 1, &d_buf, &len, &seed, out, hip_stream);
+}
+
+extern "C" int64_t zs_png_file_bound(int64_t idat_len, int64_t idat_chunk_bytes, int64_t extra_len) {
+    return png_file_bound(idat_len, idat_chunk_bytes, extra_len);
+}
+
+// Pixels -> files: the IDAT call into a buffer of the context, then KC over [signature, IHDR, extra] / every IDAT chunk / IEND
+// of every image that fits its output.
+extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *width, const int64_t *height, const int *bit_depth,
+                                          const int *color_type, const int *filter, const void *const *extra, const int64_t *extra_len, int64_t rows_per_write,
+                                          int64_t idat_chunk_bytes, void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level,
+                                          int strategy, int hash_variant, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!pixels || !width || !height || !bit_depth || !color_type || !filter || !out || !out_cap || !out_len || (extra && !extra_len)) return ZS_STREAM_ERROR;
+    if (rows_per_write < 0 || idat_chunk_bytes < 0 || idat_chunk_bytes > kPngMaxChunk || level < -1 || level > 9 || strategy < 0 || strategy > 4) {
+        c->err = "stream error";
+        return ZS_STREAM_ERROR;
+    }
+    std::vector<int64_t> rb((size_t)n), xlen((size_t)n, 0), zcap((size_t)n);
+    std::vector<int> bpp((size_t)n);
+    int64_t total_rows = 0;
+    size_t z_total = 0, x_total = 0;
+    for (int i = 0; i < n; i++) {
+        const bool dims = width[i] >= 1 && width[i] <= 0x7FFFFFFF && height[i] >= 1 && height[i] <= 0x7FFFFFFF;
+        if (!pixels[i] || !out[i] || !dims || !png_color_ok(color_type[i], bit_depth[i]) || filter[i] < 0 || filter[i] > 5 || out_cap[i] < 0) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        const int bits = bit_depth[i] * png_channels(color_type[i]);
+        rb[(size_t)i] = png_bits_row_bytes(width[i], bits);
+        bpp[(size_t)i] = png_bits_bpp(bits);
+        if (height[i] * (rb[(size_t)i] + 1) > kCrcMaxLen) {  // (a stream's input is indexed with 32 bits)
+            c->err = "stream error: a filtered image is above 2 GiB - 1 KiB";
+            return ZS_STREAM_ERROR;
+        }
+        if (extra) {
+            xlen[(size_t)i] = extra_len[i];
+            if (xlen[(size_t)i] < 0 || (xlen[(size_t)i] > 0 && !extra[i]) || !png_chunks_well_formed((const uint8_t *)extra[i], xlen[(size_t)i])) {
+                c->err = "stream error: the extra chunks of an image are not a sequence of whole chunks";
+                return ZS_STREAM_ERROR;
+            }
+        }
+        zcap[(size_t)i] = zs_deflate_bound(height[i] * (rb[(size_t)i] + 1));
+        z_total += ((size_t)zcap[(size_t)i] + 255) & ~(size_t)255;
+        x_total += 8 + 25 + (size_t)xlen[(size_t)i] + 12;
+        total_rows += height[i];
+    }
+    if (total_rows > 0x7FFFFFFF) {
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    std::vector<int> st((size_t)n, ZS_STREAM_ERROR);
+    auto finish = [&](int rc) {
+        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
+        return rc;
+    };
+    if (!ensure(c, c->png_zs, z_total + 256)) {
+        std::fill(st.begin(), st.end(), (int)ZS_MEM_ERROR);
+        return finish(ZS_MEM_ERROR);
+    }
+    std::vector<void *> zs_out((size_t)n);
+    std::vector<int64_t> zlen((size_t)n, 0);
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        zs_out[(size_t)i] = (uint8_t *)c->png_zs.p + at;
+        at += ((size_t)zcap[(size_t)i] + 255) & ~(size_t)255;
+    }
+    const int zrc = zs_png_idat_batch_device(c, n, pixels, rb.data(), height, bpp.data(), filter, rows_per_write, zs_out.data(), zcap.data(), zlen.data(), st.data(),
+                                             level, strategy, hash_variant, (void *)s);
+    if (zrc != ZS_OK) {
+        for (int i = 0; i < n; i++) out_len[i] = 0;
+        return finish(zrc);
+    }
+    // ---- the layout: which images fit, and their spans
+    int64_t n_spans = 0;
+    int rc = ZS_OK;
+    for (int i = 0; i < n; i++) {
+        out_len[i] = png_file_bound(zlen[(size_t)i], idat_chunk_bytes, xlen[(size_t)i]);
+        if (out_len[i] < 0) {  // (one chunk cannot hold the stream: unreachable below 2 GiB)
+            st[(size_t)i] = ZS_STREAM_ERROR;
+            if (rc == ZS_OK) rc = ZS_STREAM_ERROR, c->err = "stream error";
+            continue;
+        }
+        if (out_cap[i] < out_len[i]) {
+            st[(size_t)i] = ZS_BUF_ERROR;
+            if (rc == ZS_OK) rc = ZS_BUF_ERROR, c->err = "buffer error";
+            continue;
+        }
+        const int64_t chunks = idat_chunk_bytes == 0 || zlen[(size_t)i] == 0 ? 1 : (zlen[(size_t)i] + idat_chunk_bytes - 1) / idat_chunk_bytes;
+        n_spans += 2 + chunks;
+    }
+    if (n_spans > 0x3FFFFFFF) {
+        c->err = "stream error: too many IDAT chunks in one call";
+        return finish(ZS_STREAM_ERROR);
+    }
+    if (n_spans == 0) return finish(rc);
+    Crc32Job job;
+    bool no_memory = false;
+    if (!crc32_begin(c, (int)n_spans, x_total, &job, &no_memory)) {
+        for (int i = 0; i < n; i++)
+            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+        return finish(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    }
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+    static const uint8_t idat_type[4] = {'I', 'D', 'A', 'T'};
+    const uint32_t idat_init = ~crc32_bytes_slow(0, idat_type, 4);
+    size_t k = 0, b = 0;
+    for (int i = 0; i < n; i++) {
+        if (st[(size_t)i] != ZS_OK) continue;
+        uint8_t *o = (uint8_t *)out[i];
+        // signature, IHDR and the caller's chunks: host bytes, placed by a copy span
+        uint8_t *hd = job.blob + b;
+        memcpy(hd, sig, 8);
+        png_put_be32(hd + 8, 13);
+        memcpy(hd + 12, "IHDR", 4);
+        png_put_be32(hd + 16, (uint32_t)width[i]), png_put_be32(hd + 20, (uint32_t)height[i]);
+        hd[24] = (uint8_t)bit_depth[i], hd[25] = (uint8_t)color_type[i], hd[26] = 0, hd[27] = 0, hd[28] = 0;
+        png_put_be32(hd + 29, crc32_bytes_slow(0, hd + 12, 17));
+        if (xlen[(size_t)i]) memcpy(hd + 33, extra[i], (size_t)xlen[(size_t)i]);
+        const int64_t head = 33 + xlen[(size_t)i];
+        job.spans[k++] = Crc32Span{job.d_blob + b, o, nullptr, head, 0xFFFFFFFFu, 0, 0, 0};
+        b += (size_t)head;
+        int64_t pos = head, zat = 0;
+        const int64_t zl = zlen[(size_t)i], step = idat_chunk_bytes == 0 ? zl : idat_chunk_bytes;
+        do {
+            const int64_t len = std::min(step, zl - zat);
+            job.spans[k++] = Crc32Span{(const uint8_t *)zs_out[(size_t)i] + zat, o + pos + 8, o + pos, len, idat_init, 0, kPngIDAT, 0};
+            pos += 12 + len, zat += len;
+        } while (zat < zl);
+        uint8_t *tl = job.blob + b;
+        png_put_be32(tl, 0);
+        memcpy(tl + 4, "IEND", 4);
+        png_put_be32(tl + 8, crc32_bytes_slow(0, tl + 4, 4));
+        job.spans[k++] = Crc32Span{job.d_blob + b, o + pos, nullptr, 12, 0xFFFFFFFFu, 0, 0, 0};
+        b += 12;
+    }
+    if (!crc32_run(c, &job, s)) return finish(ZS_STREAM_ERROR);
+    if (c->profiling) c->stage_ms[kStCrc32] = job.ms;
+    return finish(rc);
+}
+
+extern "C" int zs_png_file_info(const void *file, int64_t len, zs_png_info *info) {
+    if (!file || !info || len < 0) return ZS_STREAM_ERROR;
+    char msg[160];
+    return png_walk_file((const uint8_t *)file, len, (PngFileInfo *)info, msg, sizeof msg, true, [](const PngChunkRef &) {}) ? ZS_OK : ZS_DATA_ERROR;
+}
+
+// Files -> pixels: the walk on the host, one upload, KC over the critical chunks (IDAT data gathered on the way), then the
+// decode call on the gathered streams of the files that are whole.
+extern "C" int zs_png_decode_files_batch(zs_ctx *c, int n, const void *const *file, const int64_t *file_len, void *const *out, const int64_t *out_cap,
+                                         zs_png_info *info, int *status, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!file || !file_len || !out || !out_cap) return ZS_STREAM_ERROR;
+    for (int i = 0; i < n; i++)
+        if (!file[i] || !out[i] || file_len[i] < 0 || out_cap[i] < 0) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+    std::vector<PngFileInfo> fi((size_t)n);
+    std::vector<std::string> why((size_t)n);
+    std::vector<int> st((size_t)n, ZS_OK);
+    std::vector<std::vector<PngChunkRef>> refs((size_t)n);
+    size_t blob = 0, gather = 0;
+    int64_t n_spans = 0, rows = 0;
+    char msg[192];
+    for (int i = 0; i < n; i++) {
+        auto &r = refs[(size_t)i];
+        PngFileInfo &f = fi[(size_t)i];
+        if (!png_walk_file((const uint8_t *)file[i], file_len[i], &f, msg, sizeof msg, false, [&](const PngChunkRef &x) { r.push_back(x); })) {
+            st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = msg;
+        } else if (f.idat_bytes > kCrcMaxLen || zs_png_idat_layout(f.width, f.height, f.bits_per_pixel, f.interlace, nullptr, nullptr) > kCrcMaxLen) {
+            st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = "the image or its IDAT data is above 2 GiB - 1 KiB";
+        } else if (out_cap[i] < f.pixel_bytes) {
+            snprintf(msg, sizeof msg, "the image needs %lld bytes, out_cap is %lld", (long long)f.pixel_bytes, (long long)out_cap[i]);
+            st[(size_t)i] = ZS_BUF_ERROR, why[(size_t)i] = msg;
+        }
+        if (info) memcpy(&info[i], &f, sizeof f);
+        if (st[(size_t)i] != ZS_OK) continue;
+        int64_t r7[kAdam7Passes];
+        (void)zs_png_idat_layout(f.width, f.height, f.bits_per_pixel, f.interlace, nullptr, r7);
+        for (int64_t v : r7) rows += v;
+        blob += ((size_t)file_len[i] + 255) & ~(size_t)255;
+        gather += ((size_t)f.idat_bytes + 255) & ~(size_t)255;
+        n_spans += (int64_t)r.size();
+    }
+    auto finish = [&](int rc) {
+        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
+        return rc;
+    };
+    auto verdict = [&]() {  // the first failing file's code and message
+        for (int i = 0; i < n; i++)
+            if (st[(size_t)i] != ZS_OK) {
+                c->err = std::string(st[(size_t)i] == ZS_BUF_ERROR ? "buffer error: file " : "data error: file ") + std::to_string(i) + ": " + why[(size_t)i];
+                return finish(st[(size_t)i]);
+            }
+        return finish(ZS_OK);
+    };
+    if (n_spans > 0x3FFFFFFF || rows > 0x7FFFFFFF) {
+        c->err = "stream error: too many chunks or rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (n_spans == 0) return verdict();
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    auto all_fail = [&](int code) {
+        for (int &v : st)
+            if (v == ZS_OK) v = code;
+        return finish(code);
+    };
+    Crc32Job job;
+    bool no_memory = false;
+    if (!ensure(c, c->png_gather, gather + 256)) return all_fail(ZS_MEM_ERROR);
+    if (!crc32_begin(c, (int)n_spans, blob, &job, &no_memory)) return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    std::vector<const void *> idat;
+    std::vector<int> who;  // the files that go on
+    size_t k = 0, b = 0, g = 0;
+    for (int i = 0; i < n; i++) {
+        if (st[(size_t)i] != ZS_OK) continue;
+        memcpy(job.blob + b, file[i], (size_t)file_len[i]);
+        who.push_back(i);
+        idat.push_back((const uint8_t *)c->png_gather.p + g);
+        size_t ga = g;
+        for (const PngChunkRef &x : refs[(size_t)i]) {
+            uint8_t *dst = x.type == kPngIDAT ? (uint8_t *)c->png_gather.p + ga : nullptr;
+            job.spans[k++] = Crc32Span{job.d_blob + b + x.at + 4, dst, nullptr, x.len + 4, 0xFFFFFFFFu, 4, 0, 0};
+            if (dst) ga += (size_t)x.len;
+        }
+        b += ((size_t)file_len[i] + 255) & ~(size_t)255;
+        g += ((size_t)fi[(size_t)i].idat_bytes + 255) & ~(size_t)255;
+    }
+    if (!crc32_run(c, &job, s)) return all_fail(ZS_STREAM_ERROR);
+    const double crc_ms = job.ms;
+    k = 0;
+    std::vector<const void *> d_idat;
+    std::vector<int64_t> d_len, d_w, d_h;
+    std::vector<int> d_bits, d_il, d_who;
+    std::vector<void *> d_out;
+    for (size_t j = 0; j < who.size(); j++) {
+        const int i = who[j];
+        const uint8_t *f = (const uint8_t *)file[i];
+        for (const PngChunkRef &x : refs[(size_t)i]) {
+            const uint32_t got = job.crc[k++];
+            if (st[(size_t)i] == ZS_OK && got != png_be32(f + x.at + 8 + x.len)) {
+                snprintf(msg, sizeof msg, "CRC error in %.4s chunk at offset %lld", (const char *)f + x.at + 4, (long long)x.at);
+                st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = msg;
+            }
+        }
+        if (st[(size_t)i] != ZS_OK) continue;
+        const PngFileInfo &p = fi[(size_t)i];
+        d_who.push_back(i), d_idat.push_back(idat[j]), d_len.push_back(p.idat_bytes), d_w.push_back(p.width), d_h.push_back(p.height);
+        d_bits.push_back(p.bits_per_pixel), d_il.push_back(p.interlace), d_out.push_back(out[i]);
+    }
+    if (!d_who.empty()) {
+        std::vector<int> dst_st(d_who.size(), ZS_STREAM_ERROR);
+        const int drc = zs_png_decode_batch_device(c, (int)d_who.size(), d_idat.data(), d_len.data(), d_w.data(), d_h.data(), d_bits.data(), d_il.data(),
+                                                   d_out.data(), dst_st.data(), (void *)s);
+        if (drc != ZS_OK && drc != ZS_DATA_ERROR) return all_fail(drc);
+        const std::string inner = c->err;
+        bool first = true;
+        for (size_t j = 0; j < d_who.size(); j++) {
+            if (dst_st[j] == ZS_OK) continue;
+            st[(size_t)d_who[j]] = dst_st[j];
+            // the decode call's message names its first failing image by its place in that call: keep the reason
+            std::string reason = "the IDAT stream does not decode";
+            if (first) {
+                const size_t colon = inner.find(": ", inner.find("image "));
+                reason = inner.find("image ") != std::string::npos && colon != std::string::npos ? inner.substr(colon + 2) : inner;
+                first = false;
+            }
+            why[(size_t)d_who[j]] = reason;
+        }
+    }
+    if (c->profiling) c->stage_ms[kStCrc32] = crc_ms;
+    return verdict();
 }
 
 // ------------------------------------------------------------------ multi-GPU batch entry points
