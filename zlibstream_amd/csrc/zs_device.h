@@ -196,7 +196,10 @@ struct K5Spec {  // the symbol kernel's arguments on the speculative grid
     uint32_t *rec;
     uint32_t *base;
     int len_bits, warm, corrupt;  // corrupt: the chunk whose recorded guess is spoiled (a test's switch; -1: none)
+    uint32_t *syms;               // the chunks' slabs of provisional symbols, `stride` words each (zs_core.h spec_slab_stride)
+    int stride;
 };
+static_assert(spec_slab_stride(kSpecMaxLenBits) - kSpecSlabPad <= 0xFFF, "spec_pack's count field holds the symbols of the longest chunk");
 constexpr int kDeferBudget = 8;   // cuts with positions to walk again that a stream may repair on its one CU before it is given up
 constexpr int kCutBudget = 12;    // ... and cuts of any kind (a cut without such positions is a scan of 32 Ki records on one CU)
 

@@ -30,10 +30,11 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
-                                           "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame"};
+                                           "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
+                                           "spec_compact"};
 
 }  // namespace
 
@@ -42,7 +43,7 @@ struct zs_ctx {
     hipStream_t stream = nullptr;
     hipStream_t aux = nullptr;  // second stream: tree building of the finished blocks runs beside the tail engine
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pre0 = nullptr, ev_pre = nullptr;
-    hipEvent_t ev_spec[2] = {};           // the speculative walk and its verdict (profiling)
+    hipEvent_t ev_spec[4] = {};           // the speculative walk and its verdict; the compaction of its symbols (profiling)
     hipEvent_t ev_part[16] = {};          // one long stream run part by part: part k's maps are ready
     std::vector<hipEvent_t> ev_pool;      // timing pairs of the part-wise launches (profiling)
     std::string err;
@@ -71,7 +72,7 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather;
     uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
     hipEvent_t ev_crc[2] = {};            // KC and its finishing launch (profiling)
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
@@ -611,7 +612,8 @@ plan_again:
         !ensure(c, c->trees, sizeof(TreeWork) * (size_t)pl.n_blocks) || !ensure(c, c->info, sizeof(BlockInfo) * (size_t)pl.n_blocks) ||
         !ensure(c, c->pieces, 4 * (size_t)pl.n_pieces + 64) || !ensure(c, c->scratch, (size_t)kScratchBytes * (size_t)n) ||
         !ensure(c, c->cut_pos, 8 * (size_t)pl.n_cuts + 64) || !ensure(c, c->cut_bkt, 8 * (size_t)pl.n_cuts + 64) ||
-        (pl.n_spec && (!ensure(c, c->spec_rec, 8 * (size_t)pl.n_spec + 64) || !ensure(c, c->spec_flags, 4 * (size_t)n + 64))))
+        (pl.n_spec && (!ensure(c, c->spec_rec, 8 * (size_t)pl.n_spec + 64) || !ensure(c, c->spec_flags, 4 * (size_t)n + 64) ||
+                       !ensure(c, c->spec_syms, 4 * (size_t)pl.n_spec * (size_t)spec_slab_stride(spec_bits) + 64))))
         return false;
     // parse-segment tables: [seg_c0 | seg_after | seg_base | seg_S : int32 x n_segs each][seg_cl : int32 x (n_segs + n)]
     // [cstart : int32 x (n_chunks + n)][head : int32 x n_chunks][cl : u32 x n_cl]
@@ -759,7 +761,8 @@ plan_again:
     const int k5_ahead = getenv("ZS_K5_AHEAD") ? atoi(getenv("ZS_K5_AHEAD")) : 1;  // lines the symbol kernel's helper wave asks for ahead of a lane
     c->dbg_blk_off = pl.sd[0].blk_off, c->dbg_chunk_off = pl.sd[0].chunk_off, c->dbg_nchunks = pl.sd[0].nchunks;
     c->dbg_spec_n = pl.sd[0].spec_n, c->dbg_n_spec = pl.n_spec;
-    const K5Spec k5s{dev<uint32_t>(c->spec_rec), dev<uint32_t>(c->spec_rec) + pl.n_spec, spec_bits, spec_warm, spec_corrupt};
+    const K5Spec k5s{dev<uint32_t>(c->spec_rec), dev<uint32_t>(c->spec_rec) + pl.n_spec, spec_bits, spec_warm, spec_corrupt,
+                     dev<uint32_t>(c->spec_syms), spec_slab_stride(spec_bits)};
     int spec_ok_streams = 0;  // streams whose speculative walk verified: the map kernels skip them (all of them: not launched)
     bool need_maps = true, spec_ran = false;
     if (!rounds) c->spec_streams = c->spec_fallbacks = c->spec_wrong_chunks = c->spec_periodic = 0;
@@ -1040,7 +1043,7 @@ plan_again:
         spec_ran = true;
         hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 1>), dim3((unsigned)((pl.max_spec_n + 63) / 64), (unsigned)n), dim3(kK5Threads), 0, stream, d_sd, d_st,
                            (const uint2 *)nullptr, 0, dev<uint2>(c->mm), dev<uint16_t>(c->link), (const uint16_t *)nullptr, (const uint32_t *)nullptr,
-                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
+                           (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
         if (prof) (void)hipEventRecord(c->ev_spec[0], stream);
         hipLaunchKernelGGL(zs_spec_verify_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, dev<uint2>(c->mm), dev<uint16_t>(c->link), c->crc_tab, lv,
                            strategy, hash_variant, k5s, dev<int32_t>(c->spec_flags));
@@ -1227,16 +1230,18 @@ plan_again:
                            d_work + o_chunks, (int)pl.w_chunks.size(), dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint16_t>(c->entry),
                            dev<uint32_t>(c->symbase), dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top),
                            c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
-    // the streams whose speculative walk verified: their symbols, from the entries that walk found.
+    // the streams whose speculative walk verified: their symbols from the walk's slabs to their places, and the block cuts.
     // (In the re-entry behind the batched cut rounds -- `rounds` -- nothing of the speculative path is launched: the verified
     // streams' symbols and block cuts are those of the call's first pass, which ran to its end for them; the rounds touch only
     // the records and maps of the streams that were given up, nothing zeroes syms / blk_end / blk_top in between, and the map
     // kernels skip the verified streams by StreamState::spec_ok, which the re-entry does not reset either.
     // tests/test_gpu_spec.py test_a_verified_stream_beside_one_in_the_cut_rounds.)
-    if (spec_ok_streams)
-        hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 2>), dim3((unsigned)((pl.max_spec_n + 63) / 64), (unsigned)n), dim3(kK5Threads), 0, stream, d_sd, d_st,
-                           (const uint2 *)nullptr, 0, dev<uint2>(c->mm), dev<uint16_t>(c->link), (const uint16_t *)nullptr, (const uint32_t *)nullptr,
-                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
+    if (spec_ok_streams) {
+        if (prof) (void)hipEventRecord(c->ev_spec[2], stream);
+        hipLaunchKernelGGL(zs_spec_compact_kernel, dim3((unsigned)((pl.max_spec_n + 3) / 4), (unsigned)n), dim3(256), 0, stream, d_sd, d_st, k5s,
+                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top));
+        if (prof) (void)hipEventRecord(c->ev_spec[3], stream);
+    }
     mark(9);
     if (tail_serial)
         hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
@@ -1383,6 +1388,10 @@ plan_again:
             (void)hipEventElapsedTime(&b, c->ev_spec[0], c->ev_spec[1]);
             (void)hipEventElapsedTime(&m, c->ev_spec[1], c->ev[kStChunkMap + 1]);
             c->stage_ms[kStSpecWalk] = a, c->stage_ms[kStSpecVerify] = b, c->stage_ms[kStChunkMap] = m;
+            // (the compaction is part of the emit_syms interval: this is its own share of it)
+            float k = 0;
+            if (spec_ok_streams) (void)hipEventElapsedTime(&k, c->ev_spec[2], c->ev_spec[3]);
+            c->stage_ms[kStSpecCompact] = k;
         }
         if (n_parts) {  // part-wise launches: every launch has its own pair of events, a stage is the sum of its launches
             for (int i = kStLinks; i <= kStTail; i++) c->stage_ms[i] = 0;
@@ -1610,7 +1619,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -1690,7 +1699,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
-    if (s == kStCrc32) return kStageNames[s];  // KC: the CRC-32 calls, the framing of PNG files, the check and gather of their chunks
+    if (s == kStCrc32 || s == kStSpecCompact) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks) and KSc (the speculative walk's compaction)
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine

@@ -1946,10 +1946,11 @@ __device__ __forceinline__ void k5_publish(lds_u32p slot, uint32_t v) {
 __device__ __forceinline__ uint32_t k5_peek(lds_u32p slot) { return *(volatile __attribute__((address_space(3))) uint32_t *)slot; }
 __device__ __forceinline__ uint64_t k5_peek64(uint32_t addr) { return *(volatile __attribute__((address_space(3))) uint64_t *)(uintptr_t)addr; }
 // MODE 0: the chunks of the work list from the entries the maps gave (K4b).  On the speculative grid (blockIdx.y = the stream,
-// K5Spec): MODE 1 -- the walk without symbols: a lane starts sp.warm positions in front of its chunk in state R with nothing
-// pending, takes the node at the first loop-top at or behind the chunk's start for its entry (the guess) and leaves guess, exit
-// and symbol count; MODE 2 -- the streams whose guesses verified (zs_spec_verify_kernel) once more from those entries, with
-// their symbols' places known: what MODE 0 does.
+// K5Spec): MODE 1 -- the speculative walk: a lane starts sp.warm positions in front of its chunk in state R with nothing
+// pending and emits nothing there, takes the node at the first loop-top at or behind the chunk's start for its entry (the
+// guess) and from there on writes the symbols into the chunk's own slab of sp.syms (spec_slab_stride, zs_core.h: their
+// final places are known only behind the verdict's prefix sum -- zs_spec_compact_kernel moves them and finds the block
+// cuts, so the sink here has no cut test); it leaves guess, exit and symbol count.
 template <int kK5Ring, int MODE>
 __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const StreamDesc *sd, const StreamState *st, const uint2 *work, int nwork, const uint2 *mm,
                                                                const uint16_t *link, const uint16_t *entry, const uint32_t *symbase, uint32_t *syms,
@@ -2045,12 +2046,15 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
     } else {
         si = (int)blockIdx.y, c = i;
         if (!sd[si].spec || c >= sd[si].spec_n) return;
-        if (MODE == 1 ? spec_periodic(sd[si], st[si]) : !st[si].spec_ok) return;
+        if (spec_periodic(sd[si], st[si])) return;
     }
     const StreamDesc s = sd[si];
     GlobalAcc acc{as_global(s.in), mm + s.pos_off, crc_tab_g, strategy, hash_variant, link + s.pos_off};
-    const uint32_t base = MODE == 0 ? symbase[s.chunk_off + c] : MODE == 2 ? sp.base[s.spec_off + c] : 0u;
-    GlobalSymSink sink(syms + s.sym_off + base, base, blk_end + s.blk_off, blk_top + s.blk_off);
+    const uint32_t base = MODE == 0 ? symbase[s.chunk_off + c] : 0u;
+    // (the walk's symbols are provisional: MODE 1 is handed no syms / blk_end / blk_top and its sink is the slab alone)
+    GlobalSymSink sink(MODE == 0 ? syms + s.sym_off + base : nullptr, base, MODE == 0 ? blk_end + s.blk_off : nullptr,
+                       MODE == 0 ? blk_top + s.blk_off : nullptr);
+    uint32_t *const slab = MODE == 1 ? sp.syms + (size_t)(s.spec_off + c) * (size_t)sp.stride : nullptr;
     // the refill-rule prefix (first chunks of segments) by the shared code, then plain automaton steps
     int kind, ns;
     int64_t p;
@@ -2062,8 +2066,7 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
         kind = kR, ns = 0, p = cx.cs - sp.warm;
         p = (c == 0 || p < 0) ? 0 : p;
     } else {
-        chunk_special_prefix(acc, sink, cx, MODE == 0 ? (int)entry[s.chunk_off + c] : spec_guess(sp.rec[s.spec_off + c]), lv, strategy, kind, p, ns,
-                             pflags, nev);
+        chunk_special_prefix(acc, sink, cx, (int)entry[s.chunk_off + c], lv, strategy, kind, p, ns, pflags, nev);
     }
     const int64_t ce = cx.ce;
     if (MODE != 1 && p >= ce) return;
@@ -2091,8 +2094,8 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
     k5_publish(sh_last, (uint32_t)(q_last - q0) >> 4);
     // the loop in two copies: with one, the literal's register is the target of a load in one case and of a shift in the
     // other, and the compiler guards the shift with a wait for everything in flight -- the loads just issued
-    auto steps = [&](auto rl_tag, auto ring_tag, const int q_end) {
-        constexpr bool kRecLits = decltype(rl_tag)::value, kRing = decltype(ring_tag)::value;
+    auto steps = [&](auto rl_tag, auto ring_tag, auto emit_tag, const int q_end) {
+        constexpr bool kRecLits = decltype(rl_tag)::value, kRing = decltype(ring_tag)::value, kEmit = decltype(emit_tag)::value;
         // a step's symbol is stored at the top of the next step, ahead of that step's loads (the wave's memory operations
         // complete in order: behind the loads, its acknowledgement would be waited for with them in the same step)
         uint32_t dsym = 0;
@@ -2102,8 +2105,11 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
         int k5steps = 0, k5miss = 0, k5lanemiss = 0, k5mysteps = 0;
 #endif
         while (q < q_end) {
-            if constexpr (MODE != 1)
-                if (dns >= 0) sink(dns, dsym, dend, dtop);
+            if constexpr (kEmit)
+                if (dns >= 0) {
+                    if constexpr (MODE == 0) sink(dns, dsym, dend, dtop);
+                    else slab[dns] = dsym;
+                }
             const int m = pend ? (int)(pend >> 16) + 3 : 2;
             int qa = q + 1, qb = q - 1 + m;
             qa = qa > q_last ? q_last : qa;
@@ -2165,38 +2171,44 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
             lit = nlit;
             q = npos;
         }
-        if constexpr (MODE != 1)
-            if (dns >= 0) sink(dns, dsym, dend, dtop);
+        if constexpr (kEmit)
+            if (dns >= 0) {
+                if constexpr (MODE == 0) sink(dns, dsym, dend, dtop);
+                else slab[dns] = dsym;
+            }
 #ifdef ZS_FV_PROF
         if (kRing && (blockIdx.x & 63) == 7 && (lane == 0 || lane == 37))
             printf("K5PROF block %d lane %d: my steps %d, my misses %d; steps with a miss in the wave %d; ticks (100 MHz) %lld\n", (int)blockIdx.x, lane,
                    k5mysteps, k5lanemiss, k5miss, wall_clock64() - k5t0);
 #endif
     };
-    auto run_to = [&](const int q_end) {
-        if (!rec_lits) steps(std::false_type{}, std::false_type{}, q_end);
-        else if (ahead > 0) steps(std::true_type{}, std::true_type{}, q_end);
-        else steps(std::true_type{}, std::false_type{}, q_end);
+    auto run_to = [&](auto emit_tag, const int q_end) {
+        if (!rec_lits) steps(std::false_type{}, std::false_type{}, emit_tag, q_end);
+        else if (ahead > 0) steps(std::true_type{}, std::true_type{}, emit_tag, q_end);
+        else steps(std::true_type{}, std::false_type{}, emit_tag, q_end);
     };
     if constexpr (MODE != 1) {
-        run_to((int)ce);
+        run_to(std::true_type{}, (int)ce);
     } else {
         // the warm-up: up to the first loop-top at or behind the chunk's start; that node is one of the chunk's entry slots
         // (R at cs + i, i <= 256, or L / XK / XK4 at cs itself, the pending match being the record of cs - 1)
         const int cs = (int)cx.cs;
-        run_to(cs);
+        run_to(std::false_type{}, cs);
         const int guess = kind == kR ? q - cs : 256 + kind;
         ns = 0;
         if (cx.m != 0) {
             // a segment's first chunk: its events by the shared code from the guessed slot, then on from where that leaves
-            NullSink nsk;
-            chunk_special_prefix(acc, nsk, cx, guess, lv, strategy, kind, p, ns, pflags, nev);
+            // (the one symbol whose loop-top is not its start + 1 -- chunk_special_prefix's nil_edge -- is named in the slab's
+            // last word, for the block cut that may fall on it)
+            SpecSlabSink ssk{slab, -1};
+            chunk_special_prefix(acc, ssk, cx, guess, lv, strategy, kind, p, ns, pflags, nev);
+            slab[sp.stride - 1] = (uint32_t)ssk.odd;
             q = (int)p;
             pend = kind == kXK ? acc.mK(p - 1) : kind == kXK4 ? acc.mK4(p - 1) : kNoMatch;
             lit = gin[p - 1];
             cur = a[p];
         }
-        run_to((int)ce);
+        run_to(std::true_type{}, (int)ce);
         const int exit_slot = kind == kR ? q - (int)ce : 256 + kind;
         const int told = c == sp.corrupt ? (guess + 1) % kSlots : guess;
         sp.rec[s.spec_off + c] = spec_pack(told, exit_slot, ns, (pflags & (kMapEqualBit | kMapPoisonBit)) != 0);
@@ -2206,7 +2218,7 @@ __global__ __launch_bounds__(kK5Threads) void zs_emit_syms_lane_kernel(const Str
 // ------------------------------------------------------------------ KSv
 // The speculative walk's verdict, one workgroup per stream: the stream is the reference's iff no chunk met an event that is
 // K4's business and every chunk's guessed entry is its predecessor's exit -- chunk 0's recorded entry is checked against the
-// stream's initial state (slot 0: the second walk starts from the record), so by induction every walk was the true one.  Then: the chunks' first symbols (prefix sum of the counts) and what the resolve kernel leaves
+// stream's initial state (slot 0: the compaction kernel takes the chunk's first position from the record), so by induction every walk was the true one.  Then: the chunks' first symbols (prefix sum of the counts) and what the resolve kernel leaves
 // in StreamState for the tail engine and the block kernels.  Otherwise the stream goes to the maps as it would have.
 __global__ __launch_bounds__(1024) void zs_spec_verify_kernel(const StreamDesc *sd, StreamState *st, const uint2 *mm, const uint16_t *link,
                                                              const uint32_t *crc_tab_g, LevelCfg lv, int strategy, int hash_variant, K5Spec sp,
@@ -2318,6 +2330,39 @@ __global__ __launch_bounds__(1024) void zs_spec_verify_kernel(const StreamDesc *
     ss.deferred = 0;
     ss.spec_ok = 1, ss.spec_wrong = 0;
     flags[si] = 1;
+}
+
+// ------------------------------------------------------------------ KSc
+// The verified streams' symbols from the walk's slabs to their places, one wave per chunk: chunk j's spec_count symbols go
+// to syms + base[j].  The block cuts are found here too: at most one falls in a chunk (spec_cut_index), and the cut symbol's
+// end and loop-top follow from where it starts -- the chunk's entry plus the lengths of the symbols in front of it, summed
+// along the wave while they are copied (zs_core.h spec_first_start / spec_sym_end / spec_sym_top: what GlobalSymSink is
+// told by the steps of K5 and by chunk_special_prefix).
+__global__ __launch_bounds__(256) void zs_spec_compact_kernel(const StreamDesc *sd, const StreamState *st, K5Spec sp, uint32_t *syms, int32_t *blk_end,
+                                                             int32_t *blk_top) {
+    const int si = (int)blockIdx.y, c = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const StreamDesc &s = sd[si];
+    if (!s.spec || c >= s.spec_n || !st[si].spec_ok) return;
+    const uint32_t r = sp.rec[s.spec_off + c], base = sp.base[s.spec_off + c];
+    const int count = spec_count(r), cut = spec_cut_index(base, count);
+    const uint32_t *slab = sp.syms + (size_t)(s.spec_off + c) * (size_t)sp.stride;
+    uint32_t *out = syms + s.sym_off + base;
+    int before = 0;  // positions covered by this lane's symbols in front of the cut symbol
+    for (int i = lane; i < count; i += 64) {
+        const uint32_t v = slab[i];
+        out[i] = v;
+        before += i < cut ? sym_len(v) : 0;
+    }
+    if (cut < 0) return;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
+    if (lane != 0) return;
+    const ChunkCtx cx = spec_chunk_ctx(s, c, sp.len_bits);
+    const int64_t start = spec_first_start(cx.cs, spec_guess(r)) + before;
+    const bool odd = cx.m != 0 && slab[sp.stride - 1] == (uint32_t)cut;
+    const uint32_t bi = (base + (uint32_t)cut) / kBlockSyms;
+    blk_end[s.blk_off + bi] = (int32_t)spec_sym_end(start, slab[cut]);
+    blk_top[s.blk_off + bi] = (int32_t)spec_sym_top(start, odd);
 }
 
 // ------------------------------------------------------------------ K5b
