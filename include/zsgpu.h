@@ -333,7 +333,9 @@ ZS_API int zs_png_decode_files_batch(zs_ctx *ctx, int n, const void *const *file
  * one of the slower paths since the context was made; "lit_engine_bytes" -- input bytes the one-wave literal engine parsed
  * beyond the streams' last 261 (a call that runs its batch again counts the plan it ends with); "spec_streams", "spec_fallbacks", "spec_wrong_chunks" -- the last deflate call's speculative
  * chunk walk (levels 4-9): streams that tried it, those of them that took the transfer maps after all, chunks whose guessed
- * entry was wrong; "spec_periodic" -- those of the fallbacks that were never walked (periodic by the match kernel's count). */
+ * entry was wrong; "spec_periodic" -- those of the fallbacks that were never walked (periodic by the match kernel's count);
+ * "inf_lane_streams" -- streams of the last inflate call whose chain had blocks for the lane decoder (blocks with checkpoints and
+ * no tokens: under 4 bits per symbol, or no room for the token buffers). */
 ZS_API int64_t zs_ctx_counter(const zs_ctx *ctx, const char *name);
 /* (A test hook, not part of the product's surface: declared only where ZS_TESTING is defined.)
  * For the tests: what the parse stage of the last deflate call left for its first stream, copied from the device -- "state"

@@ -432,6 +432,27 @@ def test_inflate_block_parallel_path_on_foreign_large_streams(engine):
         engine.inflate_batch([bytes(bad)], [len(want[1])])
 
 
+def test_inflate_blocks_with_checkpoints_and_no_tokens_take_the_lane_decoder(engine):
+    """Blocks under 4 bits per symbol (zeros: a length-258 match costs 2 to 3 bits; sparse image rows) find no room for their
+    tokens and keep checkpoints instead: zs_inf_decode_lane_kernel and zs_inf_cellflat_kernel decode them, beside a text stream
+    whose blocks are expanded from tokens.  The counter "inf_lane_streams" shows that the batch went that way, and that it is
+    the last call's alone.  (Every stream is above the 1 KiB at which the block-parallel pass starts: 4086, 5420 and 106563
+    compressed bytes.)"""
+    text = zlib.compress(datagen.english(256 << 10, 5), 6)
+    cases = [zlib.compress(bytes(4 << 20), 6), zlib.compress(datagen.sparse(512, 512), 9), text]
+    assert all(len(z) > 1024 for z in cases), [len(z) for z in cases]
+    want = [zlib.decompress(z) for z in cases]
+    assert engine.inflate_batch(cases, [len(w) for w in want]) == want
+    lane = engine.counter("inf_lane_streams")
+    alone = []
+    for z, w in zip(cases, want):  # which input it is (not asserted but for the text: the batch's count is what the test pins)
+        assert engine.inflate_batch([z], [len(w)]) == [w]
+        alone.append(engine.counter("inf_lane_streams"))
+    print("inf_lane_streams: batch %d; zeros, sparse rows, text alone: %s" % (lane, alone))
+    assert lane >= 1
+    assert alone[2] == 0  # text has no such block: the counter is the last call's, not a running sum
+
+
 @pytest.mark.parametrize("seed", [int(x) for x in os.environ.get("ZS_FUZZ_SEEDS", "2024,7").split(",")])
 def test_inflate_fuzz_foreign_streams(engine, seed):
     """Randomised streams from another encoder (levels, strategies, window sizes, memLevels, flush points of every kind,

@@ -151,9 +151,10 @@ struct StreamState {
     uint32_t adler;
     int32_t status;
     int64_t end_bits;  // bit position in the stream (zlib header included) behind the run's last block or marker
-    // the resolve kernel's position when it is run part by part behind the match kernel (one long stream: zs_engine.hip):
-    // next segment, entry slot, symbols so far, last segment whose events fired and its entry slot; and the equal-bucket cuts whose repair reaches into
-    // positions whose matches were not computed yet (cut position, last position repaired)
+    // the resolve kernel's position between its launches (every launch has the whole stream's maps and match records; a
+    // launch after the first is one of the cut rounds'): next segment, entry slot, symbols so far, last segment whose events
+    // fired and its entry slot; and the equal-bucket cuts whose repair reaches into positions whose matches were not computed
+    // yet (cut position, last position repaired) -- with the whole stream there, there are none: r_ncut stays 0
     int32_t r_seg, r_slot, r_kfired, r_kslot;
     uint32_t r_total;
     int32_t r_ncut;

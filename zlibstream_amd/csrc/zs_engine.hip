@@ -44,8 +44,6 @@ struct zs_ctx {
     hipStream_t aux = nullptr;  // second stream: tree building of the finished blocks runs beside the tail engine
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pre0 = nullptr, ev_pre = nullptr;
     hipEvent_t ev_spec[4] = {};           // the speculative walk and its verdict; the compaction of its symbols (profiling)
-    hipEvent_t ev_part[16] = {};          // one long stream run part by part: part k's maps are ready
-    std::vector<hipEvent_t> ev_pool;      // timing pairs of the part-wise launches (profiling)
     std::string err;
     bool profiling = false;
     int fast_fallbacks = 0;  // speculative DeflateFast batches that had to be redone sequentially
@@ -63,6 +61,7 @@ struct zs_ctx {
     // probing call (zs_inflate asking whether the stream's end has arrived), where the block chain ended
     std::vector<int64_t> inf_used;
     int64_t *inf_probe = nullptr;
+    int inf_lane_streams = 0;  // streams of the last inflate call whose chain had blocks for the lane decoder (checkpoints, no tokens)
     int64_t png_segments = 0;  // independent runs of rows the last unfilter call found (zs_png.h png_row_cuts)
     int fast_rounds = 0;  // rounds the last call's DeflateFast took over its chunks (0: one workgroup per stream)
     bool no_rounds_once = false;  // the next plan takes one workgroup per stream (set when the rounds gave up)
@@ -281,7 +280,7 @@ bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len
     // The speculative chunk walk.  ZS_NO_SPEC: every stream through the maps; ZS_SPEC_LEN / ZS_SPEC_WARM /
     // ZS_SPEC_MIN: the chunk length (512, 1024 or 2048), the warm-up and the shortest stream that tries it; ZS_SPEC_CORRUPT=j:
     // chunk j's recorded guess is spoiled (the tests' way to a failed verification)
-    const bool spec_on = !getenv("ZS_NO_SPEC") && !getenv("ZS_PIPE_PARTS");
+    const bool spec_on = !getenv("ZS_NO_SPEC");
     const int spec_len_env = getenv("ZS_SPEC_LEN") ? atoi(getenv("ZS_SPEC_LEN")) : 0;
     const int spec_bits = spec_len_env == 512 ? 9 : spec_len_env == 2048 ? 11 : spec_len_env == 1024 ? 10 : kSpecLenBits;
     const int spec_warm = getenv("ZS_SPEC_WARM") ? std::max(0, std::min(4096, atoi(getenv("ZS_SPEC_WARM")))) : kSpecWarm;
@@ -882,123 +881,6 @@ plan_again:
         }
         return true;
     };
-    // One long stream: the position-parallel kernels (links, matches, chunk maps) fill the chip, the kernels that follow
-    // the parse (resolve: one workgroup; symbols: one lane per chunk, a latency chain) leave it idle.  ZS_PIPE_PARTS=k cuts
-    // the stream into k parts at parse-segment boundaries: while the match kernel works on part i + 1 the second HIP stream
-    // resolves part i and emits its symbols (the resolve kernel keeps its place between launches, StreamState r_*).  Same
-    // kernels, same bytes -- and, measured on english64, the same time (5.82 ms with 2 parts, 5.90 with 4, against 5.85): the
-    // symbol kernel's ~0.65 ms latency floor is paid again behind the last part and the match kernel loses 0.2-0.3 ms to the
-    // company.  Off unless asked for.
-    int n_parts = 0;
-    if (n == 1 && !ro && pl.sd[0].body_end >= 0 && pl.sd[0].nsegs >= 256 && strategy != kHuffmanOnly && !pl.any_fv) {
-        const char *e = getenv("ZS_PIPE_PARTS");
-        n_parts = e ? atoi(e) : 0;
-        if (n_parts > 16) n_parts = 16;
-        if (n_parts < 2) n_parts = 0;
-    }
-    struct TimedPair {
-        int stage;
-        hipEvent_t a, b;
-    };
-    std::vector<TimedPair> pairs;
-    size_t pool_used = 0;
-    if (n_parts) {
-        if (!side_work()) return false;
-        for (int i = 2; i <= 9; i++) mark(i);  // stages 2..9 are timed launch by launch below; their marks only have to exist
-        auto timed = [&](int stage, hipStream_t st_, auto &&launch) {
-            if (!prof) {
-                launch();
-                if (getenv("ZS_DEBUG")) {
-                    hipError_t e_ = hipGetLastError();
-                    if (e_ != hipSuccess) fprintf(stderr, "zs: launch of stage %s failed: %s\n", kStageNames[stage], hipGetErrorString(e_));
-                }
-                return;
-            }
-            while (c->ev_pool.size() < pool_used + 2) {
-                hipEvent_t ev = nullptr;
-                (void)hipEventCreate(&ev);
-                c->ev_pool.push_back(ev);
-            }
-            hipEvent_t a = c->ev_pool[pool_used++], b = c->ev_pool[pool_used++];
-            (void)hipEventRecord(a, st_);
-            launch();
-            (void)hipEventRecord(b, st_);
-            pairs.push_back(TimedPair{stage, a, b});
-        };
-        const StreamDesc &s0 = pl.sd[0];
-        const int nsegs = s0.nsegs, nchunks = s0.nchunks;
-        const int64_t n_tiles = (int64_t)pl.w_match.size(), n_spans = (int64_t)pl.w_links.size();
-        int64_t tiles_done = 0, spans_done = 0;
-        for (int k = 0; k < n_parts; k++) {
-            const int sa = (int)((int64_t)nsegs * k / n_parts), sb = (int)((int64_t)nsegs * (k + 1) / n_parts);
-            const int ca = pl.seg_c0[(size_t)sa], cb = sb < nsegs ? pl.seg_c0[(size_t)sb] : nchunks;
-            // the chunks below cb need the match records of the positions below their end
-            const int64_t q = sb < nsegs ? (int64_t)pl.cstart[(size_t)cb] : (int64_t)s0.body_end + 1;
-            int64_t tiles_end = (q + kMatchTile - 1) / kMatchTile;
-            if (tiles_end > n_tiles || sb == nsegs) tiles_end = n_tiles;
-            int64_t spans_end = (tiles_end * kMatchTile + link_span - 1) / link_span;
-            if (spans_end > n_spans || sb == nsegs) spans_end = n_spans;
-            // the link kernel's time is that of one workgroup's span whatever the number of spans: all of them at once, up front
-            if (k == 0) spans_end = n_spans;
-            if (spans_end > spans_done)
-                timed(kStLinks, stream, [&] {
-                    hipLaunchKernelGGL(zs_links_kernel, dim3((unsigned)(spans_end - spans_done)), dim3(1024), kLkLds, stream, d_sd,
-                                       d_work + o_links + spans_done, dev<uint16_t>(c->link), c->crc_tab, hash_variant, (int)link_span);
-                });
-            if (k == 0 && ro && ro->resume)  // (one stream: a resumed run's chains are the ones the engine before it left)
-                hipLaunchKernelGGL(zs_import_chains_kernel, dim3(64), dim3(1024), 0, stream, d_sd, 0, dev<uint16_t>(c->link), c->crc_tab, hash_variant, ro->p0);
-            if (tiles_end > tiles_done)
-                timed(kStMatch, stream, [&] {
-                    hipLaunchKernelGGL(zs_match_kernel, dim3((unsigned)(tiles_end - tiles_done)), dim3(1024), kMatchLds + 16, stream, d_sd,
-                                       d_work + o_match + tiles_done, dev<uint16_t>(c->link), dev<uint2>(c->mm), lv, strategy, d_st);
-                });
-            spans_done = spans_end > spans_done ? spans_end : spans_done, tiles_done = tiles_end > tiles_done ? tiles_end : tiles_done;
-            timed(kStChunkMap, stream, [&] {
-                hipLaunchKernelGGL(zs_chunkmap_kernel, dim3((unsigned)(cb - ca)), dim3(512), 0, stream, d_sd, d_work + o_chunks + ca,
-                                   dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint32_t>(c->maps), c->crc_tab, lv, strategy, hash_variant, dev<uint16_t>(c->chunk_far));
-            });
-            timed(kStSegMap, stream, [&] {
-                hipLaunchKernelGGL(zs_segmap_kernel, dim3((unsigned)(sb - sa)), dim3(320), 0, stream, d_sd, d_work + o_segs + sa,
-                                   dev<uint32_t>(c->maps), dev<uint2>(c->segmap));
-            });
-            ZS_HIP(c, hipEventRecord(c->ev_part[k], stream));
-            ZS_HIP(c, hipStreamWaitEvent(c->aux, c->ev_part[k], 0));
-            const int64_t mm_limit = tiles_end * kMatchTile - 1;
-            timed(kStResolve, c->aux, [&] {
-                hipLaunchKernelGGL(zs_resolve_kernel, dim3(1), dim3(1024), kResolveLds, c->aux, d_sd, d_st, dev<uint16_t>(c->link),
-                                   dev<uint2>(c->mm), dev<uint32_t>(c->maps), dev<uint2>(c->segmap), dev<uint16_t>(c->seg_entry),
-                                   dev<uint32_t>(c->seg_symbase), dev<uint8_t>(c->stale), dev<uint8_t>(c->seg_stale), c->crc_tab, lv,
-                                   strategy, hash_variant, sb, (int)(mm_limit > 0x7FFFFFFF ? 0x7FFFFFFF : mm_limit), (const uint2 *)nullptr,
-                                   dev<uint16_t>(c->chunk_far), 0, (int32_t *)nullptr, (uint32_t *)nullptr, 0, 0);
-            });
-            if (k == n_parts - 1) {
-                // the tail engine needs what the last resolve launch left: it runs on the first stream beside the last part's symbols
-                ZS_HIP(c, hipEventRecord(c->ev_fork, c->aux));
-                ZS_HIP(c, hipStreamWaitEvent(stream, c->ev_fork, 0));
-                timed(kStTail, stream, [&] {
-                    hipLaunchKernelGGL(zs_tail_kernel, dim3(1), dim3(1024), kTailLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
-                                       dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks),
-                                       dev<uint8_t>(c->scratch), c->crc_tab, lv, strategy, hash_variant, level);
-                });
-            }
-            timed(kStExpand, c->aux, [&] {
-                hipLaunchKernelGGL(zs_expand_kernel, dim3((unsigned)((sb - sa + 63) / 64)), dim3(64), 0, c->aux, d_sd, d_st, d_work + o_segs + sa,
-                                   sb - sa, dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint32_t>(c->maps), dev<uint16_t>(c->seg_entry),
-                                   dev<uint32_t>(c->seg_symbase), dev<uint8_t>(c->stale), dev<uint16_t>(c->entry), dev<uint32_t>(c->symbase),
-                                   c->crc_tab, lv, strategy, hash_variant);
-            });
-            timed(kStEmitSyms, c->aux, [&] {
-                hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 0>), dim3((unsigned)((cb - ca + 63) / 64)), dim3(kK5Threads), 0, c->aux, d_sd, d_st,
-                                   d_work + o_chunks + ca, cb - ca, dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint16_t>(c->entry), dev<uint32_t>(c->symbase),
-                                   dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), c->crc_tab, lv, strategy,
-                                   hash_variant, k5_ahead, k5s);
-            });
-        }
-        ZS_HIP(c, hipEventRecord(c->ev_join, c->aux));
-        ZS_HIP(c, hipStreamWaitEvent(stream, c->ev_join, 0));
-        hipLaunchKernelGGL(zs_body_blocks_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<int32_t>(c->blk_end),
-                           dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks), dev<uint32_t>(c->syms));
-    } else {
     if (!rounds) {
     mark(2);
     if (!pl.w_links.empty())
@@ -1090,7 +972,6 @@ plan_again:
     // (Only where a walk is long -- chains of 1024 and 4096, levels 8 and 9: a round costs ~0.1 ms of launches and a
     // synchronisation, which is what a cut's repair takes on one CU at level 6.  64 MiB of short runs: level 9 7.3 s -> 2.0 s,
     // level 6 175 ms inline against 237 in rounds.)
-    // (ZS_DEFER_ALL: at every level, for the tests)
     if (need_maps) launch_resolve(defer_mode, 0);
     }
     mark(7);
@@ -1254,7 +1135,6 @@ plan_again:
         hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
                            dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks),
                            dev<uint8_t>(c->scratch), c->crc_tab, lv, strategy, hash_variant, level);
-    }
     if (pl.n_runs) {
         // DeflateFast by speculative chunk runs; a run whose hand-over state does not verify sends the batch to the
         // sequential engine (the result is the reference's bytes either way)
@@ -1392,14 +1272,6 @@ plan_again:
             float k = 0;
             if (spec_ok_streams) (void)hipEventElapsedTime(&k, c->ev_spec[2], c->ev_spec[3]);
             c->stage_ms[kStSpecCompact] = k;
-        }
-        if (n_parts) {  // part-wise launches: every launch has its own pair of events, a stage is the sum of its launches
-            for (int i = kStLinks; i <= kStTail; i++) c->stage_ms[i] = 0;
-            for (const TimedPair &t : pairs) {
-                float ms = 0;
-                (void)hipEventElapsedTime(&ms, t.a, t.b);
-                c->stage_ms[t.stage] += ms;
-            }
         }
     }
     {
@@ -1574,11 +1446,6 @@ int zs_ctx_create(int device, zs_ctx **out) {
         zs_ctx_destroy(c);  // releases whatever was created so far
         return ZS_MEM_ERROR;
     }
-    for (auto &e : c->ev_part)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-            zs_ctx_destroy(c);
-            return ZS_MEM_ERROR;
-        }
     std::vector<uint32_t> tab(1024);
     for (int t = 0; t < 4; t++)
         for (int i = 0; i < 256; i++) tab[(size_t)t * 256 + i] = crc32c_table_entry(t, (uint32_t)i);
@@ -1631,11 +1498,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     if (c->pin_out) (void)hipHostFree(c->pin_out);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->ev_part)
-        if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_spec)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->ev_pool)
         if (e) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
@@ -1669,6 +1532,7 @@ int64_t zs_ctx_counter(const zs_ctx *c, const char *name) {
     if (k == "spec_fallbacks") return c->spec_fallbacks;
     if (k == "spec_periodic") return c->spec_periodic;  // ... fallbacks that were never walked (the match kernel's count of RUNS tiles)
     if (k == "spec_wrong_chunks") return c->spec_wrong_chunks;
+    if (k == "inf_lane_streams") return c->inf_lane_streams;  // streams of the last inflate call with blocks for the lane decoder
     if (k == "png_segments") return c->png_segments;  // segments the last zs_png_unfilter_batch_device call found
     return -1;
 }
@@ -1946,6 +1810,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
                      const int64_t *out_cap, int64_t *out_len, int *status, hipStream_t stream, std::vector<int> &rest,
                      uint32_t *adler_out = nullptr) {
     const int m = (int)idx.size();
+    c->inf_lane_streams = 0;
     if (m == 0) return true;
     std::vector<ParStream> ps((size_t)m);
     int64_t nchunks = 0, ncand = 0, nblk = 0, ncells = 0, nfx = 0;
@@ -1992,24 +1857,19 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
                        dev<int32_t>(c->par_surv), dev<int32_t>(c->par_scnt), dev<int64_t>(c->par_cbits), dev<int32_t>(c->par_ccnt));
     hipLaunchKernelGGL(zs_inf_flatten_kernel, dim3((unsigned)m), dim3(256), 0, stream, d_ps, d_st, dev<int64_t>(c->par_cbits),
                        dev<int32_t>(c->par_ccnt), dev<ParCand>(c->par_cands), m);
-    // decode once (zs_inflate_tok.hip): the measuring pass writes tokens, the expand pass turns them into cells.
-    // ZS_INF_LANE_DECODE=1: round 4's form (measure, then decode again lane by lane, then chase the lanes' markers)
-    static const bool tok_mode = !getenv("ZS_INF_LANE_DECODE") && !getenv("ZS_INF_WAVE_MEASURE") && !getenv("ZS_INF_WAVE_DECODE");
+    // decode once (zs_inflate_tok.hip): the measuring pass writes tokens, the expand pass turns them into cells
     int64_t tok_total = 0;
-    if (tok_mode) {
-        if (!ensure(c, c->par_tokstat, 128) || !ensure(c, c->par_tails, 4 * (size_t)kSbTailBuf * (size_t)m)) return false;
-        hipLaunchKernelGGL(zs_inf_tails_kernel, dim3((unsigned)m), dim3(64), 0, stream, d_ps, dev<uint32_t>(c->par_tails));
-        if (!c->inf_probe) {  // (a probing call decodes nothing: no slabs, the measuring pass stores no tokens)
-            hipLaunchKernelGGL(zs_inf_tokalloc_kernel, dim3((unsigned)m), dim3(1024), 0, stream, d_ps, d_st, dev<ParCand>(c->par_cands));
-            hipLaunchKernelGGL(zs_inf_tokbase_kernel, dim3(1), dim3(1024), 0, stream, d_st, m, dev<int64_t>(c->par_tokstat));
-            ZS_HIP(c, hipMemcpyAsync(&tok_total, c->par_tokstat.p, 8, hipMemcpyDeviceToHost, stream));
-        }
+    if (!ensure(c, c->par_tokstat, 128) || !ensure(c, c->par_tails, 4 * (size_t)kSbTailBuf * (size_t)m)) return false;
+    hipLaunchKernelGGL(zs_inf_tails_kernel, dim3((unsigned)m), dim3(64), 0, stream, d_ps, dev<uint32_t>(c->par_tails));
+    if (!c->inf_probe) {  // (a probing call decodes nothing: no slabs, the measuring pass stores no tokens)
+        hipLaunchKernelGGL(zs_inf_tokalloc_kernel, dim3((unsigned)m), dim3(1024), 0, stream, d_ps, d_st, dev<ParCand>(c->par_cands));
+        hipLaunchKernelGGL(zs_inf_tokbase_kernel, dim3(1), dim3(1024), 0, stream, d_st, m, dev<int64_t>(c->par_tokstat));
+        ZS_HIP(c, hipMemcpyAsync(&tok_total, c->par_tokstat.p, 8, hipMemcpyDeviceToHost, stream));
     }
     mark(1);
     ZS_HIP(c, hipMemcpyAsync(st.data(), d_st, sizeof(ParState) * (size_t)m, hipMemcpyDeviceToHost, stream));
     ZS_HIP(c, hipStreamSynchronize(stream));
     std::vector<uint2> w;
-    bool wave_measure = false;
     // (a stream whose candidate lists overflowed -- ok == 0: it goes to the sequential decoder -- is not measured: what
     // its list holds behind the overflow is whatever was in the buffer)
     for (int j = 0; j < m; j++)
@@ -2029,64 +1889,53 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
     if (!w.empty()) {
         ZS_HIP(c, hipMemcpyAsync(c->par_work.p, w.data(), sizeof(uint2) * w.size(), hipMemcpyHostToDevice, stream));
         ZS_HIP(c, hipStreamSynchronize(stream));
-        // one wave per candidate, its lanes on subsequences of the block (self-synchronising decode); ZS_INF_WAVE_MEASURE
-        // selects the plain wave decoder (one dependency chain per block) for comparison
-        if (getenv("ZS_INF_WAVE_MEASURE")) {
-            wave_measure = true;
-            hipLaunchKernelGGL(zs_inf_measure_kernel, dim3((unsigned)w.size()), dim3(64), 0, stream, d_ps, d_st, dev<uint2>(c->par_work),
-                               dev<ParCand>(c->par_cands));
-        } else if (tok_mode) {
-            if (!ensure(c, c->par_toktabs, sizeof(TokTabs) * w.size()) || !ensure(c, c->par_tabs, sizeof(LaneTabs) * w.size())) return false;
-            // the tokens twice (the lanes' slabs, the blocks' lists); without room for them the blocks are decoded again lane by lane
-            int mdbg = getenv("ZS_INF_MEASURE_DBG") ? atoi(getenv("ZS_INF_MEASURE_DBG")) : 0;
-            // (behind the slabs: room for the blocks that are measured a second time, zs_inf_tokretry_kernel)
-            const int64_t tok_reserve = c->inf_probe ? 0 : std::max<int64_t>(tok_total / 16, 2 << 20);
-            if (!ensure(c, c->par_toks, 4 * (size_t)(tok_total + tok_reserve) + 64) || !ensure(c, c->par_ctoks, 4 * (size_t)(tok_total + tok_reserve) + 64)) {
-                c->err.clear();
-                if (!ensure(c, c->par_toks, 64) || !ensure(c, c->par_ctoks, 64)) return false;
-                mdbg = 3;
-            }
-            int32_t *stats = nullptr;
-            if (getenv("ZS_DEBUG_INF") && !c->inf_probe) {
-                ZS_HIP(c, hipMemsetAsync((uint8_t *)c->par_tokstat.p + 16, 0, 64, stream));
-                stats = (int32_t *)((uint8_t *)c->par_tokstat.p + 16);
-            }
-            hipLaunchKernelGGL(zs_inf_measure_tok_kernel, dim3((unsigned)w.size()), dim3(64), 0, stream, d_ps, d_st, dev<uint2>(c->par_work),
-                               dev<ParCand>(c->par_cands), dev<TokTabs>(c->par_toktabs), dev<LaneTabs>(c->par_tabs), dev<uint32_t>(c->par_toks), dev<uint32_t>(c->par_ctoks), dev<uint32_t>(c->par_tails), stats, mdbg, nullptr, nullptr);
-            if (mdbg != 3 && !c->inf_probe) {
-                // blocks measured without room for their tokens: once more, with room for their known length
-                if (!ensure(c, c->par_retry, 4 * (size_t)kTokRetryMax + 64)) return false;
-                uint8_t *rb = (uint8_t *)c->par_retry.p;
-                unsigned long long *d_cursor = (unsigned long long *)(rb + 4 * (size_t)kTokRetryMax);
-                int32_t *d_rcnt = (int32_t *)(rb + 4 * (size_t)kTokRetryMax + 8);
-                ZS_HIP(c, hipMemsetAsync(d_cursor, 0, 16, stream));
-                hipLaunchKernelGGL(zs_inf_tokretry_kernel, dim3((unsigned)((w.size() + 255) / 256)), dim3(256), 0, stream, d_ps, dev<uint2>(c->par_work), (int)w.size(),
-                                   dev<ParCand>(c->par_cands), tok_total, tok_reserve, d_cursor, d_rcnt, (int32_t *)rb);
-                hipLaunchKernelGGL(zs_inf_measure_tok_kernel, dim3((unsigned)std::min<size_t>(w.size(), (size_t)kTokRetryMax)), dim3(64), 0, stream, d_ps, d_st,
-                                   dev<uint2>(c->par_work), dev<ParCand>(c->par_cands), dev<TokTabs>(c->par_toktabs), dev<LaneTabs>(c->par_tabs), dev<uint32_t>(c->par_toks),
-                                   dev<uint32_t>(c->par_ctoks), dev<uint32_t>(c->par_tails), (int32_t *)nullptr, mdbg, d_rcnt, (int32_t *)rb);
-            }
-            if (stats) {
-                int32_t hs[4] = {0, 0, 0, 0};
-                ZS_HIP(c, hipMemcpyAsync(hs, stats, 16, hipMemcpyDeviceToHost, stream));
-                ZS_HIP(c, hipStreamSynchronize(stream));
-                fprintf(stderr, "[zs] inflate measure: %zu candidates, %d subsequences, %d re-entries met their first decode, %d decoded again in full, %d blocks without tokens; %lld tokens of room\n",
-                        w.size(), hs[2], hs[1], hs[0], hs[3], (long long)tok_total);
-            }
-        } else if (!ensure(c, c->par_tabs, sizeof(LaneTabs) * w.size())) {
-            return false;
-        } else {
-            hipLaunchKernelGGL(zs_inf_measure_sync_kernel, dim3((unsigned)w.size()), dim3(64), 0, stream, d_ps, d_st, dev<uint2>(c->par_work),
-                               dev<ParCand>(c->par_cands), dev<LaneTabs>(c->par_tabs));
+        // one wave per candidate, its lanes on subsequences of the block (self-synchronising decode)
+        if (!ensure(c, c->par_toktabs, sizeof(TokTabs) * w.size()) || !ensure(c, c->par_tabs, sizeof(LaneTabs) * w.size())) return false;
+        // the tokens twice (the lanes' slabs, the blocks' lists); without room for them the blocks are decoded again lane by lane
+        int mdbg = getenv("ZS_INF_MEASURE_DBG") ? atoi(getenv("ZS_INF_MEASURE_DBG")) : 0;
+        // (behind the slabs: room for the blocks that are measured a second time, zs_inf_tokretry_kernel)
+        const int64_t tok_reserve = c->inf_probe ? 0 : std::max<int64_t>(tok_total / 16, 2 << 20);
+        if (!ensure(c, c->par_toks, 4 * (size_t)(tok_total + tok_reserve) + 64) || !ensure(c, c->par_ctoks, 4 * (size_t)(tok_total + tok_reserve) + 64)) {
+            c->err.clear();
+            if (!ensure(c, c->par_toks, 64) || !ensure(c, c->par_ctoks, 64)) return false;
+            mdbg = 3;
+        }
+        int32_t *stats = nullptr;
+        if (getenv("ZS_DEBUG_INF") && !c->inf_probe) {
+            ZS_HIP(c, hipMemsetAsync((uint8_t *)c->par_tokstat.p + 16, 0, 64, stream));
+            stats = (int32_t *)((uint8_t *)c->par_tokstat.p + 16);
+        }
+        hipLaunchKernelGGL(zs_inf_measure_tok_kernel, dim3((unsigned)w.size()), dim3(64), 0, stream, d_ps, d_st, dev<uint2>(c->par_work),
+                           dev<ParCand>(c->par_cands), dev<TokTabs>(c->par_toktabs), dev<LaneTabs>(c->par_tabs), dev<uint32_t>(c->par_toks), dev<uint32_t>(c->par_ctoks), dev<uint32_t>(c->par_tails), stats, mdbg, nullptr, nullptr);
+        if (mdbg != 3 && !c->inf_probe) {
+            // blocks measured without room for their tokens: once more, with room for their known length
+            if (!ensure(c, c->par_retry, 4 * (size_t)kTokRetryMax + 64)) return false;
+            uint8_t *rb = (uint8_t *)c->par_retry.p;
+            unsigned long long *d_cursor = (unsigned long long *)(rb + 4 * (size_t)kTokRetryMax);
+            int32_t *d_rcnt = (int32_t *)(rb + 4 * (size_t)kTokRetryMax + 8);
+            ZS_HIP(c, hipMemsetAsync(d_cursor, 0, 16, stream));
+            hipLaunchKernelGGL(zs_inf_tokretry_kernel, dim3((unsigned)((w.size() + 255) / 256)), dim3(256), 0, stream, d_ps, dev<uint2>(c->par_work), (int)w.size(),
+                               dev<ParCand>(c->par_cands), tok_total, tok_reserve, d_cursor, d_rcnt, (int32_t *)rb);
+            hipLaunchKernelGGL(zs_inf_measure_tok_kernel, dim3((unsigned)std::min<size_t>(w.size(), (size_t)kTokRetryMax)), dim3(64), 0, stream, d_ps, d_st,
+                               dev<uint2>(c->par_work), dev<ParCand>(c->par_cands), dev<TokTabs>(c->par_toktabs), dev<LaneTabs>(c->par_tabs), dev<uint32_t>(c->par_toks),
+                               dev<uint32_t>(c->par_ctoks), dev<uint32_t>(c->par_tails), (int32_t *)nullptr, mdbg, d_rcnt, (int32_t *)rb);
+        }
+        if (stats) {
+            int32_t hs[4] = {0, 0, 0, 0};
+            ZS_HIP(c, hipMemcpyAsync(hs, stats, 16, hipMemcpyDeviceToHost, stream));
+            ZS_HIP(c, hipStreamSynchronize(stream));
+            fprintf(stderr, "[zs] inflate measure: %zu candidates, %d subsequences, %d re-entries met their first decode, %d decoded again in full, %d blocks without tokens; %lld tokens of room\n",
+                    w.size(), hs[2], hs[1], hs[0], hs[3], (long long)tok_total);
         }
     }
     mark(2);
-    // measured blocks carry checkpoints: they are decoded by sub-blocks, one lane each
-    const bool lane_decode = !w.empty() && !wave_measure && !getenv("ZS_INF_WAVE_DECODE");
+    // measured blocks carry tokens or, without room for those, checkpoints: the chain kernels hand them to the expand pass
+    // or to the lane decoder (sub-blocks, one lane each); blocks that were not measured go to the wave decoder
+    const bool measured = !w.empty();
     const bool chain_par = !getenv("ZS_INF_CHAIN_WALK");
     if (chain_par)
         hipLaunchKernelGGL(zs_inf_chain_par_kernel, dim3((unsigned)m), dim3(1024), kChainParLds, stream, d_ps, d_st, dev<ParCand>(c->par_cands),
-                           dev<ParBlock>(c->par_blocks), lane_decode ? 1 : 0);
+                           dev<ParBlock>(c->par_blocks), measured ? 1 : 0);
     // a stream the finder's blocks do not chain (fixed-code or stored blocks among them): its fixed blocks found ahead of the walk,
     // a wave per 64 KiB (zs_inf_fixed_scan_kernel; the waves of the streams that chained leave at once)
     const FxEntry *d_fx = nullptr;
@@ -2099,7 +1948,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
         hipLaunchKernelGGL(zs_inf_fixed_scan_kernel, dim3((unsigned)max_regions, (unsigned)m), dim3(64), 0, stream, d_ps, d_st, dev<FxEntry>(c->par_fxtab));
     }
     hipLaunchKernelGGL(zs_inf_chain_kernel, dim3((unsigned)m), dim3(64), 0, stream, d_ps, d_st, dev<ParCand>(c->par_cands),
-                       dev<ParBlock>(c->par_blocks), lane_decode ? 1 : 0, (chain_par ? 1 : 0) | (c->inf_probe ? 2 : 0), d_fx);
+                       dev<ParBlock>(c->par_blocks), measured ? 1 : 0, (chain_par ? 1 : 0) | (c->inf_probe ? 2 : 0), d_fx);
     mark(3);
     ZS_HIP(c, hipMemcpyAsync(st.data(), d_st, sizeof(ParState) * (size_t)m, hipMemcpyDeviceToHost, stream));
     ZS_HIP(c, hipStreamSynchronize(stream));
@@ -2155,9 +2004,10 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
         ZS_HIP(c, hipMemcpyAsync(d_st, st.data(), sizeof(ParState) * (size_t)m, hipMemcpyHostToDevice, stream));
         ZS_HIP(c, hipMemcpyAsync(c->par_work.p, w.data(), sizeof(uint2) * w.size(), hipMemcpyHostToDevice, stream));
         ZS_HIP(c, hipStreamSynchronize(stream));
-        bool lane_work = lane_decode && !tok_mode;
-        for (int j = 0; j < m && tok_mode; j++) lane_work = lane_work || (st[(size_t)j].ok && st[(size_t)j].lane_blocks);
-        if (lane_decode && tok_mode)
+        // (blocks with checkpoints and no tokens: the lane decoder and its flatten pass have work)
+        for (int j = 0; j < m; j++) c->inf_lane_streams += st[(size_t)j].ok && st[(size_t)j].lane_blocks;
+        const bool lane_work = c->inf_lane_streams > 0;
+        if (measured)
             hipLaunchKernelGGL(zs_inf_expand_kernel, dim3((unsigned)w.size()), dim3(kExpThreads), kExpLds, stream, d_ps, d_st, dev<uint2>(c->par_work),
                                dev<ParBlock>(c->par_blocks), dev<TokTabs>(c->par_toktabs), dev<uint32_t>(c->par_ctoks), dev<uint16_t>(c->par_cells),
                                dev<int32_t>(c->par_fail), getenv("ZS_DEBUG_INF") ? (int32_t *)((uint8_t *)c->par_tokstat.p + 16) : nullptr);
@@ -2190,7 +2040,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
         ZS_HIP(c, hipGetLastError());
         ZS_HIP(c, hipMemcpyAsync(bfail.data(), c->par_fail.p, 4 * (size_t)m, hipMemcpyDeviceToHost, stream));
         ZS_HIP(c, hipStreamSynchronize(stream));
-        if (tok_mode && getenv("ZS_DEBUG_INF")) {
+        if (getenv("ZS_DEBUG_INF")) {
             int32_t hs[16] = {};
             (void)hipMemcpy(hs, (uint8_t *)c->par_tokstat.p + 16, 64, hipMemcpyDeviceToHost);
             fprintf(stderr, "[zs] inflate expand: %d blocks with tokens, %d steps, %d rounds of pointer jumping; cycles / 256 of wave 0 in phases: scan %d, barrier %d, fetch+words %d, cells %d, rounds %d, out %d, barrier %d\n",

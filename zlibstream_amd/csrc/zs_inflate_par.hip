@@ -8,18 +8,22 @@
 //               completely (BTYPE, HLIT/HDIST ranges, a complete bit-length code, complete
 //               literal/length and distance codes with an end-of-block code) is a candidate
 //               block start; a random position passes with negligible probability.
-//   D1 measure  one wave per candidate decodes its block without output: end bit offset,
-//               output size, BFINAL, validity -- its 64 lanes on 64 subsequences of the block's
-//               bits (Huffman streams self-synchronise; exits are chained to a proven prefix),
-//               which also leaves a checkpoint (bit, output position) per subsequence.
+//   D1 measure  one wave per candidate decodes its block: end bit offset, output size, BFINAL,
+//               validity -- its 64 lanes on 64 subsequences of the block's bits (Huffman streams
+//               self-synchronise; exits are chained to a proven prefix).  The decoded symbols are
+//               kept as tokens (zs_inflate_tok.hip); a block whose tokens found no room -- fewer
+//               than 4 bits per symbol: zeros, sparse rows, image data -- keeps a checkpoint
+//               (bit, output position) per subsequence instead.
 //   C  chain    one wave per stream walks from the real first block (bit 16) through the
 //               candidates (end of block i = start of block i+1); blocks the finder cannot
 //               see (stored / fixed) are measured on the spot.  Output offsets follow.
-//   D2 decode   one wave per block, one lane per subsequence, decodes again into 16-bit cells:
-//               a literal byte, a marker 0x8000 | i for "byte i of the 32 KiB window before this
-//               block", or a marker for "the cell d positions before this lane's subsequence"
-//               (copies of markers stay markers), so subsequences and blocks decode
-//               independently; a flatten pass removes the second kind.
+//   D2 decode   into 16-bit cells: a literal byte, or a marker 0x8000 | i for "byte i of the 32 KiB
+//               window before this block" (copies of markers stay markers), so blocks decode
+//               independently.  A block with tokens is expanded (zs_inflate_tok.hip, X).  A block
+//               with checkpoints and no tokens goes to the lane decoder: one lane per subsequence
+//               decodes again, with a second kind of marker for "the cell d positions before this
+//               lane's subsequence", which a flatten pass removes.  A block that was not measured
+//               (stored, fixed, more than kCkMax subsequences) goes to the wave decoder.
 //   W  windows  per stream, block by block: the resolved last 32 KiB after each block.
 //   R  resolve  every cell of every block -> byte, in parallel.
 //
@@ -61,13 +65,13 @@ struct ParCand {
     int64_t end_bit;   // bit offset after the block's EOB
     int64_t out_bytes;
     int32_t bfinal, ok;
-    int32_t tab, pad_;  // >= 0: measured by the lane kernel, with tables and checkpoints in tabs[tab] (see zs_inf_decode_lane_kernel)
+    int32_t tab, pad_;  // >= 0: measured; with kTabTok its tokens are in toktabs[tab & ~kTabTok], without it the tables and checkpoints in tabs[tab] (zs_inf_decode_lane_kernel)
     int64_t tok_off;    // the candidate's slab in the token array (zs_inflate_tok.hip), and its room in tokens
     int32_t tok_cap, pad2_;
 };
 struct ParBlock {
     int64_t bit, out_off, out_bytes;
-    int32_t tab, pad_;  // >= 0: decoded by sub-blocks from tabs[tab]; -1: by the wave decoder
+    int32_t tab, pad_;  // >= 0: expanded from its tokens (kTabTok) or decoded by sub-blocks from tabs[tab]; -1: by the wave decoder
 };
 struct ParState {
     int32_t ncand, nblk;
@@ -696,42 +700,21 @@ __global__ __launch_bounds__(256) void zs_inf_flatten_kernel(const ParStream *ps
     }
 }
 
-// ------------------------------------------------------------------ D1, wave form: one wave per candidate (fastest chain per block;
-// used while every candidate of the batch gets a wave at once)
-__global__ __launch_bounds__(64) void zs_inf_measure_kernel(const ParStream *ps, const ParState *st, const uint2 *work, ParCand *cands) {
-    __shared__ ParLds L;
-    const uint2 w = work[blockIdx.x];
-    const ParStream s = ps[w.x];
-    if ((int)w.y >= st[w.x].ncand) return;
-    ParCand &c = cands[s.cand_off + w.y];
-    if (!st[w.x].ok || c.bit < 16 || c.bit + 17 > s.in_len * 8) {  // (as in zs_inf_measure_sync_kernel)
-        if (threadIdx.x == 0) c.ok = 0;
-        return;
-    }
-    InfBits b{s.in, s.in_len, 0, 0, 0, false, L.ibuf, -1};
-    inf_seek(b, c.bit);
-    BlockOut r = inf_block<0>(b, L.T, L.lens, L.ll, nullptr, (int64_t)1 << 40);
-    if (threadIdx.x == 0) {
-        c.end_bit = r.end_bit;
-        c.out_bytes = r.out_bytes;
-        c.bfinal = r.bfinal;
-        c.ok = r.err == 0;
-    }
-}
-
-// ------------------------------------------------------------------ D1, self-synchronising form
-// Measuring a candidate is a decode without output, and a block's decode is one dependency chain of ~16 Ki symbols.  A
-// Huffman bit stream decoded from a wrong bit offset falls into step with the true symbol boundaries after a few dozen
-// symbols, so the chain can be cut: the block's bits are divided into 64 subsequences of S bits (S from the distance to
-// the next candidate), lane j decodes subsequence j from its nominal first bit until it crosses into subsequence j + 1
-// and reports the symbol boundary it arrived at (its exit).  Lane 0 starts at the true first symbol; every other lane
-// whose entry differs from its predecessor's exit decodes again from that exit, all of them at once, until the chain of
-// exits = entries is unbroken from lane 0 on -- each pass extends the proven prefix by at least one lane, so the result
-// is that of the sequential decode however badly a subsequence synchronises (typically two or three passes in all).
-// One wave per candidate, the block's tables in LDS shared by its lanes.  The entry of every subsequence (bit position,
-// output position) is a checkpoint for the decode pass, which decodes the subsequences independently the same way.
-// Only dynamic blocks come out of the finder; whatever this kernel does not accept (ok = 0) the chain kernel measures
-// with the wave decoder, and every accepted size is checked again by the decode pass and the Adler-32.
+// ------------------------------------------------------------------ D1, self-synchronising measure
+// Measuring a candidate is a decode, and a block's decode is one dependency chain of ~16 Ki symbols.  A Huffman bit stream
+// decoded from a wrong bit offset falls into step with the true symbol boundaries after a few dozen symbols, so the chain
+// can be cut: the block's bits are divided into 64 subsequences of S bits (S from the distance to the next candidate),
+// lane j decodes subsequence j from its nominal first bit until it crosses into subsequence j + 1 and reports the symbol
+// boundary it arrived at (its exit).  Lane 0 starts at the true first symbol; every other lane whose entry differs from
+// its predecessor's exit decodes again from that exit, all of them at once, until the chain of exits = entries is
+// unbroken from lane 0 on -- each pass extends the proven prefix by at least one lane, so the result is that of the
+// sequential decode however badly a subsequence synchronises.
+// The kernel is zs_inf_measure_tok_kernel (zs_inflate_tok.hip): one wave per candidate, the block's tables in LDS shared
+// by its lanes, every decoded symbol kept as a token.  A block whose tokens found no room keeps the entry of every
+// subsequence (bit position, output position) as a checkpoint instead -- LaneTabs, below -- and the lane decoder (D2, lane
+// form) decodes its subsequences independently from those.  Only dynamic blocks come out of the finder; whatever the
+// measure does not accept (ok = 0) the chain kernel measures with the wave decoder, and every accepted size is checked
+// again by the decode pass and the Adler-32.
 #ifndef ZS_SUB_MIN
 #define ZS_SUB_MIN 1024
 #endif
@@ -749,187 +732,6 @@ struct LaneTabs {
 };
 static_assert(sizeof(InfTables) % 16 == 0 && sizeof(LaneTabs) % 16 == 0 && offsetof(LaneTabs, nsub) == sizeof(InfTables),
               "LaneTabs begins with an InfTables image copied with 16-byte stores");
-// One lane decodes (without output) from bit `entry` to the first symbol boundary at or after `gend`, or to END_BLOCK.
-// flags: 0 = crossed gend, 1 = END_BLOCK (exit_bit is the bit after it), 2 = not decodable from here.
-__device__ __forceinline__ void sub_measure(const __attribute__((address_space(1))) uint8_t *in, int64_t n, const InfTables &T, int64_t entry,
-                                            int64_t gend, int64_t &exit_bit, int &nout, int &nsym, int &flags) {
-    LaneBits b{in, n, 0, 0, 0, false};
-    b.seek(entry);
-    int out = 0, ns = 0, fl = 0;
-    int64_t cur = entry;
-    while (cur < gend) {
-        b.fill();
-        int sym, clen;
-        {
-            const uint16_t e = T.lit[b.peek(kInfLitBits)];
-            if (e != kInfEsc) sym = e >> 4, clen = e & 15;
-            else sym = lane_slow(b, T.lcount, T.lsym, clen);
-        }
-        if (sym < 0 || clen > b.cnt) {
-            fl = 2;
-            break;
-        }
-        b.drop(clen);
-        if (sym < 256) {
-            out++;
-        } else if (sym == 256) {
-            fl = 1;
-            cur = b.tell();
-            break;
-        } else {
-            sym -= 257;
-            if (sym >= 29) {
-                fl = 2;
-                break;
-            }
-            const int mlen = (sym == 28 ? 258 : base_length(sym) + 3) + (int)b.take(extra_lbits(sym));
-            b.fill();
-            int ds, dl;
-            {
-                const uint16_t e = T.dist[b.peek(kInfDistBits)];
-                if (e != kInfEsc) ds = e >> 4, dl = e & 15;
-                else ds = lane_slow(b, T.dcount, T.dsym, dl);
-            }
-            if (ds < 0 || ds >= 30 || dl > b.cnt) {
-                fl = 2;
-                break;
-            }
-            b.drop(dl);
-            (void)b.take(extra_dbits(ds));
-            out += mlen;
-        }
-        if (b.bad) {
-            fl = 2;
-            break;
-        }
-        ns++;
-        cur = b.tell();
-    }
-    exit_bit = cur, nout = out, nsym = ns, flags = fl;
-}
-__global__ __launch_bounds__(64) void zs_inf_measure_sync_kernel(const ParStream *ps, const ParState *st, const uint2 *work, ParCand *cands,
-                                                                 LaneTabs *tabs) {
-    __shared__ __attribute__((aligned(16))) ParLds L;
-    const uint2 w = work[blockIdx.x];
-    const ParStream s = ps[w.x];
-    const int ncand = st[w.x].ncand;
-    if ((int)w.y >= ncand) return;
-    ParCand &c = cands[s.cand_off + w.y];
-    const int lane = threadIdx.x;
-    const int64_t cbit = c.bit, nbits = s.in_len * 8;
-    if (!st[w.x].ok || cbit < 16 || cbit + 17 > nbits) {  // (not a header offset of this stream: nothing is read through it)
-        if (lane == 0) c.ok = 0;
-        return;
-    }
-    // the block most likely ends where the next candidate begins (candidate bits are final since the flatten pass)
-    int64_t hint = (int)w.y + 1 < ncand ? cands[s.cand_off + w.y + 1].bit : nbits;
-    if (hint <= cbit || hint > nbits) hint = nbits;
-    InfBits hb{s.in, s.in_len, 0, 0, 0, false, L.ibuf, -1};
-    inf_seek(hb, cbit);
-    hb.fill();
-    int bfinal = 0;
-    bool ok = hb.cnt >= 3;
-    if (ok) {
-        bfinal = (int)hb.take(1);
-        ok = hb.take(2) == 2;
-    }
-    ok = ok && inf_dyn_tables(hb, L.T, L.lens, L.ll) == 0;
-    __syncthreads();
-    if (!ok) {
-        if (lane == 0) c.ok = 0;
-        return;
-    }
-    const int64_t b0 = inf_tell(hb);  // first symbol of the block
-    int S = kSubMinBits;
-    if (hint > b0) {
-        const int64_t per = ((hint - b0 + 63) / 64 + 63) & ~(int64_t)63;
-        S = per < kSubMinBits ? kSubMinBits : per > kSubMaxBits ? kSubMaxBits : (int)per;
-    }
-    const __attribute__((address_space(1))) uint8_t *gin = (const __attribute__((address_space(1))) uint8_t *)(uintptr_t)s.in;
-    LaneTabs &T = tabs[blockIdx.x];
-    int64_t entry0 = b0, out_base = 0, total_syms = 0, end_bit = 0;
-    int nck = 0, result = 0;  // result: 1 = END_BLOCK reached on the proven chain, 2 = not decodable
-    bool store = true, hint_ok = true;
-    for (int round = 0; result == 0; round++) {
-        const int64_t g = b0 + ((int64_t)round * 64 + lane) * S, gend = g + S;
-        int64_t entry = lane == 0 ? entry0 : g, exit_bit = -1;
-        int nout = 0, nsym = 0, flags = 0, nvalid = 0, lf = 0;
-        bool spec = false;  // this lane has decoded its subsequence (from `entry`)
-        bool run = lane == 0 || (g < nbits && (g < hint || !hint_ok));
-        for (;;) {
-            if (run) {
-                sub_measure(gin, s.in_len, L.T, entry, gend, exit_bit, nout, nsym, flags);
-                spec = true;
-            }
-            const int64_t pe = __shfl_up(exit_bit, 1);
-            const int pf = __shfl_up(flags, 1);
-            const bool pspec = __shfl_up((int)spec, 1) != 0;
-            const bool link = lane == 0 || (pspec && pf == 0 && spec && entry == pe);
-            const uint64_t m = __ballot(link);
-            nvalid = m == ~0ull ? 64 : (int)__builtin_ctzll(~m);  // lanes [0, nvalid) are proven
-            lf = __shfl(flags, nvalid - 1);
-            if (nvalid == 64 || lf != 0) break;
-            // lane nvalid decodes from a proven exit; the lanes behind it whose entry no longer fits their predecessor's exit
-            // go again too (their predecessor's exit is usually right already: that is the self-synchronisation)
-            run = lane >= nvalid && pspec && pf == 0 && (!spec || entry != pe);
-            if (run) entry = pe;
-            // the chain has walked past the hint: it was not the block's end, so everyone behind speculates as well
-            if (__shfl((int)spec, nvalid) == 0) hint_ok = false;
-            if (!hint_ok && !spec && !run && lane > nvalid && g < nbits) run = true;
-        }
-        // checkpoints of the proven lanes
-        const bool valid = lane < nvalid;
-        int incl = valid ? nout : 0;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        int sy = valid ? nsym : 0;
-        for (int d = 32; d; d >>= 1) sy += __shfl_xor(sy, d);
-        if (store && nck + nvalid <= kCkMax) {
-            if (valid) {
-                T.ck_bit[nck + lane] = (uint32_t)(entry - cbit);
-                T.ck_out[nck + lane] = (uint32_t)(out_base + incl - nout);
-            }
-        } else {
-            store = false;
-        }
-        nck += nvalid;
-        out_base += __shfl(incl, 63);
-        total_syms += sy;
-        if (lf == 1) {
-            end_bit = __shfl(exit_bit, nvalid - 1);
-            result = 1;
-        } else if (lf == 2 || total_syms > kParMaxSyms || out_base >= ((int64_t)1 << 31)) {
-            result = 2;
-        } else {
-            entry0 = __shfl(exit_bit, 63);
-            if (entry0 - cbit >= ((int64_t)1 << 32)) result = 2;
-        }
-    }
-    if (result != 1) {
-        if (lane == 0) c.ok = 0;
-        return;
-    }
-    if (store && end_bit - cbit < ((int64_t)1 << 32)) {
-        // the decode pass takes the block by subsequences: tables and checkpoints
-        const uint4 *src = (const uint4 *)&L.T;
-        uint4 *dst = (uint4 *)&T;
-        for (int i = lane; i < (int)(sizeof(InfTables) / 16); i += 64) dst[i] = src[i];
-        if (lane == 0) {
-            T.ck_bit[nck] = (uint32_t)(end_bit - cbit);
-            T.ck_out[nck] = (uint32_t)out_base;
-            T.nsub = nck;
-            c.tab = (int32_t)blockIdx.x;
-        }
-    }
-    if (lane == 0) {
-        c.end_bit = end_bit;
-        c.out_bytes = out_base;
-        c.bfinal = bfinal;
-        c.ok = 1;
-    }
-}
 
 // ------------------------------------------------------------------ C
 // The chain of a stream's blocks without the walk, for the stream whose blocks the finder has all reported (dynamic blocks:
@@ -1395,7 +1197,7 @@ __global__ __launch_bounds__(64) void zs_inf_chain_kernel(const ParStream *ps, P
     }
 }
 
-// ------------------------------------------------------------------ D2
+// ------------------------------------------------------------------ D2, wave form: the blocks that were not measured
 __global__ __launch_bounds__(64) void zs_inf_decode_kernel(const ParStream *ps, const ParState *st, const uint2 *work, const ParBlock *blocks,
                                                            uint16_t *cells, int32_t *fail) {
     __shared__ ParLds L;
@@ -1403,14 +1205,16 @@ __global__ __launch_bounds__(64) void zs_inf_decode_kernel(const ParStream *ps, 
     const ParStream s = ps[w.x];
     if (!st[w.x].ok || (int)w.y >= st[w.x].nblk) return;
     const ParBlock k = blocks[s.blk_off + w.y];
-    if (k.tab >= 0) return;  // decoded by sub-blocks (zs_inf_decode_lane_kernel)
+    if (k.tab >= 0) return;  // expanded from its tokens (zs_inf_expand_kernel) or decoded by sub-blocks (zs_inf_decode_lane_kernel)
     InfBits b{s.in, s.in_len, 0, 0, 0, false, L.ibuf, -1};
     inf_seek(b, k.bit);
     BlockOut r = inf_block<1>(b, L.T, L.lens, L.ll, cells + s.cell_off + k.out_off, k.out_bytes, k.out_off);
     if (threadIdx.x == 0 && (r.err || r.out_bytes != k.out_bytes)) fail[w.x] = 1;
 }
 
-// ------------------------------------------------------------------ D2, lane form
+// ------------------------------------------------------------------ D2, lane form: the blocks with checkpoints and no tokens
+// (highly compressible data -- under 4 bits per symbol -- whose tokens did not fit their slabs, and every measured block when
+// the token buffers themselves found no room).
 // The wave decoder spends ~130 instructions of a whole wave on every symbol, and a CU issues about one per cycle: the
 // pass is bound by instruction issue with 63 of 64 lanes doing nothing useful.  Here every lane decodes something of
 // its own: the measure pass left a checkpoint at the first symbol of every subsequence, so a block falls into

@@ -1,9 +1,10 @@
 // zs_inflate_tok.hip -- block-parallel inflate, every symbol decoded ONCE (round 5).
 //
-// Until round 4 a block was decoded twice: zs_inf_measure_sync_kernel decoded it without output to learn where its
+// Until round 4 every block was decoded twice: a measuring kernel decoded it without output to learn where its
 // subsequences begin (bit and output position), zs_inf_decode_lane_kernel decoded it again into cells, one lane per
 // subsequence, and zs_inf_cellflat_kernel chased the markers the lanes had to leave for sources outside their own
-// subsequence (13.3 ms of a 20.4 ms call per GiB; 38 GB of HBM traffic for 1.5 GB of stream and output).
+// subsequence (13.3 ms of a 20.4 ms call per GiB; 38 GB of HBM traffic for 1.5 GB of stream and output).  Those two
+// kernels remain for the blocks with checkpoints and no tokens, below.
 //
 //   D1' measure + tokens  (zs_inf_measure_tok_kernel)  the measuring decode writes what it decodes: one 32-bit TOKEN per
 //        symbol -- a literal's byte, or a match's (length, distance) -- into a slab of the lane's own.  Tokens do not depend
@@ -18,12 +19,15 @@
 //        lines stored: a tile of up to 8192 cells per step, the token that owns a cell from a bitmap of token starts and a
 //        prefix popcount, a match cell's source taken from an LDS ring of the block's last 32 Ki flattened cells (one
 //        gather, no chase: what lies before the tile is flat already), sources inside the tile by pointer jumping in LDS.
-//        The lane decoder's per-lane stores, its read-back of its own cells through L2 and the whole marker-chasing pass are
-//        gone.
+//        For these blocks the lane decoder's per-lane stores, its read-back of its own cells through L2 and the whole
+//        marker-chasing pass are gone.
 //
 // The window and resolve passes (zs_inflate_par.hip, W and R) read the same cells as before.  A block whose tokens do not
-// fit their slab (fewer than 2 bits per symbol, a decode that runs past the next candidate, more than kCkMax
-// subsequences) is decoded by the wave decoder (zs_inf_decode_kernel), as blocks without candidates always were.
+// fit their slab (fewer than 4 bits per symbol -- zeros, sparse rows, image data --, a decode that runs past the next
+// candidate) keeps its checkpoints instead and is decoded by the lane decoder (zs_inf_decode_lane_kernel, then
+// zs_inf_cellflat_kernel): that is what the lane decoder is now, the decoder for blocks with checkpoints and no tokens, and
+// it takes every measured block when the token buffers themselves find no room on the device.  A block with more than
+// kCkMax subsequences is decoded by the wave decoder (zs_inf_decode_kernel), as blocks without candidates always were.
 #include <hip/hip_runtime.h>
 
 namespace zs {
@@ -359,7 +363,7 @@ __device__ __forceinline__ int tok_symbol(SyncBits &b, const InfTables &T, const
 
 // A lane's decode from `entry` to the first symbol boundary at or after gend (or END_BLOCK), its tokens into w, the state in
 // front of its first kTokBnd symbols into bnd[k * 64] (bit position relative to `rel0` | output bytes so far << 16).
-// flags as in sub_measure: 0 = crossed gend, 1 = END_BLOCK (exit_bit behind it), 2 = not decodable from here.
+// flags: 0 = crossed gend, 1 = END_BLOCK (exit_bit behind it), 2 = not decodable from here.
 __device__ __forceinline__ void sub_decode_tok(SyncBits &b, int64_t nbits, const InfTables &T, const LongCodes &A, const LongEnds &E, int64_t entry, int64_t gend,
                                                int64_t rel0, TokW &w, uint32_t *bnd, int64_t &exit_bit, int &nout, int &nsym, int &flags, int &nb) {
     b.seek(entry);

@@ -1247,8 +1247,9 @@ __global__ __launch_bounds__(1024) void zs_resolve_kernel(const StreamDesc *sd, 
     const long long k4_t0 = wall_clock64();
 #endif
     load_crc_tab(tab, crc_tab_g);
-    // seg_limit / mm_limit (one long stream run part by part, else "everything"): segments below seg_limit have their maps,
-    // positions up to mm_limit their match records; the kernel goes on from where the launch before stopped
+    // seg_limit / mm_limit: segments below seg_limit have their maps, positions up to mm_limit their match records.  Every
+    // launch passes 0x7FFFFFFF for both -- the whole stream is there -- so the limits never bind; the kernel still goes on from
+    // where the launch before stopped (StreamState r_*), which is what the cut rounds' launches after the first use
     if (threadIdx.x == 0)
         sh_seg = ss.r_seg, sh_slot = ss.r_slot, sh_total = ss.r_total, sh_kfired = ss.r_kfired, sh_kslot = ss.r_kslot, sh_scan = ss.r_scan,
         ss.r_scan = dry ? ss.r_scan : 0, b_seg0 = 0, b_nrow = 0, b_groups = 0, sh_defer = 0, sh_nexp = 0, sh_ncut_any = 0, sh_cutidx = ss.r_cutidx, sh_poison = 0,
