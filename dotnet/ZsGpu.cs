@@ -115,6 +115,13 @@ namespace SixLabors.ZlibStream
         [DllImport(Lib)] public static extern int zs_png_file_info(IntPtr file, long len, PngInfo* info);
         [DllImport(Lib)] public static extern int zs_png_decode_files_batch(IntPtr ctx, int n, IntPtr* file, long* fileLen, IntPtr* output, long* outCap,
                                                                             PngInfo* info, int* status, IntPtr hipStream);
+        // raw scanlines -> RGBA8 (format 0) or RGBA16 (format 1), PLTE and tRNS applied; the files' colours; files -> RGBA
+        [DllImport(Lib)] public static extern int zs_png_expand_batch_device(IntPtr ctx, int n, IntPtr* input, long* width, long* height, int* bitDepth,
+                                                                             int* colorType, IntPtr* plte, int* plteEntries, IntPtr* trns, int* trnsLen,
+                                                                             int format, IntPtr* output, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_file_colors(IntPtr file, long len, byte* plte768, int* plteEntries, byte* trns256, int* trnsLen);
+        [DllImport(Lib)] public static extern int zs_png_decode_files_rgba_batch(IntPtr ctx, int n, IntPtr* file, long* fileLen, int format, IntPtr* output,
+                                                                                 long* outCap, PngInfo* info, int* status, IntPtr hipStream);
         // bytes fed behind a stream's trailer before its end was seen (the engine looks for the end now and then)
         [DllImport(Lib)] public static extern long zs_inflate_surplus(IntPtr s, IntPtr* p);
     }

@@ -326,6 +326,61 @@ ZS_API int zs_png_file_info(const void *file, int64_t len, zs_png_info *info);
 ZS_API int zs_png_decode_files_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, void *const *out,
                                      const int64_t *out_cap, zs_png_info *info, int *status, void *hip_stream);
 
+/* ------------------------------------------------------------------ */
+/* Raw scanlines to pixels a caller can show: RGBA, 8 or 16 bits a channel, for every legal (colour type, bit depth) pair,
+ * PLTE and tRNS applied.  Rows of width * 4 (ZS_PNG_RGBA8: bytes R, G, B, A) or width * 8 bytes (ZS_PNG_RGBA16: four uint16 in
+ * host order, R, G, B, A), no padding.  Exact integer arithmetic:
+ *   a sample v of depth d to 8 bits: v * 255 / (2^d - 1) below 8 bits, v at 8, (v * 255 + 32895) >> 16 at 16 (the rounding of
+ *   libpng's png_set_scale_16, not the high byte); to 16 bits: v * 65535 / (2^d - 1), 16-bit samples read big-endian;
+ *   gray: R = G = B; alpha: the scaled alpha sample (types 4, 6), else 0 where the pixel's samples at their original depth
+ *   equal the tRNS key's low d bits and the maximum elsewhere (no tRNS: the maximum);
+ *   palette: index k gives PLTE entry k with alpha k < trns_len ? tRNS[k] : 255, an index at or beyond the PLTE's entries
+ *   gives opaque black; to 16 bits every channel times 257. */
+#define ZS_PNG_RGBA8 0
+#define ZS_PNG_RGBA16 1
+
+/* The expansion on the device, n images a call, one launch over the flat list of all output rows (KX).
+ * in[i]: raw scanlines exactly as the decode calls leave them (DEVICE pointer, any alignment); out[i]: height[i] rows of
+ * width[i] * 4 or * 8 bytes (DEVICE pointer aligned to 4 or 8), must not overlap in[i].  in / out / width / height /
+ * bit_depth / color_type are HOST arrays of n entries.  plte / trns: HOST arrays of HOST pointers to the chunks' data bytes,
+ * plte_entries / trns_len their counts: plte_entries[i] 1 .. 256, required at type 3; trns_len[i] 0 (none), 2 at type 0, 6 at
+ * type 2, 1 .. plte_entries[i] at type 3.  Both are ignored at types 4 and 6, plte also at types 0 and 2; any of the four
+ * arrays may be NULL when no image needs it (trns_len == NULL: no image has a tRNS).  format: ZS_PNG_RGBA8 or ZS_PNG_RGBA16,
+ * one value for the call.
+ * Returns ZS_OK, ZS_MEM_ERROR (the descriptors do not fit) or, before any device work, ZS_STREAM_ERROR: null context, n < 0,
+ * null arrays or pointers, an illegal (type, depth) pair, width or height outside 1 .. 2^31 - 1, counts outside the rules
+ * above, a bad format, an out[i] not aligned to the pixel size, more than 2^31 - 1 rows in one call.  n == 0 is ZS_OK.
+ * Ordered on hip_stream (NULL: the context's, and the call returns when the pixels are written); the call waits for the
+ * stream once, for its descriptors' upload, like zs_png_adam7_merge_batch_device.  zs_ctx_stage_ms shows the launch as
+ * "png_expand". */
+ZS_API int zs_png_expand_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *width, const int64_t *height,
+                                      const int *bit_depth, const int *color_type, const void *const *plte,
+                                      const int *plte_entries, const void *const *trns, const int *trns_len, int format,
+                                      void *const *out, void *hip_stream);
+
+/* The colours of one file in HOST memory, pure host code, no context and no GPU: zs_png_file_info's walk and checks, and the
+ * data bytes of PLTE (plte768, *plte_entries = bytes / 3; 0: none) and tRNS (trns256, *trns_len; 0: none) as
+ * zs_png_expand_batch_device takes them.  ZS_DATA_ERROR for what zs_png_file_info rejects and for: a PLTE whose length is no
+ * multiple of 3 or outside 3 .. 768, a second PLTE or tRNS, either of them behind the first IDAT, a type-3 file without a
+ * PLTE in front of its IDAT, a tRNS in front of the PLTE of a type-3 file, a tRNS whose length is not 2 (type 0), 6 (type 2)
+ * or 1 .. the PLTE's entries (type 3), a tRNS whose CRC is wrong (the chunk is interpreted, so it is verified -- on the host:
+ * it holds at most 256 bytes).  A tRNS of a type 4 or 6 file and a PLTE of a type 0 or 4 file are ignored (0 is returned
+ * for them).  ZS_STREAM_ERROR: null pointers or a negative len. */
+ZS_API int zs_png_file_colors(const void *file, int64_t len, void *plte768, int *plte_entries, void *trns256, int *trns_len);
+
+/* zs_png_decode_files_batch with the expansion behind it: PNG files to RGBA pixels, n files a call.  The host walk also
+ * captures PLTE and tRNS (zs_png_file_colors); the same upload, CRC-and-gather launch, inflate, reconstruction and Adam7
+ * interleave leave raw scanlines in a buffer the context owns (pixel_bytes per file, each on a 256-byte boundary, kept
+ * until zs_ctx_destroy), and one zs_png_expand_batch_device launch takes the files that are whole from there to out[i]:
+ * width * height * 4 (ZS_PNG_RGBA8) or * 8 (ZS_PNG_RGBA16) bytes, DEVICE pointer aligned to 4 or 8.  status[i]: ZS_OK,
+ * ZS_BUF_ERROR (out_cap[i] below that), or ZS_DATA_ERROR for anything zs_png_decode_files_batch or zs_png_file_colors
+ * rejects; a file fails for itself only, and zs_ctx_last_error names the first failing file ("data error: file i: ...").
+ * Arguments, return values and ZS_STREAM_ERROR cases as for zs_png_decode_files_batch, plus a bad format and an out[i]
+ * that is not aligned.  The call waits for hip_stream once more than that call (the descriptors of the expansion). */
+ZS_API int zs_png_decode_files_rgba_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, int format,
+                                          void *const *out, const int64_t *out_cap, zs_png_info *info, int *status,
+                                          void *hip_stream);
+
 /* Stage timing of the last *_batch_device call, measured with hipEvents on
  * the stream the kernels ran on.  Enable before the call. */
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took

@@ -668,6 +668,96 @@ def png_decode_files_batch(engine, files, out_ptrs, out_caps, stream=None):
     return list(status), [{k: int(getattr(i, k)) for k in _PNG_INFO_FIELDS} for i in info]
 
 
+PNG_RGBA8, PNG_RGBA16 = 0, 1  # ZS_PNG_RGBA8 / ZS_PNG_RGBA16: 4 bytes a pixel, or four uint16 in host order
+
+
+def _host_ptr(b):
+    return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p).value if b else None
+
+
+def png_expand_batch_device(engine, in_ptrs, widths, heights, bit_depths, color_types, out_ptrs, plte=None, trns=None, format=PNG_RGBA8,
+                            stream=None):
+    """Raw scanlines -> RGBA pixels for many device-resident images in one launch (zs_png_expand_batch_device): every legal
+    (color type, bit depth) pair to rows of widths[i] * 4 bytes (PNG_RGBA8) or widths[i] * 4 uint16 (PNG_RGBA16), PLTE and tRNS
+    applied.  plte / trns: None, or one entry per image -- the chunk's data as bytes, or None (plte is required at color type
+    3; trns holds 2 bytes at type 0, 6 at type 2, 1 .. the PLTE's entries at type 3; both are ignored at types 4 and 6).
+    out_ptrs[i] must be aligned to a pixel (4 or 8 bytes) and must not overlap in_ptrs[i]."""
+    n = len(in_ptrs)
+    if not (len(widths) == len(heights) == len(bit_depths) == len(color_types) == len(out_ptrs) == n) or \
+            (plte is not None and len(plte) != n) or (trns is not None and len(trns) != n):
+        raise ValueError("png_expand_batch_device: the argument lists differ in length")
+    if format not in (PNG_RGBA8, PNG_RGBA16):
+        raise ValueError("png_expand_batch_device: format is PNG_RGBA8 or PNG_RGBA16")
+    px = 8 if format == PNG_RGBA16 else 4
+    plte = [bytes(x) if x is not None else b"" for x in plte] if plte is not None else [b""] * n
+    trns = [bytes(x) if x is not None else b"" for x in trns] if trns is not None else [b""] * n
+    for p, w, h, bd, ct, o, pl, tr in zip(in_ptrs, widths, heights, bit_depths, color_types, out_ptrs, plte, trns):
+        if not p or not o or int(o) % px or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF:
+            raise ValueError("png_expand_batch_device: 1 <= width, height <= 2^31 - 1, non-null device pointers and outputs aligned to a pixel are required")
+        if int(ct) not in PNG_COLOR_TYPES or int(bd) not in PNG_COLOR_TYPES[int(ct)][1]:
+            raise ValueError("png_expand_batch_device: color type %r with bit depth %r is not in PNG specification table 11.1" % (ct, bd))
+        if int(ct) == 3 and (len(pl) % 3 or not 3 <= len(pl) <= 768 or len(tr) > len(pl) // 3):
+            raise ValueError("png_expand_batch_device: a palette image needs a PLTE of 1 .. 256 entries and a tRNS no longer than it")
+        if int(ct) in (0, 2) and len(tr) not in (0, 2 if int(ct) == 0 else 6):
+            raise ValueError("png_expand_batch_device: a tRNS holds 2 bytes at color type 0 and 6 at color type 2")
+    if sum(int(h) for h in heights) > 0x7FFFFFFF:
+        raise ValueError("png_expand_batch_device: more than 2^31 - 1 rows in one call")
+    if n == 0:
+        return
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    # (the bytes objects are read in place: they outlive the call)
+    rc = _native.lib().zs_png_expand_batch_device(engine.handle, n, VP(*[int(p) for p in in_ptrs]), I64(*[int(x) for x in widths]),
+                                                  I64(*[int(x) for x in heights]), I32(*[int(x) for x in bit_depths]),
+                                                  I32(*[int(x) for x in color_types]), VP(*[_host_ptr(x) for x in plte]),
+                                                  I32(*[len(x) // 3 for x in plte]), VP(*[_host_ptr(x) for x in trns]),
+                                                  I32(*[len(x) if int(ct) in (0, 2, 3) else 0 for x, ct in zip(trns, color_types)]), int(format),
+                                                  VP(*[int(p) for p in out_ptrs]), ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_expand_batch_device failed (%d): %s" % (rc, engine.last_error()))
+
+
+def png_file_colors(data):
+    """zs_png_file_colors (host code, no GPU, no engine): png_file_info's walk and checks, and the data bytes of the file's PLTE
+    and tRNS chunks -> (plte, trns), b"" where the file has none or the chunk means nothing at its color type (a tRNS at
+    types 4 and 6, a PLTE at types 0 and 4).  ZlibStreamException for what png_file_info rejects and for a PLTE or tRNS of a
+    wrong length, a second one, one behind IDAT, a palette image without PLTE or with its tRNS in front of it, a tRNS whose
+    CRC is wrong."""
+    data = bytes(data)
+    plte, trns = (ctypes.c_uint8 * 768)(), (ctypes.c_uint8 * 256)()
+    n_plte, n_trns = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _native.lib().zs_png_file_colors(data, len(data), plte, ctypes.byref(n_plte), trns, ctypes.byref(n_trns))
+    if rc != 0:
+        raise ZlibStreamException("png_file_colors: not a whole PNG file, or its PLTE / tRNS chunks break the rules (%d)" % rc)
+    return bytes(plte[:3 * n_plte.value]), bytes(trns[:n_trns.value])
+
+
+def png_decode_files_rgba_batch(engine, files, out_ptrs, out_caps, format=PNG_RGBA8, stream=None):
+    """PNG files (bytes objects in host memory) -> RGBA pixels in device buffers, many files a call
+    (zs_png_decode_files_rgba_batch): png_decode_files_batch into a buffer of the engine with png_expand_batch_device behind it,
+    the files' own PLTE and tRNS applied.  out_ptrs[i] receives width * height * 4 bytes (PNG_RGBA8) or * 8 (PNG_RGBA16) and
+    must be aligned to a pixel.  Returns (statuses, infos) like png_decode_files_batch: 0, -5 (ZS_BUF_ERROR: out_caps[i] is
+    below that size) or -3 (ZS_DATA_ERROR; engine.last_error() names the first failing file and the reason)."""
+    n = len(files)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("png_decode_files_rgba_batch: the argument lists differ in length")
+    if format not in (PNG_RGBA8, PNG_RGBA16):
+        raise ValueError("png_decode_files_rgba_batch: format is PNG_RGBA8 or PNG_RGBA16")
+    if any(not o or int(o) % (8 if format == PNG_RGBA16 else 4) or int(cap) < 0 for o, cap in zip(out_ptrs, out_caps)):
+        raise ValueError("png_decode_files_rgba_batch: non-null device pointers aligned to a pixel and non-negative capacities are required")
+    if n == 0:
+        return [], []
+    files = [bytes(f) for f in files]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    info, status = (_native.PngInfo * n)(), I32()
+    rc = _native.lib().zs_png_decode_files_rgba_batch(engine.handle, n, VP(*[_host_ptr(f) for f in files]),  # (read in place)
+                                                      I64(*[len(f) for f in files]), int(format),
+                                                      VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), info, status,
+                                                      ctypes.c_void_p(stream or 0))
+    if rc not in (0, -3, -5):
+        raise ValueError("zs_png_decode_files_rgba_batch failed (%d): %s" % (rc, engine.last_error()))
+    return list(status), [{k: int(getattr(i, k)) for k in _PNG_INFO_FIELDS} for i in info]
+
+
 _default_engine = None
 
 

@@ -249,4 +249,53 @@ inline bool png_walk_file(const uint8_t *f, int64_t len, PngFileInfo *info, char
     return true;
 }
 
+// What a file says about its colours: the data bytes of its PLTE and tRNS chunks (0 entries / 0 bytes: none, or ignored).
+struct PngFileColors {
+    uint8_t plte[768], trns[256];
+    int plte_entries, trns_len;
+};
+constexpr uint32_t kPngtRNS = png_type('t', 'R', 'N', 'S');
+// The second walk, over a chain png_walk_file has accepted (`info` is its result): captures PLTE and tRNS, the one ancillary
+// chunk that is interpreted -- so its CRC is checked, here on the host (it holds at most 256 bytes).  False with the reason
+// in msg for: a PLTE whose length is no multiple of 3 or outside 3 .. 768, a second PLTE or tRNS, either of them behind the
+// first IDAT, a type-3 file without a PLTE in front of its IDAT, a tRNS in front of the PLTE of a type-3 file, a tRNS whose
+// length is not 2 (type 0), 6 (type 2) or 1 .. the PLTE's entries (type 3), a tRNS with a wrong CRC.  A tRNS of a type 4 or
+// 6 file and a PLTE of a type 0 or 4 file are stepped over like any other chunk.
+inline bool png_file_colors(const uint8_t *f, int64_t len, const PngFileInfo &info, PngFileColors *col, char *msg, size_t msg_cap) {
+    memset(col, 0, sizeof *col);
+    const int ct = info.color_type;
+    const bool plte_counts = ct != 0 && ct != 4, trns_counts = ct != 4 && ct != 6;
+    bool have_plte = false, have_trns = false, idat_seen = false;
+    for (int64_t at = 8; at + 12 <= len;) {
+        const int64_t n = png_be32(f + at);
+        uint32_t type;
+        memcpy(&type, f + at + 4, 4);
+        if (type == kPngIDAT) idat_seen = true;
+        if (type == kPngPLTE && plte_counts) {
+            if (have_plte) return snprintf(msg, msg_cap, "a second PLTE at offset %lld", (long long)at), false;
+            if (idat_seen) return snprintf(msg, msg_cap, "PLTE behind IDAT (offset %lld)", (long long)at), false;
+            if (n % 3 != 0 || n < 3 || n > 768) return snprintf(msg, msg_cap, "PLTE holds %lld bytes", (long long)n), false;
+            have_plte = true;
+            col->plte_entries = (int)(n / 3);
+            memcpy(col->plte, f + at + 8, (size_t)n);
+        }
+        if (type == kPngtRNS && trns_counts) {
+            if (have_trns) return snprintf(msg, msg_cap, "a second tRNS at offset %lld", (long long)at), false;
+            if (idat_seen) return snprintf(msg, msg_cap, "tRNS behind IDAT (offset %lld)", (long long)at), false;
+            if (ct == 3 && !have_plte) return snprintf(msg, msg_cap, "tRNS in front of PLTE (offset %lld)", (long long)at), false;
+            const bool fits = ct == 0 ? n == 2 : ct == 2 ? n == 6 : n >= 1 && n <= col->plte_entries;
+            if (!fits) return snprintf(msg, msg_cap, "tRNS holds %lld bytes at color type %d", (long long)n, ct), false;
+            if (crc32_bytes_slow(0, f + at + 4, (uint64_t)n + 4) != png_be32(f + at + 8 + n))
+                return snprintf(msg, msg_cap, "CRC error in tRNS chunk at offset %lld", (long long)at), false;
+            have_trns = true;
+            col->trns_len = (int)n;
+            memcpy(col->trns, f + at + 8, (size_t)n);
+        }
+        at += 12 + n;
+        if (type == kPngIEND) break;
+    }
+    if (ct == 3 && !have_plte) return snprintf(msg, msg_cap, "color type 3 without a PLTE in front of IDAT"), false;
+    return true;
+}
+
 }  // namespace zs

@@ -30,11 +30,11 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
                                            "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
-                                           "spec_compact"};
+                                           "spec_compact", "png_expand"};
 
 }  // namespace
 
@@ -71,9 +71,10 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw;
     uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
     hipEvent_t ev_crc[2] = {};            // KC and its finishing launch (profiling)
+    hipEvent_t ev_expand[2] = {};         // KX (profiling)
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1421,6 +1422,7 @@ int zs_ctx_create(int device, zs_ctx **out) {
     for (auto &e : c->ev) (void)hipEventCreate(&e);
     for (auto &e : c->ev_spec) (void)hipEventCreate(&e);
     for (auto &e : c->ev_crc) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_expand) (void)hipEventCreate(&e);
     {
         // the link kernel relies on the LDS applying the lanes of one DS_MSKOR_RTN_B32 in lane order: check it here
         int *d_ok = nullptr, ok = 0;
@@ -1486,12 +1488,14 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
     if (c->crc32_tab) (void)hipFree(c->crc32_tab);
     for (auto &e : c->ev_crc)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_expand)
         if (e) (void)hipEventDestroy(e);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pin_io) (void)hipHostFree(c->pin_io);
@@ -1563,7 +1567,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
-    if (s == kStCrc32 || s == kStSpecCompact) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks) and KSc (the speculative walk's compaction)
+    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction) and KX (the expansion to RGBA)
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine
@@ -2634,6 +2638,122 @@ extern "C" int zs_png_decode_batch_device(zs_ctx *c, int n, const void *const *i
     return finish(rc);
 }
 
+// ------------------------------------------------------------------ expansion to RGBA (KX, zs_png.hip): raw scanlines -> pixels a caller can show
+namespace {
+constexpr int64_t kExpandSlice = 1 << 25;  // rows a launch, as for KA
+
+// The images of one KX launch: descriptors, the row offsets of the flat row list, and one table per palette image.
+struct PngExpandJob {
+    std::vector<PngExpandImg> img;
+    std::vector<int32_t> off;
+    std::vector<uint32_t> tables;
+    int64_t rows = 0;
+    double ms = 0;  // profiling: the launches
+    void add(const void *in, void *out, int64_t w, int64_t h, int depth, int color, int format, const uint8_t *plte, int entries, const uint8_t *trns, int trns_len) {
+        PngExpandImg im{(const uint8_t *)in, (uint8_t *)out, (int32_t)w, (int32_t)h, depth, color, format, 0, {0, 0, 0}, 0};
+        if (color == 3) {
+            im.pal_off = (int32_t)tables.size();
+            tables.resize(tables.size() + kPngPalEntries);
+            png_expand_table(plte, entries, trns, trns_len, tables.data() + im.pal_off);
+        } else if (trns_len > 0 && (color == 0 || color == 2)) {
+            for (int k = 0; k < (color == 0 ? 1 : 3); k++) im.key[k] = (uint16_t)(trns[2 * k] << 8 | trns[2 * k + 1]);
+            im.has_key = 1;
+        }
+        img.push_back(im);
+        off.push_back((int32_t)rows);
+        rows += h;
+    }
+};
+
+// Uploads the job through the staging buffer and launches KX on `s`.  Waits for `s` once: for the upload (the staging buffer
+// is the caller's again), or, with profiling on, for the launches.
+bool png_expand_run(zs_ctx *c, PngExpandJob &job, int format, hipStream_t s, bool *no_memory) {
+    *no_memory = false;
+    const int m = (int)job.img.size();
+    const size_t b_img = sizeof(PngExpandImg) * (size_t)m, b_off = (sizeof(int32_t) * ((size_t)m + 1) + 15) & ~(size_t)15, b_tab = sizeof(uint32_t) * job.tables.size();
+    if (!ensure(c, c->png_ximg, b_img + b_off + b_tab) || !ensure_pinned(c, b_img + b_off + b_tab)) {
+        *no_memory = true;
+        return false;
+    }
+    uint8_t *hp = (uint8_t *)c->pinned;
+    memcpy(hp, job.img.data(), b_img);
+    memcpy(hp + b_img, job.off.data(), sizeof(int32_t) * (size_t)m);
+    const int32_t total = (int32_t)job.rows;
+    memcpy(hp + b_img + sizeof(int32_t) * (size_t)m, &total, sizeof total);
+    if (b_tab) memcpy(hp + b_img + b_off, job.tables.data(), b_tab);
+    ZS_HIP(c, hipMemcpyAsync(c->png_ximg.p, c->pinned, b_img + b_off + b_tab, hipMemcpyHostToDevice, s));
+    const bool prof = c->profiling;
+    if (!prof) ZS_HIP(c, hipStreamSynchronize(s));
+    else (void)hipEventRecord(c->ev_expand[0], s);
+    const PngExpandImg *d_img = (const PngExpandImg *)c->png_ximg.p;
+    const int32_t *d_off = (const int32_t *)((const uint8_t *)c->png_ximg.p + b_img);
+    const uint32_t *d_tab = (const uint32_t *)((const uint8_t *)c->png_ximg.p + b_img + b_off);
+    for (int64_t row0 = 0; row0 < job.rows; row0 += kExpandSlice) {
+        const int64_t rows = std::min<int64_t>(kExpandSlice, job.rows - row0);
+        const dim3 grid((unsigned)((rows + kExpandRowsPerWg - 1) / kExpandRowsPerWg)), block(64 * kExpandRowsPerWg);
+        if (format == ZS_PNG_FMT_RGBA16) hipLaunchKernelGGL(zs_png_expand_kernel<ZS_PNG_FMT_RGBA16>, grid, block, 0, s, d_img, d_off, d_tab, m, row0);
+        else hipLaunchKernelGGL(zs_png_expand_kernel<ZS_PNG_FMT_RGBA8>, grid, block, 0, s, d_img, d_off, d_tab, m, row0);
+        ZS_HIP(c, hipGetLastError());
+    }
+    if (prof) {
+        (void)hipEventRecord(c->ev_expand[1], s);
+        ZS_HIP(c, hipStreamSynchronize(s));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev_expand[0], c->ev_expand[1]);
+        job.ms = ms;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int zs_png_expand_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *width, const int64_t *height, const int *bit_depth,
+                                          const int *color_type, const void *const *plte, const int *plte_entries, const void *const *trns, const int *trns_len,
+                                          int format, void *const *out, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!in || !width || !height || !bit_depth || !color_type || !out) return ZS_STREAM_ERROR;
+    if (format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) {
+        c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return ZS_STREAM_ERROR;
+    }
+    const int px = png_expand_bytes(format);
+    int64_t total_rows = 0;
+    for (int i = 0; i < n; i++) {
+        bool ok = in[i] && out[i] && width[i] >= 1 && height[i] >= 1 && width[i] <= 0x7FFFFFFF && height[i] <= 0x7FFFFFFF && png_color_ok(color_type[i], bit_depth[i]) &&
+                  ((uintptr_t)out[i] & (uintptr_t)(px - 1)) == 0;
+        if (ok) {
+            const int ct = color_type[i], tl = trns_len && ct != 4 && ct != 6 ? trns_len[i] : 0;
+            if (ct == 3) ok = plte && plte[i] && plte_entries && plte_entries[i] >= 1 && plte_entries[i] <= 256 && tl >= 0 && tl <= plte_entries[i];
+            else ok = tl == 0 || (ct == 0 && tl == 2) || (ct == 2 && tl == 6);
+            if (ok && tl > 0) ok = trns && trns[i];
+        }
+        if (!ok) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        total_rows += height[i];
+    }
+    if (total_rows > 0x7FFFFFFF) {  // (the grid is the row list)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    PngExpandJob job;
+    for (int i = 0; i < n; i++) {
+        const int ct = color_type[i], tl = trns_len && ct != 4 && ct != 6 ? trns_len[i] : 0;
+        job.add(in[i], out[i], width[i], height[i], bit_depth[i], ct, format, ct == 3 ? (const uint8_t *)plte[i] : nullptr, ct == 3 ? plte_entries[i] : 0,
+                tl > 0 ? (const uint8_t *)trns[i] : nullptr, tl);
+    }
+    bool no_memory = false;
+    if (!png_expand_run(c, job, format, s, &no_memory)) return no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+    if (c->profiling) {
+        for (double &v : c->stage_ms) v = 0;
+        c->stage_ms[kStPngExpand] = job.ms;
+    }
+    return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
+}
+
 // ------------------------------------------------------------------ CRC-32 (KC, zs_crc32.hip), PNG files on top of it
 namespace {
 static_assert(sizeof(zs_png_info) == sizeof(PngFileInfo) && offsetof(zs_png_info, n_idat) == offsetof(PngFileInfo, n_idat), "zs_png_info mirrors PngFileInfo");
@@ -2903,18 +3023,42 @@ extern "C" int zs_png_file_info(const void *file, int64_t len, zs_png_info *info
     return png_walk_file((const uint8_t *)file, len, (PngFileInfo *)info, msg, sizeof msg, true, [](const PngChunkRef &) {}) ? ZS_OK : ZS_DATA_ERROR;
 }
 
+extern "C" int zs_png_file_colors(const void *file, int64_t len, void *plte768, int *plte_entries, void *trns256, int *trns_len) {
+    if (!file || len < 0 || !plte768 || !plte_entries || !trns256 || !trns_len) return ZS_STREAM_ERROR;
+    char msg[160];
+    PngFileInfo info;
+    PngFileColors col;
+    if (!png_walk_file((const uint8_t *)file, len, &info, msg, sizeof msg, true, [](const PngChunkRef &) {}) ||
+        !png_file_colors((const uint8_t *)file, len, info, &col, msg, sizeof msg))
+        return ZS_DATA_ERROR;
+    memcpy(plte768, col.plte, 3 * (size_t)col.plte_entries), *plte_entries = col.plte_entries;
+    memcpy(trns256, col.trns, (size_t)col.trns_len), *trns_len = col.trns_len;
+    return ZS_OK;
+}
+
+namespace {
 // Files -> pixels: the walk on the host, one upload, KC over the critical chunks (IDAT data gathered on the way), then the
-// decode call on the gathered streams of the files that are whole.
-extern "C" int zs_png_decode_files_batch(zs_ctx *c, int n, const void *const *file, const int64_t *file_len, void *const *out, const int64_t *out_cap,
-                                         zs_png_info *info, int *status, void *hip_stream) {
+// decode call on the gathered streams of the files that are whole.  format < 0: the raw scanlines go to out[i]; otherwise
+// (zs_png_decode_files_rgba_batch) into a buffer of the context, and KX takes them from there to out[i] in that format.
+int png_decode_files(zs_ctx *c, int n, const void *const *file, const int64_t *file_len, int format, void *const *out, const int64_t *out_cap,
+                     zs_png_info *info, int *status, void *hip_stream) {
     if (!c || n < 0) return ZS_STREAM_ERROR;
     if (n == 0) return ZS_OK;
     if (!file || !file_len || !out || !out_cap) return ZS_STREAM_ERROR;
+    const bool expand = format >= 0;
+    if (expand && format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) {
+        c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return ZS_STREAM_ERROR;
+    }
+    const int px = expand ? png_expand_bytes(format) : 1;
     for (int i = 0; i < n; i++)
-        if (!file[i] || !out[i] || file_len[i] < 0 || out_cap[i] < 0) {
+        if (!file[i] || !out[i] || file_len[i] < 0 || out_cap[i] < 0 || ((uintptr_t)out[i] & (uintptr_t)(px - 1)) != 0) {
             c->err = "stream error";
             return ZS_STREAM_ERROR;
         }
+    std::vector<PngFileColors> colors(expand ? (size_t)n : 0);
+    std::vector<int64_t> raw_at((size_t)n, 0);
+    size_t raw_total = 0;
     std::vector<PngFileInfo> fi((size_t)n);
     std::vector<std::string> why((size_t)n);
     std::vector<int> st((size_t)n, ZS_OK);
@@ -2925,16 +3069,18 @@ extern "C" int zs_png_decode_files_batch(zs_ctx *c, int n, const void *const *fi
     for (int i = 0; i < n; i++) {
         auto &r = refs[(size_t)i];
         PngFileInfo &f = fi[(size_t)i];
-        if (!png_walk_file((const uint8_t *)file[i], file_len[i], &f, msg, sizeof msg, false, [&](const PngChunkRef &x) { r.push_back(x); })) {
+        if (!png_walk_file((const uint8_t *)file[i], file_len[i], &f, msg, sizeof msg, false, [&](const PngChunkRef &x) { r.push_back(x); }) ||
+            (expand && !png_file_colors((const uint8_t *)file[i], file_len[i], f, &colors[(size_t)i], msg, sizeof msg))) {
             st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = msg;
         } else if (f.idat_bytes > kCrcMaxLen || zs_png_idat_layout(f.width, f.height, f.bits_per_pixel, f.interlace, nullptr, nullptr) > kCrcMaxLen) {
             st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = "the image or its IDAT data is above 2 GiB - 1 KiB";
-        } else if (out_cap[i] < f.pixel_bytes) {
-            snprintf(msg, sizeof msg, "the image needs %lld bytes, out_cap is %lld", (long long)f.pixel_bytes, (long long)out_cap[i]);
+        } else if (out_cap[i] < (expand ? f.width * f.height * px : f.pixel_bytes)) {  // (an image below 2 GiB of scanlines has fewer than 2^34 pixels)
+            snprintf(msg, sizeof msg, "the image needs %lld bytes, out_cap is %lld", (long long)(expand ? f.width * f.height * px : f.pixel_bytes), (long long)out_cap[i]);
             st[(size_t)i] = ZS_BUF_ERROR, why[(size_t)i] = msg;
         }
         if (info) memcpy(&info[i], &f, sizeof f);
         if (st[(size_t)i] != ZS_OK) continue;
+        if (expand) raw_at[(size_t)i] = (int64_t)raw_total, raw_total += ((size_t)f.pixel_bytes + 255) & ~(size_t)255;
         int64_t r7[kAdam7Passes];
         (void)zs_png_idat_layout(f.width, f.height, f.bits_per_pixel, f.interlace, nullptr, r7);
         for (int64_t v : r7) rows += v;
@@ -2968,7 +3114,7 @@ extern "C" int zs_png_decode_files_batch(zs_ctx *c, int n, const void *const *fi
     };
     Crc32Job job;
     bool no_memory = false;
-    if (!ensure(c, c->png_gather, gather + 256)) return all_fail(ZS_MEM_ERROR);
+    if (!ensure(c, c->png_gather, gather + 256) || (expand && !ensure(c, c->png_raw, raw_total + 256))) return all_fail(ZS_MEM_ERROR);
     if (!crc32_begin(c, (int)n_spans, blob, &job, &no_memory)) return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
     std::vector<const void *> idat;
     std::vector<int> who;  // the files that go on
@@ -3007,7 +3153,7 @@ extern "C" int zs_png_decode_files_batch(zs_ctx *c, int n, const void *const *fi
         if (st[(size_t)i] != ZS_OK) continue;
         const PngFileInfo &p = fi[(size_t)i];
         d_who.push_back(i), d_idat.push_back(idat[j]), d_len.push_back(p.idat_bytes), d_w.push_back(p.width), d_h.push_back(p.height);
-        d_bits.push_back(p.bits_per_pixel), d_il.push_back(p.interlace), d_out.push_back(out[i]);
+        d_bits.push_back(p.bits_per_pixel), d_il.push_back(p.interlace), d_out.push_back(expand ? (void *)((uint8_t *)c->png_raw.p + raw_at[(size_t)i]) : out[i]);
     }
     if (!d_who.empty()) {
         std::vector<int> dst_st(d_who.size(), ZS_STREAM_ERROR);
@@ -3029,8 +3175,39 @@ extern "C" int zs_png_decode_files_batch(zs_ctx *c, int n, const void *const *fi
             why[(size_t)d_who[j]] = reason;
         }
     }
-    if (c->profiling) c->stage_ms[kStCrc32] = crc_ms;
+    double expand_ms = 0;
+    if (expand) {  // KX over the files that are whole
+        PngExpandJob xjob;
+        for (int i : d_who) {
+            if (st[(size_t)i] != ZS_OK) continue;
+            const PngFileInfo &p = fi[(size_t)i];
+            const PngFileColors &col = colors[(size_t)i];
+            xjob.add((const uint8_t *)c->png_raw.p + raw_at[(size_t)i], out[i], p.width, p.height, p.bit_depth, p.color_type, format, col.plte, col.plte_entries,
+                     col.trns, col.trns_len);
+        }
+        if (!xjob.img.empty()) {
+            if (!png_expand_run(c, xjob, format, s, &no_memory)) return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+            if (!hip_stream && hipStreamSynchronize(s) != hipSuccess) return all_fail(ZS_STREAM_ERROR);
+            expand_ms = xjob.ms;
+        }
+    }
+    if (c->profiling) c->stage_ms[kStCrc32] = crc_ms, c->stage_ms[kStPngExpand] = expand_ms;
     return verdict();
+}
+}  // namespace
+
+extern "C" int zs_png_decode_files_batch(zs_ctx *c, int n, const void *const *file, const int64_t *file_len, void *const *out, const int64_t *out_cap,
+                                         zs_png_info *info, int *status, void *hip_stream) {
+    return png_decode_files(c, n, file, file_len, -1, out, out_cap, info, status, hip_stream);
+}
+
+extern "C" int zs_png_decode_files_rgba_batch(zs_ctx *c, int n, const void *const *file, const int64_t *file_len, int format, void *const *out,
+                                              const int64_t *out_cap, zs_png_info *info, int *status, void *hip_stream) {
+    if (format < 0) {
+        if (c) c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return ZS_STREAM_ERROR;
+    }
+    return png_decode_files(c, n, file, file_len, format, out, out_cap, info, status, hip_stream);
 }
 
 // ------------------------------------------------------------------ multi-GPU batch entry points

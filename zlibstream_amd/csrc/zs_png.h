@@ -225,4 +225,148 @@ ZS_HD void adam7_group(const Adam7Img &im, int64_t y, int64_t rb, uint8_t *dst, 
 ZS_HD int64_t adam7_row_groups(uint64_t row_addr, int64_t rb, int G) { return ((int64_t)(row_addr & (uint64_t)(G - 1)) + rb + G - 1) / G; }
 ZS_HD int64_t adam7_row_b0(uint64_t row_addr, int G) { return -(int64_t)(row_addr & (uint64_t)(G - 1)); }
 
+// ---- expansion to RGBA (KX, zs_png.hip, and its host model tests/cpp/test_png_expand.cpp) ----
+// Raw scanlines of any legal (colour type, bit depth) pair -> rows of width * 4 bytes (R, G, B, A) or of width * 4 uint16 in
+// host order (R, G, B, A), no padding.  Exact integer arithmetic:
+//   a sample v of depth d to 8 bits:  d < 8: v * 255 / (2^d - 1) (x255, x85, x17);  d = 8: v;  d = 16: (v * 255 + 32895) >> 16
+//   ... to 16 bits:                   d < 16: v * 65535 / (2^d - 1) (x65535, x21845, x4369, x257);  d = 16: v, read big-endian
+//   gray (types 0, 4): R = G = B = the scaled sample
+//   alpha: types 4, 6: the scaled alpha sample; types 0, 2 with a tRNS key: 0 where the pixel's samples at their original
+//          depth equal the key's low d bits (gray: one sample, RGB: all three), the maximum elsewhere; without a key: the maximum
+//   palette (type 3): index k -> entry k of the image's 256-entry RGBA8 table, which the host fills from PLTE and tRNS
+//          (entries past PLTE: 0, 0, 0, 255), so no index is range-checked; to 16 bits every channel x257
+constexpr int ZS_PNG_FMT_RGBA8 = 0, ZS_PNG_FMT_RGBA16 = 1;
+ZS_HD constexpr int png_expand_bytes(int format) { return format == ZS_PNG_FMT_RGBA16 ? 8 : 4; }
+constexpr int kPngPalEntries = 256;  // a palette image's table: entry k = R | G << 8 | B << 16 | A << 24
+constexpr int kPngExpandGroup = 16;  // output bytes of one store: 4 pixels of RGBA8, 2 of RGBA16
+
+struct PngExpandImg {
+    const uint8_t *in;  // height rows of ceil(width * depth * channels / 8) bytes
+    uint8_t *out;       // height rows of width * png_expand_bytes(format) bytes, aligned to a pixel
+    int32_t width, height, depth, color, format;
+    int32_t pal_off;    // type 3: the table's first entry in the call's list of tables
+    uint16_t key[3];    // tRNS of types 0 (key[0]) and 2: the 16-bit values as the chunk holds them
+    uint16_t has_key;
+};
+
+// the host's share: the table of a palette image from its PLTE (entries * 3 bytes) and tRNS (trns_len bytes) data
+inline void png_expand_table(const uint8_t *plte, int entries, const uint8_t *trns, int trns_len, uint32_t *table) {
+    for (int k = 0; k < kPngPalEntries; k++) {
+        if (k >= entries) table[k] = 0xFF000000u;
+        else table[k] = (uint32_t)plte[3 * k] | (uint32_t)plte[3 * k + 1] << 8 | (uint32_t)plte[3 * k + 2] << 16 | (uint32_t)(k < trns_len ? trns[k] : 255) << 24;
+    }
+}
+
+template <int F, int D>
+ZS_HD uint32_t png_expand_scale(uint32_t v) {
+    if constexpr (F == ZS_PNG_FMT_RGBA8) return D == 16 ? (v * 255 + 32895) >> 16 : v * (255u / ((1u << (D < 8 ? D : 8)) - 1));
+    else return v * (65535u / ((1u << D) - 1));
+}
+template <int F>
+ZS_HD uint64_t png_expand_pack(uint32_t r, uint32_t g, uint32_t b, uint32_t a) {
+    if constexpr (F == ZS_PNG_FMT_RGBA8) return (uint64_t)(r | g << 8 | b << 16 | a << 24);
+    else return (uint64_t)r | (uint64_t)g << 16 | (uint64_t)b << 32 | (uint64_t)a << 48;
+}
+
+// One pixel from its samples s[0 .. channels) at their original depth (a palette image: s[0] is the index).
+template <int F, int CT, int D>
+ZS_HD uint64_t png_expand_samples(const PngExpandImg &im, const uint32_t *pal, const uint32_t *s) {
+    constexpr uint32_t top = F == ZS_PNG_FMT_RGBA8 ? 255u : 65535u, mask = (1u << D) - 1;
+    if constexpr (CT == 3) {
+        const uint32_t e = pal[s[0]];
+        if constexpr (F == ZS_PNG_FMT_RGBA8) return e;
+        else return ((uint64_t)(e & 255) | (uint64_t)(e >> 8 & 255) << 16 | (uint64_t)(e >> 16 & 255) << 32 | (uint64_t)(e >> 24) << 48) * 257;
+    } else if constexpr (CT == 0) {
+        const uint32_t v = png_expand_scale<F, D>(s[0]);
+        return png_expand_pack<F>(v, v, v, im.has_key && s[0] == (im.key[0] & mask) ? 0 : top);
+    } else if constexpr (CT == 4) {
+        const uint32_t v = png_expand_scale<F, D>(s[0]);
+        return png_expand_pack<F>(v, v, v, png_expand_scale<F, D>(s[1]));
+    } else if constexpr (CT == 2) {
+        const bool keyed = im.has_key && s[0] == (im.key[0] & mask) && s[1] == (im.key[1] & mask) && s[2] == (im.key[2] & mask);
+        return png_expand_pack<F>(png_expand_scale<F, D>(s[0]), png_expand_scale<F, D>(s[1]), png_expand_scale<F, D>(s[2]), keyed ? 0 : top);
+    } else
+        return png_expand_pack<F>(png_expand_scale<F, D>(s[0]), png_expand_scale<F, D>(s[1]), png_expand_scale<F, D>(s[2]), png_expand_scale<F, D>(s[3]));
+}
+
+// NPX pixels from x on (all inside the row), pixel j in px[j].  At 8 and 16 bits the bytes that hold them are taken in with
+// one copy of constant length; below that a pixel is a part of one byte, and neighbours share bytes.
+template <int F, int CT, int D, int NPX>
+ZS_HD void png_expand_pixels(const PngExpandImg &im, const uint32_t *pal, const uint8_t *row, int64_t x, uint64_t *px) {
+    constexpr int CH = CT == 2 ? 3 : CT == 4 ? 2 : CT == 6 ? 4 : 1;
+    if constexpr (D < 8) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < NPX; j++) {
+            const int64_t bit = (x + j) * D;
+            const uint32_t s = ((uint32_t)row[bit >> 3] >> (8 - D - (int)(bit & 7))) & ((1u << D) - 1);
+            px[j] = png_expand_samples<F, CT, D>(im, pal, &s);
+        }
+    } else {
+        constexpr int SB = D / 8, BPP = CH * SB;
+        uint8_t raw[NPX * BPP];
+        __builtin_memcpy(raw, row + x * BPP, NPX * BPP);
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < NPX; j++) {
+            uint32_t s[CH];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < CH; k++) s[k] = SB == 1 ? raw[j * BPP + k] : (uint32_t)raw[j * BPP + 2 * k] << 8 | raw[j * BPP + 2 * k + 1];
+            px[j] = png_expand_samples<F, CT, D>(im, pal, s);
+        }
+    }
+}
+
+template <int F, int CT, int D>
+ZS_HD void png_expand_group_as(const PngExpandImg &im, const uint32_t *pal, int64_t y, uint8_t *dst, int64_t b0) {
+    constexpr int P = png_expand_bytes(F), N = kPngExpandGroup / P;
+    constexpr int CH = CT == 2 ? 3 : CT == 4 ? 2 : CT == 6 ? 4 : 1;
+    const int64_t rb = (int64_t)im.width * P;
+    const int64_t lo = b0 < 0 ? 0 : b0, hi = b0 + kPngExpandGroup < rb ? b0 + kPngExpandGroup : rb;  // the group's bytes inside the row
+    const uint8_t *row = im.in + y * png_bits_row_bytes(im.width, D * CH);
+    if (lo == b0 && hi == b0 + kPngExpandGroup) {
+        uint64_t px[N], v[2];
+        png_expand_pixels<F, CT, D, N>(im, pal, row, b0 / P, px);
+        if constexpr (F == ZS_PNG_FMT_RGBA8) v[0] = px[0] | px[1] << 32, v[1] = px[2] | px[3] << 32;
+        else v[0] = px[0], v[1] = px[1];
+        __builtin_memcpy(__builtin_assume_aligned(dst + b0, kPngExpandGroup), v, kPngExpandGroup);
+    } else
+        for (int64_t b = lo; b < hi; b += P) {  // (dst and b0 are multiples of P: whole pixels)
+            uint64_t px;
+            png_expand_pixels<F, CT, D, 1>(im, pal, row, b / P, &px);
+            __builtin_memcpy(__builtin_assume_aligned(dst + b, P), &px, P);
+        }
+}
+
+// Bytes [b0, b0 + 16) of output row y (`dst` = the row's first byte, aligned to a pixel; dst + b0 is 16-aligned, so the
+// first group of a row may begin in front of it and the last one end behind it: those two store pixel by pixel, every other
+// group is one aligned store of 16 bytes).  pal: the image's table (type 3 only).  No byte outside the row is touched,
+// and none is touched twice.  The (colour type, depth) pair is the same for a whole row: one jump, then straight code.
+template <int F>
+ZS_HD void png_expand_group(const PngExpandImg &im, const uint32_t *pal, int64_t y, uint8_t *dst, int64_t b0) {
+    switch (im.color * 32 + im.depth) {
+    case 0 * 32 + 1: png_expand_group_as<F, 0, 1>(im, pal, y, dst, b0); break;
+    case 0 * 32 + 2: png_expand_group_as<F, 0, 2>(im, pal, y, dst, b0); break;
+    case 0 * 32 + 4: png_expand_group_as<F, 0, 4>(im, pal, y, dst, b0); break;
+    case 0 * 32 + 8: png_expand_group_as<F, 0, 8>(im, pal, y, dst, b0); break;
+    case 0 * 32 + 16: png_expand_group_as<F, 0, 16>(im, pal, y, dst, b0); break;
+    case 2 * 32 + 8: png_expand_group_as<F, 2, 8>(im, pal, y, dst, b0); break;
+    case 2 * 32 + 16: png_expand_group_as<F, 2, 16>(im, pal, y, dst, b0); break;
+    case 3 * 32 + 1: png_expand_group_as<F, 3, 1>(im, pal, y, dst, b0); break;
+    case 3 * 32 + 2: png_expand_group_as<F, 3, 2>(im, pal, y, dst, b0); break;
+    case 3 * 32 + 4: png_expand_group_as<F, 3, 4>(im, pal, y, dst, b0); break;
+    case 3 * 32 + 8: png_expand_group_as<F, 3, 8>(im, pal, y, dst, b0); break;
+    case 4 * 32 + 8: png_expand_group_as<F, 4, 8>(im, pal, y, dst, b0); break;
+    case 4 * 32 + 16: png_expand_group_as<F, 4, 16>(im, pal, y, dst, b0); break;
+    case 6 * 32 + 8: png_expand_group_as<F, 6, 8>(im, pal, y, dst, b0); break;
+    case 6 * 32 + 16: png_expand_group_as<F, 6, 16>(im, pal, y, dst, b0); break;
+    default: break;  // (the host admits the fifteen pairs of table 11.1 only)
+    }
+}
+
+
 }  // namespace zs

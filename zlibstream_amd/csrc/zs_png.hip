@@ -1,4 +1,4 @@
-// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip).  What inflate leaves for
+// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip); KA and KX behind it.  What inflate leaves for
 // an IDAT payload is, per row, a filter-type byte and the filtered bytes; reconstruction reads reconstructed neighbours
 // (left, above, above-left), so it is serial along a row and across rows.  Two kernels:
 //   zs_png_scan_kernel      one workgroup per image over its type bytes: the first invalid one, and the segments
@@ -285,6 +285,35 @@ __global__ __launch_bounds__(64 * kAdam7RowsPerWg) void zs_png_adam7_kernel(cons
         const int64_t ng = adam7_row_groups(addr, rb, G), b0 = adam7_row_b0(addr, G);
         for (int64_t g = lane; g < ng; g += 64) adam7_group<G>(im, y, rb, dst, b0 + g * G);
     }
+}
+
+// KX: raw scanlines to RGBA8 / RGBA16 (zs_png.h png_expand_group), shaped like KA.  The grid is the flat list of all images'
+// output rows, four rows a workgroup: wave w takes row 4 * block + w, and its lanes the row's address-aligned groups of 16
+// bytes, 64 at a time -- one full-width store per lane, 1 KiB contiguous over the wave; the ragged first and last groups of
+// a row go out pixel by pixel.  A lane reads the input bytes that hold its 4 (RGBA16: 2) pixels with plain cached loads,
+// contiguous over the wave as well (at 1, 2 and 4 bits neighbouring lanes share bytes).  The wave of a palette row first
+// copies its image's table (1 KiB) into an LDS slice of its own.  No atomics, no traffic between waves: no output byte has
+// two writers.
+constexpr int kExpandRowsPerWg = 4;
+
+template <int F>
+__global__ __launch_bounds__(64 * kExpandRowsPerWg) void zs_png_expand_kernel(const PngExpandImg *imgs, const int32_t *row_off, const uint32_t *tables, int n,
+                                                                               int64_t row0) {
+    __shared__ uint32_t s_pal[kExpandRowsPerWg][kPngPalEntries];
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    const int64_t r = row0 + (int64_t)blockIdx.x * kExpandRowsPerWg + w;
+    const bool active = r < (int64_t)row_off[n];
+    const int i = active ? png_row_image(row_off, n, r) : 0;
+    const PngExpandImg im = imgs[i];
+    if (active && im.color == 3)
+        for (int k = lane; k < kPngPalEntries; k += 64) s_pal[w][k] = tables[(int64_t)im.pal_off + k];
+    __syncthreads();  // (every wave arrives: none has left yet)
+    if (!active) return;
+    const int64_t y = r - row_off[i], rb = (int64_t)im.width * png_expand_bytes(F);
+    uint8_t *dst = im.out + y * rb;
+    const uint64_t addr = (uint64_t)(uintptr_t)dst;
+    const int64_t ng = adam7_row_groups(addr, rb, kPngExpandGroup), b0 = adam7_row_b0(addr, kPngExpandGroup);
+    for (int64_t g = lane; g < ng; g += 64) png_expand_group<F>(im, s_pal[w], y, dst, b0 + g * kPngExpandGroup);
 }
 
 }  // namespace zs
