@@ -390,7 +390,10 @@ ZS_API int zs_png_decode_files_rgba_batch(zs_ctx *ctx, int n, const void *const 
  * chunk walk (levels 4-9): streams that tried it, those of them that took the transfer maps after all, chunks whose guessed
  * entry was wrong; "spec_periodic" -- those of the fallbacks that were never walked (periodic by the match kernel's count);
  * "inf_lane_streams" -- streams of the last inflate call whose chain had blocks for the lane decoder (blocks with checkpoints and
- * no tokens: under 4 bits per symbol, or no room for the token buffers). */
+ * no tokens: under 4 bits per symbol, or no room for the token buffers); "inf_wave_streams" -- streams of the last inflate call
+ * at or above the block-parallel minimum (1 KiB) that the block-parallel pass could not finish and handed to the one-wave decoder
+ * (a chain that does not close, a table or list that overflows, a block that reports failure; streams below the minimum go to
+ * that decoder without being counted). */
 ZS_API int64_t zs_ctx_counter(const zs_ctx *ctx, const char *name);
 /* (A test hook, not part of the product's surface: declared only where ZS_TESTING is defined.)
  * For the tests: what the parse stage of the last deflate call left for its first stream, copied from the device -- "state"

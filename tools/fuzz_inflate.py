@@ -1,11 +1,14 @@
 """Random zlib streams through the block-parallel inflate (zs_inflate_batch) against their plaintext, for a number of seconds:
 data kinds (text, zeros, runs, noise, image rows, mixtures), producers (system zlib at every level / strategy / memLevel with
-random flush points, this library's deflate), sizes from below the parallel path's threshold to a few MiB, batches of 1-6.
+random flush points, this library's deflate, and "built": tests/deflate_builder.py's random complete codes over random symbol
+subsets with random legal tokens, which no encoder emits), sizes from below the parallel path's threshold to a few MiB, batches of 1-6.
    python tools/fuzz_inflate.py [seconds] [seed] [small]     (prints every failing case with its seed; `small`: streams of a few bytes
    to a few hundred KiB in batches of up to 40 -- the sizes around the line between the one-wave decoder and the block-parallel pass)"""
-import os, sys, time, zlib
+import os, random, sys, time, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import deflate_builder
 import numpy as np
 from zlibstream_amd import Engine, datagen
 eng = Engine(0)
@@ -69,8 +72,13 @@ while time.time() < t_end:
             n = int(rng.choice([int(rng.integers(1, 3000)), int(rng.integers(3000, 40000)), int(rng.integers(40000, 700000))], p=[0.3, 0.4, 0.3]))
         else:
             n = int(rng.choice([int(rng.integers(1, 300000)), int(rng.integers(300000, 4 << 20)), int(rng.integers(4 << 20, 12 << 20))], p=[0.2, 0.6, 0.2]))
-        d = make_data(rng, n)
-        z, note = make_stream(rng, d)
+        if rng.integers(0, 8) == 0:  # a hand-built stream: its plaintext is what the builder's tokens spell
+            bseed = int(rng.integers(0, 1 << 31))
+            z, d = deflate_builder.random_codes_stream(random.Random(bseed))
+            note = "built, random_codes_stream(random.Random(%d))" % bseed
+        else:
+            d = make_data(rng, n)
+            z, note = make_stream(rng, d)
         datas.append(d), streams.append(z), notes.append("%d bytes -> %d, %s" % (len(d), len(z), note))
     try:
         got = eng.inflate_batch(streams, [len(d) for d in datas])

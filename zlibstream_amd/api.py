@@ -111,7 +111,9 @@ class Engine:
     def counter(self, name):
         """zs_ctx_counter: "fast_rounds", "fast_fallbacks", "round_runs", "cut_rounds", "lit_fallbacks", "lit_engine_bytes",
         "spec_streams", "spec_fallbacks", "spec_periodic", "spec_wrong_chunks", "png_segments", "inf_lane_streams" (streams of
-        the last inflate call whose chain had blocks for the lane decoder: checkpoints and no tokens)."""
+        the last inflate call whose chain had blocks for the lane decoder: checkpoints and no tokens), "inf_wave_streams"
+        (streams of the last inflate call at or above the block-parallel minimum that the block-parallel pass handed to the
+        one-wave decoder; streams below the minimum are not counted)."""
         return int(self._lib.zs_ctx_counter(self._h, name.encode()))
 
     def stage_ms(self):

@@ -62,6 +62,7 @@ struct zs_ctx {
     std::vector<int64_t> inf_used;
     int64_t *inf_probe = nullptr;
     int inf_lane_streams = 0;  // streams of the last inflate call whose chain had blocks for the lane decoder (checkpoints, no tokens)
+    int inf_wave_streams = 0;  // streams of the last inflate call that the block-parallel pass took and handed on to the one-wave decoder
     int64_t png_segments = 0;  // independent runs of rows the last unfilter call found (zs_png.h png_row_cuts)
     int fast_rounds = 0;  // rounds the last call's DeflateFast took over its chunks (0: one workgroup per stream)
     bool no_rounds_once = false;  // the next plan takes one workgroup per stream (set when the rounds gave up)
@@ -1537,6 +1538,7 @@ int64_t zs_ctx_counter(const zs_ctx *c, const char *name) {
     if (k == "spec_periodic") return c->spec_periodic;  // ... fallbacks that were never walked (the match kernel's count of RUNS tiles)
     if (k == "spec_wrong_chunks") return c->spec_wrong_chunks;
     if (k == "inf_lane_streams") return c->inf_lane_streams;  // streams of the last inflate call with blocks for the lane decoder
+    if (k == "inf_wave_streams") return c->inf_wave_streams;  // ... at or above the parallel minimum that run_inflate_par handed to `rest`
     if (k == "png_segments") return c->png_segments;  // segments the last zs_png_unfilter_batch_device call found
     return -1;
 }
@@ -1815,6 +1817,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
                      uint32_t *adler_out = nullptr) {
     const int m = (int)idx.size();
     c->inf_lane_streams = 0;
+    c->inf_wave_streams = 0;
     if (m == 0) return true;
     std::vector<ParStream> ps((size_t)m);
     int64_t nchunks = 0, ncand = 0, nblk = 0, ncells = 0, nfx = 0;
@@ -1978,6 +1981,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
             // no room for the windows (streams cut into very many small blocks): the one-wave decoder needs none
             c->err.clear();
             for (int j = 0; j < m; j++) rest.push_back(idx[(size_t)j]);
+            c->inf_wave_streams = m;
             return true;
         }
         // the window pass runs over groups of blocks (zs_inflate_par.hip, W): enough groups to give every CU one, none
@@ -2070,6 +2074,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
         const int64_t tb = (q.end_bit + 7) >> 3;
         if (!q.ok || bfail[(size_t)j] || tb + 4 > in_len[i]) {
             rest.push_back(i);  // not decodable here, or truncated: the sequential decoder classifies it
+            c->inf_wave_streams++;
             continue;
         }
         abuf.push_back(out[i]), alen.push_back(q.out_len), atr.push_back((const uint8_t *)in[i] + tb), aidx.push_back(j);
