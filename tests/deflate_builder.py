@@ -142,6 +142,7 @@ class Builder:
         self.acc, self.n = 0, 0  # the bits behind them, LSB first
         self.plaintext = bytearray()
         self.blocks = []         # (kind, first bit, bits)
+        self.lengths = []        # per dynamic block, as written: (first bit, literal/length, distance, bit-length code lengths)
 
     # ---- bits
     @property
@@ -167,7 +168,7 @@ class Builder:
         self.put((1 << k) - 1 if ones else 0, k)
 
     def mark(self):
-        return (len(self.buf), self.acc, self.n, len(self.plaintext), len(self.blocks))
+        return (len(self.buf), self.acc, self.n, len(self.plaintext), len(self.blocks), len(self.lengths))
 
     def rollback(self, m):
         """Forget everything written since mark() returned m (cases that are placed by a block's measured bit length)."""
@@ -175,6 +176,7 @@ class Builder:
         self.acc, self.n = m[1], m[2]
         del self.plaintext[m[3]:]
         del self.blocks[m[4]:]
+        del self.lengths[m[5]:]
 
     # ---- blocks
     def _tokens(self, tokens, lit, dist, alt258):
@@ -248,6 +250,7 @@ class Builder:
         clc = canonical_codes(cl)
         hclen = max(4, max(i for i, s in enumerate(CL_ORDER) if cl[s]) + 1)
         start = self.bit_pos
+        self.lengths.append((start, seq[:hlit], seq[hlit:], cl))
         self.put(1 if final else 0, 1), self.put(2, 2)
         self.put(hlit - 257, 5), self.put(hdist - 1, 5), self.put(hclen - 4, 4)
         for s in CL_ORDER[:hclen]:
@@ -286,8 +289,13 @@ class Builder:
         return body + zlib.adler32(bytes(self.plaintext)).to_bytes(4, "big")
 
 
+LAYOUT = {}  # stream -> (its Builder's blocks, its Builder's lengths), for tests/test_deflate_reader.py
+
+
 def _finish(b, pad_ones=False):
-    return b.finish(pad_ones), bytes(b.plaintext)
+    z = b.finish(pad_ones)
+    LAYOUT[z] = (tuple(b.blocks), tuple(b.lengths))
+    return z, bytes(b.plaintext)
 
 
 # ------------------------------------------------------------------ random complete codes and legal tokens (N; tools/fuzz_inflate.py)

@@ -362,3 +362,20 @@ def test_tail_records_match_the_engine_search(model, tmp_path):
         run(str(tmp_path / "tail_3"), 6)
     finally:
         del os.environ["ZS_NO_TAIL_RECORDS"]
+
+
+def test_emit_cases_through_the_sequential_trees(model, tmp_path):
+    """tests/emit_cases.py -- the 15-bit and 7-bit repairs, forced codes, ties, scan_tree's repeat codes, stored blocks at every
+    bit phase, the longest symbols -- through the host's build_block_trees, emit_dyn_header and encode_symbol of zs_core.h:
+    the sequential twin of what tests/test_gpu_emit_cases.py asks of build_tree_wave and the bit-packing kernel.  Every case
+    at its own level and strategy, the HuffmanOnly ones at levels 1 and 9 as well; dist_overflow (1 MiB, a third of a second
+    in the chunked form) is in."""
+    import emit_cases as ec
+    with batch():
+        for name, data, level, strategy, _ in ec.catalogue():
+            (tmp_path / name).write_bytes(data)
+            settings = [(level, strategy)] + ([(1, ec.HO), (9, ec.HO)] if strategy == ec.HO else [])
+            if name == "dist_overflow":
+                settings += list(ec.DIST_OVERFLOW_ALSO + ec.DIST_OVERFLOW_BYTES_ONLY)
+            for lvl, strat in dict.fromkeys(settings):
+                run(str(tmp_path / name), lvl, strat, "rle" if strat == ec.RLE else "chunk" if lvl >= 4 else "seq")
