@@ -70,7 +70,7 @@ struct zs_ctx {
     hipEvent_t ev[kStCount + 1] = {};
     double stage_ms[kStCount] = {};
     uint32_t *crc_tab = nullptr;
-    DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, pieces, scratch,
+    DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, tile_bits, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
         par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw;
     uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
@@ -608,9 +608,10 @@ plan_again:
         !ensure(c, c->seg_entry, 2 * (size_t)(pl.n_segs + 2)) || !ensure(c, c->seg_symbase, 4 * (size_t)(pl.n_segs + 2)) ||
         !ensure(c, c->seg_stale, (size_t)pl.n_segs + 64) || !ensure(c, c->entry, 2 * (size_t)(pl.n_chunks + 2)) ||
         !ensure(c, c->symbase, 4 * (size_t)(pl.n_chunks + 2)) || !ensure(c, c->stale, (size_t)pl.n_chunks + 64) ||
-        !ensure(c, c->syms, 4 * (size_t)pl.n_syms + 64) || !ensure(c, c->blk_end, 4 * (size_t)pl.n_blocks + 64) ||
+        !ensure(c, c->syms, 4 * (size_t)pl.n_syms + kSymsSlack) || !ensure(c, c->blk_end, 4 * (size_t)pl.n_blocks + 64) ||
         !ensure(c, c->blk_top, 4 * (size_t)pl.n_blocks + 64) || !ensure(c, c->blocks, sizeof(BlockRec) * (size_t)pl.n_blocks) ||
         !ensure(c, c->trees, sizeof(TreeWork) * (size_t)pl.n_blocks) || !ensure(c, c->info, sizeof(BlockInfo) * (size_t)pl.n_blocks) ||
+        !ensure(c, c->tile_bits, 4 * (size_t)kEbTiles * (size_t)pl.n_blocks + 64) ||
         !ensure(c, c->pieces, 4 * (size_t)pl.n_pieces + 64) || !ensure(c, c->scratch, (size_t)kScratchBytes * (size_t)n) ||
         !ensure(c, c->cut_pos, 8 * (size_t)pl.n_cuts + 64) || !ensure(c, c->cut_bkt, 8 * (size_t)pl.n_cuts + 64) ||
         (pl.n_spec && (!ensure(c, c->spec_rec, 8 * (size_t)pl.n_spec + 64) || !ensure(c, c->spec_flags, 4 * (size_t)n + 64) ||
@@ -1213,14 +1214,25 @@ plan_again:
                            (uint32_t)pl.w_blocks.size(), dev<uint2>(c->work) + o_blocks);
     }
     hipLaunchKernelGGL(zs_trees_kernel, dim3((unsigned)pl.w_blocks.size()), dim3(trees_threads), 0, stream, d_sd, d_st, d_work + o_blocks,
-                       dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info), strategy, level, 2);
+                       dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info), dev<int32_t>(c->tile_bits), strategy, level);
     mark(11);
     ZS_HIP(c, hipStreamWaitEvent(stream, c->ev_pre, 0));  // the cleared output and the Adler pieces (second stream, above)
     hipLaunchKernelGGL(zs_offsets_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<BlockRec>(c->blocks),
                        dev<BlockInfo>(c->info), dev<TreeWork>(c->trees), dev<uint32_t>(c->pieces), level, n);
     mark(12);
-    hipLaunchKernelGGL(zs_emit_bits_kernel, dim3((unsigned)pl.w_blocks.size()), dim3(256), 0, stream, d_sd, d_st, d_work + o_blocks,
-                       dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info));
+    // one workgroup for a block's header and one for each of its tiles of symbols, whose bit counts the tree kernel left
+    // (a workgroup takes every eb_tiles-th tile: any number covers them all); a symbol is at least one input byte
+    int eb_tiles = kEbTiles;
+    if (level != 0) {
+        int64_t longest = 0;
+        for (int i = 0; i < n; i++) longest = std::max(longest, in_len[i]);
+        eb_tiles = (int)std::min<int64_t>(kEbTiles, (longest + 1) / kEbTile + 1);
+    }
+    static const char *const eb_env = getenv("ZS_EB_TILES");  // (read once per process)
+    if (eb_env) eb_tiles = std::max(1, std::min(kEbTiles, atoi(eb_env)));
+    hipLaunchKernelGGL(zs_emit_bits_kernel, dim3((unsigned)pl.w_blocks.size(), (unsigned)(1 + eb_tiles)), dim3(256), 0, stream, d_sd, d_st,
+                       d_work + o_blocks, dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info),
+                       dev<int32_t>(c->tile_bits));
     mark(13);
     ZS_HIP(c, hipGetLastError());
     StreamState *hst = (StreamState *)c->pinned;
@@ -1373,7 +1385,7 @@ bool device_adlers(zs_ctx *c, int m, const void *const *bufs, const int64_t *len
 int batch_prefix_that_fits(zs_ctx *c, int n, const int64_t *in_len, const int64_t *out_cap, int lo, int per_byte) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return n;
-    const DevBuf *held[] = {&c->link, &c->mm, &c->maps, &c->segmap, &c->supmap, &c->syms, &c->trees, &c->blocks, &c->info, &c->stage_in, &c->stage_out,
+    const DevBuf *held[] = {&c->link, &c->mm, &c->maps, &c->segmap, &c->supmap, &c->syms, &c->trees, &c->blocks, &c->info, &c->tile_bits, &c->stage_in, &c->stage_out,
                             &c->scratch, &c->ins_bits, &c->mm_bak};
     size_t have = 0;
     for (const DevBuf *b : held) have += b->cap;
@@ -1487,7 +1499,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
-                      &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
+                      &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->tile_bits, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
                       &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw};
     for (DevBuf *b : bufs)

@@ -2995,8 +2995,19 @@ __global__ __launch_bounds__(64) void zs_fast_blocks_kernel(const StreamDesc *sd
 //     overflow repair (the sequential gen_bitlen, untouched);
 //   * Gen_codes (Trees.cs:1123-1151): `next_code[len]++` in symbol order is a returning LDS add per symbol (the LDS
 //     applies the lanes of one instruction in lane order, see K1).
-// `pd`: kHeapSize words, `nc`: 16 words of LDS scratch.  Every lane returns max_code.
-__device__ int build_tree_wave(TreeWork &w, uint32_t *hk, uint32_t *pd, uint32_t *nc, CtData *tree, const TreeDesc &d, int lane) {
+// `pd`: W::kHeap words, `nc`: 16 words of LDS scratch.  Every lane returns max_code.
+// `W` is what Build_tree keeps per tree: TreeWork, or SideTree for the distance tree, which another wave builds at the
+// same time.  Each has its own opt_len / static_len: the forced codes, the lengths and the overflow repair all add to them.
+struct SideTree {
+    static constexpr int kHeap = 2 * kDCodes + 1;
+    uint16_t heap[kHeap];
+    uint16_t bl_count[kMaxBits + 1];
+    CtData bltree[kBlCodes];  // scan_tree's tallies for the distance tree
+    int heap_len, heap_max;
+    int opt_len, static_len;
+};
+template <class W>
+__device__ int build_tree_wave(W &w, uint32_t *hk, uint32_t *pd, uint32_t *nc, CtData *tree, const TreeDesc &d, int lane) {
     int len = 0, max_code = -1;
     for (int base = 0; base < d.elems; base += 64) {
         const int n = base + lane;
@@ -3019,7 +3030,7 @@ __device__ int build_tree_wave(TreeWork &w, uint32_t *hk, uint32_t *pd, uint32_t
     }
     __threadfence_block();
     if (lane == 0) {
-        w.heap_max = kHeapSize;
+        w.heap_max = W::kHeap;
         int hl = len;
         for (int n = hl / 2; n >= 1; n--) pqdownheap_packed(hk, hl, n);
         int node = d.elems;
@@ -3043,13 +3054,13 @@ __device__ int build_tree_wave(TreeWork &w, uint32_t *hk, uint32_t *pd, uint32_t
     __threadfence_block();
     // ---- lengths = depths
     const int hmax = w.heap_max, root = w.heap[hmax];
-    for (int h = hmax + lane; h < kHeapSize; h += 64) {
+    for (int h = hmax + lane; h < W::kHeap; h += 64) {
         const int n = w.heap[h];
         pd[n] = h == hmax ? ((uint32_t)n << 8) : (((uint32_t)tree[n].dl << 8) | 1u);
     }
     __threadfence_block();
     for (int r = 0; r < 6; r++) {  // 2^6 >= any depth a tree over <= 65535 counts can have
-        for (int h = hmax + lane; h < kHeapSize; h += 64) {
+        for (int h = hmax + lane; h < W::kHeap; h += 64) {
             const int n = w.heap[h];
             const uint32_t v = pd[n], pv = pd[v >> 8];
             pd[n] = (pv & ~0xFFu) | ((v & 0xFFu) + (pv & 0xFFu));  // one word: always a consistent (ancestor, distance) pair
@@ -3057,7 +3068,7 @@ __device__ int build_tree_wave(TreeWork &w, uint32_t *hk, uint32_t *pd, uint32_t
         __threadfence_block();
     }
     bool over = false;
-    for (int h = hmax + lane; h < kHeapSize; h += 64) over |= (int)(pd[w.heap[h]] & 0xFFu) > d.max_length;
+    for (int h = hmax + lane; h < W::kHeap; h += 64) over |= (int)(pd[w.heap[h]] & 0xFFu) > d.max_length;
     (void)root;
     if (__ballot(over)) {
         if (lane == 0) gen_bitlen(w, tree, max_code, d);  // the reference's walk with its overflow repair
@@ -3066,7 +3077,7 @@ __device__ int build_tree_wave(TreeWork &w, uint32_t *hk, uint32_t *pd, uint32_t
         if (lane < 16) nc[lane] = 0;
         __threadfence_block();
         int opt = 0, stat = 0;
-        for (int h = hmax + lane; h < kHeapSize; h += 64) {
+        for (int h = hmax + lane; h < W::kHeap; h += 64) {
             const int n = w.heap[h];
             const int bits = (int)(pd[n] & 0xFFu);
             tree[n].dl = (uint16_t)bits;
@@ -3105,25 +3116,34 @@ __device__ int build_tree_wave(TreeWork &w, uint32_t *hk, uint32_t *pd, uint32_t
     __threadfence_block();
     return max_code;
 }
-// Tr_flush_block's tree phase (zs_core.h build_block_trees) with the wave form of Build_tree; lane 0's return value counts.
-__device__ int build_block_trees_wave(TreeWork &w, uint32_t *hk, uint32_t *pd, uint32_t *nc, int stored_len, bool can_store,
-                                      int strategy, int lane) {
-    if (lane == 0) {
-        w.opt_len = w.static_len = 0;
-        for (int i = 0; i < kBlCodes; i++) w.bltree[i].fc = 0;
-    }
-    __threadfence_block();
+// Tr_flush_block's tree phase (zs_core.h build_block_trees) with the wave form of Build_tree, in two steps.  The literal
+// and the distance tree do not depend on each other, nor do their scan_trees, which only add to bltree's frequencies:
+// wave 0 takes the literal tree, wave 1 the distance tree with a work area of its own, and what wave 1 counted is added
+// behind a barrier.  Then one wave builds bltree and picks the block type; lane 0's return value counts.
+__device__ void build_ld_tree_wave(TreeWork &w, SideTree &sw, uint32_t *hk, uint32_t *pd, uint32_t *nc, uint32_t *hk2, uint32_t *pd2,
+                                   uint32_t *nc2, int wave, int lane) {
     const TreeDesc ld = {0, kLCodes, kMaxBits, kLiterals + 1};
     const TreeDesc dd = {1, kDCodes, kMaxBits, 0};
-    const TreeDesc bd = {2, kBlCodes, kMaxBlBits, 0};
-    const int lmax = build_tree_wave(w, hk, pd, nc, w.ltree, ld, lane);
-    const int dmax = build_tree_wave(w, hk, pd, nc, w.dtree, dd, lane);
-    if (lane == 0) {
-        w.l_max_code = lmax, w.d_max_code = dmax;
-        scan_tree(w, w.ltree, lmax);
-        scan_tree(w, w.dtree, dmax);
+    if (wave == 0) {
+        const int lmax = build_tree_wave(w, hk, pd, nc, w.ltree, ld, lane);
+        if (lane == 0) {
+            w.l_max_code = lmax;
+            scan_tree(w, w.ltree, lmax);
+        }
+    } else {
+        const int dmax = build_tree_wave(sw, hk2, pd2, nc2, w.dtree, dd, lane);
+        if (lane == 0) {
+            w.d_max_code = dmax;
+            scan_tree(sw, w.dtree, dmax);
+        }
     }
+}
+__device__ int build_bl_tree_wave(TreeWork &w, const SideTree &sw, uint32_t *hk, uint32_t *pd, uint32_t *nc, int stored_len,
+                                  bool can_store, int strategy, int lane) {
+    if (lane < kBlCodes) w.bltree[lane].fc += sw.bltree[lane].fc;
+    if (lane == 0) w.opt_len += sw.opt_len, w.static_len += sw.static_len;
     __threadfence_block();
+    const TreeDesc bd = {2, kBlCodes, kMaxBlBits, 0};
     build_tree_wave(w, hk, pd, nc, w.bltree, bd, lane);
     int type = 2;
     if (lane == 0) {
@@ -3150,6 +3170,12 @@ __device__ int build_block_trees_wave(TreeWork &w, uint32_t *hk, uint32_t *pd, u
 // rewritten once the block counts are known: a prefix sum over the streams, then (stream, block) pairs for the live
 // entries and a mark on the rest.
 constexpr uint32_t kNoWork = 0xFFFFFFFFu;
+// K9 packs a block's bits by tiles of symbols; K7 counts each tile's bits for it
+constexpr int kEbTile = 2048;  // symbols per tile
+constexpr int kEbTiles = 8;    // tiles of a full block: kBlockSyms symbols and END_BLOCK
+static_assert(kEbTile * kEbTiles >= kBlockSyms + 1, "a block's symbols and END_BLOCK fit its tiles");
+constexpr int kSymsSlack = 64;  // bytes of room behind the symbol array: K7 reads a block's symbols in vectors of four
+static_assert(kSymsSlack >= 16, "a 16-byte load that starts inside the symbols ends inside the array");
 __global__ __launch_bounds__(1024) void zs_live_scan_kernel(const StreamState *st, int n, int32_t *live_pre) {
     __shared__ int32_t wsum[16];
     __shared__ int32_t carry;
@@ -3193,22 +3219,35 @@ __global__ __launch_bounds__(256) void zs_live_fill_kernel(const int32_t *live_p
 }
 
 // ------------------------------------------------------------------ K7
-// One workgroup per block: histogram the block's symbols (Tr_tally_*), then wave 0 replays Build_tree x3 exactly
-// (build_tree_wave) and picks the block type.
+// One workgroup per block: histogram the block's symbols (Tr_tally_*), then waves 0 and 1 replay Build_tree exactly
+// (build_tree_wave) for the literal and the distance tree side by side, wave 0 builds bltree and picks the block type.
+// A block of more than one K9 tile gets the bits of each tile counted beside the last tree, once the code lengths are known.
+#ifdef ZS_BS_PROF
+#define BS_PF(i) { const long long now_ = wall_clock64(); pf[i] += now_ - pf_t; pf_t = now_; }
+#else
+#define BS_PF(i)
+#endif
+typedef u32x4 __attribute__((aligned(4))) u32x4a4;
+typedef u32x4 __attribute__((aligned(8))) u32x4a8;
 __global__ __launch_bounds__(256) void zs_trees_kernel(const StreamDesc *sd, const StreamState *st, const uint2 *work,
                                                        const uint32_t *syms, const BlockRec *blocks, TreeWork *trees,
-                                                       BlockInfo *info, int strategy, int level, int phase) {
-    __shared__ TreeWork tw;
+                                                       BlockInfo *info, int32_t *tile_bits, int strategy, int level) {
+    __shared__ __attribute__((aligned(16))) TreeWork tw;
+    __shared__ SideTree sw;
     __shared__ uint32_t hl[kLCodes], hd[kDCodes];
     __shared__ uint32_t hk[kHeapSize + 8];  // Build_tree's priority queue (the sift reads a few entries past the end)
     __shared__ uint32_t pd[kHeapSize + 1], nc[16];  // (ancestor, distance) words of the depth pass; per-length counters
+    __shared__ uint32_t hk2[SideTree::kHeap + 8], pd2[SideTree::kHeap + 1], nc2[16];  // the same for the distance tree's wave
+    __shared__ uint32_t sh_tile[2 * kEbTiles];  // bits per K9 tile under the dynamic and under the static codes
+    __shared__ int sh_type;
+#ifdef ZS_BS_PROF
+    long long pf[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pf_t = wall_clock64();
+#endif
     uint2 w = work[blockIdx.x];
     if (w.x == kNoWork || st[w.x].deferred) return;
     const StreamDesc s = sd[w.x];
     const int b = (int)w.y;
-    // phase 0: the blocks that end inside the bulk parse; phase 1: the rest; 2: all
-    const int nb_body = s.fast_runs > 0 ? 0 : (int)(st[w.x].body_syms / kBlockSyms);
-    if (phase == 0 ? b >= nb_body : ((phase == 1 && b < nb_body) || b >= st[w.x].nblocks)) return;
+    if (b >= st[w.x].nblocks) return;
     const BlockRec r = blocks[s.blk_off + b];
     if (level == 0 && r.nsyms == 0 && s.plan_nblk > 0) {
         // DeflateStored tallies nothing and level 0 skips the tree comparison (Trees.cs:601-620): stored while the block
@@ -3222,50 +3261,159 @@ __global__ __launch_bounds__(256) void zs_trees_kernel(const StreamDesc *sd, con
         }
         return;
     }
-    for (int i = threadIdx.x; i < kLCodes; i += blockDim.x) hl[i] = 0;
-    for (int i = threadIdx.x; i < kDCodes; i += blockDim.x) hd[i] = 0;
+    const int tid = (int)threadIdx.x, nthr = (int)blockDim.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < kLCodes; i += nthr) hl[i] = 0;
+    for (int i = tid; i < kDCodes; i += nthr) hd[i] = 0;
+    if (tid < 2 * kEbTiles) sh_tile[tid] = 0;
     __syncthreads();
+    BS_PF(0);
     const uint32_t *sy = syms + s.sym_off + r.sym_start;
-    for (int i = threadIdx.x; i < r.nsyms; i += blockDim.x) {
-        uint32_t v = sy[i];
-        int dist = (int)(v >> 16), lc = (int)(v & 0xFFFF);
+    auto tally = [&](uint32_t v) {
+        const int dist = (int)(v >> 16), lc = (int)(v & 0xFFFF);
         if (dist == 0) atomicAdd(&hl[lc], 1u);
         else {
             atomicAdd(&hl[length_code(lc) + kLiterals + 1], 1u);
             atomicAdd(&hd[dist_code(dist - 1)], 1u);
         }
+    };
+    {
+        // four symbols per lane and load (a block starts at any symbol: global memory takes 16 bytes at 4-byte alignment),
+        // four loads in flight
+        const int nvec = r.nsyms >> 2;
+        const __attribute__((address_space(1))) u32x4a4 *sv = (const __attribute__((address_space(1))) u32x4a4 *)(uintptr_t)sy;
+        int i = tid;
+        for (; i + 3 * nthr < nvec; i += 4 * nthr) {
+            const u32x4 q0 = sv[i], q1 = sv[i + nthr], q2 = sv[i + 2 * nthr], q3 = sv[i + 3 * nthr];
+#pragma unroll
+            for (int k = 0; k < 4; k++) tally(q0[k]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) tally(q1[k]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) tally(q2[k]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) tally(q3[k]);
+        }
+        for (; i < nvec; i += nthr) {
+            const u32x4 q = sv[i];
+#pragma unroll
+            for (int k = 0; k < 4; k++) tally(q[k]);
+        }
+        for (int j = (nvec << 2) + tid; j < r.nsyms; j += nthr) tally(sy[j]);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < kHeapSize; i += blockDim.x) {
+    BS_PF(1);
+    for (int i = tid; i < kHeapSize; i += nthr) {
         tw.ltree[i].fc = i < kLCodes ? (uint16_t)hl[i] : 0;
         tw.ltree[i].dl = 0;
     }
-    for (int i = threadIdx.x; i < 2 * kDCodes + 1; i += blockDim.x) {
+    for (int i = tid; i < 2 * kDCodes + 1; i += nthr) {
         tw.dtree[i].fc = i < kDCodes ? (uint16_t)hd[i] : 0;
         tw.dtree[i].dl = 0;
     }
-    for (int i = threadIdx.x; i < 2 * kBlCodes + 1; i += blockDim.x) tw.bltree[i].fc = 0, tw.bltree[i].dl = 0;
+    for (int i = tid; i < 2 * kBlCodes + 1; i += nthr) tw.bltree[i].fc = 0, tw.bltree[i].dl = 0;
+    if (tid < kBlCodes) sw.bltree[tid].fc = 0, sw.bltree[tid].dl = 0;
+    if (tid == 0) tw.opt_len = tw.static_len = 0, sw.opt_len = sw.static_len = 0;
     __syncthreads();
-    if (threadIdx.x == 0) tw.ltree[kEndBlock].fc = 1;
+    if (tid == 0) tw.ltree[kEndBlock].fc = 1;
     __syncthreads();
-    if (threadIdx.x < 64) {
-        int type = build_block_trees_wave(tw, hk, pd, nc, r.stored_len, r.can_store != 0, strategy, (int)threadIdx.x);
-        if (threadIdx.x == 0) {
-        // level 0 skips the tree comparison: opt_lenb = static_lenb = stored_len + 5, i.e. stored when the block
-        // start is still in the window, else static trees (Trees.cs:601-620)
-        if (level == 0) type = r.can_store ? 0 : 1;
-        BlockInfo bi;
-        bi.type = type;
-        bi.bits = type == 1 ? 3 + tw.static_len : type == 2 ? 3 + tw.opt_len : 0;
-        bi.bit_start = 0;
-        info[s.blk_off + b] = bi;
+    BS_PF(2);
+    if (wave < 2) build_ld_tree_wave(tw, sw, hk, pd, nc, hk2, pd2, nc2, wave, lane);
+#ifdef ZS_BS_PROF
+    if (wave == 1) BS_PF(4);  // the distance tree and its scan_tree
+#endif
+    __syncthreads();
+    BS_PF(3);  // (wave 0: the literal tree and its scan_tree; wave 1: its wait for them)
+    // ---- the bits of each K9 tile (END_BLOCK is symbol number nsyms), for K9 to find where a tile starts: the code lengths
+    // are final, the block type is not, so the waves beside wave 0 sum both the dynamic and the static lengths while wave 0
+    // builds the bit-length tree.  hl / hd become length tables: dynamic | static << 8, extra bits included.
+    const int total = r.nsyms + 1;
+    const bool tiled = total > kEbTile;
+    if (tiled) {
+        for (int i = tid; i < kLCodes; i += nthr) {
+            const uint32_t x = i > kLiterals ? (uint32_t)extra_lbits(i - kLiterals - 1) : 0;
+            hl[i] = (((uint32_t)tw.ltree[i].dl + x) & 0xFFu) | (((uint32_t)static_llen(i) + x) << 8);
+        }
+        for (int i = tid; i < kDCodes; i += nthr) {
+            const uint32_t x = (uint32_t)extra_dbits(i);
+            hd[i] = (((uint32_t)tw.dtree[i].dl + x) & 0xFFu) | ((5u + x) << 8);
+        }
+        __syncthreads();
+    }
+    if (wave == 0) {
+        int type = build_bl_tree_wave(tw, sw, hk, pd, nc, r.stored_len, r.can_store != 0, strategy, lane);
+        if (lane == 0) {
+            // level 0 skips the tree comparison: opt_lenb = static_lenb = stored_len + 5, i.e. stored when the block
+            // start is still in the window, else static trees (Trees.cs:601-620)
+            if (level == 0) type = r.can_store ? 0 : 1;
+            BlockInfo bi;
+            bi.type = type;
+            bi.bits = type == 1 ? 3 + tw.static_len : type == 2 ? 3 + tw.opt_len : 0;
+            bi.bit_start = 0;
+            info[s.blk_off + b] = bi;
+            sh_type = type;
+        }
+    } else if (tiled) {
+        const int wk = tid - 64, nwk = nthr - 64;
+        const __attribute__((address_space(1))) u32x4a4 *sv = (const __attribute__((address_space(1))) u32x4a4 *)(uintptr_t)sy;
+        uint32_t dyn[kEbTiles], stat[kEbTiles];
+#pragma unroll
+        for (int t = 0; t < kEbTiles; t++) {
+            dyn[t] = stat[t] = 0;
+            if (t * kEbTile < total) {
+                // (a vector may reach up to 12 bytes past the block's symbols: what it reads there does not count, and the
+                // symbol array ends in kSymsSlack bytes of room.  The tables' entries of codes without a length -- scan_tree's
+                // 0xFFFF guard behind max_code among them -- are never looked up: no symbol of the block has such a code)
+                const int nv = ((total < (t + 1) * kEbTile ? total : (t + 1) * kEbTile) - t * kEbTile + 3) >> 2;
+#pragma unroll 4
+                for (int j = wk; j < nv; j += nwk) {
+                    const u32x4 q = sv[t * (kEbTile / 4) + j];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const int i = t * kEbTile + 4 * j + k;
+                        const uint32_t v = q[k];
+                        const int dist = (int)(v >> 16), lc = (int)(v & 0xFFFF);
+                        uint32_t e = 0;
+                        if (i < r.nsyms) e = dist == 0 ? hl[lc] : hl[length_code(lc) + kLiterals + 1] + hd[dist_code(dist - 1)];
+                        else if (i == r.nsyms) e = hl[kEndBlock];
+                        dyn[t] += e & 0xFFu;
+                        stat[t] += e >> 8;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < kEbTiles; t++) {
+            if (t * kEbTile < total) {
+                uint32_t a = dyn[t], c = stat[t];
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o), c += __shfl_xor(c, o);
+                if (lane == 0) atomicAdd(&sh_tile[t], a), atomicAdd(&sh_tile[kEbTiles + t], c);
+            }
         }
     }
     __syncthreads();
-    uint32_t *dst = (uint32_t *)&trees[s.blk_off + b];
-    const uint32_t *src = (const uint32_t *)&tw;
-    for (int i = threadIdx.x; i < (int)(sizeof(TreeWork) / 4); i += blockDim.x) dst[i] = src[i];
+    BS_PF(5);
+    {
+        // 16 bytes per lane and store (a TreeWork is 8-byte aligned in the array)
+        __attribute__((address_space(1))) u32x4a8 *dv = (__attribute__((address_space(1))) u32x4a8 *)(uintptr_t)&trees[s.blk_off + b];
+        const u32x4 *src4 = (const u32x4 *)&tw;
+        constexpr int nw = (int)(sizeof(TreeWork) / 4);
+        for (int i = tid; i < nw / 4; i += nthr) dv[i] = src4[i];
+        uint32_t *dst = (uint32_t *)&trees[s.blk_off + b];
+        const uint32_t *src = (const uint32_t *)&tw;
+        if (tid < (nw & 3)) dst[(nw & ~3) + tid] = src[(nw & ~3) + tid];
+    }
+    BS_PF(6);
+    const int type = sh_type;
+    if (tiled && type != 0 && tid < kEbTiles) tile_bits[(int64_t)(s.blk_off + b) * kEbTiles + tid] = (int32_t)sh_tile[(type == 2 ? 0 : kEbTiles) + tid];
+#ifdef ZS_BS_PROF
+    BS_PF(7);
+    if (lane == 0 && wave < 2 && (blockIdx.x & 255) == 7)
+        printf("BSPROF K7 block %d wave %d nsyms %d type %d ticks(100MHz): zero=%lld histogram=%lld fill=%lld ltree+scan/wait=%lld dtree+scan=%lld bltree+type (tile bits beside it)=%lld copy-out=%lld tile bits out=%lld\n",
+               (int)blockIdx.x, wave, r.nsyms, type, pf[0], pf[1], pf[2], pf[3], pf[4], pf[5], pf[6], pf[7]);
+#endif
 }
+#undef BS_PF
 
 // ------------------------------------------------------------------ K8
 // One workgroup per stream: bit offset of every block (Send_bits is a pure concatenation; stored blocks and
@@ -3478,14 +3626,15 @@ struct LdsTree {
         return {(uint16_t)v, (uint16_t)(v >> 16)};
     }
 };
-// One workgroup per block.  The block's bit string is assembled in LDS and leaves as whole 32-bit words: thread 0
-// puts the block header (and the dynamic trees) at the front; then, 2048 symbols at a time, every thread takes 8
-// consecutive symbols, a workgroup scan of their code lengths gives each thread its bit offset, the codes are
-// OR-ed into the LDS words (ds_or), and the complete words are stored coalesced.  The partial word at the end of a
-// tile is carried into the next tile; only the first and the last word of a block can be shared with its
-// neighbours, and only those go out with atomicOr (the output was zeroed by K0).
-constexpr int kEbTile = 2048;                            // symbols per tile
-constexpr int kEbWords = kEbTile * 48 / 32 + 256;        // worst case 48 bits per symbol + dynamic header (<= 141 words) + carry
+// One workgroup per (block, part): part 0 puts the block header (thread 0; the dynamic trees with it), part 1 + t the
+// block's tiles t, t + (gridDim.y - 1), ... of 2048 symbols, END_BLOCK being symbol number nsyms.  Nobody waits for
+// anybody: a tile ends where the later tiles' bits begin, counted from the block's end -- BlockInfo.bits less the later
+// tiles' counts (zs_trees_kernel left them in `tile_bits`, eight per block) less its own, which its scan gives -- and
+// the header starts at the block's start.  A part's bit string is assembled in LDS: every thread takes 8 consecutive
+// symbols, a workgroup scan of their code lengths gives each thread its bit offset, the codes are OR-ed into the LDS
+// words (ds_or), and the words leave coalesced.  Parts meet inside words: a part's first and last word go out with
+// atomicOr (the output was zeroed by K0), the words between are its own and are stored.
+constexpr int kEbWords = kEbTile * 48 / 32 + 256;  // worst case 48 bits per symbol, or the dynamic header (<= 141 words), + carry
 struct LdsBitPut {
     uint32_t *w;   // zeroed words
     uint32_t pos;  // bit position
@@ -3501,13 +3650,21 @@ struct LdsBitPut {
     }
     __device__ void operator()(unsigned value, int nbits) { put64(value, nbits); }
 };
+#ifdef ZS_BS_PROF
+#define BS_PF(i) { const long long now_ = wall_clock64(); pf[i] += now_ - pf_t; pf_t = now_; }
+#else
+#define BS_PF(i)
+#endif
 __global__ __launch_bounds__(256) void zs_emit_bits_kernel(const StreamDesc *sd, const StreamState *st, const uint2 *work,
                                                            const uint32_t *syms, const BlockRec *blocks, const TreeWork *trees,
-                                                           const BlockInfo *info) {
+                                                           const BlockInfo *info, const int32_t *tile_bits) {
     __shared__ uint32_t lt[kLCodes], dt[kDCodes];
     __shared__ uint32_t obuf[kEbWords];
     __shared__ uint32_t wsum[4];
     __shared__ uint32_t sh_bits;
+#ifdef ZS_BS_PROF
+    long long pf[4] = {0, 0, 0, 0}, pf_t = wall_clock64();
+#endif
     uint2 w = work[blockIdx.x];
     if (w.x == kNoWork || st[w.x].deferred) return;
     const StreamDesc s = sd[w.x];
@@ -3517,26 +3674,76 @@ __global__ __launch_bounds__(256) void zs_emit_bits_kernel(const StreamDesc *sd,
     const BlockInfo bi = info[s.blk_off + b];
     uint8_t *out = s.out;
     const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    const int part = (int)blockIdx.y, ntl = (int)gridDim.y - 1;
     if (bi.type == 0) {
         int64_t pos = bi.bit_start;
-        if (tid == 0) or_bits(out, pos, (uint64_t)(r.eof & 1), 3);
         int64_t byte = (pos + 3 + 7) >> 3;
-        if (tid == 0) {
+        if (part == 0 && tid == 0) {
+            or_bits(out, pos, (uint64_t)(r.eof & 1), 3);
             unsigned len = (unsigned)r.stored_len;
             out[byte] = (uint8_t)len, out[byte + 1] = (uint8_t)(len >> 8);
             out[byte + 2] = (uint8_t)~len, out[byte + 3] = (uint8_t)(~len >> 8);
         }
-        // Copy_block (Deflate.cs:710-722): 16 bytes per lane and trip (global memory takes them at any alignment), bytes at the end
+        // Copy_block (Deflate.cs:710-722), shared by the parts: 16 bytes per lane and trip (global memory takes them at any
+        // alignment), the bytes at the end by part 0
         const gcbytes src = as_global(s.in) + (r.start - s.abs_off);  // abs_off: stream position of in[0] (0 unless the run continues a stream)
         const gbytes_w dst = as_global(out) + byte + 4;
         typedef u32x4 __attribute__((aligned(1))) u32x4u;
         const int nvec = r.stored_len >> 4;
-        for (int i = tid; i < nvec; i += 256)
+        for (int i = part * 256 + tid; i < nvec; i += 256 * (int)gridDim.y)
             *(__attribute__((address_space(1))) u32x4u *)(dst + 16 * i) = *(const __attribute__((address_space(1))) u32x4u *)(src + 16 * i);
-        for (int i = (nvec << 4) + tid; i < r.stored_len; i += 256) dst[i] = src[i];
+        if (part == 0)
+            for (int i = (nvec << 4) + tid; i < r.stored_len; i += 256) dst[i] = src[i];
         return;
     }
+    // global bit cursor of the block's start, relative to the 4-byte aligned word at or below `out`
+    uint32_t *const W = (uint32_t *)((uintptr_t)out & ~(uintptr_t)3);
+    const int64_t cur0 = bi.bit_start + (int64_t)(((uintptr_t)out & 3) << 3);
+    // `nb` bits that sit in obuf from bit (cur & 31) leave; obuf is zero again afterwards
+    auto flush = [&](int64_t cur, uint32_t nb) {
+        const uint32_t nw = ((uint32_t)(cur & 31) + nb + 31) >> 5;
+        uint32_t *g = W + (cur >> 5);
+        for (uint32_t k = tid; k < nw; k += 256) {
+            const uint32_t v = obuf[k];
+            if (k == 0 || k == nw - 1) {
+                if (v) atomicOr(g + k, v);
+            } else {
+                g[k] = v;
+            }
+            obuf[k] = 0;
+        }
+        __syncthreads();
+    };
     const TreeWork &tw = trees[s.blk_off + b];
+    if (part == 0) {
+        if (bi.type == 1) {
+            if (tid == 0) or_bits(out, bi.bit_start, 2u + (unsigned)(r.eof & 1), 3);
+            return;
+        }
+        // thread 0 sends the trees: ~350 dependent reads of code lengths, from a copy in LDS (behind the header's words)
+        constexpr int kHdrWords = 160, kTwWords = (int)(sizeof(TreeWork) / 4);
+        static_assert(kHdrWords + kTwWords <= kEbWords && sizeof(TreeWork) % 4 == 0, "the header and a TreeWork fit obuf");
+        for (int i = tid; i < kHdrWords; i += 256) obuf[i] = 0;
+        for (int i = tid; i < kTwWords; i += 256) obuf[kHdrWords + i] = ((const uint32_t *)&tw)[i];
+        __syncthreads();
+        if (tid == 0) {
+            LdsBitPut put{obuf, (uint32_t)(cur0 & 31)};
+            put(4u + (unsigned)(r.eof & 1), 3);
+            emit_dyn_header(*(const TreeWork *)(obuf + kHdrWords), put);
+            sh_bits = put.pos - (uint32_t)(cur0 & 31);
+        }
+        __syncthreads();
+        BS_PF(1);
+        flush(cur0, sh_bits);
+#ifdef ZS_BS_PROF
+        BS_PF(3);
+        if (tid == 0 && (blockIdx.x & 255) == 7) printf("BSPROF K9 block %d header ticks(100MHz): header=%lld flush=%lld\n", (int)blockIdx.x, pf[1], pf[3]);
+#endif
+        return;
+    }
+    const int total = r.nsyms + 1;  // + END_BLOCK
+    const int ntiles = (total + kEbTile - 1) / kEbTile;
+    if (part - 1 >= ntiles) return;
     if (bi.type == 2) {
         for (int i = tid; i < kLCodes; i += 256) lt[i] = (uint32_t)tw.ltree[i].fc | ((uint32_t)tw.ltree[i].dl << 16);
         if (tid < kDCodes) dt[tid] = (uint32_t)tw.dtree[tid].fc | ((uint32_t)tw.dtree[tid].dl << 16);
@@ -3546,52 +3753,15 @@ __global__ __launch_bounds__(256) void zs_emit_bits_kernel(const StreamDesc *sd,
     }
     for (int i = tid; i < kEbWords; i += 256) obuf[i] = 0;
     __syncthreads();
-    // global bit cursor, relative to the 4-byte aligned word at or below `out`
-    uint32_t *const W = (uint32_t *)((uintptr_t)out & ~(uintptr_t)3);
-    int64_t cur = bi.bit_start + (int64_t)(((uintptr_t)out & 3) << 3);
-    if (tid == 0) {
-        LdsBitPut put{obuf, (uint32_t)(cur & 31)};
-        put((unsigned)(bi.type << 1) + (unsigned)(r.eof & 1), 3);
-        if (bi.type == 2) emit_dyn_header(tw, put);
-        sh_bits = put.pos - (uint32_t)(cur & 31);
-    }
-    __syncthreads();
+    BS_PF(0);
     LdsTree L{lt}, D{dt};
     const uint32_t *sy = syms + s.sym_off + r.sym_start;
-    const int total = r.nsyms + 1;  // + END_BLOCK
-    bool first = true;              // the next flush starts with the block's first word
-    uint32_t pending = sh_bits;     // bits already in obuf behind (cur & 31)
-    // flush `nb` bits that sit in obuf from bit (cur & 31): complete words out, the partial one carried to obuf[0]
-    auto flush = [&](uint32_t nb, bool last) {
-        const uint32_t end = (uint32_t)(cur & 31) + nb;
-        const uint32_t nfull = end >> 5;
-        uint32_t *g = W + (cur >> 5);
-        const uint32_t carry = obuf[nfull];
-        __syncthreads();
-        for (uint32_t k = tid; k < nfull; k += 256) {
-            const uint32_t v = obuf[k];
-            if (k == 0 && first) {
-                if (v) atomicOr(g, v);
-            } else {
-                g[k] = v;
-            }
-            obuf[k] = 0;
-        }
-        if (tid == 0) {
-            obuf[nfull] = 0;
-            if (last) {
-                if (carry) atomicOr(g + nfull, carry);
-            } else {
-                obuf[0] = carry;
-            }
-        }
-        if (nfull) first = false;
-        cur += nb;
-        __syncthreads();
-    };
-    for (int t0 = 0; t0 < total; t0 += kEbTile) {
-        // ---- this thread's 8 symbols (END_BLOCK is symbol number nsyms)
-        const int i0 = t0 + tid * 8;
+    const int32_t *tb = tile_bits + (int64_t)(s.blk_off + b) * kEbTiles;  // written for blocks of more than one tile
+    for (int t = part - 1; t < ntiles; t += ntl) {
+        uint32_t later = 0;  // bits of the tiles behind this one
+        for (int u = t + 1; u < ntiles; u++) later += (uint32_t)tb[u];
+        // ---- this thread's 8 symbols
+        const int i0 = t * kEbTile + tid * 8;
         uint32_t v[8];
         uint32_t mybits = 0;
 #pragma unroll
@@ -3610,15 +3780,16 @@ __global__ __launch_bounds__(256) void zs_emit_bits_kernel(const StreamDesc *sd,
         }
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
-        uint32_t before = 0, tile_bits = 0;
+        uint32_t before = 0, mine = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const uint32_t x = wsum[k];
             if (k < wave) before += x;
-            tile_bits += x;
+            mine += x;
         }
+        const int64_t cur = cur0 + (int64_t)((uint32_t)bi.bits - later - mine);
         // ---- pack
-        LdsBitPut put{obuf, (uint32_t)(cur & 31) + pending + before + inc - mybits};
+        LdsBitPut put{obuf, (uint32_t)(cur & 31) + before + inc - mybits};
         uint64_t acc = 0;
         int fill = 0;
 #pragma unroll
@@ -3639,9 +3810,14 @@ __global__ __launch_bounds__(256) void zs_emit_bits_kernel(const StreamDesc *sd,
         }
         if (fill) put.put64(acc, fill);
         __syncthreads();
-        flush(pending + tile_bits, t0 + kEbTile >= total);
-        pending = 0;
+        BS_PF(2);
+        flush(cur, mine);
+        BS_PF(3);
     }
+#ifdef ZS_BS_PROF
+    if (tid == 0 && (blockIdx.x & 255) == 7)
+        printf("BSPROF K9 block %d part %d ticks(100MHz): tables=%lld tile=%lld flush=%lld\n", (int)blockIdx.x, part, pf[0], pf[2], pf[3]);
+#endif
 }
 
 // ------------------------------------------------------------------ KA
