@@ -104,6 +104,19 @@ namespace SixLabors.ZlibStream
                                                                              int* colorType, int* filter, IntPtr* extra, long* extraLen, long rowsPerWrite,
                                                                              long idatChunkBytes, IntPtr* output, long* outCap, long* outLen, int* status,
                                                                              int level, int strategy, int hashVariant, IntPtr hipStream);
+        // ---- interlaced encoding (PngEncoder's Adam7 option): the split alone (the inverse of the merge), pixels -> IDAT payloads
+        //      and pixels -> files with an interlace value of 0 or 1 per image (interlace == null: all 0)
+        [DllImport(Lib)] public static extern int zs_png_adam7_split_batch_device(IntPtr ctx, int n, IntPtr* pixels, long* width, long* height,
+                                                                                  int* bitsPerPixel, IntPtr* passesOut, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_idat_interlace_batch_device(IntPtr ctx, int n, IntPtr* pixels, long* width, long* height,
+                                                                                     int* bitsPerPixel, int* interlace, int* filter, long rowsPerWrite,
+                                                                                     IntPtr* output, long* outCap, long* outLen, int* status, int level,
+                                                                                     int strategy, int hashVariant, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_encode_interlace_batch_device(IntPtr ctx, int n, IntPtr* pixels, long* width, long* height,
+                                                                                       int* bitDepth, int* colorType, int* filter, int* interlace,
+                                                                                       IntPtr* extra, long* extraLen, long rowsPerWrite, long idatChunkBytes,
+                                                                                       IntPtr* output, long* outCap, long* outLen, int* status, int level,
+                                                                                       int strategy, int hashVariant, IntPtr hipStream);
         [StructLayout(LayoutKind.Sequential)]
         public struct PngInfo
         {

@@ -294,6 +294,52 @@ ZS_API int zs_png_encode_batch_device(zs_ctx *ctx, int n, const void *const *pix
                                       const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy,
                                       int hash_variant, void *hip_stream);
 
+/* ------------------------------------------------------------------ */
+/* Interlaced encoding (Adam7, PNG specification 8.2): the three calls below mirror the decode side.
+ *
+ * The Adam7 split on the device, n images a call, one launch over the flat list of all pass rows (KS):
+ * the exact inverse of zs_png_adam7_merge_batch_device.  pixels[i]: height[i] rows of ceil(width[i] * bits_per_pixel[i] / 8)
+ * bytes; passes_out[i] receives the image's present passes back to back in pass order, no filter bytes, absent passes absent:
+ * zs_png_idat_layout(width, height, bits, 1, ..) bytes minus one per pass row.  Both are DEVICE pointers of any alignment and
+ * must not overlap.  At 1, 2 and 4 bits the unused low bits of a pass row's last byte are written as zero, and the unused
+ * bits of a source row's last byte are never read into the output.  Arguments, ordering on hip_stream (the call waits for the
+ * stream once, for its descriptors' upload), n == 0, ZS_STREAM_ERROR (also: more than 2^31 - 1 pass rows in one call) and
+ * ZS_MEM_ERROR as for the merge call.  zs_ctx_stage_ms shows the launch as "png_split". */
+ZS_API int zs_png_adam7_split_batch_device(zs_ctx *ctx, int n, const void *const *pixels, const int64_t *width,
+                                           const int64_t *height, const int *bits_per_pixel, void *const *passes_out,
+                                           void *hip_stream);
+
+/* Pixels to IDAT payloads, interlaced or not, n images a call, nothing leaving HBM: the encode-side mirror of
+ * zs_png_decode_batch_device.  interlace: HOST array of 0 or 1 per image, NULL = all 0.  An image with interlace 0 gets
+ * byte for byte the stream of zs_png_idat_batch_device with row_bytes = ceil(width * bits / 8) and bpp = max(1, bits / 8).
+ * An image with interlace 1 is split into its passes (into a buffer the context owns, kept until zs_ctx_destroy), every
+ * present pass is filtered as an image of its own -- filtering restarts per pass, PNG specification 9.2 -- and the seven
+ * filtered passes back to back, zs_png_idat_layout(.., 1, ..) bytes, are the stream's input.  filter[i] 0..5 applies to every
+ * pass, the adaptive choice is made per pass row.  rows_per_write counts rows of the stream in stream order -- pass rows for
+ * an interlaced image, and a Write may span a pass boundary; 1: the scanline-by-scanline encoder, 0: one Write per image.
+ * out / out_cap / out_len / status / level / strategy / hash_variant as for zs_deflate_writes_batch_device, whose remarks on
+ * the literal engine apply.  ZS_STREAM_ERROR before any device work, status and out_len untouched: a null context, n < 0,
+ * null arrays, a null pixels[i] or out[i], a negative out_cap[i], width or height outside 1 .. 2^31 - 1, a bits_per_pixel
+ * outside the set, an interlace other than 0 or 1, a filter outside 0..5, a negative rows_per_write, a filtered image
+ * (zs_png_idat_layout) above 2 GiB - 1 KiB, more than 2^31 - 1 rows in one call, pass rows counted. */
+ZS_API int zs_png_idat_interlace_batch_device(zs_ctx *ctx, int n, const void *const *pixels, const int64_t *width,
+                                              const int64_t *height, const int *bits_per_pixel, const int *interlace,
+                                              const int *filter, int64_t rows_per_write, void *const *out,
+                                              const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy,
+                                              int hash_variant, void *hip_stream);
+
+/* zs_png_encode_batch_device with IHDR's interlace byte per image (HOST array of 0 or 1, NULL = all 0): the call above, then
+ * the framing launch; everything else in the file is the same.  zs_png_file_bound(zs_deflate_bound(zs_png_idat_layout(width,
+ * height, bits, interlace, 0, 0)), idat_chunk_bytes, extra_len) is always enough room.  With interlace NULL or all 0 the
+ * files are byte for byte those of zs_png_encode_batch_device.  An interlace value other than 0 or 1 is ZS_STREAM_ERROR
+ * before any device work, status and out_len untouched, like the other argument errors. */
+ZS_API int zs_png_encode_interlace_batch_device(zs_ctx *ctx, int n, const void *const *pixels, const int64_t *width,
+                                                const int64_t *height, const int *bit_depth, const int *color_type,
+                                                const int *filter, const int *interlace, const void *const *extra,
+                                                const int64_t *extra_len, int64_t rows_per_write, int64_t idat_chunk_bytes,
+                                                void *const *out, const int64_t *out_cap, int64_t *out_len, int *status,
+                                                int level, int strategy, int hash_variant, void *hip_stream);
+
 /* What a PNG file's IHDR and chunk chain say.  bits_per_pixel = bit depth times channels; idat_bytes: the IDAT chunks' data
  * together (the zlib stream); pixel_bytes: height rows of ceil(width * bits_per_pixel / 8) bytes, what the decoder writes (2^63 - 1 where that is more);
  * n_idat: IDAT chunks. */

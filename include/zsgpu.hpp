@@ -120,6 +120,36 @@ inline uint32_t Crc32Device(const void *buf, int64_t len, uint32_t seed = 0, zs_
 
 // Whole PNG files.  Room for the file around a zlib stream of idatLen bytes (host code; -1 for bad arguments) ...
 inline int64_t PngFileBound(int64_t idatLen, int64_t idatChunkBytes = 0, int64_t extraLen = 0) { return zs_png_file_bound(idatLen, idatChunkBytes, extraLen); }
+namespace detail {
+// the one body of PngEncodeBatchDevice and PngEncodeInterlaceBatchDevice: the length checks, the extra chunks' pointers and the
+// error mapping.  interlace null: zs_png_encode_batch_device; else zs_png_encode_interlace_batch_device (an empty list: all 0)
+inline std::vector<int64_t> PngEncodeFiles(const std::vector<const void *> &pixels, const std::vector<int64_t> &width, const std::vector<int64_t> &height,
+                                           const std::vector<int> &bitDepth, const std::vector<int> &colorType, const std::vector<int> &filter,
+                                           const std::vector<int> *interlace, const std::vector<std::string> &extra, int64_t rowsPerWrite, int64_t idatChunkBytes,
+                                           const std::vector<void *> &out, const std::vector<int64_t> &outCap, std::vector<int> *status, int level, int strategy,
+                                           zs_ctx *ctx, void *hipStream) {
+    const size_t n = pixels.size();
+    if (width.size() != n || height.size() != n || bitDepth.size() != n || colorType.size() != n || filter.size() != n || out.size() != n || outCap.size() != n ||
+        (!extra.empty() && extra.size() != n) || (interlace && !interlace->empty() && interlace->size() != n))
+        throw ZlibStreamException("png: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    std::vector<const void *> xp(n, nullptr);
+    std::vector<int64_t> xl(n, 0), outLen(n, 0);
+    for (size_t i = 0; i < extra.size(); i++) xp[i] = extra[i].data(), xl[i] = (int64_t)extra[i].size();
+    std::vector<int> st(n, 0);
+    const void *const *xpp = extra.empty() ? nullptr : xp.data();
+    const int64_t *xlp = extra.empty() ? nullptr : xl.data();
+    const int rc = interlace ? zs_png_encode_interlace_batch_device(c, (int)n, pixels.data(), width.data(), height.data(), bitDepth.data(), colorType.data(),
+                                                                    filter.data(), interlace->empty() ? nullptr : interlace->data(), xpp, xlp, rowsPerWrite,
+                                                                    idatChunkBytes, out.data(), outCap.data(), outLen.data(), st.data(), level, strategy, 0, hipStream)
+                             : zs_png_encode_batch_device(c, (int)n, pixels.data(), width.data(), height.data(), bitDepth.data(), colorType.data(), filter.data(), xpp,
+                                                          xlp, rowsPerWrite, idatChunkBytes, out.data(), outCap.data(), outLen.data(), st.data(), level, strategy, 0,
+                                                          hipStream);
+    if (status) *status = st;
+    if (rc != ZS_OK && !(rc == ZS_BUF_ERROR && status)) throw ZlibStreamException(std::string("png encode: ") + zs_ctx_last_error(c));
+    return outLen;
+}
+}  // namespace detail
 // ... pixels on the GPU -> complete files on the GPU, n a call: pixels[i] (device pointer, height[i] rows of raw scanline data)
 // -> out[i] (device pointer, outCap[i] bytes): signature, IHDR, extra[i] (chunks the caller has framed, host bytes, verbatim; the
 // list may be empty), the stream of PngIdatBatchDevice in IDAT chunks of at most idatChunkBytes data bytes (0: one chunk), IEND.
@@ -131,21 +161,54 @@ inline std::vector<int64_t> PngEncodeBatchDevice(const std::vector<const void *>
                                                  CompressionLevel level = CompressionLevel::DefaultCompression,
                                                  CompressionStrategy strategy = CompressionStrategy::DefaultStrategy, zs_ctx *ctx = nullptr,
                                                  void *hipStream = nullptr) {
+    return detail::PngEncodeFiles(pixels, width, height, bitDepth, colorType, filter, nullptr, extra, rowsPerWrite, idatChunkBytes, out, outCap, status, (int)level,
+                                  (int)strategy, ctx, hipStream);
+}
+// ... the same with IHDR's interlace byte per image (zs_png_encode_interlace_batch_device; interlace empty: all 0, and the files
+// are PngEncodeBatchDevice's): an image with interlace 1 is split into its Adam7 passes on the device, every pass filtered on
+// its own, rowsPerWrite counting pass rows ...
+inline std::vector<int64_t> PngEncodeInterlaceBatchDevice(const std::vector<const void *> &pixels, const std::vector<int64_t> &width,
+                                                          const std::vector<int64_t> &height, const std::vector<int> &bitDepth, const std::vector<int> &colorType,
+                                                          const std::vector<int> &filter, const std::vector<int> &interlace, const std::vector<std::string> &extra,
+                                                          int64_t rowsPerWrite, int64_t idatChunkBytes, const std::vector<void *> &out,
+                                                          const std::vector<int64_t> &outCap, std::vector<int> *status = nullptr,
+                                                          CompressionLevel level = CompressionLevel::DefaultCompression,
+                                                          CompressionStrategy strategy = CompressionStrategy::DefaultStrategy, zs_ctx *ctx = nullptr,
+                                                          void *hipStream = nullptr) {
+    return detail::PngEncodeFiles(pixels, width, height, bitDepth, colorType, filter, &interlace, extra, rowsPerWrite, idatChunkBytes, out, outCap, status, (int)level,
+                                  (int)strategy, ctx, hipStream);
+}
+// ... its first half, pixels -> the IDAT payloads' zlib streams (zs_png_idat_interlace_batch_device; interlace empty: all 0) ...
+inline std::vector<int64_t> PngIdatInterlaceBatchDevice(const std::vector<const void *> &pixels, const std::vector<int64_t> &width,
+                                                        const std::vector<int64_t> &height, const std::vector<int> &bitsPerPixel, const std::vector<int> &interlace,
+                                                        const std::vector<int> &filter, int64_t rowsPerWrite, const std::vector<void *> &out,
+                                                        const std::vector<int64_t> &outCap, CompressionLevel level = CompressionLevel::DefaultCompression,
+                                                        CompressionStrategy strategy = CompressionStrategy::DefaultStrategy, zs_ctx *ctx = nullptr,
+                                                        void *hipStream = nullptr) {
     const size_t n = pixels.size();
-    if (width.size() != n || height.size() != n || bitDepth.size() != n || colorType.size() != n || filter.size() != n || out.size() != n || outCap.size() != n ||
-        (!extra.empty() && extra.size() != n))
+    if (width.size() != n || height.size() != n || bitsPerPixel.size() != n || filter.size() != n || out.size() != n || outCap.size() != n ||
+        (!interlace.empty() && interlace.size() != n))
         throw ZlibStreamException("png: the argument lists differ in length");
     zs_ctx *c = ctx ? ctx : GpuContext::Shared();
-    std::vector<const void *> xp(n, nullptr);
-    std::vector<int64_t> xl(n, 0), outLen(n, 0);
-    for (size_t i = 0; i < extra.size(); i++) xp[i] = extra[i].data(), xl[i] = (int64_t)extra[i].size();
+    std::vector<int64_t> outLen(n, 0);
     std::vector<int> st(n, 0);
-    const int rc = zs_png_encode_batch_device(c, (int)n, pixels.data(), width.data(), height.data(), bitDepth.data(), colorType.data(), filter.data(),
-                                              extra.empty() ? nullptr : xp.data(), extra.empty() ? nullptr : xl.data(), rowsPerWrite, idatChunkBytes, out.data(),
-                                              outCap.data(), outLen.data(), st.data(), (int)level, (int)strategy, 0, hipStream);
-    if (status) *status = st;
-    if (rc != ZS_OK && !(rc == ZS_BUF_ERROR && status)) throw ZlibStreamException(std::string("png encode: ") + zs_ctx_last_error(c));
+    if (zs_png_idat_interlace_batch_device(c, (int)n, pixels.data(), width.data(), height.data(), bitsPerPixel.data(), interlace.empty() ? nullptr : interlace.data(),
+                                           filter.data(), rowsPerWrite, out.data(), outCap.data(), outLen.data(), st.data(), (int)level, (int)strategy, 0,
+                                           hipStream) != ZS_OK)
+        throw ZlibStreamException(std::string("png idat: ") + zs_ctx_last_error(c));
     return outLen;
+}
+// ... and the split alone, the inverse of PngAdam7MergeBatchDevice: pixels[i] -> passes[i] (device pointers; the present passes
+// back to back without filter bytes, PngIdatLayout's size minus one byte per pass row)
+inline void PngAdam7SplitBatchDevice(const std::vector<const void *> &pixels, const std::vector<int64_t> &width, const std::vector<int64_t> &height,
+                                     const std::vector<int> &bitsPerPixel, const std::vector<void *> &passes, zs_ctx *ctx = nullptr,
+                                     void *hipStream = nullptr) {
+    const size_t n = pixels.size();
+    if (width.size() != n || height.size() != n || bitsPerPixel.size() != n || passes.size() != n)
+        throw ZlibStreamException("png: the argument lists differ in length");
+    zs_ctx *c = ctx ? ctx : GpuContext::Shared();
+    if (zs_png_adam7_split_batch_device(c, (int)n, pixels.data(), width.data(), height.data(), bitsPerPixel.data(), passes.data(), hipStream) != ZS_OK)
+        throw ZlibStreamException(std::string("png split: ") + zs_ctx_last_error(c));
 }
 // ... the chunk walk of one file in host memory (host code; throws for a file that is not a whole PNG) ...
 inline zs_png_info PngFileInfo(const void *file, int64_t len) {

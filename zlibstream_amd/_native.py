@@ -20,6 +20,7 @@ SYMBOLS = [
     "zs_crc32_device", "zs_crc32_batch_device", "zs_png_file_bound", "zs_png_encode_batch_device", "zs_png_file_info",
     "zs_png_decode_files_batch",
     "zs_png_expand_batch_device", "zs_png_file_colors", "zs_png_decode_files_rgba_batch",
+    "zs_png_adam7_split_batch_device", "zs_png_idat_interlace_batch_device", "zs_png_encode_interlace_batch_device",
 ]
 
 
@@ -159,5 +160,14 @@ def lib():
         L.zs_png_file_colors.argtypes = [vp, i64, vp, P(i32), vp, P(i32)]
         L.zs_png_decode_files_rgba_batch.restype = i32
         L.zs_png_decode_files_rgba_batch.argtypes = [vp, i32, P(vp), P(i64), i32, P(vp), P(i64), P(PngInfo), P(i32), vp]
+    if hasattr(L, "zs_png_adam7_split_batch_device"):  # (an older build selected with ZS_LIB for an A/B run lacks the interlaced encoder)
+        L.zs_png_adam7_split_batch_device.restype = i32
+        L.zs_png_adam7_split_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(vp), vp]
+        L.zs_png_idat_interlace_batch_device.restype = i32
+        L.zs_png_idat_interlace_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), P(i32), i64, P(vp), P(i64), P(i64), P(i32),
+                                                         i32, i32, i32, vp]
+        L.zs_png_encode_interlace_batch_device.restype = i32
+        L.zs_png_encode_interlace_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), P(i32), P(i32), P(vp), P(i64), i64, i64,
+                                                           P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
     _lib = L
     return L

@@ -580,6 +580,66 @@ def _png_chunks_well_formed(b):
     return True
 
 
+def _png_encode_files(name, engine, pixel_ptrs, widths, heights, bit_depths, color_types, filters, interlace, out_ptrs, out_caps, extra, rows_per_write,
+                      idat_chunk_bytes, level, strategy, hash_variant, stream, return_status):
+    """The one body of png_encode_batch_device (interlace False: zs_png_encode_batch_device) and png_encode_interlace_batch_device
+    (interlace None or a list: zs_png_encode_interlace_batch_device): the argument checks, the extra chunks and the error
+    mapping."""
+    n = len(pixel_ptrs)
+    with_interlace = interlace is not False
+    if not with_interlace or interlace is None:
+        interlace = [0] * n
+    if not (len(widths) == len(heights) == len(bit_depths) == len(color_types) == len(filters) == len(out_ptrs) == len(out_caps) == len(interlace) == n) or \
+            (extra is not None and len(extra) != n):
+        raise ValueError(name + ": the argument lists differ in length")
+    if int(rows_per_write) < 0 or not 0 <= int(idat_chunk_bytes) <= 0x7FFFFFFF:
+        raise ValueError(name + ": rows_per_write >= 0 and 0 <= idat_chunk_bytes <= 2^31 - 1 are required")
+    if not -1 <= int(level) <= 9 or not 0 <= int(strategy) <= 4:
+        raise ValueError(name + ": level -1..9 and strategy 0..4 are required")
+    total_rows = 0
+    for p, w, h, bd, ct, f, il, o, cap in zip(pixel_ptrs, widths, heights, bit_depths, color_types, filters, interlace, out_ptrs, out_caps):
+        if not p or not o or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF or not 0 <= int(f) <= 5 or int(cap) < 0 or int(il) not in (0, 1):
+            raise ValueError(name + ": 1 <= width, height <= 2^31 - 1, filter 0..5%s and non-null device pointers are required" %
+                             (", interlace 0 or 1" if with_interlace else ""))
+        if int(ct) not in PNG_COLOR_TYPES or int(bd) not in PNG_COLOR_TYPES[int(ct)][1]:
+            raise ValueError(name + ": color type %r with bit depth %r is not in PNG specification table 11.1" % (ct, bd))
+        bits = int(bd) * PNG_COLOR_TYPES[int(ct)][0]
+        if int(il):
+            total, _, rows = png_idat_layout(w, h, bits, 1)
+            rows = sum(rows)
+        else:
+            total, rows = int(h) * ((int(w) * bits + 7) // 8 + 1), int(h)
+        if total > _CRC_MAX_LEN:
+            raise ValueError(name + ": a filtered image is above 2 GiB - 1 KiB")
+        total_rows += rows
+    if total_rows > 0x7FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 rows in one call")
+    if extra is not None:
+        extra = [bytes(x) if x is not None else b"" for x in extra]
+        if not all(_png_chunks_well_formed(x) for x in extra):
+            raise ValueError(name + ": an image's extra chunks are not a sequence of whole chunks")
+    if n == 0:
+        return (0, [], []) if return_status else []
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    # (the bytes objects are read in place: they outlive the call)
+    x_ptr = VP(*[ctypes.cast(ctypes.c_char_p(x), ctypes.c_void_p).value if x else None for x in extra]) if extra is not None else None
+    x_len = I64(*[len(x) for x in extra]) if extra is not None else None
+    head = (engine.handle, n, VP(*[int(p) for p in pixel_ptrs]), I64(*[int(x) for x in widths]), I64(*[int(x) for x in heights]),
+            I32(*[int(x) for x in bit_depths]), I32(*[int(x) for x in color_types]), I32(*[int(x) for x in filters]))
+    tail = (x_ptr, x_len, int(rows_per_write), int(idat_chunk_bytes), VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, status,
+            int(level), int(strategy), int(hash_variant), ctypes.c_void_p(stream or 0))
+    if with_interlace:
+        rc = _native.lib().zs_png_encode_interlace_batch_device(*head, I32(*[int(x) for x in interlace]), *tail)
+    else:
+        rc = _native.lib().zs_png_encode_batch_device(*head, *tail)
+    if return_status:
+        return rc, list(out_len), list(status)
+    if rc != 0:
+        raise ZlibStreamException("png encode: " + engine.last_error())
+    return list(out_len)
+
+
 def png_encode_batch_device(engine, pixel_ptrs, widths, heights, bit_depths, color_types, filters, out_ptrs, out_caps, extra=None,
                             rows_per_write=1, idat_chunk_bytes=0, level=6, strategy=0, hash_variant=0, stream=None, return_status=False):
     """Pixels -> complete PNG files for many device-resident images in one call (zs_png_encode_batch_device): the zlib stream
@@ -588,45 +648,76 @@ def png_encode_batch_device(engine, pixel_ptrs, widths, heights, bit_depths, col
     ceil(widths[i] * bit_depths[i] * channels / 8) bytes; extra: None or one bytes object per image of chunks framed already
     (PLTE, tRNS, ...), written verbatim behind IHDR.  Returns the file lengths; return_status: (rc, lengths, statuses), -5
     (ZS_BUF_ERROR) for an image whose out_caps entry is below its file's length."""
+    return _png_encode_files("png_encode_batch_device", engine, pixel_ptrs, widths, heights, bit_depths, color_types, filters, False, out_ptrs, out_caps, extra,
+                             rows_per_write, idat_chunk_bytes, level, strategy, hash_variant, stream, return_status)
+
+
+def png_adam7_split_batch_device(engine, pixel_ptrs, widths, heights, bits_per_pixel, pass_ptrs, stream=None):
+    """The Adam7 split of many device-resident images in one launch (zs_png_adam7_split_batch_device), the exact inverse of
+    png_adam7_merge_batch_device: pixel_ptrs[i] holds heights[i] rows of ceil(widths[i] * bits_per_pixel[i] / 8) bytes,
+    pass_ptrs[i] receives the present passes back to back (png_idat_layout gives their sizes; no filter bytes).  At 1, 2 and
+    4 bits the unused low bits of a pass row's last byte are zero whatever the input's padding bits hold."""
     n = len(pixel_ptrs)
-    if not (len(widths) == len(heights) == len(bit_depths) == len(color_types) == len(filters) == len(out_ptrs) == len(out_caps) == n) or \
-            (extra is not None and len(extra) != n):
-        raise ValueError("png_encode_batch_device: the argument lists differ in length")
-    if int(rows_per_write) < 0 or not 0 <= int(idat_chunk_bytes) <= 0x7FFFFFFF:
-        raise ValueError("png_encode_batch_device: rows_per_write >= 0 and 0 <= idat_chunk_bytes <= 2^31 - 1 are required")
+    if not (len(widths) == len(heights) == len(bits_per_pixel) == len(pass_ptrs) == n):
+        raise ValueError("png_adam7_split_batch_device: the argument lists differ in length")
+    _png_image_check("png_adam7_split_batch_device", pixel_ptrs, widths, heights, bits_per_pixel, [1] * n, pass_ptrs)
+    if n == 0:
+        return
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    rc = _native.lib().zs_png_adam7_split_batch_device(engine.handle, n, VP(*[int(p) for p in pixel_ptrs]), I64(*[int(x) for x in widths]),
+                                                       I64(*[int(x) for x in heights]), I32(*[int(x) for x in bits_per_pixel]),
+                                                       VP(*[int(p) for p in pass_ptrs]), ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_adam7_split_batch_device failed (%d): %s" % (rc, engine.last_error()))
+
+
+def png_idat_interlace_batch_device(engine, pixel_ptrs, widths, heights, bits_per_pixel, interlace, filters, out_ptrs, out_caps, rows_per_write=1,
+                                    level=6, strategy=0, hash_variant=0, stream=None, return_status=False):
+    """Pixels -> IDAT payloads, interlaced (Adam7) or not, for many device-resident images in one call
+    (zs_png_idat_interlace_batch_device).  interlace: None (all 0) or 0 / 1 per image.  An image with interlace 0 gets the
+    stream of png_idat_batch_device; one with interlace 1 is split into its passes on the device, every present pass is
+    filtered on its own with filters[i], and the filtered passes back to back are the stream's input.  rows_per_write counts
+    rows of the stream in stream order (pass rows for an interlaced image; a Write may span a pass boundary).  Returns the
+    stream lengths; return_status as Engine.deflate_writes_batch_device."""
+    name = "png_idat_interlace_batch_device"
+    n = len(pixel_ptrs)
+    if interlace is None:
+        interlace = [0] * n
+    if not (len(filters) == len(out_caps) == n):
+        raise ValueError(name + ": the argument lists differ in length")
+    _png_image_check(name, pixel_ptrs, widths, heights, bits_per_pixel, interlace, out_ptrs)
+    if any(not 0 <= int(f) <= 5 for f in filters) or int(rows_per_write) < 0:
+        raise ValueError(name + ": filter 0..5 and rows_per_write >= 0 are required")
     if not -1 <= int(level) <= 9 or not 0 <= int(strategy) <= 4:
-        raise ValueError("png_encode_batch_device: level -1..9 and strategy 0..4 are required")
-    for p, w, h, bd, ct, f, o, cap in zip(pixel_ptrs, widths, heights, bit_depths, color_types, filters, out_ptrs, out_caps):
-        if not p or not o or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF or not 0 <= int(f) <= 5 or int(cap) < 0:
-            raise ValueError("png_encode_batch_device: 1 <= width, height <= 2^31 - 1, filter 0..5 and non-null device pointers are required")
-        if int(ct) not in PNG_COLOR_TYPES or int(bd) not in PNG_COLOR_TYPES[int(ct)][1]:
-            raise ValueError("png_encode_batch_device: color type %r with bit depth %r is not in PNG specification table 11.1" % (ct, bd))
-        if int(h) * ((int(w) * int(bd) * PNG_COLOR_TYPES[int(ct)][0] + 7) // 8 + 1) > _CRC_MAX_LEN:
-            raise ValueError("png_encode_batch_device: a filtered image is above 2 GiB - 1 KiB")
-    if sum(int(h) for h in heights) > 0x7FFFFFFF:
-        raise ValueError("png_encode_batch_device: more than 2^31 - 1 rows in one call")
-    if extra is not None:
-        extra = [bytes(x) if x is not None else b"" for x in extra]
-        if not all(_png_chunks_well_formed(x) for x in extra):
-            raise ValueError("png_encode_batch_device: an image's extra chunks are not a sequence of whole chunks")
+        raise ValueError(name + ": level -1..9 and strategy 0..4 are required")
+    for w, h, b, il in zip(widths, heights, bits_per_pixel, interlace):
+        if png_idat_layout(w, h, b, il)[0] > _CRC_MAX_LEN:
+            raise ValueError(name + ": a filtered image is above 2 GiB - 1 KiB")
     if n == 0:
         return (0, [], []) if return_status else []
     VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
     out_len, status = I64(), I32()
-    # (the bytes objects are read in place: they outlive the call)
-    x_ptr = VP(*[ctypes.cast(ctypes.c_char_p(x), ctypes.c_void_p).value if x else None for x in extra]) if extra is not None else None
-    x_len = I64(*[len(x) for x in extra]) if extra is not None else None
-    rc = _native.lib().zs_png_encode_batch_device(engine.handle, n, VP(*[int(p) for p in pixel_ptrs]), I64(*[int(x) for x in widths]),
-                                                  I64(*[int(x) for x in heights]), I32(*[int(x) for x in bit_depths]),
-                                                  I32(*[int(x) for x in color_types]), I32(*[int(x) for x in filters]), x_ptr, x_len,
-                                                  int(rows_per_write), int(idat_chunk_bytes), VP(*[int(p) for p in out_ptrs]),
-                                                  I64(*[int(x) for x in out_caps]), out_len, status, int(level), int(strategy),
-                                                  int(hash_variant), ctypes.c_void_p(stream or 0))
+    rc = _native.lib().zs_png_idat_interlace_batch_device(engine.handle, n, VP(*[int(p) for p in pixel_ptrs]), I64(*[int(x) for x in widths]),
+                                                          I64(*[int(x) for x in heights]), I32(*[int(x) for x in bits_per_pixel]),
+                                                          I32(*[int(x) for x in interlace]), I32(*[int(x) for x in filters]), int(rows_per_write),
+                                                          VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, status,
+                                                          int(level), int(strategy), int(hash_variant), ctypes.c_void_p(stream or 0))
     if return_status:
         return rc, list(out_len), list(status)
     if rc != 0:
-        raise ZlibStreamException("png encode: " + engine.last_error())
+        raise ZlibStreamException("deflating: " + engine.last_error())
     return list(out_len)
+
+
+def png_encode_interlace_batch_device(engine, pixel_ptrs, widths, heights, bit_depths, color_types, filters, out_ptrs, out_caps, interlace=None,
+                                      extra=None, rows_per_write=1, idat_chunk_bytes=0, level=6, strategy=0, hash_variant=0, stream=None,
+                                      return_status=False):
+    """png_encode_batch_device with IHDR's interlace byte per image (zs_png_encode_interlace_batch_device): interlace None (all 0)
+    or 0 / 1 per image; the IDAT chunks hold the stream of png_idat_interlace_batch_device.  With interlace None or all 0 the
+    files are png_encode_batch_device's byte for byte.  png_file_bound(deflate_bound(png_idat_layout(w, h, bits, interlace)[0]),
+    idat_chunk_bytes, len(extra[i])) is always enough room."""
+    return _png_encode_files("png_encode_interlace_batch_device", engine, pixel_ptrs, widths, heights, bit_depths, color_types, filters, interlace, out_ptrs,
+                             out_caps, extra, rows_per_write, idat_chunk_bytes, level, strategy, hash_variant, stream, return_status)
 
 
 _PNG_INFO_FIELDS = ("width", "height", "bit_depth", "color_type", "interlace", "bits_per_pixel", "idat_bytes", "pixel_bytes", "n_idat")

@@ -30,11 +30,11 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
                                            "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
-                                           "spec_compact", "png_expand"};
+                                           "spec_compact", "png_expand", "png_split"};
 
 }  // namespace
 
@@ -72,10 +72,11 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, tile_bits, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw, png_simg, png_split;
     uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
     hipEvent_t ev_crc[2] = {};            // KC and its finishing launch (profiling)
     hipEvent_t ev_expand[2] = {};         // KX (profiling)
+    hipEvent_t ev_split[2] = {};          // KS (profiling)
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1436,6 +1437,7 @@ int zs_ctx_create(int device, zs_ctx **out) {
     for (auto &e : c->ev_spec) (void)hipEventCreate(&e);
     for (auto &e : c->ev_crc) (void)hipEventCreate(&e);
     for (auto &e : c->ev_expand) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_split) (void)hipEventCreate(&e);
     {
         // the link kernel relies on the LDS applying the lanes of one DS_MSKOR_RTN_B32 in lane order: check it here
         int *d_ok = nullptr, ok = 0;
@@ -1501,7 +1503,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->tile_bits, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw, &c->png_simg, &c->png_split};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -1509,6 +1511,8 @@ void zs_ctx_destroy(zs_ctx *c) {
     for (auto &e : c->ev_crc)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_expand)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_split)
         if (e) (void)hipEventDestroy(e);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pin_io) (void)hipHostFree(c->pin_io);
@@ -1581,7 +1585,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
-    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction) and KX (the expansion to RGBA)
+    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA) and KS (the Adam7 split)
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine
@@ -2771,6 +2775,217 @@ extern "C" int zs_png_expand_batch_device(zs_ctx *c, int n, const void *const *i
     return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
 }
 
+// ------------------------------------------------------------------ the Adam7 split (KS, zs_png.hip) and the interlaced encode call: pixels -> IDAT payloads
+namespace {
+constexpr int64_t kSplitSlice = 1 << 25;  // pass rows a launch, as for KA
+
+// The images of one KS launch: descriptors and the offsets of the flat list of pass rows.
+struct PngSplitJob {
+    std::vector<Adam7SplitImg> img;
+    std::vector<int32_t> off;
+    int64_t rows = 0;
+    double ms = 0;  // profiling: the launches
+    void add(const void *pixels, void *passes, int64_t w, int64_t h, int bits) {
+        Adam7SplitImg im{(const uint8_t *)pixels, (uint8_t *)passes, {}, {}, (int32_t)w, (int32_t)h, bits, 0};
+        adam7_split_layout(im);
+        img.push_back(im);
+        off.push_back((int32_t)rows);
+        rows += im.row0[kAdam7Passes];
+    }
+};
+
+// Uploads the job through the staging buffer and launches KS on `s`.  Waits for `s` once: for the upload (the staging buffer
+// is the caller's again), or, with profiling on, for the launches.
+bool png_split_run(zs_ctx *c, PngSplitJob &job, hipStream_t s, bool *no_memory) {
+    *no_memory = false;
+    const int m = (int)job.img.size();
+    const size_t b_img = sizeof(Adam7SplitImg) * (size_t)m, b_off = sizeof(int32_t) * ((size_t)m + 1);
+    if (!ensure(c, c->png_simg, b_img + b_off) || !ensure_pinned(c, b_img + b_off)) {
+        *no_memory = true;
+        return false;
+    }
+    uint8_t *hp = (uint8_t *)c->pinned;
+    memcpy(hp, job.img.data(), b_img);
+    memcpy(hp + b_img, job.off.data(), sizeof(int32_t) * (size_t)m);
+    const int32_t total = (int32_t)job.rows;
+    memcpy(hp + b_img + sizeof(int32_t) * (size_t)m, &total, sizeof total);
+    ZS_HIP(c, hipMemcpyAsync(c->png_simg.p, c->pinned, b_img + b_off, hipMemcpyHostToDevice, s));
+    const bool prof = c->profiling;
+    if (!prof) ZS_HIP(c, hipStreamSynchronize(s));
+    else (void)hipEventRecord(c->ev_split[0], s);
+    static const int group = getenv("ZS_PNG_SPLIT_GROUP") ? atoi(getenv("ZS_PNG_SPLIT_GROUP")) : 8;  // (measurements: DESIGN.md section 4, KS)
+    const Adam7SplitImg *d_img = (const Adam7SplitImg *)c->png_simg.p;
+    const int32_t *d_off = (const int32_t *)((const uint8_t *)c->png_simg.p + b_img);
+    // (a call of more than kSplitSlice pass rows is several launches, each with its first row)
+    for (int64_t row0 = 0; row0 < job.rows; row0 += kSplitSlice) {
+        const int64_t rows = std::min<int64_t>(kSplitSlice, job.rows - row0);
+        const dim3 grid((unsigned)((rows + kSplitRowsPerWg - 1) / kSplitRowsPerWg)), block(64 * kSplitRowsPerWg);
+        if (group == 4) hipLaunchKernelGGL(zs_png_split_kernel<4>, grid, block, 0, s, d_img, d_off, m, row0);
+        else if (group == 16) hipLaunchKernelGGL(zs_png_split_kernel<16>, grid, block, 0, s, d_img, d_off, m, row0);
+        else hipLaunchKernelGGL(zs_png_split_kernel<8>, grid, block, 0, s, d_img, d_off, m, row0);
+        ZS_HIP(c, hipGetLastError());
+    }
+    if (prof) {
+        (void)hipEventRecord(c->ev_split[1], s);
+        ZS_HIP(c, hipStreamSynchronize(s));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev_split[0], c->ev_split[1]);
+        job.ms = ms;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int zs_png_adam7_split_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *width, const int64_t *height,
+                                               const int *bits_per_pixel, void *const *passes_out, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!pixels || !width || !height || !bits_per_pixel || !passes_out) {
+        c->err = "stream error: a null array";
+        return ZS_STREAM_ERROR;
+    }
+    int64_t total_rows = 0;
+    for (int i = 0; i < n; i++) {
+        if (!pixels[i] || !passes_out[i] || width[i] < 1 || height[i] < 1 || width[i] > 0x7FFFFFFF || height[i] > 0x7FFFFFFF || !png_bits_ok(bits_per_pixel[i])) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        total_rows += adam7_pass_rows(width[i], height[i]);
+    }
+    if (total_rows > 0x7FFFFFFF) {  // (the grid is the list of pass rows)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) {
+        c->err = "stream error: the context's device cannot be selected";
+        return ZS_STREAM_ERROR;
+    }
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    PngSplitJob job;
+    for (int i = 0; i < n; i++) job.add(pixels[i], passes_out[i], width[i], height[i], bits_per_pixel[i]);
+    bool no_memory = false;
+    if (!png_split_run(c, job, s, &no_memory)) return no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+    if (c->profiling) {
+        for (double &v : c->stage_ms) v = 0;
+        c->stage_ms[kStPngSplit] = job.ms;
+    }
+    if (hip_stream) return ZS_OK;
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) fail(c, "hipStreamSynchronize(s)", e);
+    return e == hipSuccess ? ZS_OK : ZS_STREAM_ERROR;
+}
+
+// Pixels -> IDAT payloads, interlaced images among them: KS into a buffer of the context, the batch filter over every image
+// and every present pass as an image of its own (the row above a pass's first row is zero: PNG specification 9.2), its outputs
+// back to back, so that an image's filtered passes are one payload; then every image's rows -- pass rows in stream order -- as
+// the Writes of its own stream.  Nothing leaves the device in between.
+extern "C" int zs_png_idat_interlace_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *width, const int64_t *height,
+                                                  const int *bits_per_pixel, const int *interlace, const int *filter, int64_t rows_per_write, void *const *out,
+                                                  const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy, int hash_variant,
+                                                  void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!pixels || !width || !height || !bits_per_pixel || !filter || !out || !out_cap || !out_len || rows_per_write < 0) return ZS_STREAM_ERROR;
+    std::vector<int64_t> rb((size_t)n), len((size_t)n);
+    std::vector<int> bpp((size_t)n);
+    int64_t total_rows = 0, split_bytes = 0;
+    int n_il = 0;
+    size_t n_items = 0;
+    for (int i = 0; i < n; i++) {
+        const int il = interlace ? interlace[i] : 0;
+        if (!pixels[i] || !out[i] || out_cap[i] < 0 || width[i] < 1 || height[i] < 1 || width[i] > 0x7FFFFFFF || height[i] > 0x7FFFFFFF ||
+            !png_bits_ok(bits_per_pixel[i]) || (il != 0 && il != 1) || filter[i] < 0 || filter[i] > 5) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        rb[(size_t)i] = png_bits_row_bytes(width[i], bits_per_pixel[i]);
+        bpp[(size_t)i] = png_bits_bpp(bits_per_pixel[i]);
+        len[(size_t)i] = zs_png_idat_layout(width[i], height[i], bits_per_pixel[i], il, nullptr, nullptr);
+        if (len[(size_t)i] > 0x7FFFFFFF - 1024) {  // (a stream's input is indexed with 32 bits)
+            c->err = "stream error: a filtered image is above 2 GiB - 1 KiB";
+            return ZS_STREAM_ERROR;
+        }
+        const int64_t rows = il ? adam7_pass_rows(width[i], height[i]) : height[i];
+        total_rows += rows;
+        if (il) n_il++, split_bytes += ((len[(size_t)i] - rows) + 255) & ~(int64_t)255;
+        for (int p = 0; p < kAdam7Passes; p++) n_items += il ? (adam7_pass_width(width[i], p) > 0 && adam7_pass_height(height[i], p) > 0) : p == 0;
+    }
+    if (total_rows > 0x7FFFFFFF) {  // (the grids are the row lists)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    // no interlaced image: the call is zs_png_idat_batch_device's, byte for byte and status for status
+    if (n_il == 0)
+        return zs_png_idat_batch_device(c, n, pixels, rb.data(), height, bpp.data(), filter, rows_per_write, out, out_cap, out_len, status, level, strategy,
+                                        hash_variant, hip_stream);
+    if (!check_args(c, n, len.data(), level, strategy)) return ZS_STREAM_ERROR;
+    for (int i = 0; i < n; i++) {
+        out_len[i] = 0;
+        if (status) status[i] = ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    size_t total = 0;
+    for (int i = 0; i < n; i++) total += ((size_t)len[(size_t)i] + 255) & ~(size_t)255;
+    if (!ensure(c, c->png_scratch, total + 256) || !ensure(c, c->png_split, (size_t)split_bytes + 256)) return ZS_MEM_ERROR;
+    // ---- KS over the interlaced images
+    PngSplitJob job;
+    {
+        int64_t at = 0;
+        for (int i = 0; i < n; i++) {
+            if (!(interlace && interlace[i])) continue;
+            job.add(pixels[i], (uint8_t *)c->png_split.p + at, width[i], height[i], bits_per_pixel[i]);
+            at += ((len[(size_t)i] - job.img.back().row0[kAdam7Passes]) + 255) & ~(int64_t)255;
+        }
+    }
+    bool no_memory = false;
+    if (!png_split_run(c, job, s, &no_memory)) return no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+    // ---- the filter's items (an image, or a present pass), and every image's Write ends: rows of the stream in stream order
+    std::vector<const void *> f_in(n_items);
+    std::vector<void *> f_out(n_items);
+    std::vector<int64_t> f_rb(n_items), f_h(n_items);
+    std::vector<int> f_bpp(n_items), f_filter(n_items);
+    std::vector<const void *> rows_in((size_t)n);
+    std::vector<std::vector<int64_t>> ends((size_t)n);
+    std::vector<const int64_t *> ends_p((size_t)n, nullptr);
+    std::vector<int64_t> n_ends((size_t)n, 0);
+    size_t at = 0, k = 0, j = 0;
+    for (int i = 0; i < n; i++) {
+        uint8_t *payload = (uint8_t *)c->png_scratch.p + at;
+        rows_in[(size_t)i] = payload;
+        at += ((size_t)len[(size_t)i] + 255) & ~(size_t)255;
+        const bool il = interlace && interlace[i];
+        const Adam7SplitImg *sp = il ? &job.img[j++] : nullptr;
+        int64_t pos = 0, row = 0;  // where the stream stands: bytes and rows
+        const int64_t all_rows = il ? sp->row0[kAdam7Passes] : height[i];
+        const bool cut = rows_per_write > 0 && rows_per_write < all_rows;
+        for (int p = 0; p < (il ? kAdam7Passes : 1); p++) {
+            const int64_t pw = il ? adam7_pass_width(width[i], p) : width[i], ph = il ? adam7_pass_height(height[i], p) : height[i];
+            if (pw <= 0 || ph <= 0) continue;
+            const int64_t prb = png_bits_row_bytes(pw, bits_per_pixel[i]);
+            f_in[k] = il ? (const void *)(sp->passes + sp->off[p]) : pixels[i];
+            f_out[k] = payload + pos;
+            f_rb[k] = prb, f_h[k] = ph, f_bpp[k] = bpp[(size_t)i], f_filter[k] = filter[i];
+            k++;
+            if (cut) {
+                // the Write ends inside this pass: after stream rows rows_per_write, 2 * rows_per_write, ...
+                int64_t r = (row / rows_per_write + 1) * rows_per_write;  // the first multiple above `row`
+                for (; r <= row + ph && r < all_rows; r += rows_per_write) ends[(size_t)i].push_back(pos + (r - row) * (prb + 1));
+            }
+            pos += ph * (prb + 1), row += ph;
+        }
+        if (cut) {
+            ends[(size_t)i].push_back(len[(size_t)i]);
+            ends_p[(size_t)i] = ends[(size_t)i].data(), n_ends[(size_t)i] = (int64_t)ends[(size_t)i].size();
+        }
+    }
+    if (!run_png_filter_batch(c, (int)n_items, f_in.data(), f_rb.data(), f_h.data(), f_bpp.data(), f_filter.data(), f_out.data(), total_rows, s)) return ZS_STREAM_ERROR;
+    const int rc = zs_deflate_writes_batch_device(c, n, rows_in.data(), len.data(), ends_p.data(), n_ends.data(), out, out_cap, out_len, status, level, strategy,
+                                                  hash_variant, hip_stream);
+    if (c->profiling) c->stage_ms[kStPngSplit] = job.ms;
+    return rc;
+}
+
 // ------------------------------------------------------------------ CRC-32 (KC, zs_crc32.hip), PNG files on top of it
 namespace {
 static_assert(sizeof(zs_png_info) == sizeof(PngFileInfo) && offsetof(zs_png_info, n_idat) == offsetof(PngFileInfo, n_idat), "zs_png_info mirrors PngFileInfo");
@@ -2897,11 +3112,13 @@ extern "C" int64_t zs_png_file_bound(int64_t idat_len, int64_t idat_chunk_bytes,
 }
 
 // Pixels -> files: the IDAT call into a buffer of the context, then KC over [signature, IHDR, extra] / every IDAT chunk / IEND
-// of every image that fits its output.
-extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *width, const int64_t *height, const int *bit_depth,
-                                          const int *color_type, const int *filter, const void *const *extra, const int64_t *extra_len, int64_t rows_per_write,
-                                          int64_t idat_chunk_bytes, void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level,
-                                          int strategy, int hash_variant, void *hip_stream) {
+// of every image that fits its output.  interlace: null (zs_png_encode_batch_device) or IHDR's interlace byte per image; with
+// no interlaced image the IDAT call, and so every byte and status, is zs_png_idat_batch_device's.
+namespace {
+int png_encode_files(zs_ctx *c, int n, const void *const *pixels, const int64_t *width, const int64_t *height, const int *bit_depth, const int *color_type,
+                     const int *filter, const int *interlace, const void *const *extra, const int64_t *extra_len, int64_t rows_per_write,
+                     int64_t idat_chunk_bytes, void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy,
+                     int hash_variant, void *hip_stream) {
     if (!c || n < 0) return ZS_STREAM_ERROR;
     if (n == 0) return ZS_OK;
     if (!pixels || !width || !height || !bit_depth || !color_type || !filter || !out || !out_cap || !out_len || (extra && !extra_len)) return ZS_STREAM_ERROR;
@@ -2910,10 +3127,16 @@ extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *p
         return ZS_STREAM_ERROR;
     }
     std::vector<int64_t> rb((size_t)n), xlen((size_t)n, 0), zcap((size_t)n);
-    std::vector<int> bpp((size_t)n);
+    std::vector<int> bpp((size_t)n), bits_pp((size_t)n);
     int64_t total_rows = 0;
     size_t z_total = 0, x_total = 0;
+    bool any_interlaced = false;
     for (int i = 0; i < n; i++) {
+        const int il = interlace ? interlace[i] : 0;
+        if (il != 0 && il != 1) {
+            c->err = "stream error: interlace is neither 0 nor 1";
+            return ZS_STREAM_ERROR;
+        }
         const bool dims = width[i] >= 1 && width[i] <= 0x7FFFFFFF && height[i] >= 1 && height[i] <= 0x7FFFFFFF;
         if (!pixels[i] || !out[i] || !dims || !png_color_ok(color_type[i], bit_depth[i]) || filter[i] < 0 || filter[i] > 5 || out_cap[i] < 0) {
             c->err = "stream error";
@@ -2922,7 +3145,11 @@ extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *p
         const int bits = bit_depth[i] * png_channels(color_type[i]);
         rb[(size_t)i] = png_bits_row_bytes(width[i], bits);
         bpp[(size_t)i] = png_bits_bpp(bits);
-        if (height[i] * (rb[(size_t)i] + 1) > kCrcMaxLen) {  // (a stream's input is indexed with 32 bits)
+        bits_pp[(size_t)i] = bits;
+        any_interlaced = any_interlaced || il;
+        // the filtered image: the rows, or the present passes' rows, each with its filter byte
+        const int64_t filtered = il ? zs_png_idat_layout(width[i], height[i], bits, 1, nullptr, nullptr) : height[i] * (rb[(size_t)i] + 1);
+        if (filtered > kCrcMaxLen) {  // (a stream's input is indexed with 32 bits)
             c->err = "stream error: a filtered image is above 2 GiB - 1 KiB";
             return ZS_STREAM_ERROR;
         }
@@ -2933,10 +3160,10 @@ extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *p
                 return ZS_STREAM_ERROR;
             }
         }
-        zcap[(size_t)i] = zs_deflate_bound(height[i] * (rb[(size_t)i] + 1));
+        zcap[(size_t)i] = zs_deflate_bound(filtered);
         z_total += ((size_t)zcap[(size_t)i] + 255) & ~(size_t)255;
         x_total += 8 + 25 + (size_t)xlen[(size_t)i] + 12;
-        total_rows += height[i];
+        total_rows += il ? adam7_pass_rows(width[i], height[i]) : height[i];
     }
     if (total_rows > 0x7FFFFFFF) {
         c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
@@ -2960,8 +3187,10 @@ extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *p
         zs_out[(size_t)i] = (uint8_t *)c->png_zs.p + at;
         at += ((size_t)zcap[(size_t)i] + 255) & ~(size_t)255;
     }
-    const int zrc = zs_png_idat_batch_device(c, n, pixels, rb.data(), height, bpp.data(), filter, rows_per_write, zs_out.data(), zcap.data(), zlen.data(), st.data(),
-                                             level, strategy, hash_variant, (void *)s);
+    const int zrc = any_interlaced ? zs_png_idat_interlace_batch_device(c, n, pixels, width, height, bits_pp.data(), interlace, filter, rows_per_write, zs_out.data(),
+                                                                        zcap.data(), zlen.data(), st.data(), level, strategy, hash_variant, (void *)s)
+                                   : zs_png_idat_batch_device(c, n, pixels, rb.data(), height, bpp.data(), filter, rows_per_write, zs_out.data(), zcap.data(),
+                                                              zlen.data(), st.data(), level, strategy, hash_variant, (void *)s);
     if (zrc != ZS_OK) {
         for (int i = 0; i < n; i++) out_len[i] = 0;
         return finish(zrc);
@@ -3009,7 +3238,7 @@ extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *p
         png_put_be32(hd + 8, 13);
         memcpy(hd + 12, "IHDR", 4);
         png_put_be32(hd + 16, (uint32_t)width[i]), png_put_be32(hd + 20, (uint32_t)height[i]);
-        hd[24] = (uint8_t)bit_depth[i], hd[25] = (uint8_t)color_type[i], hd[26] = 0, hd[27] = 0, hd[28] = 0;
+        hd[24] = (uint8_t)bit_depth[i], hd[25] = (uint8_t)color_type[i], hd[26] = 0, hd[27] = 0, hd[28] = (uint8_t)(interlace ? interlace[i] : 0);
         png_put_be32(hd + 29, crc32_bytes_slow(0, hd + 12, 17));
         if (xlen[(size_t)i]) memcpy(hd + 33, extra[i], (size_t)xlen[(size_t)i]);
         const int64_t head = 33 + xlen[(size_t)i];
@@ -3032,6 +3261,24 @@ extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *p
     if (!crc32_run(c, &job, s)) return finish(ZS_STREAM_ERROR);
     if (c->profiling) c->stage_ms[kStCrc32] = job.ms;
     return finish(rc);
+}
+}  // namespace
+
+extern "C" int zs_png_encode_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *width, const int64_t *height, const int *bit_depth,
+                                          const int *color_type, const int *filter, const void *const *extra, const int64_t *extra_len, int64_t rows_per_write,
+                                          int64_t idat_chunk_bytes, void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level,
+                                          int strategy, int hash_variant, void *hip_stream) {
+    return png_encode_files(c, n, pixels, width, height, bit_depth, color_type, filter, nullptr, extra, extra_len, rows_per_write, idat_chunk_bytes, out, out_cap,
+                            out_len, status, level, strategy, hash_variant, hip_stream);
+}
+
+extern "C" int zs_png_encode_interlace_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *width, const int64_t *height,
+                                                    const int *bit_depth, const int *color_type, const int *filter, const int *interlace,
+                                                    const void *const *extra, const int64_t *extra_len, int64_t rows_per_write, int64_t idat_chunk_bytes,
+                                                    void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy,
+                                                    int hash_variant, void *hip_stream) {
+    return png_encode_files(c, n, pixels, width, height, bit_depth, color_type, filter, interlace, extra, extra_len, rows_per_write, idat_chunk_bytes, out,
+                            out_cap, out_len, status, level, strategy, hash_variant, hip_stream);
 }
 
 extern "C" int zs_png_file_info(const void *file, int64_t len, zs_png_info *info) {

@@ -225,6 +225,114 @@ ZS_HD void adam7_group(const Adam7Img &im, int64_t y, int64_t rb, uint8_t *dst, 
 ZS_HD int64_t adam7_row_groups(uint64_t row_addr, int64_t rb, int G) { return ((int64_t)(row_addr & (uint64_t)(G - 1)) + rb + G - 1) / G; }
 ZS_HD int64_t adam7_row_b0(uint64_t row_addr, int G) { return -(int64_t)(row_addr & (uint64_t)(G - 1)); }
 
+// ---- the Adam7 split (KS, zs_png.hip, and its host model tests/cpp/test_png_adam7_split.cpp): KA's inverse ----
+// One image for KS.  pixels: height rows of png_bits_row_bytes(width, bits) bytes; passes: where the present passes go, back
+// to back (adam7_layout's picture: off[p]); row0[p]: pass rows of the image in front of pass p, row0[7] all of them -- the
+// image's share of the flat list of pass rows.  An absent pass has no rows.
+struct Adam7SplitImg {
+    const uint8_t *pixels;
+    uint8_t *passes;
+    int64_t off[kAdam7Passes];
+    int32_t row0[kAdam7Passes + 1];
+    int32_t width, height, bits, pad;
+};
+// ... filled in from the geometry; returns the bytes of all passes (row0[7]: the pass rows, below 2^31 for every legal image:
+// at most 15 for every 8 of its own, and the callers bound the sum)
+ZS_HD int64_t adam7_split_layout(Adam7SplitImg &im) {
+    int64_t at = 0, rows = 0;
+    for (int p = 0; p < kAdam7Passes; p++) {
+        const int64_t pw = adam7_pass_width(im.width, p), ph = adam7_pass_height(im.height, p);
+        im.off[p] = at;
+        im.row0[p] = (int32_t)rows;
+        at += png_bits_row_bytes(pw, im.bits) * ph;
+        rows += pw > 0 ? ph : 0;
+    }
+    im.row0[kAdam7Passes] = (int32_t)rows;
+    return at;
+}
+ZS_HD int64_t adam7_pass_rows(int64_t w, int64_t h) {  // pass rows of an interlaced image, absent passes left out
+    int64_t rows = 0;
+    for (int p = 0; p < kAdam7Passes; p++) rows += adam7_pass_width(w, p) > 0 ? adam7_pass_height(h, p) : 0;
+    return rows;
+}
+// the pass of the image's pass row r (0 <= r < row0[7]): the last present one that begins at or in front of it
+ZS_HD int adam7_split_pass(const Adam7SplitImg &im, int64_t r) {
+    int p = 0;
+    for (int q = 1; q < kAdam7Passes; q++)
+        if (im.row0[q + 1] > im.row0[q] && r >= im.row0[q]) p = q;
+    return p;
+}
+
+ZS_HD uint64_t adam7_load_px(const uint8_t *src, int bpp) {  // a pixel of 1, 2, 3, 4, 6 or 8 bytes at any alignment
+    uint64_t px = 0;
+    switch (bpp) {
+    case 1: px = src[0]; break;
+    case 2: __builtin_memcpy(&px, src, 2); break;
+    case 3: __builtin_memcpy(&px, src, 3); break;
+    case 4: __builtin_memcpy(&px, src, 4); break;
+    case 6: __builtin_memcpy(&px, src, 6); break;
+    default: __builtin_memcpy(&px, src, 8); break;
+    }
+    return px;
+}
+
+// Bytes [b0, b0 + G) of row j of pass p (`dst` = the pass row's first byte, `prb` its length; dst + b0 is G-aligned: the
+// first group of a row may begin in front of it and the last one end behind it, those two store byte by byte, every other
+// group is one aligned store of G bytes).  G = 4, 8 or 16.  Output pixel k is source pixel xstart + (k << xshift) of source
+// row ystart + (j << yshift).  No byte outside [0, prb) is touched, and none is touched twice; the unused low bits of the
+// pass row's last byte are zero, and the unused bits of the source row's last byte are never taken over.
+template <int G>
+ZS_HD void adam7_split_group(const Adam7SplitImg &im, int p, int64_t j, int64_t prb, uint8_t *dst, int64_t b0) {
+    static_assert(G == 4 || G == 8 || G == 16, "a group is one store");
+    uint64_t v[2] = {0, 0};  // byte k of the group in bits 8k.. of v[k / 8]
+    const int64_t lo = b0 < 0 ? 0 : b0, hi = b0 + G < prb ? b0 + G : prb;  // the group's bytes inside the row
+    const bool full = lo == b0 && hi == b0 + G;
+    const int xs = adam7_xstart(p), xsh = adam7_xshift(p), bits = im.bits;
+    const uint8_t *src = im.pixels + (adam7_ystart(p) + (j << adam7_yshift(p))) * png_bits_row_bytes(im.width, bits);
+    if (xsh == 0) {
+        // pass 7's rows are the odd source rows as they stand
+        if (full) __builtin_memcpy(v, src + b0, G);
+        else
+            for (int64_t b = lo; b < hi; b++) v[(b - b0) >> 3] |= (uint64_t)src[b] << (8 * ((b - b0) & 7));
+        const int used = (int)(((int64_t)im.width * bits) & 7);  // bits of the row's last byte that hold pixels (0: all)
+        if (used && hi == prb) {
+            const int k = (int)(prb - 1 - b0);
+            v[k >> 3] &= ~((uint64_t)(0xFFu >> used) << (8 * (k & 7)));
+        }
+    } else if (bits < 8) {
+        // an output byte collects 8 / 4 / 2 pixels of the one source row, leftmost in the high bits
+        const int ppb = 8 / bits;
+        const int64_t pw = adam7_pass_width(im.width, p);
+        for (int64_t b = lo; b < hi; b++) {
+            uint32_t byte = 0;
+            for (int q = 0; q < ppb; q++) {
+                const int64_t k = b * ppb + q;
+                if (k >= pw) break;
+                const int64_t bit = (xs + (k << xsh)) * bits;
+                byte |= (((uint32_t)src[bit >> 3] >> (8 - bits - (int)(bit & 7))) & ((1u << bits) - 1)) << (8 - bits - q * bits);
+            }
+            v[(b - b0) >> 3] |= (uint64_t)byte << (8 * ((b - b0) & 7));
+        }
+    } else {
+        // whole pixels of bpp bytes; the first and the last may lie partly in a neighbouring group
+        const int bpp = bits >> 3;
+        for (int64_t k = lo / bpp; k * bpp < hi; k++) {
+            uint64_t px = adam7_load_px(src + (xs + (k << xsh)) * bpp, bpp);
+            int o = (int)(k * bpp - b0);  // the pixel's first byte in the group: -7 .. G - 1
+            if (o < 0) px >>= -8 * o, o = 0;
+            if (o < 8) {
+                v[0] |= px << (8 * o);
+                if (o > 0) v[1] |= px >> (8 * (8 - o));
+            } else
+                v[1] |= px << (8 * (o - 8));
+        }
+    }
+    if (full) {
+        __builtin_memcpy(__builtin_assume_aligned(dst + b0, G), v, G);
+    } else
+        for (int64_t b = lo; b < hi; b++) dst[b] = (uint8_t)(v[(b - b0) >> 3] >> (8 * ((b - b0) & 7)));
+}
+
 // ---- expansion to RGBA (KX, zs_png.hip, and its host model tests/cpp/test_png_expand.cpp) ----
 // Raw scanlines of any legal (colour type, bit depth) pair -> rows of width * 4 bytes (R, G, B, A) or of width * 4 uint16 in
 // host order (R, G, B, A), no padding.  Exact integer arithmetic:

@@ -287,6 +287,34 @@ __global__ __launch_bounds__(64 * kAdam7RowsPerWg) void zs_png_adam7_kernel(cons
     }
 }
 
+// KS: the Adam7 split, KA's inverse and shaped like it.  The grid is the flat list of all images' pass rows (absent passes
+// have none), four a workgroup: wave w takes pass row 4 * block + w, finds its image (png_row_image), its pass and its row in
+// the pass (all uniform over the wave), and its lanes take the pass row's aligned groups of G bytes (zs_png.h
+// adam7_split_group), 64 at a time -- one full-width store per lane, contiguous over the wave.  The reads are plain cached
+// loads from the one source row, at a stride of 1, 2, 4 or 8 pixels.  No atomics, no LDS: no output byte has two writers.
+constexpr int kSplitRowsPerWg = 4;
+
+template <int G>
+__global__ __launch_bounds__(64 * kSplitRowsPerWg) void zs_png_split_kernel(const Adam7SplitImg *imgs, const int32_t *row_off, int n, int64_t row0) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    const int64_t r = row0 + (int64_t)blockIdx.x * kSplitRowsPerWg + w;
+    if (r >= (int64_t)row_off[n]) return;
+    const int i = png_row_image(row_off, n, r);
+    const Adam7SplitImg &im = imgs[i];
+    const int64_t local = r - row_off[i];
+    const int p = adam7_split_pass(im, local);
+    const int64_t j = local - im.row0[p], prb = png_bits_row_bytes(adam7_pass_width(im.width, p), im.bits);
+    uint8_t *dst = im.passes + im.off[p] + j * prb;
+    const uint64_t addr = (uint64_t)(uintptr_t)dst;
+    if (im.bits < 8 && p != 6) {
+        const int64_t ng = adam7_row_groups(addr, prb, kAdam7GroupBits), b0 = adam7_row_b0(addr, kAdam7GroupBits);
+        for (int64_t g = lane; g < ng; g += 64) adam7_split_group<kAdam7GroupBits>(im, p, j, prb, dst, b0 + g * kAdam7GroupBits);
+    } else {
+        const int64_t ng = adam7_row_groups(addr, prb, G), b0 = adam7_row_b0(addr, G);
+        for (int64_t g = lane; g < ng; g += 64) adam7_split_group<G>(im, p, j, prb, dst, b0 + g * G);
+    }
+}
+
 // KX: raw scanlines to RGBA8 / RGBA16 (zs_png.h png_expand_group), shaped like KA.  The grid is the flat list of all images'
 // output rows, four rows a workgroup: wave w takes row 4 * block + w, and its lanes the row's address-aligned groups of 16
 // bytes, 64 at a time -- one full-width store per lane, 1 KiB contiguous over the wave; the ragged first and last groups of
