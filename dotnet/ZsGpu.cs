@@ -135,6 +135,25 @@ namespace SixLabors.ZlibStream
         [DllImport(Lib)] public static extern int zs_png_file_colors(IntPtr file, long len, byte* plte768, int* plteEntries, byte* trns256, int* trnsLen);
         [DllImport(Lib)] public static extern int zs_png_decode_files_rgba_batch(IntPtr ctx, int n, IntPtr* file, long* fileLen, int format, IntPtr* output,
                                                                                  long* outCap, PngInfo* info, int* status, IntPtr hipStream);
+        // RGBA8 (Rgba32) or RGBA16 (Rgba64) pixels -> raw scanlines of a named pair; what the pixels allow; the pair for that; pixels -> files
+        [DllImport(Lib)] public static extern int zs_png_pack_batch_device(IntPtr ctx, int n, IntPtr* input, long* width, long* height, int* bitDepth,
+                                                                           int* colorType, IntPtr* plte, int* plteEntries, IntPtr* trns, int* trnsLen,
+                                                                           int format, IntPtr* output, long* unmatched, IntPtr hipStream);
+        [StructLayout(LayoutKind.Sequential)]
+        public struct PngSurvey
+        {
+            public int Opaque, Gray, Low8, SampleDepth, ColorCount;
+            public fixed byte Colors[1024];  // ColorCount x (R, G, B, A), ascending by (A, R, G, B)
+        }
+
+        [DllImport(Lib)] public static extern int zs_png_survey_batch_device(IntPtr ctx, int n, IntPtr* input, long* width, long* height, int format,
+                                                                             PngSurvey* output, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_choose_format(PngSurvey* survey, int* colorType, int* bitDepth);
+        [DllImport(Lib)] public static extern int zs_png_encode_rgba_batch_device(IntPtr ctx, int n, IntPtr* pixels, long* width, long* height, int format,
+                                                                                  int* filter, int* interlace, IntPtr* extra, long* extraLen,
+                                                                                  long rowsPerWrite, long idatChunkBytes, IntPtr* output, long* outCap,
+                                                                                  long* outLen, int* status, int* colorTypeOut, int* bitDepthOut, int level,
+                                                                                  int strategy, int hashVariant, IntPtr hipStream);
         // bytes fed behind a stream's trailer before its end was seen (the engine looks for the end now and then)
         [DllImport(Lib)] public static extern long zs_inflate_surplus(IntPtr s, IntPtr* p);
     }

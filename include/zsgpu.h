@@ -427,6 +427,88 @@ ZS_API int zs_png_decode_files_rgba_batch(zs_ctx *ctx, int n, const void *const 
                                           void *const *out, const int64_t *out_cap, zs_png_info *info, int *status,
                                           void *hip_stream);
 
+/* ------------------------------------------------------------------ */
+/* RGBA pixels to raw scanlines, the inverse of the expansion above: what an encoder needs in front of filter, deflate and
+ * framing when the caller holds RGBA8 or RGBA16 pixels.  Exact integer arithmetic:
+ *   a sample v to depth d, from ZS_PNG_RGBA8: v >> (8 - d) for d <= 8, v * 257 for d = 16; from ZS_PNG_RGBA16: v for d = 16,
+ *   and for d <= 8 first v8 = (v * 255 + 32895) >> 16 (the expansion's own rounding), then v8 >> (8 - d).  Both invert the
+ *   expansion's scaling on every value the expansion can produce;
+ *   16-bit samples are written big-endian; below 8 bits pixels are packed most-significant-bit first, and the unused low
+ *   bits of a row's last byte are written as zero;
+ *   types 0 and 4 take the R sample as gray (the call is meant for pixels zs_png_survey_batch_device found gray; luminance
+ *   weighting is the caller's business); types 4 and 6 write the alpha sample; types 0 and 2 without a tRNS ignore alpha;
+ *   types 0 and 2 with a tRNS key (the chunk's bytes, as for the expansion) write the key's low d bits for every pixel whose
+ *   alpha is 0, and every other pixel's own samples;
+ *   type 3 reduces the pixel to RGBA8 as above and writes the index of the first palette entry equal to it in all four
+ *   channels, an entry's alpha being trns[k] for k < trns_len and 255 otherwise; a pixel with no equal entry gets index 0
+ *   (an entry at or beyond 2^d has no index at depth d and is not looked at).
+ *
+ * The pack on the device, n images a call, one launch over the flat list of all output rows (KG).
+ * in[i]: height[i] rows of width[i] * 4 (ZS_PNG_RGBA8) or * 8 bytes (ZS_PNG_RGBA16: four host-order uint16), DEVICE pointer
+ * aligned to 4 or 8; out[i]: height[i] rows of ceil(width[i] * bits / 8) bytes (DEVICE pointer, any alignment), must not
+ * overlap in[i].  The arrays, plte / plte_entries / trns / trns_len and their rules are those of zs_png_expand_batch_device.
+ * unmatched (HOST, n entries, may be NULL): unmatched[i] receives the number of pixels of a type-3 image that found no equal
+ * entry, 0 for the other types.
+ * Returns ZS_OK, ZS_MEM_ERROR (the descriptors do not fit) or, before any device work, ZS_STREAM_ERROR for everything
+ * zs_png_expand_batch_device refuses, an in[i] not aligned to the pixel size in place of its out[i].  n == 0 is ZS_OK.
+ * Ordered on hip_stream (NULL: the context's, and the call returns when the scanlines are written); the call waits for the
+ * stream once, for its descriptors' upload, and a second time, for the counts, only when unmatched is not NULL.
+ * zs_ctx_stage_ms shows the launch as "png_pack". */
+ZS_API int zs_png_pack_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *width, const int64_t *height,
+                                    const int *bit_depth, const int *color_type, const void *const *plte,
+                                    const int *plte_entries, const void *const *trns, const int *trns_len, int format,
+                                    void *const *out, int64_t *unmatched, void *hip_stream);
+
+/* What an image's pixels allow a lossless encoder to drop. */
+typedef struct zs_png_survey {
+    int opaque;        /* every alpha is the format's maximum */
+    int gray;          /* R == G == B at every pixel (all pixels, whatever their alpha) */
+    int low8;          /* RGBA8: 1.  RGBA16: every sample of every pixel is a multiple of 257 */
+    int sample_depth;  /* low8: the smallest d of 1, 2, 4, 8 such that every R, G and B, as 8-bit values, is a multiple of
+                          255 / (2^d - 1); otherwise 16 */
+    int n_colors;      /* low8: distinct RGBA8 values, 1 .. 256, or 257 for "more than 256"; otherwise 257 */
+    uint8_t colors[256][4];  /* the n_colors values as R, G, B, A, ascending by (A, R, G, B); zero beyond (all zero at 257) */
+} zs_png_survey;
+
+/* The survey on the device, n images a call (KV): in[i] as for zs_png_pack_batch_device, out: HOST
+ * array of n results.  Two launches: workgroups over runs of rows that each keep a violation mask and a set of at most 256
+ * colours in LDS and write a record of their own, then one workgroup per image that merges the records; no atomics outside
+ * LDS, and the host sorts the colours, so the results are the same on every run.
+ * Returns ZS_OK, ZS_MEM_ERROR or, before any device work, ZS_STREAM_ERROR: null context, n < 0, null arrays or pointers,
+ * width or height outside 1 .. 2^31 - 1, a bad format, an in[i] not aligned to the pixel size, too many rows in one call.
+ * n == 0 is ZS_OK.  Ordered on hip_stream (NULL: the context's); the call waits for the stream twice, for the upload and
+ * for the results.  zs_ctx_stage_ms shows the two launches as "png_survey". */
+ZS_API int zs_png_survey_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *width, const int64_t *height,
+                                      int format, zs_png_survey *out, void *hip_stream);
+
+/* The (colour type, bit depth) pair for a survey, pure host code, no context and no GPU:
+ *   !low8: (0,16) if gray and opaque, (4,16) if gray, (2,16) if opaque, else (6,16);
+ *   low8: the base is (0, sample_depth) if gray and opaque, (4,8) if gray, (2,8) if opaque, else (6,8); with n_colors <= 256
+ *   the palette depth p is 1, 2, 4 or 8 for <= 2, <= 4, <= 16 or more colours, and (3, p) is chosen only if p is strictly
+ *   less than the base's bits per pixel -- a tie keeps the base, which needs no PLTE.
+ * The rule compares bits per pixel.  It does not promise the smallest file: for a tiny image the PLTE chunk can cost more
+ * than the palette saves.  It never chooses a tRNS colour key.  ZS_STREAM_ERROR: null pointers, or a survey whose
+ * sample_depth or n_colors is outside its values. */
+ZS_API int zs_png_choose_format(const zs_png_survey *s, int *color_type, int *bit_depth);
+
+/* RGBA pixels to complete PNG files, n images a call: the survey, zs_png_choose_format per image, for palette images a PLTE
+ * of the survey's colours in its order and a tRNS of their alphas up to the last one below 255 (none when all are 255),
+ * both framed on the host, the pack into a buffer the context owns (kept until zs_ctx_destroy), then
+ * zs_png_encode_interlace_batch_device on that buffer with extra[i] + PLTE + tRNS as the extra chunks -- the files are byte
+ * for byte that call's.  pixels[i] / format as in[i] / format of zs_png_pack_batch_device; every other argument as for
+ * zs_png_encode_interlace_batch_device.  color_type_out / bit_depth_out (HOST, n entries, may be NULL): the chosen pairs.
+ * A caller's chunks that must follow PLTE (bKGD, hIST) are not supported: extra[i] goes in front of it.
+ * zs_png_file_bound(zs_deflate_bound(zs_png_idat_layout(width, height, 32 or 64, interlace, 0, 0)), idat_chunk_bytes,
+ * extra_len + 1048) is always enough room; a short out_cap[i] is ZS_BUF_ERROR for that image only.  Argument errors are
+ * ZS_STREAM_ERROR before any device work, status and out_len untouched; the 2 GiB - 1 KiB limit of a filtered image is held
+ * against the pixels at 32 or 64 bits, whatever pair would be chosen. */
+ZS_API int zs_png_encode_rgba_batch_device(zs_ctx *ctx, int n, const void *const *pixels, const int64_t *width,
+                                           const int64_t *height, int format, const int *filter, const int *interlace,
+                                           const void *const *extra, const int64_t *extra_len, int64_t rows_per_write,
+                                           int64_t idat_chunk_bytes, void *const *out, const int64_t *out_cap, int64_t *out_len,
+                                           int *status, int *color_type_out, int *bit_depth_out, int level, int strategy,
+                                           int hash_variant, void *hip_stream);
+
 /* Stage timing of the last *_batch_device call, measured with hipEvents on
  * the stream the kernels ran on.  Enable before the call. */
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took

@@ -21,6 +21,7 @@ SYMBOLS = [
     "zs_png_decode_files_batch",
     "zs_png_expand_batch_device", "zs_png_file_colors", "zs_png_decode_files_rgba_batch",
     "zs_png_adam7_split_batch_device", "zs_png_idat_interlace_batch_device", "zs_png_encode_interlace_batch_device",
+    "zs_png_pack_batch_device", "zs_png_survey_batch_device", "zs_png_choose_format", "zs_png_encode_rgba_batch_device",
 ]
 
 
@@ -28,6 +29,11 @@ class PngInfo(ctypes.Structure):  # zs_png_info
     _fields_ = [("width", ctypes.c_int64), ("height", ctypes.c_int64), ("bit_depth", ctypes.c_int), ("color_type", ctypes.c_int),
                 ("interlace", ctypes.c_int), ("bits_per_pixel", ctypes.c_int), ("idat_bytes", ctypes.c_int64),
                 ("pixel_bytes", ctypes.c_int64), ("n_idat", ctypes.c_int64)]
+
+
+class PngSurvey(ctypes.Structure):  # zs_png_survey
+    _fields_ = [("opaque", ctypes.c_int), ("gray", ctypes.c_int), ("low8", ctypes.c_int), ("sample_depth", ctypes.c_int),
+                ("n_colors", ctypes.c_int), ("colors", ctypes.c_uint8 * 4 * 256)]
 
 _lib = None
 
@@ -169,5 +175,15 @@ def lib():
         L.zs_png_encode_interlace_batch_device.restype = i32
         L.zs_png_encode_interlace_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), P(i32), P(i32), P(vp), P(i64), i64, i64,
                                                            P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
+    if hasattr(L, "zs_png_pack_batch_device"):  # (an older build selected with ZS_LIB for an A/B run lacks the encoder from RGBA)
+        L.zs_png_pack_batch_device.restype = i32
+        L.zs_png_pack_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i32), P(i32), P(vp), P(i32), P(vp), P(i32), i32, P(vp), P(i64), vp]
+        L.zs_png_survey_batch_device.restype = i32
+        L.zs_png_survey_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), i32, P(PngSurvey), vp]
+        L.zs_png_choose_format.restype = i32
+        L.zs_png_choose_format.argtypes = [P(PngSurvey), P(i32), P(i32)]
+        L.zs_png_encode_rgba_batch_device.restype = i32
+        L.zs_png_encode_rgba_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), i32, P(i32), P(i32), P(vp), P(i64), i64, i64, P(vp), P(i64),
+                                                      P(i64), P(i32), P(i32), P(i32), i32, i32, i32, vp]
     _lib = L
     return L

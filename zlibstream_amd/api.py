@@ -851,6 +851,173 @@ def png_decode_files_rgba_batch(engine, files, out_ptrs, out_caps, format=PNG_RG
     return list(status), [{k: int(getattr(i, k)) for k in _PNG_INFO_FIELDS} for i in info]
 
 
+def png_pack_batch_device(engine, in_ptrs, widths, heights, bit_depths, color_types, out_ptrs, plte=None, trns=None, format=PNG_RGBA8,
+                          stream=None, return_unmatched=False):
+    """RGBA pixels -> raw scanlines for many device-resident images in one launch (zs_png_pack_batch_device), the inverse of
+    png_expand_batch_device: in_ptrs[i] holds heights[i] rows of widths[i] * 4 bytes (PNG_RGBA8) or widths[i] * 4 uint16
+    (PNG_RGBA16) and must be aligned to a pixel; out_ptrs[i] receives rows of ceil(widths[i] * bits / 8) bytes at any
+    alignment.  plte / trns as for png_expand_batch_device.  A palette pixel with no equal entry gets index 0;
+    return_unmatched: the list of their counts per image (0 for the other color types) -- the call then waits for it."""
+    name = "png_pack_batch_device"
+    n = len(in_ptrs)
+    if not (len(widths) == len(heights) == len(bit_depths) == len(color_types) == len(out_ptrs) == n) or \
+            (plte is not None and len(plte) != n) or (trns is not None and len(trns) != n):
+        raise ValueError(name + ": the argument lists differ in length")
+    if format not in (PNG_RGBA8, PNG_RGBA16):
+        raise ValueError(name + ": format is PNG_RGBA8 or PNG_RGBA16")
+    px = 8 if format == PNG_RGBA16 else 4
+    plte = [bytes(x) if x is not None else b"" for x in plte] if plte is not None else [b""] * n
+    trns = [bytes(x) if x is not None else b"" for x in trns] if trns is not None else [b""] * n
+    for p, w, h, bd, ct, o, pl, tr in zip(in_ptrs, widths, heights, bit_depths, color_types, out_ptrs, plte, trns):
+        if not p or not o or int(p) % px or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF:
+            raise ValueError(name + ": 1 <= width, height <= 2^31 - 1, non-null device pointers and inputs aligned to a pixel are required")
+        if int(ct) not in PNG_COLOR_TYPES or int(bd) not in PNG_COLOR_TYPES[int(ct)][1]:
+            raise ValueError(name + ": color type %r with bit depth %r is not in PNG specification table 11.1" % (ct, bd))
+        if int(ct) == 3 and (len(pl) % 3 or not 3 <= len(pl) <= 768 or len(tr) > len(pl) // 3):
+            raise ValueError(name + ": a palette image needs a PLTE of 1 .. 256 entries and a tRNS no longer than it")
+        if int(ct) in (0, 2) and len(tr) not in (0, 2 if int(ct) == 0 else 6):
+            raise ValueError(name + ": a tRNS holds 2 bytes at color type 0 and 6 at color type 2")
+    if sum(int(h) for h in heights) > 0x7FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 rows in one call")
+    if n == 0:
+        return [] if return_unmatched else None
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    unmatched = I64() if return_unmatched else None
+    # (the bytes objects are read in place: they outlive the call)
+    rc = _native.lib().zs_png_pack_batch_device(engine.handle, n, VP(*[int(p) for p in in_ptrs]), I64(*[int(x) for x in widths]),
+                                                I64(*[int(x) for x in heights]), I32(*[int(x) for x in bit_depths]),
+                                                I32(*[int(x) for x in color_types]), VP(*[_host_ptr(x) for x in plte]),
+                                                I32(*[len(x) // 3 for x in plte]), VP(*[_host_ptr(x) for x in trns]),
+                                                I32(*[len(x) if int(ct) in (0, 2, 3) else 0 for x, ct in zip(trns, color_types)]), int(format),
+                                                VP(*[int(p) for p in out_ptrs]), unmatched, ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_pack_batch_device failed (%d): %s" % (rc, engine.last_error()))
+    return [int(v) for v in unmatched] if return_unmatched else None
+
+
+_PNG_SURVEY_FLAGS = ("opaque", "gray", "low8", "sample_depth", "n_colors")
+
+
+def _survey_dict(s):
+    d = {k: int(getattr(s, k)) for k in _PNG_SURVEY_FLAGS}
+    d["colors"] = [tuple(s.colors[k]) for k in range(d["n_colors"] if d["n_colors"] <= 256 else 0)]
+    return d
+
+
+def _survey_struct(d):
+    s = _native.PngSurvey()
+    for k in _PNG_SURVEY_FLAGS:
+        setattr(s, k, int(d[k]))
+    for k, c in enumerate(d.get("colors", ())[:256]):
+        for j in range(4):
+            s.colors[k][j] = int(c[j])
+    return s
+
+
+def png_survey_batch_device(engine, in_ptrs, widths, heights, format=PNG_RGBA8, stream=None):
+    """What the pixels of many device-resident RGBA images allow (zs_png_survey_batch_device): one dict per image of opaque,
+    gray, low8 (0 / 1), sample_depth (1, 2, 4, 8; 16 where low8 is 0), n_colors (1 .. 256, or 257 for more, and where low8 is
+    0) and colors, the n_colors distinct (R, G, B, A) tuples at 8 bits ascending by (A, R, G, B) (empty at 257).  in_ptrs[i]
+    as for png_pack_batch_device.  The same on every run."""
+    name = "png_survey_batch_device"
+    n = len(in_ptrs)
+    if not (len(widths) == len(heights) == n):
+        raise ValueError(name + ": the argument lists differ in length")
+    if format not in (PNG_RGBA8, PNG_RGBA16):
+        raise ValueError(name + ": format is PNG_RGBA8 or PNG_RGBA16")
+    px = 8 if format == PNG_RGBA16 else 4
+    for p, w, h in zip(in_ptrs, widths, heights):
+        if not p or int(p) % px or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF:
+            raise ValueError(name + ": 1 <= width, height <= 2^31 - 1 and non-null device pointers aligned to a pixel are required")
+    if sum(int(h) for h in heights) > 0x7FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 rows in one call")
+    if n == 0:
+        return []
+    VP, I64 = ctypes.c_void_p * n, ctypes.c_int64 * n
+    out = (_native.PngSurvey * n)()
+    rc = _native.lib().zs_png_survey_batch_device(engine.handle, n, VP(*[int(p) for p in in_ptrs]), I64(*[int(x) for x in widths]),
+                                                  I64(*[int(x) for x in heights]), int(format), out, ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_survey_batch_device failed (%d): %s" % (rc, engine.last_error()))
+    return [_survey_dict(s) for s in out]
+
+
+def png_choose_format(survey):
+    """zs_png_choose_format (host code, no GPU, no engine): a survey dict (opaque, gray, low8, sample_depth, n_colors) ->
+    (color_type, bit_depth).  The rule compares bits per pixel -- a palette only where its depth is strictly below the
+    base's -- and does not promise the smallest file.  ValueError for a sample_depth or n_colors outside their values."""
+    try:
+        d = {k: int(survey[k]) for k in _PNG_SURVEY_FLAGS}
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("png_choose_format: a survey holds opaque, gray, low8, sample_depth and n_colors")
+    if d["sample_depth"] not in (1, 2, 4, 8, 16) or (d["sample_depth"] == 16) != (not d["low8"]) or not 1 <= d["n_colors"] <= 257:
+        raise ValueError("png_choose_format: sample_depth is 1, 2, 4 or 8 (16 exactly where low8 is 0) and n_colors 1 .. 257")
+    ct, bd = ctypes.c_int(-1), ctypes.c_int(-1)
+    rc = _native.lib().zs_png_choose_format(ctypes.byref(_survey_struct(d)), ctypes.byref(ct), ctypes.byref(bd))
+    if rc != 0:
+        raise ValueError("zs_png_choose_format failed (%d)" % rc)
+    return ct.value, bd.value
+
+
+def png_encode_rgba_batch_device(engine, pixel_ptrs, widths, heights, filters, out_ptrs, out_caps, format=PNG_RGBA8, interlace=None, extra=None,
+                                 rows_per_write=1, idat_chunk_bytes=0, level=6, strategy=0, hash_variant=0, stream=None, return_status=False):
+    """RGBA pixels -> complete PNG files for many device-resident images in one call (zs_png_encode_rgba_batch_device): the
+    survey, png_choose_format per image, PLTE and tRNS for the palette images, the pack, then
+    png_encode_interlace_batch_device's body -- the files are that call's byte for byte.  pixel_ptrs[i] / format as for
+    png_pack_batch_device; the rest as for png_encode_interlace_batch_device, with extra[i] in front of PLTE (chunks that must
+    follow PLTE are not supported).  png_file_bound(deflate_bound(png_idat_layout(w, h, 32 or 64, interlace)[0]),
+    idat_chunk_bytes, len(extra[i]) + 1048) is always enough room.  Returns (lengths, color_types, bit_depths);
+    return_status: (rc, lengths, statuses, color_types, bit_depths)."""
+    name = "png_encode_rgba_batch_device"
+    n = len(pixel_ptrs)
+    if interlace is None:
+        interlace = [0] * n
+    if not (len(widths) == len(heights) == len(filters) == len(out_ptrs) == len(out_caps) == len(interlace) == n) or (extra is not None and len(extra) != n):
+        raise ValueError(name + ": the argument lists differ in length")
+    if format not in (PNG_RGBA8, PNG_RGBA16):
+        raise ValueError(name + ": format is PNG_RGBA8 or PNG_RGBA16")
+    px = 8 if format == PNG_RGBA16 else 4
+    if int(rows_per_write) < 0 or not 0 <= int(idat_chunk_bytes) <= 0x7FFFFFFF:
+        raise ValueError(name + ": rows_per_write >= 0 and 0 <= idat_chunk_bytes <= 2^31 - 1 are required")
+    if not -1 <= int(level) <= 9 or not 0 <= int(strategy) <= 4:
+        raise ValueError(name + ": level -1..9 and strategy 0..4 are required")
+    total_rows = 0
+    for p, w, h, f, il, o, cap in zip(pixel_ptrs, widths, heights, filters, interlace, out_ptrs, out_caps):
+        if not p or not o or int(p) % px or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF or not 0 <= int(f) <= 5 or int(cap) < 0 or \
+                int(il) not in (0, 1):
+            raise ValueError(name + ": 1 <= width, height <= 2^31 - 1, filter 0..5, interlace 0 or 1 and non-null device pointers, the pixels' aligned "
+                             "to a pixel, are required")
+        if int(w) * int(h) * px > _CRC_MAX_LEN:  # (held against the pixels as they come, whatever pair would be chosen)
+            raise ValueError(name + ": a filtered image is above 2 GiB - 1 KiB")
+        total, _, rows = png_idat_layout(w, h, 8 * px, int(il))
+        if total > _CRC_MAX_LEN:
+            raise ValueError(name + ": a filtered image is above 2 GiB - 1 KiB")
+        total_rows += sum(rows)
+    if total_rows > 0x7FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 rows in one call")
+    if extra is not None:
+        extra = [bytes(x) if x is not None else b"" for x in extra]
+        if not all(_png_chunks_well_formed(x) for x in extra):
+            raise ValueError(name + ": an image's extra chunks are not a sequence of whole chunks")
+    if n == 0:
+        return (0, [], [], [], []) if return_status else ([], [], [])
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status, ct, bd = I64(), I32(), I32(), I32()
+    # (the bytes objects are read in place: they outlive the call)
+    x_ptr = VP(*[_host_ptr(x) for x in extra]) if extra is not None else None
+    x_len = I64(*[len(x) for x in extra]) if extra is not None else None
+    rc = _native.lib().zs_png_encode_rgba_batch_device(engine.handle, n, VP(*[int(p) for p in pixel_ptrs]), I64(*[int(x) for x in widths]),
+                                                       I64(*[int(x) for x in heights]), int(format), I32(*[int(x) for x in filters]),
+                                                       I32(*[int(x) for x in interlace]), x_ptr, x_len, int(rows_per_write), int(idat_chunk_bytes),
+                                                       VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, status, ct, bd,
+                                                       int(level), int(strategy), int(hash_variant), ctypes.c_void_p(stream or 0))
+    if return_status:
+        return rc, list(out_len), list(status), list(ct), list(bd)
+    if rc != 0:
+        raise ZlibStreamException("png encode: " + engine.last_error())
+    return list(out_len), list(ct), list(bd)
+
+
 _default_engine = None
 
 

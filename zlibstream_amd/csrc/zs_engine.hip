@@ -30,11 +30,11 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
                                            "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
-                                           "spec_compact", "png_expand", "png_split"};
+                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey"};
 
 }  // namespace
 
@@ -72,11 +72,13 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, tile_bits, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw, png_simg, png_split;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw, png_simg, png_split, png_gimg, png_vimg, png_vrec, png_packed;
     uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
     hipEvent_t ev_crc[2] = {};            // KC and its finishing launch (profiling)
     hipEvent_t ev_expand[2] = {};         // KX (profiling)
     hipEvent_t ev_split[2] = {};          // KS (profiling)
+    hipEvent_t ev_pack[2] = {};           // KG (profiling)
+    hipEvent_t ev_survey[2] = {};         // KV, both launches (profiling)
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1438,6 +1440,8 @@ int zs_ctx_create(int device, zs_ctx **out) {
     for (auto &e : c->ev_crc) (void)hipEventCreate(&e);
     for (auto &e : c->ev_expand) (void)hipEventCreate(&e);
     for (auto &e : c->ev_split) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_pack) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_survey) (void)hipEventCreate(&e);
     {
         // the link kernel relies on the LDS applying the lanes of one DS_MSKOR_RTN_B32 in lane order: check it here
         int *d_ok = nullptr, ok = 0;
@@ -1503,7 +1507,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->tile_bits, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw, &c->png_simg, &c->png_split};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw, &c->png_simg, &c->png_split, &c->png_gimg, &c->png_vimg, &c->png_vrec, &c->png_packed};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -1513,6 +1517,10 @@ void zs_ctx_destroy(zs_ctx *c) {
     for (auto &e : c->ev_expand)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_split)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_pack)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_survey)
         if (e) (void)hipEventDestroy(e);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pin_io) (void)hipHostFree(c->pin_io);
@@ -1585,7 +1593,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
-    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA) and KS (the Adam7 split)
+    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA) and KV (the survey)
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine
@@ -2775,6 +2783,232 @@ extern "C" int zs_png_expand_batch_device(zs_ctx *c, int n, const void *const *i
     return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
 }
 
+// ------------------------------------------------------------------ the pack from RGBA (KG, zs_png.hip): pixels a caller holds -> raw scanlines
+namespace {
+constexpr int64_t kPackSlice = 1 << 25;  // rows a launch, as for KA
+
+// The images of one KG launch: descriptors, the row offsets of the flat row list, and one lookup table per palette image.
+struct PngPackJob {
+    std::vector<PngPackImg> img;
+    std::vector<int32_t> off;
+    std::vector<uint32_t> tables;
+    int64_t rows = 0;
+    double ms = 0;  // profiling: the launches
+    void add(const void *in, void *out, int64_t w, int64_t h, int depth, int color, int format, const uint8_t *plte, int entries, const uint8_t *trns, int trns_len) {
+        PngPackImg im{(const uint8_t *)in, (uint8_t *)out, (int32_t)w, (int32_t)h, depth, color, format, 0, {0, 0, 0}, 0};
+        if (color == 3) {
+            im.pal_off = (int32_t)tables.size();
+            tables.resize(tables.size() + kPngPackTableWords);
+            // (an entry at or beyond 2^depth has no index in the file: it cannot be named, and is left out)
+            png_pack_table(plte, std::min(entries, 1 << depth), trns, trns_len, tables.data() + im.pal_off);
+        } else if (trns_len > 0 && (color == 0 || color == 2)) {
+            for (int k = 0; k < (color == 0 ? 1 : 3); k++) im.key[k] = (uint16_t)(trns[2 * k] << 8 | trns[2 * k + 1]);
+            im.has_key = 1;
+        }
+        img.push_back(im);
+        off.push_back((int32_t)rows);
+        rows += h;
+    }
+};
+
+// The arguments zs_png_expand_batch_device and zs_png_pack_batch_device share: `pix` is the RGBA side (aligned to a pixel),
+// `raw` the scanline side.
+bool png_rgba_args_ok(zs_ctx *c, int n, const void *const *pix, const void *const *raw, const int64_t *width, const int64_t *height, const int *bit_depth,
+                      const int *color_type, const void *const *plte, const int *plte_entries, const void *const *trns, const int *trns_len, int format) {
+    if (!pix || !width || !height || !bit_depth || !color_type || !raw) return false;
+    if (format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) {
+        c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return false;
+    }
+    const int px = png_expand_bytes(format);
+    int64_t total_rows = 0;
+    for (int i = 0; i < n; i++) {
+        bool ok = pix[i] && raw[i] && width[i] >= 1 && height[i] >= 1 && width[i] <= 0x7FFFFFFF && height[i] <= 0x7FFFFFFF && png_color_ok(color_type[i], bit_depth[i]) &&
+                  ((uintptr_t)pix[i] & (uintptr_t)(px - 1)) == 0;
+        if (ok) {
+            const int ct = color_type[i], tl = trns_len && ct != 4 && ct != 6 ? trns_len[i] : 0;
+            if (ct == 3) ok = plte && plte[i] && plte_entries && plte_entries[i] >= 1 && plte_entries[i] <= 256 && tl >= 0 && tl <= plte_entries[i];
+            else ok = tl == 0 || (ct == 0 && tl == 2) || (ct == 2 && tl == 6);
+            if (ok && tl > 0) ok = trns && trns[i];
+        }
+        if (!ok) {
+            c->err = "stream error";
+            return false;
+        }
+        total_rows += height[i];
+    }
+    if (total_rows > 0x7FFFFFFF) {  // (the grid is the row list)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return false;
+    }
+    return true;
+}
+
+// Uploads the job through the staging buffer -- descriptors, offsets, tables and a zeroed word per image for the palette
+// pixels without an entry -- and launches KG on `s`.  Waits for `s` once: for the upload (the staging buffer is the caller's
+// again), or, with profiling on, for the launches; and once more, for the counts, where `unmatched` is given.
+bool png_pack_run(zs_ctx *c, PngPackJob &job, int format, int64_t *unmatched, hipStream_t s, bool *no_memory) {
+    *no_memory = false;
+    const int m = (int)job.img.size();
+    const size_t b_img = sizeof(PngPackImg) * (size_t)m, b_off = (sizeof(int32_t) * ((size_t)m + 1) + 15) & ~(size_t)15, b_tab = sizeof(uint32_t) * job.tables.size(),
+                 b_cnt = sizeof(uint64_t) * (size_t)m, b_all = b_img + b_off + b_tab + b_cnt;
+    if (!ensure(c, c->png_gimg, b_all) || !ensure_pinned(c, b_all)) {
+        *no_memory = true;
+        return false;
+    }
+    uint8_t *hp = (uint8_t *)c->pinned;
+    memcpy(hp, job.img.data(), b_img);
+    memcpy(hp + b_img, job.off.data(), sizeof(int32_t) * (size_t)m);
+    const int32_t total = (int32_t)job.rows;
+    memcpy(hp + b_img + sizeof(int32_t) * (size_t)m, &total, sizeof total);
+    if (b_tab) memcpy(hp + b_img + b_off, job.tables.data(), b_tab);
+    memset(hp + b_img + b_off + b_tab, 0, b_cnt);
+    ZS_HIP(c, hipMemcpyAsync(c->png_gimg.p, c->pinned, b_all, hipMemcpyHostToDevice, s));
+    const bool prof = c->profiling;
+    if (!prof) ZS_HIP(c, hipStreamSynchronize(s));
+    else (void)hipEventRecord(c->ev_pack[0], s);
+    uint8_t *dp = (uint8_t *)c->png_gimg.p;
+    const PngPackImg *d_img = (const PngPackImg *)dp;
+    const int32_t *d_off = (const int32_t *)(dp + b_img);
+    const uint32_t *d_tab = (const uint32_t *)(dp + b_img + b_off);
+    unsigned long long *d_cnt = (unsigned long long *)(dp + b_img + b_off + b_tab);  // (8-aligned: every part in front is a multiple of 8)
+    for (int64_t row0 = 0; row0 < job.rows; row0 += kPackSlice) {
+        const int64_t rows = std::min<int64_t>(kPackSlice, job.rows - row0);
+        const dim3 grid((unsigned)((rows + kPackRowsPerWg - 1) / kPackRowsPerWg)), block(64 * kPackRowsPerWg);
+        if (format == ZS_PNG_FMT_RGBA16) hipLaunchKernelGGL(zs_png_pack_kernel<ZS_PNG_FMT_RGBA16>, grid, block, 0, s, d_img, d_off, d_tab, d_cnt, m, row0);
+        else hipLaunchKernelGGL(zs_png_pack_kernel<ZS_PNG_FMT_RGBA8>, grid, block, 0, s, d_img, d_off, d_tab, d_cnt, m, row0);
+        ZS_HIP(c, hipGetLastError());
+    }
+    if (prof) {
+        (void)hipEventRecord(c->ev_pack[1], s);
+        ZS_HIP(c, hipStreamSynchronize(s));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev_pack[0], c->ev_pack[1]);
+        job.ms = ms;
+    }
+    if (unmatched) {
+        ZS_HIP(c, hipMemcpyAsync(c->pinned, d_cnt, b_cnt, hipMemcpyDeviceToHost, s));
+        ZS_HIP(c, hipStreamSynchronize(s));
+        memcpy(unmatched, c->pinned, b_cnt);
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int zs_png_pack_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *width, const int64_t *height, const int *bit_depth,
+                                        const int *color_type, const void *const *plte, const int *plte_entries, const void *const *trns, const int *trns_len,
+                                        int format, void *const *out, int64_t *unmatched, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!png_rgba_args_ok(c, n, in, (const void *const *)out, width, height, bit_depth, color_type, plte, plte_entries, trns, trns_len, format)) return ZS_STREAM_ERROR;
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    PngPackJob job;
+    for (int i = 0; i < n; i++) {
+        const int ct = color_type[i], tl = trns_len && ct != 4 && ct != 6 ? trns_len[i] : 0;
+        job.add(in[i], out[i], width[i], height[i], bit_depth[i], ct, format, ct == 3 ? (const uint8_t *)plte[i] : nullptr, ct == 3 ? plte_entries[i] : 0,
+                tl > 0 ? (const uint8_t *)trns[i] : nullptr, tl);
+    }
+    bool no_memory = false;
+    if (!png_pack_run(c, job, format, unmatched, s, &no_memory)) return no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+    if (c->profiling) {
+        for (double &v : c->stage_ms) v = 0;
+        c->stage_ms[kStPngPack] = job.ms;
+    }
+    return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
+}
+
+// ------------------------------------------------------------------ the survey (KV, zs_png.hip): what an image's pixels allow
+extern "C" int zs_png_survey_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *width, const int64_t *height, int format, zs_png_survey *out,
+                                          void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!in || !width || !height || !out) return ZS_STREAM_ERROR;
+    if (format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) {
+        c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return ZS_STREAM_ERROR;
+    }
+    const int px = png_expand_bytes(format);
+    int64_t items = 0;
+    for (int i = 0; i < n; i++) {
+        if (!in[i] || width[i] < 1 || height[i] < 1 || width[i] > 0x7FFFFFFF || height[i] > 0x7FFFFFFF || ((uintptr_t)in[i] & (uintptr_t)(px - 1)) != 0) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        items += (height[i] + kSurveyRows - 1) / kSurveyRows;
+    }
+    if (items > 0x7FFFFFFF) {  // (the first grid is the item list)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const size_t b_img = sizeof(PngSurveyImg) * (size_t)n, b_off = sizeof(int32_t) * ((size_t)n + 1), b_res = sizeof(PngSurveyRec) * (size_t)n;
+    // the records: the images' n in front, the items' behind them
+    if (!ensure(c, c->png_vimg, b_img + b_off) || !ensure(c, c->png_vrec, sizeof(PngSurveyRec) * ((size_t)n + (size_t)items)) || !ensure_pinned(c, std::max(b_img + b_off, b_res)))
+        return ZS_MEM_ERROR;
+    {
+        PngSurveyImg *h_img = (PngSurveyImg *)c->pinned;
+        int32_t *h_off = (int32_t *)((uint8_t *)c->pinned + b_img);
+        int64_t at = 0;
+        for (int i = 0; i < n; i++) {
+            h_img[i] = PngSurveyImg{(const uint8_t *)in[i], width[i], (int32_t)height[i], 0};
+            h_off[i] = (int32_t)at;
+            at += (height[i] + kSurveyRows - 1) / kSurveyRows;
+        }
+        h_off[n] = (int32_t)at;
+    }
+    auto hip_ok = [&](hipError_t e, const char *what) { return e == hipSuccess || fail(c, what, e); };
+    if (!hip_ok(hipMemcpyAsync(c->png_vimg.p, c->pinned, b_img + b_off, hipMemcpyHostToDevice, s), "hipMemcpyAsync")) return ZS_STREAM_ERROR;
+    const bool prof = c->profiling;
+    if (prof) (void)hipEventRecord(c->ev_survey[0], s);
+    const PngSurveyImg *d_img = (const PngSurveyImg *)c->png_vimg.p;
+    const int32_t *d_off = (const int32_t *)((const uint8_t *)c->png_vimg.p + b_img);
+    PngSurveyRec *d_res = (PngSurveyRec *)c->png_vrec.p, *d_rec = d_res + n;
+    if (format == ZS_PNG_FMT_RGBA16) hipLaunchKernelGGL(zs_png_survey_kernel<ZS_PNG_FMT_RGBA16>, dim3((unsigned)items), dim3(256), 0, s, d_img, d_off, n, d_rec);
+    else hipLaunchKernelGGL(zs_png_survey_kernel<ZS_PNG_FMT_RGBA8>, dim3((unsigned)items), dim3(256), 0, s, d_img, d_off, n, d_rec);
+    if (!hip_ok(hipGetLastError(), "zs_png_survey_kernel")) return ZS_STREAM_ERROR;
+    hipLaunchKernelGGL(zs_png_survey_merge_kernel, dim3((unsigned)n), dim3(256), 0, s, d_off, d_rec, d_res);
+    if (!hip_ok(hipGetLastError(), "zs_png_survey_merge_kernel")) return ZS_STREAM_ERROR;
+    if (prof) (void)hipEventRecord(c->ev_survey[1], s);
+    // the one wait for the upload: the staging buffer is written again only by the copy behind it on the same stream
+    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return ZS_STREAM_ERROR;
+    if (!hip_ok(hipMemcpyAsync(c->pinned, d_res, b_res, hipMemcpyDeviceToHost, s), "hipMemcpyAsync") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize"))
+        return ZS_STREAM_ERROR;
+    if (prof) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev_survey[0], c->ev_survey[1]);
+        for (double &v : c->stage_ms) v = 0;
+        c->stage_ms[kStPngSurvey] = ms;
+    }
+    const PngSurveyRec *res = (const PngSurveyRec *)c->pinned;
+    for (int i = 0; i < n; i++) {
+        const PngSurveyRec &r = res[i];
+        zs_png_survey &o = out[i];
+        memset(&o, 0, sizeof o);
+        o.opaque = !(r.mask & kSvNotOpaque), o.gray = !(r.mask & kSvNotGray), o.low8 = !(r.mask & kSvNotLow8);
+        o.sample_depth = !o.low8 ? 16 : (r.mask & kSvNot17) ? 8 : (r.mask & kSvNot85) ? 4 : (r.mask & kSvNot255) ? 2 : 1;
+        const uint32_t white = (r.mask & kSvWhite) ? 1 : 0;
+        o.n_colors = !o.low8 || r.count == kSurveyMany || r.count + white > 256 ? (int)kSurveyMany : (int)(r.count + white);
+        if (o.n_colors > 256) continue;
+        uint32_t key[256];  // A, R, G, B from the top byte down: ascending keys are the order asked for
+        for (uint32_t k = 0; k < r.count; k++) key[k] = (r.colors[k] >> 24) << 24 | (r.colors[k] & 255) << 16 | (r.colors[k] >> 8 & 255) << 8 | (r.colors[k] >> 16 & 255);
+        if (white) key[r.count] = 0xFFFFFFFFu;
+        std::sort(key, key + o.n_colors);
+        for (int k = 0; k < o.n_colors; k++)
+            o.colors[k][0] = (uint8_t)(key[k] >> 16), o.colors[k][1] = (uint8_t)(key[k] >> 8), o.colors[k][2] = (uint8_t)key[k], o.colors[k][3] = (uint8_t)(key[k] >> 24);
+    }
+    return ZS_OK;
+}
+
+extern "C" int zs_png_choose_format(const zs_png_survey *sv, int *color_type, int *bit_depth) {
+    if (!sv || !color_type || !bit_depth) return ZS_STREAM_ERROR;
+    const int d = sv->sample_depth;
+    if ((d != 1 && d != 2 && d != 4 && d != 8 && d != 16) || (d == 16) != !sv->low8 || sv->n_colors < 1 || sv->n_colors > 257) return ZS_STREAM_ERROR;
+    png_choose_format(sv->opaque != 0, sv->gray != 0, sv->low8 != 0, d, sv->n_colors, color_type, bit_depth);
+    return ZS_OK;
+}
+
 // ------------------------------------------------------------------ the Adam7 split (KS, zs_png.hip) and the interlaced encode call: pixels -> IDAT payloads
 namespace {
 constexpr int64_t kSplitSlice = 1 << 25;  // pass rows a launch, as for KA
@@ -3279,6 +3513,126 @@ extern "C" int zs_png_encode_interlace_batch_device(zs_ctx *c, int n, const void
                                                     int hash_variant, void *hip_stream) {
     return png_encode_files(c, n, pixels, width, height, bit_depth, color_type, filter, interlace, extra, extra_len, rows_per_write, idat_chunk_bytes, out,
                             out_cap, out_len, status, level, strategy, hash_variant, hip_stream);
+}
+
+// RGBA pixels -> files: the survey (KV), the choice per image on the host, PLTE and tRNS of the palette images framed on the
+// host behind the caller's chunks, the pack (KG) into a buffer of the context, then the body of the two calls above on that
+// buffer.  Every argument is checked here first, so that nothing the later steps refuse has touched status by then.
+extern "C" int zs_png_encode_rgba_batch_device(zs_ctx *c, int n, const void *const *pixels, const int64_t *width, const int64_t *height, int format,
+                                               const int *filter, const int *interlace, const void *const *extra, const int64_t *extra_len,
+                                               int64_t rows_per_write, int64_t idat_chunk_bytes, void *const *out, const int64_t *out_cap, int64_t *out_len,
+                                               int *status, int *color_type_out, int *bit_depth_out, int level, int strategy, int hash_variant,
+                                               void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!pixels || !width || !height || !filter || !out || !out_cap || !out_len || (extra && !extra_len)) return ZS_STREAM_ERROR;
+    if (format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) {
+        c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return ZS_STREAM_ERROR;
+    }
+    if (rows_per_write < 0 || idat_chunk_bytes < 0 || idat_chunk_bytes > kPngMaxChunk || level < -1 || level > 9 || strategy < 0 || strategy > 4) {
+        c->err = "stream error";
+        return ZS_STREAM_ERROR;
+    }
+    const int px = png_expand_bytes(format);
+    int64_t total_rows = 0;
+    for (int i = 0; i < n; i++) {
+        const int il = interlace ? interlace[i] : 0;
+        if (il != 0 && il != 1) {
+            c->err = "stream error: interlace is neither 0 nor 1";
+            return ZS_STREAM_ERROR;
+        }
+        const bool dims = width[i] >= 1 && width[i] <= 0x7FFFFFFF && height[i] >= 1 && height[i] <= 0x7FFFFFFF;
+        if (!pixels[i] || !out[i] || !dims || filter[i] < 0 || filter[i] > 5 || out_cap[i] < 0 || ((uintptr_t)pixels[i] & (uintptr_t)(px - 1)) != 0) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        // (the pair is not chosen yet: the limit is held against the pixels as they come, which no choice exceeds)
+        if (width[i] * height[i] > kCrcMaxLen / px || zs_png_idat_layout(width[i], height[i], 8 * px, il, nullptr, nullptr) > kCrcMaxLen) {
+            c->err = "stream error: a filtered image is above 2 GiB - 1 KiB";
+            return ZS_STREAM_ERROR;
+        }
+        if (extra && (extra_len[i] < 0 || (extra_len[i] > 0 && !extra[i]) || !png_chunks_well_formed((const uint8_t *)extra[i], extra_len[i]))) {
+            c->err = "stream error: the extra chunks of an image are not a sequence of whole chunks";
+            return ZS_STREAM_ERROR;
+        }
+        total_rows += il ? adam7_pass_rows(width[i], height[i]) : height[i];
+    }
+    if (total_rows > 0x7FFFFFFF) {
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    auto all_fail = [&](int rc) {
+        for (int i = 0; i < n; i++) {
+            out_len[i] = 0;
+            if (status) status[i] = rc;
+        }
+        return rc;
+    };
+    // ---- the survey and the choice
+    std::vector<zs_png_survey> sv((size_t)n);
+    int rc = zs_png_survey_batch_device(c, n, pixels, width, height, format, sv.data(), (void *)s);
+    if (rc != ZS_OK) return all_fail(rc);
+    const double survey_ms = c->profiling ? c->stage_ms[kStPngSurvey] : 0;
+    std::vector<int> ct((size_t)n), bd((size_t)n), entries((size_t)n, 0), tlen((size_t)n, 0);
+    std::vector<std::vector<uint8_t>> xs((size_t)n), plte((size_t)n), trns((size_t)n);
+    std::vector<const void *> x_ptr((size_t)n), plte_ptr((size_t)n, nullptr), trns_ptr((size_t)n, nullptr), packed((size_t)n);
+    std::vector<int64_t> x_len((size_t)n);
+    size_t pack_total = 0;
+    auto put_chunk = [](std::vector<uint8_t> &to, const char *type, const std::vector<uint8_t> &data) {
+        const size_t at = to.size();
+        to.resize(at + 12 + data.size());
+        png_put_be32(to.data() + at, (uint32_t)data.size());
+        memcpy(to.data() + at + 4, type, 4);
+        if (!data.empty()) memcpy(to.data() + at + 8, data.data(), data.size());
+        png_put_be32(to.data() + at + 8 + data.size(), crc32_bytes_slow(0, to.data() + at + 4, (int64_t)(4 + data.size())));
+    };
+    for (int i = 0; i < n; i++) {
+        const size_t k = (size_t)i;
+        if (zs_png_choose_format(&sv[k], &ct[k], &bd[k]) != ZS_OK) return all_fail(ZS_STREAM_ERROR);  // (unreachable: the survey is our own)
+        if (color_type_out) color_type_out[i] = ct[k];
+        if (bit_depth_out) bit_depth_out[i] = bd[k];
+        if (extra && extra_len[i] > 0) xs[k].assign((const uint8_t *)extra[i], (const uint8_t *)extra[i] + extra_len[i]);
+        if (ct[k] == 3) {
+            // PLTE in the survey's order; tRNS up to the last entry below 255, none when all are 255
+            const int m = sv[k].n_colors;
+            entries[k] = m;
+            plte[k].resize(3 * (size_t)m);
+            for (int e = 0; e < m; e++) {
+                memcpy(plte[k].data() + 3 * (size_t)e, sv[k].colors[e], 3);
+                if (sv[k].colors[e][3] != 255) tlen[k] = e + 1;
+            }
+            trns[k].resize((size_t)tlen[k]);
+            for (int e = 0; e < tlen[k]; e++) trns[k][(size_t)e] = sv[k].colors[e][3];
+            put_chunk(xs[k], "PLTE", plte[k]);
+            if (tlen[k] > 0) put_chunk(xs[k], "tRNS", trns[k]);
+            plte_ptr[k] = plte[k].data();
+            trns_ptr[k] = tlen[k] > 0 ? trns[k].data() : nullptr;
+        }
+        x_ptr[k] = xs[k].empty() ? nullptr : xs[k].data();
+        x_len[k] = (int64_t)xs[k].size();
+        pack_total += ((size_t)(png_bits_row_bytes(width[i], bd[k] * png_channels(ct[k])) * height[i]) + 255) & ~(size_t)255;
+    }
+    // ---- the pack
+    if (!ensure(c, c->png_packed, pack_total + 256)) return all_fail(ZS_MEM_ERROR);
+    PngPackJob job;
+    {
+        size_t at = 0;
+        for (int i = 0; i < n; i++) {
+            const size_t k = (size_t)i;
+            packed[k] = (uint8_t *)c->png_packed.p + at;
+            job.add(pixels[i], (void *)packed[k], width[i], height[i], bd[k], ct[k], format, (const uint8_t *)plte_ptr[k], entries[k], (const uint8_t *)trns_ptr[k], tlen[k]);
+            at += ((size_t)(png_bits_row_bytes(width[i], bd[k] * png_channels(ct[k])) * height[i]) + 255) & ~(size_t)255;
+        }
+    }
+    bool no_memory = false;
+    if (!png_pack_run(c, job, format, nullptr, s, &no_memory)) return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    rc = png_encode_files(c, n, packed.data(), width, height, bd.data(), ct.data(), filter, interlace, x_ptr.data(), x_len.data(), rows_per_write, idat_chunk_bytes, out,
+                          out_cap, out_len, status, level, strategy, hash_variant, hip_stream);
+    if (c->profiling) c->stage_ms[kStPngSurvey] = survey_ms, c->stage_ms[kStPngPack] = job.ms;
+    return rc;
 }
 
 extern "C" int zs_png_file_info(const void *file, int64_t len, zs_png_info *info) {

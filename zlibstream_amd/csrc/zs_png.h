@@ -476,5 +476,256 @@ ZS_HD void png_expand_group(const PngExpandImg &im, const uint32_t *pal, int64_t
     }
 }
 
+// ---- packing RGBA into raw scanlines (KG, zs_png.hip, and its host model tests/cpp/test_png_pack.cpp): KX's inverse ----
+// Rows of width * 4 bytes (R, G, B, A) or of width * 4 uint16 in host order -> raw scanlines of the (colour type, bit depth)
+// pair the caller names, rows of ceil(width * bits / 8) bytes.  Exact integer arithmetic:
+//   a sample v to depth d, from RGBA8:   d <= 8: v >> (8 - d);  d = 16: v * 257
+//   ...                    from RGBA16:  d = 16: v;  d <= 8: v8 = (v * 255 + 32895) >> 16 (KX's own rounding), then v8 >> (8 - d)
+//       (both invert KX's scaling on every value KX can produce)
+//   16-bit samples are written big-endian; below 8 bits pixels are packed most-significant-bit first, and the unused low
+//   bits of a row's last byte are zero
+//   gray (types 0, 4): the R sample; alpha (types 4, 6): the A sample; types 0 and 2 without a tRNS key ignore alpha
+//   types 0 and 2 with a key: a pixel whose alpha is 0 gets the key's low d bits in every sample, every other pixel its own
+//   palette (type 3): the pixel reduced to RGBA8 by the rule above (d = 8), then the index of the first palette entry equal to
+//       it in all four channels (an entry's alpha: trns[k] for k < trns_len, else 255); no equal entry: index 0, and counted
+// The palette lookup is a hash table the host builds per image: kPngPackColors words of entries (R | G << 8 | B << 16 |
+// A << 24, as KX's table, zero past the PLTE's entries) and behind them kPngPackSlots 16-bit slots, two a word, that hold
+// entry index + 1 or 0 for "empty" -- 0x00000000 is a legal colour, so emptiness is not a colour value.  Open addressing,
+// linear probing; at most 256 of the 512 slots are taken, so every probe sequence ends.
+constexpr int kPngPackColors = 256, kPngPackSlots = 512;
+constexpr int kPngPackTableWords = kPngPackColors + kPngPackSlots / 2;  // 2 KiB an image
+ZS_HD uint32_t png_color_hash(uint32_t rgba, int bits) { return (rgba * 0x9E3779B1u) >> (32 - bits); }
+ZS_HD uint32_t png_pack_slot(const uint32_t *table, uint32_t h) { return (table[kPngPackColors + (h >> 1)] >> (16 * (h & 1))) & 0xFFFFu; }
+
+// the host's share: the table of a palette image.  The first entry wins among duplicates.
+inline void png_pack_table(const uint8_t *plte, int entries, const uint8_t *trns, int trns_len, uint32_t *table) {
+    for (int k = 0; k < kPngPackTableWords; k++) table[k] = 0;
+    for (int k = 0; k < entries; k++) {
+        const uint32_t c = (uint32_t)plte[3 * k] | (uint32_t)plte[3 * k + 1] << 8 | (uint32_t)plte[3 * k + 2] << 16 | (uint32_t)(k < trns_len ? trns[k] : 255) << 24;
+        table[k] = c;
+        uint32_t h = png_color_hash(c, 9);
+        for (;;) {
+            const uint32_t s = png_pack_slot(table, h);
+            if (s == 0) {
+                table[kPngPackColors + (h >> 1)] |= (uint32_t)(k + 1) << (16 * (h & 1));
+                break;
+            }
+            if (table[s - 1] == c) break;  // (an earlier entry of the same colour)
+            h = (h + 1) & (kPngPackSlots - 1);
+        }
+    }
+}
+// the index of colour c, or -1
+ZS_HD int png_pack_lookup(const uint32_t *table, uint32_t c) {
+    uint32_t h = png_color_hash(c, 9);
+    for (int t = 0; t < kPngPackSlots; t++) {  // (an empty slot is met long before)
+        const uint32_t s = png_pack_slot(table, h);
+        if (s == 0) return -1;
+        if (table[s - 1] == c) return (int)s - 1;
+        h = (h + 1) & (kPngPackSlots - 1);
+    }
+    return -1;
+}
+
+struct PngPackImg {
+    const uint8_t *in;  // height rows of width * png_expand_bytes(format) bytes, aligned to a pixel
+    uint8_t *out;       // height rows of ceil(width * depth * channels / 8) bytes, any alignment
+    int32_t width, height, depth, color, format;
+    int32_t pal_off;    // type 3: the table's first word in the call's list of tables
+    uint16_t key[3];    // tRNS of types 0 (key[0]) and 2: the 16-bit values as the chunk holds them
+    uint16_t has_key;
+};
+
+constexpr int kPngPackGroup = 16;  // output bytes of one store at 8 bits a pixel and above; below: kAdam7GroupBits
+
+template <int F, int D>
+ZS_HD uint32_t png_pack_scale(uint32_t v) {
+    if constexpr (F == ZS_PNG_FMT_RGBA8) return D == 16 ? v * 257 : v >> (8 - (D < 8 ? D : 8));
+    else return D == 16 ? v : ((v * 255 + 32895) >> 16) >> (8 - (D < 8 ? D : 8));
+}
+
+// Pixel x of a source row -> its bytes in the file's layout, byte j in bits 8j.. (below 8 bits: the one sample); *miss is
+// advanced for a palette pixel without an entry.
+template <int F, int CT, int D>
+ZS_HD uint64_t png_pack_pixel(const PngPackImg &im, const uint32_t *table, const uint8_t *src, int64_t x, uint32_t *miss) {
+    uint32_t c[4];
+    if constexpr (F == ZS_PNG_FMT_RGBA8) {
+        uint32_t v;
+        __builtin_memcpy(&v, __builtin_assume_aligned(src + x * 4, 4), 4);
+        c[0] = v & 255, c[1] = v >> 8 & 255, c[2] = v >> 16 & 255, c[3] = v >> 24;
+    } else {
+        uint64_t v;
+        __builtin_memcpy(&v, __builtin_assume_aligned(src + x * 8, 8), 8);
+        c[0] = (uint32_t)v & 0xFFFFu, c[1] = (uint32_t)(v >> 16) & 0xFFFFu, c[2] = (uint32_t)(v >> 32) & 0xFFFFu, c[3] = (uint32_t)(v >> 48);
+    }
+    if constexpr (CT == 3) {
+        const uint32_t rgba = png_pack_scale<F, 8>(c[0]) | png_pack_scale<F, 8>(c[1]) << 8 | png_pack_scale<F, 8>(c[2]) << 16 | png_pack_scale<F, 8>(c[3]) << 24;
+        const int k = png_pack_lookup(table, rgba);
+        if (k < 0) ++*miss;
+        return k < 0 ? 0 : (uint64_t)k;
+    } else {
+        constexpr int CH = CT == 2 ? 3 : CT == 4 ? 2 : CT == 6 ? 4 : 1;
+        constexpr uint32_t mask = (1u << D) - 1;
+        uint32_t s[CH];
+        if constexpr (CT == 0 || CT == 2) {
+            const bool keyed = im.has_key && c[3] == 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < CH; k++) s[k] = keyed ? (im.key[k] & mask) : png_pack_scale<F, D>(c[k]);
+        } else if constexpr (CT == 4) {
+            s[0] = png_pack_scale<F, D>(c[0]), s[1] = png_pack_scale<F, D>(c[3]);
+        } else {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < 4; k++) s[k] = png_pack_scale<F, D>(c[k]);
+        }
+        uint64_t px = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int k = 0; k < CH; k++) {
+            if constexpr (D == 16) px |= (uint64_t)((s[k] >> 8) | (s[k] & 255) << 8) << (16 * k);  // big-endian
+            else px |= (uint64_t)s[k] << (8 * k);
+        }
+        return px;
+    }
+}
+
+// Bytes [b0, b0 + G) of output row y (`dst` = the row's first byte, `rb` its length; dst + b0 is G-aligned, so the first
+// group of a row may begin in front of it and the last one end behind it: those two store byte by byte, every other group is
+// one aligned store of G bytes).  G = 4, 8 or 16.  No byte outside [0, rb) is touched, and none is touched twice.  Returns
+// the palette pixels of the group that found no entry: below 8 bits a pixel lies in one byte, at 8 bits it is one, so each is
+// counted by one group.
+template <int F, int CT, int D, int G>
+ZS_HD uint32_t png_pack_group_as(const PngPackImg &im, const uint32_t *table, int64_t y, int64_t rb, uint8_t *dst, int64_t b0) {
+    static_assert(G == 4 || G == 8 || G == 16, "a group is one store");
+    constexpr int CH = CT == 2 ? 3 : CT == 4 ? 2 : CT == 6 ? 4 : 1;
+    // byte k of the group in bits 8k.. of v0 (k < 8) or v1: two scalars, not an array -- an array indexed by k would live in
+    // scratch memory on the device
+    uint64_t v0 = 0, v1 = 0;
+    uint32_t miss = 0;
+    const int64_t lo = b0 < 0 ? 0 : b0, hi = b0 + G < rb ? b0 + G : rb;  // the group's bytes inside the row
+    const uint8_t *src = im.in + y * ((int64_t)im.width * png_expand_bytes(F));
+    if constexpr (D < 8) {
+        static_assert(G <= 8, "the sub-byte groups fit v0");
+        constexpr int ppb = 8 / D;
+        for (int64_t b = lo; b < hi; b++) {
+            uint32_t byte = 0;
+            for (int q = 0; q < ppb; q++) {
+                const int64_t x = b * ppb + q;
+                if (x >= im.width) break;  // (the unused low bits of the row's last byte stay zero)
+                byte |= (uint32_t)png_pack_pixel<F, CT, D>(im, table, src, x, &miss) << (8 - D - q * D);
+            }
+            v0 |= (uint64_t)byte << (8 * (b - b0));
+        }
+    } else {
+        // whole pixels of BPP bytes; the first and the last may lie partly in a neighbouring group
+        constexpr int BPP = CH * D / 8;
+        for (int64_t x = lo / BPP; x * BPP < hi; x++) {
+            uint64_t px = png_pack_pixel<F, CT, D>(im, table, src, x, &miss);
+            int o = (int)(x * BPP - b0);  // the pixel's first byte in the group: -7 .. G - 1
+            if (o < 0) px >>= -8 * o, o = 0;
+            if (o < 8) {
+                v0 |= px << (8 * o);
+                if (o > 0) v1 |= px >> (8 * (8 - o));
+            } else
+                v1 |= px << (8 * (o - 8));
+        }
+    }
+    if (lo == b0 && hi == b0 + G) {
+        const uint64_t v[2] = {v0, v1};
+        __builtin_memcpy(__builtin_assume_aligned(dst + b0, G), v, G);
+    } else
+        for (int64_t b = lo; b < hi; b++) {
+            const int k = (int)(b - b0);
+            dst[b] = (uint8_t)((k < 8 ? v0 : v1) >> (8 * (k & 7)));
+        }
+    return miss;
+}
+
+// ... the (colour type, depth) pair is the same for a whole row: one jump, then straight code.  G: kAdam7GroupBits below 8
+// bits a pixel (a lane reads 8 .. 32 source pixels for its 4 bytes), kPngPackGroup from there on.
+template <int F>
+ZS_HD uint32_t png_pack_group(const PngPackImg &im, const uint32_t *table, int64_t y, int64_t rb, uint8_t *dst, int64_t b0) {
+    constexpr int GB = kAdam7GroupBits, GP = kPngPackGroup;
+    switch (im.color * 32 + im.depth) {
+    case 0 * 32 + 1: return png_pack_group_as<F, 0, 1, GB>(im, table, y, rb, dst, b0);
+    case 0 * 32 + 2: return png_pack_group_as<F, 0, 2, GB>(im, table, y, rb, dst, b0);
+    case 0 * 32 + 4: return png_pack_group_as<F, 0, 4, GB>(im, table, y, rb, dst, b0);
+    case 0 * 32 + 8: return png_pack_group_as<F, 0, 8, GP>(im, table, y, rb, dst, b0);
+    case 0 * 32 + 16: return png_pack_group_as<F, 0, 16, GP>(im, table, y, rb, dst, b0);
+    case 2 * 32 + 8: return png_pack_group_as<F, 2, 8, GP>(im, table, y, rb, dst, b0);
+    case 2 * 32 + 16: return png_pack_group_as<F, 2, 16, GP>(im, table, y, rb, dst, b0);
+    case 3 * 32 + 1: return png_pack_group_as<F, 3, 1, GB>(im, table, y, rb, dst, b0);
+    case 3 * 32 + 2: return png_pack_group_as<F, 3, 2, GB>(im, table, y, rb, dst, b0);
+    case 3 * 32 + 4: return png_pack_group_as<F, 3, 4, GB>(im, table, y, rb, dst, b0);
+    case 3 * 32 + 8: return png_pack_group_as<F, 3, 8, GP>(im, table, y, rb, dst, b0);
+    case 4 * 32 + 8: return png_pack_group_as<F, 4, 8, GP>(im, table, y, rb, dst, b0);
+    case 4 * 32 + 16: return png_pack_group_as<F, 4, 16, GP>(im, table, y, rb, dst, b0);
+    case 6 * 32 + 8: return png_pack_group_as<F, 6, 8, GP>(im, table, y, rb, dst, b0);
+    case 6 * 32 + 16: return png_pack_group_as<F, 6, 16, GP>(im, table, y, rb, dst, b0);
+    default: return 0;  // (the host admits the fifteen pairs of table 11.1 only)
+    }
+}
+ZS_HD constexpr int png_pack_group_bytes(int bits) { return bits < 8 ? kAdam7GroupBits : kPngPackGroup; }
+
+// ---- the survey (KV, zs_png.hip): what an image's pixels allow ----
+// A pixel's share of the violation mask, and its colour reduced to RGBA8 (meaningful where the pixel is low8).
+constexpr uint32_t kSvNotOpaque = 1, kSvNotGray = 2, kSvNotLow8 = 4, kSvNot17 = 8, kSvNot85 = 16, kSvNot255 = 32, kSvWhite = 64;
+constexpr int kSurveyRows = 16;       // rows of one image a workgroup of the first launch takes
+constexpr int kSurveySlots = 1024;    // a workgroup's colour set: <= 257 counted and <= 256 on their way in, so never full
+constexpr uint32_t kSurveyEmpty = 0xFFFFFFFFu;  // (that colour itself is kept as a bit of the mask: kSvWhite)
+constexpr uint32_t kSurveyMany = 257;
+struct PngSurveyImg {
+    const uint8_t *in;   // height rows of row_pixels pixels, no padding, aligned to a pixel
+    int64_t row_pixels;
+    int32_t height, pad;
+};
+struct PngSurveyRec {
+    uint32_t mask, count;  // count: colours in colors[] (the white of kSvWhite is not among them), or kSurveyMany
+    uint32_t colors[256];
+};
+template <int F>
+ZS_HD uint32_t png_survey_pixel(uint64_t raw, uint32_t *rgba8) {
+    uint32_t m = 0, r, g, b, a;
+    if constexpr (F == ZS_PNG_FMT_RGBA8) {
+        r = (uint32_t)raw & 255, g = (uint32_t)raw >> 8 & 255, b = (uint32_t)raw >> 16 & 255, a = (uint32_t)raw >> 24;
+        *rgba8 = (uint32_t)raw;
+    } else {
+        const uint32_t r16 = (uint32_t)raw & 0xFFFFu, g16 = (uint32_t)(raw >> 16) & 0xFFFFu, b16 = (uint32_t)(raw >> 32) & 0xFFFFu, a16 = (uint32_t)(raw >> 48);
+        if (a16 != 0xFFFFu) m |= kSvNotOpaque;
+        if (r16 != g16 || g16 != b16) m |= kSvNotGray;
+        if (r16 % 257 || g16 % 257 || b16 % 257 || a16 % 257) m |= kSvNotLow8;
+        r = r16 >> 8, g = g16 >> 8, b = b16 >> 8, a = a16 >> 8;
+        *rgba8 = r | g << 8 | b << 16 | a << 24;
+    }
+    if constexpr (F == ZS_PNG_FMT_RGBA8) {
+        if (a != 255) m |= kSvNotOpaque;
+        if (r != g || g != b) m |= kSvNotGray;
+    }
+    if (r % 17 || g % 17 || b % 17) m |= kSvNot17;
+    if (r % 85 || g % 85 || b % 85) m |= kSvNot85;
+    if (r % 255 || g % 255 || b % 255) m |= kSvNot255;
+    return m;
+}
+
+// ---- the choice of a file format from a survey (zs_png_choose_format): compares bits per pixel, nothing else ----
+inline void png_choose_format(bool opaque, bool gray, bool low8, int sample_depth, int n_colors, int *color_type, int *bit_depth) {
+    if (!low8) {
+        *color_type = gray ? (opaque ? 0 : 4) : (opaque ? 2 : 6);
+        *bit_depth = 16;
+        return;
+    }
+    int ct = gray ? (opaque ? 0 : 4) : (opaque ? 2 : 6), bd = ct == 0 ? sample_depth : 8;
+    const int base_bits = bd * (ct == 2 ? 3 : ct == 4 ? 2 : ct == 6 ? 4 : 1);
+    if (n_colors <= 256) {
+        const int p = n_colors <= 2 ? 1 : n_colors <= 4 ? 2 : n_colors <= 16 ? 4 : 8;
+        if (p < base_bits) ct = 3, bd = p;  // (a tie keeps the base, which needs no PLTE)
+    }
+    *color_type = ct, *bit_depth = bd;
+}
+
 
 }  // namespace zs

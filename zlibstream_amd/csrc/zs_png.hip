@@ -1,4 +1,4 @@
-// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip); KA and KX behind it.  What inflate leaves for
+// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip); KA, KS, KX, KG and KV behind it.  What inflate leaves for
 // an IDAT payload is, per row, a filter-type byte and the filtered bytes; reconstruction reads reconstructed neighbours
 // (left, above, above-left), so it is serial along a row and across rows.  Two kernels:
 //   zs_png_scan_kernel      one workgroup per image over its type bytes: the first invalid one, and the segments
@@ -342,6 +342,157 @@ __global__ __launch_bounds__(64 * kExpandRowsPerWg) void zs_png_expand_kernel(co
     const uint64_t addr = (uint64_t)(uintptr_t)dst;
     const int64_t ng = adam7_row_groups(addr, rb, kPngExpandGroup), b0 = adam7_row_b0(addr, kPngExpandGroup);
     for (int64_t g = lane; g < ng; g += 64) png_expand_group<F>(im, s_pal[w], y, dst, b0 + g * kPngExpandGroup);
+}
+
+// KG: RGBA8 / RGBA16 to raw scanlines (zs_png.h png_pack_group), KX's inverse and shaped like it.  The grid is the flat list of
+// all images' output rows, four rows a workgroup: wave w takes row 4 * block + w, and its lanes the row's address-aligned
+// groups of 16 output bytes (4 at 1, 2 and 4 bits a pixel, where 16 bytes would be up to 128 source pixels a lane), 64 at a
+// time -- one full-width store per lane, contiguous over the wave; the ragged first and last groups of a row go out byte by
+// byte.  The source pixels are aligned loads of 4 or 8 bytes, contiguous over the wave.  The wave of a palette row first
+// copies its image's lookup table (2 KiB) into an LDS slice of its own; the pixels that find no entry are counted per lane,
+// summed over the wave, and added once per wave to the image's word of `unmatched` (zeroed by the host).  No other atomics,
+// no traffic between waves: no output byte has two writers.
+constexpr int kPackRowsPerWg = 4;
+
+template <int F>
+__global__ __launch_bounds__(64 * kPackRowsPerWg) void zs_png_pack_kernel(const PngPackImg *imgs, const int32_t *row_off, const uint32_t *tables,
+                                                                          unsigned long long *unmatched, int n, int64_t row0) {
+    __shared__ uint32_t s_tab[kPackRowsPerWg][kPngPackTableWords];
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    const int64_t r = row0 + (int64_t)blockIdx.x * kPackRowsPerWg + w;
+    const bool active = r < (int64_t)row_off[n];
+    const int i = active ? png_row_image(row_off, n, r) : 0;
+    const PngPackImg im = imgs[i];
+    if (active && im.color == 3)
+        for (int k = lane; k < kPngPackTableWords; k += 64) s_tab[w][k] = tables[(int64_t)im.pal_off + k];
+    __syncthreads();  // (every wave arrives: none has left yet)
+    if (!active) return;
+    const int bits = im.depth * (im.color == 2 ? 3 : im.color == 4 ? 2 : im.color == 6 ? 4 : 1), G = png_pack_group_bytes(bits);
+    const int64_t y = r - row_off[i], rb = png_bits_row_bytes(im.width, bits);
+    uint8_t *dst = im.out + y * rb;
+    const uint64_t addr = (uint64_t)(uintptr_t)dst;
+    const int64_t ng = adam7_row_groups(addr, rb, G), b0 = adam7_row_b0(addr, G);
+    uint32_t miss = 0;
+    for (int64_t g = lane; g < ng; g += 64) miss += png_pack_group<F>(im, s_tab[w], y, rb, dst, b0 + g * G);
+    if (im.color == 3) {  // (the same for the whole wave)
+        for (int o = 32; o > 0; o >>= 1) miss += __shfl_xor(miss, o);
+        if (lane == 0 && miss) atomicAdd(&unmatched[i], (unsigned long long)miss);
+    }
+}
+
+// KV: the survey.  Two launches.  The first runs over the flat list of (image, kSurveyRows rows of it) items, one workgroup
+// an item: the item's pixels are one contiguous run, taken in address-aligned groups of 16 bytes (the ragged ends pixel by
+// pixel).  Every lane ORs its pixels' violation bits (zs_png.h png_survey_pixel), the workgroup ORs the lanes' through LDS;
+// low8 pixels go into a set of the workgroup in LDS -- open addressing, atomicCAS on the slot, a counter behind it -- unless
+// they equal the pixel in front of them in the lane's group, and until the counter passes 256.  The workgroup then writes its
+// record (mask, count, colours) to its own slot.  The second launch merges an image's records with one workgroup through the
+// same set.  No atomics outside LDS, no byte with two writers; the order of a record's colours depends on the run, their set
+// and count do not, and the host sorts them.
+__device__ __forceinline__ void png_survey_insert(uint32_t *slots, int *count, uint32_t c) {
+    if (*(volatile int *)count > 256) return;  // (257 are enough to know)
+    uint32_t h = png_color_hash(c, 10);
+    for (int t = 0; t < kSurveySlots; t++) {
+        uint32_t cur = ((volatile uint32_t *)slots)[h];
+        if (cur == kSurveyEmpty) {
+            cur = atomicCAS(&slots[h], kSurveyEmpty, c);
+            if (cur == kSurveyEmpty) {
+                atomicAdd(count, 1);
+                return;
+            }
+        }
+        if (cur == c) return;
+        h = (h + 1) & (kSurveySlots - 1);
+    }
+}
+
+// the workgroup's set and mask -> *rec (every thread calls; s_pos is zero on entry)
+__device__ __forceinline__ void png_survey_emit(const uint32_t *slots, const int *count, int *s_pos, uint32_t mask, PngSurveyRec *rec) {
+    const int tid = (int)threadIdx.x;
+    const int cnt = *count;
+    if (cnt <= 256)
+        for (int k = tid; k < kSurveySlots; k += 256) {
+            const uint32_t c = slots[k];
+            if (c != kSurveyEmpty) rec->colors[atomicAdd(s_pos, 1)] = c;  // (cnt slots are taken: the positions stay below 256)
+        }
+    if (tid == 0) rec->mask = mask, rec->count = cnt <= 256 ? (uint32_t)cnt : kSurveyMany;
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void zs_png_survey_kernel(const PngSurveyImg *imgs, const int32_t *item_off, int n, PngSurveyRec *recs) {
+    __shared__ uint32_t s_slots[kSurveySlots];
+    __shared__ int s_count, s_pos;
+    __shared__ uint32_t s_mask;
+    constexpr int P = png_expand_bytes(F), N = 16 / P;
+    const int tid = (int)threadIdx.x;
+    const int64_t item = (int64_t)blockIdx.x;
+    const int i = png_row_image(item_off, n, item);
+    const PngSurveyImg im = imgs[i];
+    for (int k = tid; k < kSurveySlots; k += 256) s_slots[k] = kSurveyEmpty;
+    if (tid == 0) s_count = 0, s_pos = 0, s_mask = 0;
+    __syncthreads();
+    const int64_t y0 = (item - item_off[i]) * kSurveyRows, y1 = y0 + kSurveyRows < im.height ? y0 + kSurveyRows : im.height;
+    const uint8_t *p = im.in + y0 * im.row_pixels * P;
+    const int64_t nb = (y1 - y0) * im.row_pixels * P;  // the item's bytes
+    int64_t head = (int64_t)((16 - ((uint64_t)(uintptr_t)p & 15)) & 15);  // bytes in front of the first aligned group (whole pixels: p is P-aligned)
+    if (head > nb) head = nb;
+    const int64_t groups = (nb - head) >> 4, tail = nb - head - (groups << 4);
+    uint32_t mask = 0;
+    auto take = [&](uint64_t raw, bool have_prev, uint64_t prev) {
+        uint32_t c;
+        const uint32_t m = png_survey_pixel<F>(raw, &c);
+        mask |= m;
+        if (m & kSvNotLow8) return;  // (the image's colours are not asked for)
+        if (c == kSurveyEmpty) mask |= kSvWhite;
+        else if (!(have_prev && raw == prev)) png_survey_insert(s_slots, &s_count, c);
+    };
+    for (int64_t g = tid; g < groups; g += 256) {
+        uint64_t v[2];
+        __builtin_memcpy(v, __builtin_assume_aligned(p + head + (g << 4), 16), 16);
+        if constexpr (N == 4) {
+            const uint64_t px[4] = {v[0] & 0xFFFFFFFFu, v[0] >> 32, v[1] & 0xFFFFFFFFu, v[1] >> 32};
+#pragma unroll
+            for (int j = 0; j < 4; j++) take(px[j], j > 0, j > 0 ? px[j - 1] : 0);
+        } else {
+            take(v[0], false, 0);
+            take(v[1], true, v[0]);
+        }
+    }
+    {  // the ragged ends: fewer than 2 * N pixels, one a thread
+        const int64_t nh = head / P, nt = tail / P;
+        if (tid < nh + nt) {
+            const uint8_t *q = tid < nh ? p + (int64_t)tid * P : p + head + (groups << 4) + ((int64_t)tid - nh) * P;
+            uint64_t raw = 0;
+            __builtin_memcpy(&raw, __builtin_assume_aligned(q, P), P);
+            take(raw, false, 0);
+        }
+    }
+    if (mask) atomicOr(&s_mask, mask);
+    __syncthreads();
+    png_survey_emit(s_slots, &s_count, &s_pos, s_mask, &recs[item]);
+}
+
+// one workgroup an image: its items' records -> the image's record
+__global__ __launch_bounds__(256) void zs_png_survey_merge_kernel(const int32_t *item_off, const PngSurveyRec *recs, PngSurveyRec *out) {
+    __shared__ uint32_t s_slots[kSurveySlots];
+    __shared__ int s_count, s_pos;
+    __shared__ uint32_t s_mask;
+    const int tid = (int)threadIdx.x, i = (int)blockIdx.x;
+    for (int k = tid; k < kSurveySlots; k += 256) s_slots[k] = kSurveyEmpty;
+    if (tid == 0) s_count = 0, s_pos = 0, s_mask = 0;
+    __syncthreads();
+    const int64_t r0 = item_off[i], r1 = item_off[i + 1];
+    uint32_t mask = 0;
+    for (int64_t k = r0 * 256 + tid; k < r1 * 256; k += 256) {  // record k >> 8 (the same for the workgroup), colour tid of it
+        const PngSurveyRec &rc = recs[k >> 8];
+        if (tid == 0) mask |= rc.mask;
+        if (rc.count == kSurveyMany) {
+            if (tid == 0) atomicAdd(&s_count, (int)kSurveyMany);  // (past 256 for good)
+        } else if ((uint32_t)tid < rc.count)
+            png_survey_insert(s_slots, &s_count, rc.colors[tid]);
+    }
+    if (mask) atomicOr(&s_mask, mask);
+    __syncthreads();
+    png_survey_emit(s_slots, &s_count, &s_pos, s_mask, &out[i]);
 }
 
 }  // namespace zs
