@@ -154,6 +154,28 @@ namespace SixLabors.ZlibStream
                                                                                   long rowsPerWrite, long idatChunkBytes, IntPtr* output, long* outCap,
                                                                                   long* outLen, int* status, int* colorTypeOut, int* bitDepthOut, int level,
                                                                                   int strategy, int hashVariant, IntPtr hipStream);
+        // animated PNG: the frames of a file (host code); frames -> canvases on the device; files -> composed canvases
+        [StructLayout(LayoutKind.Sequential)]
+        public struct PngFrame
+        {
+            public long X, Y, Width, Height;
+            public int DelayNum, DelayDen;
+            public int DisposeOp, BlendOp;  // 0 NONE, 1 BACKGROUND, 2 PREVIOUS; 0 SOURCE, 1 OVER
+            public long DataBytes, DataChunks;
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
+        public struct PngAnim
+        {
+            public PngInfo Png;
+            public int Animated, FrameCount, PlayCount, DefaultIsFrame;
+        }
+
+        [DllImport(Lib)] public static extern int zs_png_anim_info(IntPtr file, long len, PngAnim* anim, PngFrame* frames, int framesCap);
+        [DllImport(Lib)] public static extern int zs_png_compose_batch_device(IntPtr ctx, int n, IntPtr** framePixels, PngFrame** frames, int* frameCount,
+                                                                              long* width, long* height, int format, IntPtr* output, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_decode_anim_batch(IntPtr ctx, int n, IntPtr* file, long* fileLen, int format, IntPtr* output,
+                                                                           long* outCap, PngAnim* anim, int* status, IntPtr hipStream);
         // bytes fed behind a stream's trailer before its end was seen (the engine looks for the end now and then)
         [DllImport(Lib)] public static extern long zs_inflate_surplus(IntPtr s, IntPtr* p);
     }

@@ -509,6 +509,79 @@ ZS_API int zs_png_encode_rgba_batch_device(zs_ctx *ctx, int n, const void *const
                                            int *status, int *color_type_out, int *bit_depth_out, int level, int strategy,
                                            int hash_variant, void *hip_stream);
 
+/* ------------------------------------------------------------------ */
+/* Animated PNG (APNG specification 1.0).  One play's canvases are produced: delays and n_plays are reported, not
+ * interpreted -- timing and looping are the viewer's business.  Frames share IHDR's colour type, bit depth and interlace
+ * method, and the file's PLTE / tRNS. */
+typedef struct zs_png_frame {
+    int64_t x, y, width, height;  /* the frame's region of the canvas */
+    int delay_num, delay_den;     /* as in the file, not interpreted (0 is legal) */
+    int dispose_op, blend_op;     /* 0 NONE, 1 BACKGROUND, 2 PREVIOUS; 0 SOURCE, 1 OVER */
+    int64_t data_bytes, n_chunks; /* the frame's zlib stream: IDAT data, or fdAT data without the sequence numbers */
+} zs_png_frame;
+typedef struct zs_png_anim {
+    zs_png_info png;       /* what zs_png_file_info gives */
+    int animated;          /* the file has an acTL */
+    int n_frames, n_plays; /* acTL's; a file without acTL: 1 and 0 */
+    int default_is_frame;  /* an fcTL stands in front of IDAT (always 1 for a file without acTL) */
+} zs_png_anim;
+
+/* The animation of one file in HOST memory, pure host code, no context and no GPU: zs_png_file_info's and
+ * zs_png_file_colors' walks and checks, then the walk over acTL, fcTL and fdAT.  frames (may be NULL with frames_cap 0)
+ * receives the first min(frames_cap, n_frames) frames.  A file without an acTL is an animation of one frame: the whole canvas,
+ * dispose NONE, blend SOURCE, its data the IDAT stream; any fcTL / fdAT it holds is stepped over like other ancillary chunks.
+ * ZS_BUF_ERROR: frames_cap < n_frames (*anim is filled all the same).  ZS_DATA_ERROR for what the two other walks reject and for:
+ *   acTL: a second one, a length other than 8, one behind the first IDAT, num_frames 0 or above 2^31 - 1;
+ *   fcTL: a length other than 26, a sequence number that is not the next one (fcTL and fdAT share one counter from 0), more
+ *     than one in front of IDAT, one in front of IDAT that is not exactly the canvas at (0, 0), two in a row with no frame data
+ *     between them or a last one with none, width or height 0, x + width or y + height beyond the canvas, dispose above 2,
+ *     blend above 1;
+ *   fdAT: one shorter than 4 bytes, one with the wrong sequence number, one in front of IDAT, one with no fcTL since IDAT;
+ *   a number of fcTLs other than num_frames; a wrong CRC in acTL or fcTL (they are interpreted, so they are verified here).
+ * fdAT CRCs are not read here: zs_png_decode_anim_batch checks them on the device with the IDAT ones.  Other chunks between a
+ * frame's fdATs are stepped over.  ZS_STREAM_ERROR: null file or anim, a negative len or frames_cap, frames NULL with
+ * frames_cap > 0. */
+ZS_API int zs_png_anim_info(const void *file, int64_t len, zs_png_anim *anim, zs_png_frame *frames, int frames_cap);
+
+/* Frames to canvases on the device, n animations a call, one launch over the flat list of all canvas rows (DESIGN.md
+ * section 4, KM).  frame_px[i][f]: DEVICE pointer to frame f's own pixels, frames[i][f].height rows of frames[i][f].width * 4
+ * (ZS_PNG_RGBA8) or * 8 (ZS_PNG_RGBA16) bytes as zs_png_expand_batch_device writes them, aligned to 4 or 8.  out[i]: DEVICE
+ * pointer, aligned likewise, to n_frames[i] canvases of height[i] * width[i] * 4 or * 8 bytes back to back; canvas f is what a
+ * viewer shows while frame f is up.  frame_px, frame_px[i], frames, frames[i], n_frames, width, height and out are HOST
+ * arrays; of a frame only x, y, width, height, dispose_op and blend_op are read.  Exact integer arithmetic:
+ *   the canvas starts as transparent black; blend SOURCE: the region takes the frame's pixels; blend OVER, per pixel, with
+ *   M = 255 or 65535, foreground (f, fa), canvas (b, ba): fa == 0 leaves the canvas alone, fa == M or ba == 0 copies the
+ *   frame's pixel, otherwise u = fa * M, v = (M - fa) * ba, al = u + v, every colour channel becomes (f * u + b * v) / al and
+ *   alpha al / M, both floor divisions -- the arithmetic of the APNG specification's sample code;
+ *   dispose, after canvas f is written: NONE keeps the canvas, BACKGROUND sets the region to transparent black, PREVIOUS
+ *   puts back what the region held before frame f was drawn and acts as BACKGROUND on frame 0.
+ * Returns ZS_OK, ZS_MEM_ERROR (the descriptors do not fit) or, before any device work, ZS_STREAM_ERROR: null context, n < 0,
+ * null arrays or pointers, n_frames[i] < 1, width or height outside 1 .. 2^31 - 1, a region outside the canvas, a dispose or
+ * blend value outside the above, a bad format, a misaligned pointer, more than 2^31 - 1 canvas rows (a row counted once per
+ * 1024 bytes of it) or frames in one call.
+ * n == 0 is ZS_OK.  Ordered on hip_stream (NULL: the context's, and the call returns when the canvases are written); the
+ * call waits for the stream once, for its descriptors' upload, like zs_png_expand_batch_device.  zs_ctx_stage_ms shows the
+ * launch as "png_compose". */
+ZS_API int zs_png_compose_batch_device(zs_ctx *ctx, int n, const void *const *const *frame_px, const zs_png_frame *const *frames,
+                                       const int *n_frames, const int64_t *width, const int64_t *height, int format,
+                                       void *const *out, void *hip_stream);
+
+/* PNG files, animated or not, to composed canvases, n files a call.  The host walks of zs_png_anim_info (the CRCs of the
+ * critical chunks and of fdAT aside), one upload, one CRC-32 launch that checks the critical chunks and every frame's fdAT
+ * chunks and gathers each frame's data -- IDAT data, or fdAT data without the sequence numbers -- into a buffer the context
+ * owns; one zs_png_decode_batch_device call over all frames of all files as images of their own size; one
+ * zs_png_expand_batch_device launch into a second buffer of the context; the compose launch into out[i]: anim[i].n_frames
+ * canvases of width * height * 4 (ZS_PNG_RGBA8) or * 8 (ZS_PNG_RGBA16) bytes, DEVICE pointer aligned to 4 or 8.  A default
+ * image that is not a frame is not decoded.  A still file gives one canvas: zs_png_decode_files_rgba_batch's pixels.
+ * anim (HOST, may be NULL): filled for every file whose chain could be walked.  status[i] (may be NULL): ZS_OK, ZS_BUF_ERROR
+ * (out_cap[i] below the canvases' size) or ZS_DATA_ERROR; a file fails for itself only -- for its chunk chain, any CRC, any
+ * frame's stream or a frame's length -- and none of its canvases is then specified; zs_ctx_last_error names the first failing
+ * file, the frame and the reason ("data error: file i: frame f: ...").  Arguments, return values, ZS_STREAM_ERROR cases and
+ * waits as for zs_png_decode_files_rgba_batch, one wait more for the descriptors of the compose launch.  zs_ctx_stage_ms
+ * shows "crc32_frame", "png_expand" and "png_compose". */
+ZS_API int zs_png_decode_anim_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, int format,
+                                    void *const *out, const int64_t *out_cap, zs_png_anim *anim, int *status, void *hip_stream);
+
 /* Stage timing of the last *_batch_device call, measured with hipEvents on
  * the stream the kernels ran on.  Enable before the call. */
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took

@@ -12,4 +12,6 @@ from .api import (CompressionLevel, CompressionState, CompressionStrategy, Engin
                   crc32_device, crc32_batch_device, png_file_bound, png_encode_batch_device, png_file_info, png_decode_files_batch,
                   png_expand_batch_device, png_file_colors, png_decode_files_rgba_batch, PNG_RGBA8, PNG_RGBA16,
                   png_adam7_split_batch_device, png_idat_interlace_batch_device, png_encode_interlace_batch_device,
-                  png_pack_batch_device, png_survey_batch_device, png_choose_format, png_encode_rgba_batch_device)
+                  png_pack_batch_device, png_survey_batch_device, png_choose_format, png_encode_rgba_batch_device,
+                  png_anim_info, png_compose_batch_device, png_decode_anim_batch, PNG_DISPOSE_NONE, PNG_DISPOSE_BACKGROUND,
+                  PNG_DISPOSE_PREVIOUS, PNG_BLEND_SOURCE, PNG_BLEND_OVER)

@@ -22,6 +22,7 @@ SYMBOLS = [
     "zs_png_expand_batch_device", "zs_png_file_colors", "zs_png_decode_files_rgba_batch",
     "zs_png_adam7_split_batch_device", "zs_png_idat_interlace_batch_device", "zs_png_encode_interlace_batch_device",
     "zs_png_pack_batch_device", "zs_png_survey_batch_device", "zs_png_choose_format", "zs_png_encode_rgba_batch_device",
+    "zs_png_anim_info", "zs_png_compose_batch_device", "zs_png_decode_anim_batch",
 ]
 
 
@@ -34,6 +35,18 @@ class PngInfo(ctypes.Structure):  # zs_png_info
 class PngSurvey(ctypes.Structure):  # zs_png_survey
     _fields_ = [("opaque", ctypes.c_int), ("gray", ctypes.c_int), ("low8", ctypes.c_int), ("sample_depth", ctypes.c_int),
                 ("n_colors", ctypes.c_int), ("colors", ctypes.c_uint8 * 4 * 256)]
+
+
+class PngFrame(ctypes.Structure):  # zs_png_frame
+    _fields_ = [("x", ctypes.c_int64), ("y", ctypes.c_int64), ("width", ctypes.c_int64), ("height", ctypes.c_int64),
+                ("delay_num", ctypes.c_int), ("delay_den", ctypes.c_int), ("dispose_op", ctypes.c_int), ("blend_op", ctypes.c_int),
+                ("data_bytes", ctypes.c_int64), ("n_chunks", ctypes.c_int64)]
+
+
+class PngAnim(ctypes.Structure):  # zs_png_anim
+    _fields_ = [("png", PngInfo), ("animated", ctypes.c_int), ("n_frames", ctypes.c_int), ("n_plays", ctypes.c_int),
+                ("default_is_frame", ctypes.c_int)]
+
 
 _lib = None
 
@@ -185,5 +198,12 @@ def lib():
         L.zs_png_encode_rgba_batch_device.restype = i32
         L.zs_png_encode_rgba_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), i32, P(i32), P(i32), P(vp), P(i64), i64, i64, P(vp), P(i64),
                                                       P(i64), P(i32), P(i32), P(i32), i32, i32, i32, vp]
+    if hasattr(L, "zs_png_compose_batch_device"):  # (an older build selected with ZS_LIB for an A/B run lacks animated PNG)
+        L.zs_png_anim_info.restype = i32
+        L.zs_png_anim_info.argtypes = [vp, i64, P(PngAnim), P(PngFrame), i32]
+        L.zs_png_compose_batch_device.restype = i32
+        L.zs_png_compose_batch_device.argtypes = [vp, i32, P(P(vp)), P(P(PngFrame)), P(i32), P(i64), P(i64), i32, P(vp), vp]
+        L.zs_png_decode_anim_batch.restype = i32
+        L.zs_png_decode_anim_batch.argtypes = [vp, i32, P(vp), P(i64), i32, P(vp), P(i64), P(PngAnim), P(i32), vp]
     _lib = L
     return L

@@ -1018,6 +1018,106 @@ def png_encode_rgba_batch_device(engine, pixel_ptrs, widths, heights, filters, o
     return list(out_len), list(ct), list(bd)
 
 
+PNG_DISPOSE_NONE, PNG_DISPOSE_BACKGROUND, PNG_DISPOSE_PREVIOUS = 0, 1, 2  # fcTL's dispose_op
+PNG_BLEND_SOURCE, PNG_BLEND_OVER = 0, 1                                   # fcTL's blend_op
+_PNG_FRAME_FIELDS = ("x", "y", "width", "height", "delay_num", "delay_den", "dispose_op", "blend_op", "data_bytes", "n_chunks")
+_PNG_ANIM_FIELDS = ("animated", "n_frames", "n_plays", "default_is_frame")
+
+
+def _anim_dict(a):
+    d = {k: int(getattr(a.png, k)) for k in _PNG_INFO_FIELDS}
+    d.update({k: int(getattr(a, k)) for k in _PNG_ANIM_FIELDS})
+    return d
+
+
+def png_anim_info(data):
+    """zs_png_anim_info (host code, no GPU, no engine): the animation of one PNG file given as bytes -> (anim, frames): anim
+    is png_file_info's dict plus animated, n_frames, n_plays and default_is_frame; frames one dict per frame of x, y, width,
+    height, delay_num, delay_den, dispose_op, blend_op, data_bytes, n_chunks.  A file without an acTL is one frame: the whole
+    canvas, dispose NONE, blend SOURCE.  Delays and n_plays are reported as the file holds them, never interpreted.
+    ZlibStreamException for what png_file_info and png_file_colors reject and for acTL / fcTL / fdAT chunks that break the
+    APNG specification's rules (include/zsgpu.h lists them)."""
+    data = bytes(data)
+    L = _native.lib()
+    anim = _native.PngAnim()
+    rc = L.zs_png_anim_info(data, len(data), ctypes.byref(anim), None, 0)
+    if rc not in (0, -5):
+        raise ZlibStreamException("png_anim_info: not a whole PNG file, or its acTL / fcTL / fdAT chunks break the rules (%d)" % rc)
+    frames = (_native.PngFrame * anim.n_frames)()
+    rc = L.zs_png_anim_info(data, len(data), ctypes.byref(anim), frames, anim.n_frames)
+    if rc != 0:
+        raise ZlibStreamException("png_anim_info failed (%d)" % rc)
+    return _anim_dict(anim), [{k: int(getattr(f, k)) for k in _PNG_FRAME_FIELDS} for f in frames]
+
+
+def png_compose_batch_device(engine, frame_ptrs, frames, widths, heights, out_ptrs, format=PNG_RGBA8, stream=None):
+    """Frames -> canvases for many device-resident animations in one launch (zs_png_compose_batch_device).  frame_ptrs[i][f]:
+    device pointer to frame f's own pixels (frames[i][f]["height"] rows of ["width"] * 4 or * 8 bytes, as
+    png_expand_batch_device writes them); frames[i][f]: a dict with x, y, width, height, dispose_op, blend_op (png_anim_info's
+    dicts do); out_ptrs[i] receives len(frames[i]) canvases of heights[i] * widths[i] * 4 (PNG_RGBA8) or * 8 (PNG_RGBA16)
+    bytes back to back, canvas f being what a viewer shows while frame f is up.  Every pointer must be aligned to a pixel.
+    Blend OVER is the APNG specification's integer arithmetic (include/zsgpu.h)."""
+    n = len(frame_ptrs)
+    if not (len(frames) == len(widths) == len(heights) == len(out_ptrs) == n) or any(len(p) != len(f) for p, f in zip(frame_ptrs, frames)):
+        raise ValueError("png_compose_batch_device: the argument lists differ in length")
+    if format not in (PNG_RGBA8, PNG_RGBA16):
+        raise ValueError("png_compose_batch_device: format is PNG_RGBA8 or PNG_RGBA16")
+    px = 8 if format == PNG_RGBA16 else 4
+    for ptrs, frs, w, h, o in zip(frame_ptrs, frames, widths, heights, out_ptrs):
+        if not o or int(o) % px or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF or len(frs) < 1:
+            raise ValueError("png_compose_batch_device: 1 <= width, height <= 2^31 - 1, at least one frame and outputs aligned to a pixel are required")
+        for p, f in zip(ptrs, frs):
+            if not p or int(p) % px:
+                raise ValueError("png_compose_batch_device: a frame's pixels need a non-null device pointer aligned to a pixel")
+            if f["x"] < 0 or f["y"] < 0 or f["width"] < 1 or f["height"] < 1 or f["x"] + f["width"] > int(w) or f["y"] + f["height"] > int(h):
+                raise ValueError("png_compose_batch_device: a frame's region lies outside the canvas")
+            if f["dispose_op"] not in (0, 1, 2) or f["blend_op"] not in (0, 1):
+                raise ValueError("png_compose_batch_device: dispose_op is 0, 1 or 2 and blend_op 0 or 1")
+    if sum(int(h) for h in heights) > 0x7FFFFFFF:
+        raise ValueError("png_compose_batch_device: more than 2^31 - 1 canvas rows in one call")
+    if n == 0:
+        return
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    px_arrays = [(ctypes.c_void_p * len(p))(*[int(x) for x in p]) for p in frame_ptrs]
+    fr_arrays = [(_native.PngFrame * len(frs))(*[_native.PngFrame(x=f["x"], y=f["y"], width=f["width"], height=f["height"], dispose_op=f["dispose_op"],
+                                                                   blend_op=f["blend_op"]) for f in frs]) for frs in frames]
+    rc = _native.lib().zs_png_compose_batch_device(engine.handle, n,
+                                                   (ctypes.POINTER(ctypes.c_void_p) * n)(*[ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)) for a in px_arrays]),
+                                                   (ctypes.POINTER(_native.PngFrame) * n)(*[ctypes.cast(a, ctypes.POINTER(_native.PngFrame)) for a in fr_arrays]),
+                                                   I32(*[len(f) for f in frames]), I64(*[int(x) for x in widths]), I64(*[int(x) for x in heights]),
+                                                   int(format), VP(*[int(p) for p in out_ptrs]), ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_compose_batch_device failed (%d): %s" % (rc, engine.last_error()))
+
+
+def png_decode_anim_batch(engine, files, out_ptrs, out_caps, format=PNG_RGBA8, stream=None):
+    """PNG files, animated or not (bytes objects in host memory) -> composed canvases in device buffers, many files a call
+    (zs_png_decode_anim_batch): every frame of every file is one image of the batched decode, and one compose launch draws
+    them.  out_ptrs[i] receives n_frames canvases of width * height * 4 bytes (PNG_RGBA8) or * 8 (PNG_RGBA16) back to back
+    and must be aligned to a pixel.  Returns (statuses, anims): 0, -5 (ZS_BUF_ERROR: out_caps[i] below the canvases' size) or
+    -3 (ZS_DATA_ERROR; engine.last_error() names the first failing file, the frame and the reason), and one png_anim_info
+    dict per file.  One play's canvases are produced; delays and n_plays are the caller's to interpret (png_anim_info)."""
+    n = len(files)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("png_decode_anim_batch: the argument lists differ in length")
+    if format not in (PNG_RGBA8, PNG_RGBA16):
+        raise ValueError("png_decode_anim_batch: format is PNG_RGBA8 or PNG_RGBA16")
+    if any(not o or int(o) % (8 if format == PNG_RGBA16 else 4) or int(cap) < 0 for o, cap in zip(out_ptrs, out_caps)):
+        raise ValueError("png_decode_anim_batch: non-null device pointers aligned to a pixel and non-negative capacities are required")
+    if n == 0:
+        return [], []
+    files = [bytes(f) for f in files]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    anim, status = (_native.PngAnim * n)(), I32()
+    rc = _native.lib().zs_png_decode_anim_batch(engine.handle, n, VP(*[_host_ptr(f) for f in files]),  # (read in place)
+                                                I64(*[len(f) for f in files]), int(format),
+                                                VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), anim, status,
+                                                ctypes.c_void_p(stream or 0))
+    if rc not in (0, -3, -5):
+        raise ValueError("zs_png_decode_anim_batch failed (%d): %s" % (rc, engine.last_error()))
+    return list(status), [_anim_dict(a) for a in anim]
+
+
 _default_engine = None
 
 

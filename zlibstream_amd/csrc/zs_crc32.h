@@ -298,4 +298,141 @@ inline bool png_file_colors(const uint8_t *f, int64_t len, const PngFileInfo &in
     return true;
 }
 
+// ---- animated PNG (APNG specification 1.0: acTL, fcTL, fdAT) ----
+// One frame of an animation.  Mirrors zs_png_frame of the C ABI field for field (zs_engine.hip asserts it).
+struct PngFrame {
+    int64_t x, y, width, height;
+    int delay_num, delay_den;
+    int dispose_op, blend_op;
+    int64_t data_bytes, n_chunks;
+};
+// What the animation walk finds in one file.  Mirrors zs_png_anim.
+struct PngAnimInfo {
+    PngFileInfo png;
+    int animated;
+    int n_frames, n_plays;
+    int default_is_frame;
+};
+constexpr uint32_t kPngacTL = png_type('a', 'c', 'T', 'L'), kPngfcTL = png_type('f', 'c', 'T', 'L'), kPngfdAT = png_type('f', 'd', 'A', 'T');
+constexpr int kPngDisposeNone = 0, kPngDisposeBackground = 1, kPngDisposePrevious = 2, kPngBlendSource = 0, kPngBlendOver = 1;
+
+// The third walk, over a chain png_walk_file and png_file_colors have accepted (`info` is the first one's result): the
+// animation.  A file without an acTL is an animation of one frame -- the whole canvas, dispose NONE, blend SOURCE, its data
+// the IDAT stream -- and any fcTL / fdAT it holds is stepped over like other ancillary chunks.  With an acTL, the fcTL and
+// fdAT chunks are interpreted: acTL and fcTL are verified here on the host (they hold 8 and 26 bytes); the fdAT CRCs are left
+// to the device with the IDAT ones.  False with the reason in msg for: a second acTL, one that does not hold 8 bytes, one
+// behind the first IDAT, num_frames 0 or above 2^31 - 1; an fcTL that does not hold 26 bytes, whose sequence number is not
+// the next one (fcTL and fdAT share one counter from 0), a second one in front of IDAT, one in front of IDAT that is not
+// the canvas at (0, 0), one without frame data behind it, one with width or height 0, a region beyond the canvas, dispose
+// above 2 or blend above 1; an fdAT shorter than 4 bytes, with the wrong sequence number, in front of IDAT, or with no fcTL
+// since IDAT; a number of fcTLs other than num_frames; a wrong CRC in acTL or fcTL.
+// emit_frame(k, frame) is called once per frame, in order, when its last data chunk has been seen; emit_data(k, ref) for
+// every chunk that holds data of frame k (IDAT: ref.len bytes at ref.at + 8; fdAT: ref.len - 4 bytes at ref.at + 12).
+template <class EmitFrame, class EmitData>
+inline bool png_walk_anim(const uint8_t *f, int64_t len, const PngFileInfo &info, PngAnimInfo *anim, char *msg, size_t msg_cap, EmitFrame emit_frame,
+                          EmitData emit_data) {
+    anim->png = info;
+    anim->animated = 0, anim->n_frames = 1, anim->n_plays = 0, anim->default_is_frame = 1;
+    for (int64_t at = 8; at + 12 <= len;) {  // is there an acTL at all?
+        const int64_t n = png_be32(f + at);
+        uint32_t type;
+        memcpy(&type, f + at + 4, 4);
+        if (type == kPngacTL) anim->animated = 1;
+        at += 12 + n;
+        if (type == kPngIEND) break;
+    }
+    PngFrame cur;
+    memset(&cur, 0, sizeof cur);
+    if (!anim->animated) {
+        cur.width = info.width, cur.height = info.height;
+        cur.dispose_op = kPngDisposeNone, cur.blend_op = kPngBlendSource;
+        for (int64_t at = 8; at + 12 <= len;) {
+            const int64_t n = png_be32(f + at);
+            uint32_t type;
+            memcpy(&type, f + at + 4, 4);
+            if (type == kPngIDAT) {
+                cur.data_bytes += n, cur.n_chunks++;
+                emit_data(0, PngChunkRef{type, at, n});
+            }
+            at += 12 + n;
+            if (type == kPngIEND) break;
+        }
+        emit_frame(0, cur);
+        return true;
+    }
+    auto crc_ok = [&](int64_t at, int64_t n) { return crc32_bytes_slow(0, f + at + 4, (uint64_t)n + 4) == png_be32(f + at + 8 + n); };
+    bool have_actl = false, idat_seen = false, open = false;  // open: an fcTL whose frame has not been emitted yet
+    int64_t num_frames = 0, n_fctl = 0;
+    uint32_t seq = 0;
+    int fctl_before_idat = 0;
+    anim->default_is_frame = 0;
+    auto close = [&](int64_t at) {  // the open frame ends in front of the chunk at `at`
+        if (!open) return true;
+        if (cur.n_chunks == 0) return snprintf(msg, msg_cap, "fcTL of frame %lld has no frame data (offset %lld)", (long long)(n_fctl - 1), (long long)at), false;
+        emit_frame((int)(n_fctl - 1), cur);
+        open = false;
+        return true;
+    };
+    for (int64_t at = 8; at + 12 <= len;) {
+        const int64_t n = png_be32(f + at);
+        uint32_t type;
+        memcpy(&type, f + at + 4, 4);
+        const uint8_t *d = f + at + 8;
+        if (type == kPngacTL) {
+            if (have_actl) return snprintf(msg, msg_cap, "a second acTL at offset %lld", (long long)at), false;
+            if (idat_seen) return snprintf(msg, msg_cap, "acTL behind IDAT (offset %lld)", (long long)at), false;
+            if (n != 8) return snprintf(msg, msg_cap, "acTL holds %lld bytes, not 8", (long long)n), false;
+            if (!crc_ok(at, n)) return snprintf(msg, msg_cap, "CRC error in acTL chunk at offset %lld", (long long)at), false;
+            have_actl = true;
+            num_frames = png_be32(d);
+            if (num_frames < 1 || num_frames > 0x7FFFFFFF) return snprintf(msg, msg_cap, "acTL: num_frames outside 1 .. 2^31 - 1"), false;
+            anim->n_frames = (int)num_frames, anim->n_plays = (int)(png_be32(d + 4) & 0x7FFFFFFFu);
+        } else if (type == kPngfcTL) {
+            if (n != 26) return snprintf(msg, msg_cap, "fcTL holds %lld bytes, not 26 (offset %lld)", (long long)n, (long long)at), false;
+            if (!crc_ok(at, n)) return snprintf(msg, msg_cap, "CRC error in fcTL chunk at offset %lld (frame %lld)", (long long)at, (long long)n_fctl), false;
+            if (png_be32(d) != seq)
+                return snprintf(msg, msg_cap, "fcTL at offset %lld has sequence number %u, not %u", (long long)at, png_be32(d), seq), false;
+            seq++;
+            if (!idat_seen && ++fctl_before_idat > 1) return snprintf(msg, msg_cap, "a second fcTL in front of IDAT (offset %lld)", (long long)at), false;
+            if (!close(at)) return false;
+            memset(&cur, 0, sizeof cur);
+            cur.width = png_be32(d + 4), cur.height = png_be32(d + 8), cur.x = png_be32(d + 12), cur.y = png_be32(d + 16);
+            cur.delay_num = d[20] << 8 | d[21], cur.delay_den = d[22] << 8 | d[23];
+            cur.dispose_op = d[24], cur.blend_op = d[25];
+            if (cur.width < 1 || cur.height < 1) return snprintf(msg, msg_cap, "fcTL of frame %lld: width or height 0", (long long)n_fctl), false;
+            if (cur.x + cur.width > info.width || cur.y + cur.height > info.height)
+                return snprintf(msg, msg_cap, "fcTL of frame %lld: the region reaches beyond the canvas", (long long)n_fctl), false;
+            if (cur.dispose_op > 2 || cur.blend_op > 1)
+                return snprintf(msg, msg_cap, "fcTL of frame %lld: dispose %d, blend %d", (long long)n_fctl, cur.dispose_op, cur.blend_op), false;
+            if (!idat_seen && (cur.x != 0 || cur.y != 0 || cur.width != info.width || cur.height != info.height))
+                return snprintf(msg, msg_cap, "the fcTL in front of IDAT is not the whole canvas"), false;
+            if (!idat_seen) anim->default_is_frame = 1;
+            open = true;
+            n_fctl++;
+        } else if (type == kPngIDAT) {
+            idat_seen = true;
+            if (anim->default_is_frame) {
+                cur.data_bytes += n, cur.n_chunks++;
+                emit_data(0, PngChunkRef{type, at, n});
+            }
+        } else if (type == kPngfdAT) {
+            if (n < 4) return snprintf(msg, msg_cap, "fdAT holds %lld bytes (offset %lld)", (long long)n, (long long)at), false;
+            if (!idat_seen) return snprintf(msg, msg_cap, "fdAT in front of IDAT (offset %lld)", (long long)at), false;
+            if (n_fctl - fctl_before_idat < 1) return snprintf(msg, msg_cap, "fdAT without an fcTL since IDAT (offset %lld)", (long long)at), false;
+            if (png_be32(d) != seq)
+                return snprintf(msg, msg_cap, "fdAT at offset %lld has sequence number %u, not %u", (long long)at, png_be32(d), seq), false;
+            seq++;
+            cur.data_bytes += n - 4, cur.n_chunks++;
+            emit_data((int)(n_fctl - 1), PngChunkRef{type, at, n});
+        }
+        at += 12 + n;
+        if (type == kPngIEND) {
+            if (!close(at - 12 - n)) return false;
+            break;
+        }
+    }
+    if (n_fctl != num_frames) return snprintf(msg, msg_cap, "acTL announces %lld frames, the file has %lld fcTL chunks", (long long)num_frames, (long long)n_fctl), false;
+    return true;
+}
+
 }  // namespace zs

@@ -30,11 +30,11 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStPngCompose, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
                                            "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
-                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey"};
+                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey", "png_compose"};
 
 }  // namespace
 
@@ -72,13 +72,14 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, tile_bits, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw, png_simg, png_split, png_gimg, png_vimg, png_vrec, png_packed;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw, png_simg, png_split, png_gimg, png_vimg, png_vrec, png_packed, png_cimg, png_frames;
     uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
     hipEvent_t ev_crc[2] = {};            // KC and its finishing launch (profiling)
     hipEvent_t ev_expand[2] = {};         // KX (profiling)
     hipEvent_t ev_split[2] = {};          // KS (profiling)
     hipEvent_t ev_pack[2] = {};           // KG (profiling)
     hipEvent_t ev_survey[2] = {};         // KV, both launches (profiling)
+    hipEvent_t ev_compose[2] = {};        // KM (profiling)
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1439,6 +1440,7 @@ int zs_ctx_create(int device, zs_ctx **out) {
     for (auto &e : c->ev_spec) (void)hipEventCreate(&e);
     for (auto &e : c->ev_crc) (void)hipEventCreate(&e);
     for (auto &e : c->ev_expand) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_compose) (void)hipEventCreate(&e);
     for (auto &e : c->ev_split) (void)hipEventCreate(&e);
     for (auto &e : c->ev_pack) (void)hipEventCreate(&e);
     for (auto &e : c->ev_survey) (void)hipEventCreate(&e);
@@ -1507,7 +1509,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->tile_bits, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw, &c->png_simg, &c->png_split, &c->png_gimg, &c->png_vimg, &c->png_vrec, &c->png_packed};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw, &c->png_simg, &c->png_split, &c->png_gimg, &c->png_vimg, &c->png_vrec, &c->png_packed, &c->png_cimg, &c->png_frames};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -1521,6 +1523,8 @@ void zs_ctx_destroy(zs_ctx *c) {
     for (auto &e : c->ev_pack)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_survey)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_compose)
         if (e) (void)hipEventDestroy(e);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pin_io) (void)hipHostFree(c->pin_io);
@@ -1593,7 +1597,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
-    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA) and KV (the survey)
+    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey || s == kStPngCompose) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA), KV (the survey) and KM (the frames of an animation composed)
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine
@@ -3826,6 +3830,357 @@ extern "C" int zs_png_decode_files_rgba_batch(zs_ctx *c, int n, const void *cons
         return ZS_STREAM_ERROR;
     }
     return png_decode_files(c, n, file, file_len, format, out, out_cap, info, status, hip_stream);
+}
+
+// ------------------------------------------------------------------ animated PNG: the walk, the compose launch (KM, zs_png.hip), files to canvases
+static_assert(sizeof(zs_png_frame) == sizeof(PngFrame) && offsetof(zs_png_frame, n_chunks) == offsetof(PngFrame, n_chunks) &&
+                  offsetof(zs_png_frame, blend_op) == offsetof(PngFrame, blend_op),
+              "zs_png_frame mirrors PngFrame");
+static_assert(sizeof(zs_png_anim) == sizeof(PngAnimInfo) && offsetof(zs_png_anim, default_is_frame) == offsetof(PngAnimInfo, default_is_frame),
+              "zs_png_anim mirrors PngAnimInfo");
+
+extern "C" int zs_png_anim_info(const void *file, int64_t len, zs_png_anim *anim, zs_png_frame *frames, int frames_cap) {
+    if (!file || !anim || len < 0 || frames_cap < 0 || (frames_cap > 0 && !frames)) return ZS_STREAM_ERROR;
+    char msg[192];
+    PngFileInfo info;
+    PngFileColors col;
+    PngAnimInfo a;
+    const uint8_t *f = (const uint8_t *)file;
+    if (!png_walk_file(f, len, &info, msg, sizeof msg, true, [](const PngChunkRef &) {}) || !png_file_colors(f, len, info, &col, msg, sizeof msg) ||
+        !png_walk_anim(f, len, info, &a, msg, sizeof msg, [&](int k, const PngFrame &fr) { if (k < frames_cap) memcpy(&frames[k], &fr, sizeof fr); },
+                       [](int, const PngChunkRef &) {}))
+        return ZS_DATA_ERROR;
+    memcpy(anim, &a, sizeof a);
+    return frames_cap < a.n_frames ? ZS_BUF_ERROR : ZS_OK;
+}
+
+namespace {
+constexpr int64_t kComposeSlice = 1 << 25;  // waves a launch, as KX's rows
+
+// The animations of one KM launch: descriptors, their offsets in the flat list of waves (canvas rows times the waves that
+// share a row), and all their frames.
+struct PngComposeJob {
+    std::vector<PngComposeAnim> anim;
+    std::vector<int32_t> off;
+    std::vector<PngComposeFrame> frames;
+    int64_t waves = 0;
+    double ms = 0;  // profiling: the launches
+    void add(void *out, int64_t w, int64_t h, int n_frames, int format) {
+        anim.push_back(PngComposeAnim{(uint8_t *)out, (int32_t)w, (int32_t)h, (int32_t)frames.size(), (int32_t)n_frames});
+        off.push_back((int32_t)waves);
+        waves += h * png_compose_row_waves(w, format);
+    }
+    void add_frame(const void *px, const PngFrame &f) {
+        frames.push_back(PngComposeFrame{(const uint8_t *)px, (int32_t)f.x, (int32_t)f.y, (int32_t)f.width, (int32_t)f.height, f.dispose_op, f.blend_op});
+    }
+};
+
+// Uploads the job through the staging buffer and launches KM on `s`.  Waits for `s` once: for the upload (the staging buffer
+// is the caller's again), or, with profiling on, for the launches.
+bool png_compose_run(zs_ctx *c, PngComposeJob &job, int format, hipStream_t s, bool *no_memory) {
+    *no_memory = false;
+    const int m = (int)job.anim.size();
+    const size_t b_anim = sizeof(PngComposeAnim) * (size_t)m, b_off = (sizeof(int32_t) * ((size_t)m + 1) + 15) & ~(size_t)15,
+                 b_fr = sizeof(PngComposeFrame) * job.frames.size();
+    if (!ensure(c, c->png_cimg, b_anim + b_off + b_fr) || !ensure_pinned(c, b_anim + b_off + b_fr)) {
+        *no_memory = true;
+        return false;
+    }
+    uint8_t *hp = (uint8_t *)c->pinned;
+    memcpy(hp, job.anim.data(), b_anim);
+    memcpy(hp + b_anim, job.off.data(), sizeof(int32_t) * (size_t)m);
+    const int32_t total = (int32_t)job.waves;
+    memcpy(hp + b_anim + sizeof(int32_t) * (size_t)m, &total, sizeof total);
+    memcpy(hp + b_anim + b_off, job.frames.data(), b_fr);
+    ZS_HIP(c, hipMemcpyAsync(c->png_cimg.p, c->pinned, b_anim + b_off + b_fr, hipMemcpyHostToDevice, s));
+    const bool prof = c->profiling;
+    if (!prof) ZS_HIP(c, hipStreamSynchronize(s));
+    else (void)hipEventRecord(c->ev_compose[0], s);
+    const PngComposeAnim *d_anim = (const PngComposeAnim *)c->png_cimg.p;
+    const int32_t *d_off = (const int32_t *)((const uint8_t *)c->png_cimg.p + b_anim);
+    const PngComposeFrame *d_fr = (const PngComposeFrame *)((const uint8_t *)c->png_cimg.p + b_anim + b_off);
+    for (int64_t wave0 = 0; wave0 < job.waves; wave0 += kComposeSlice) {
+        const int64_t waves = std::min<int64_t>(kComposeSlice, job.waves - wave0);
+        const dim3 grid((unsigned)((waves + kComposeWavesPerWg - 1) / kComposeWavesPerWg)), block(64 * kComposeWavesPerWg);
+        if (format == ZS_PNG_FMT_RGBA16) hipLaunchKernelGGL(zs_png_compose_kernel<ZS_PNG_FMT_RGBA16>, grid, block, 0, s, d_anim, d_off, d_fr, m, wave0);
+        else hipLaunchKernelGGL(zs_png_compose_kernel<ZS_PNG_FMT_RGBA8>, grid, block, 0, s, d_anim, d_off, d_fr, m, wave0);
+        ZS_HIP(c, hipGetLastError());
+    }
+    if (prof) {
+        (void)hipEventRecord(c->ev_compose[1], s);
+        ZS_HIP(c, hipStreamSynchronize(s));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev_compose[0], c->ev_compose[1]);
+        job.ms = ms;
+    }
+    return true;
+}
+
+bool png_frame_fits(const PngFrame &f, int64_t w, int64_t h) {
+    return f.x >= 0 && f.y >= 0 && f.width >= 1 && f.height >= 1 && f.x <= w - f.width && f.y <= h - f.height && f.dispose_op >= 0 && f.dispose_op <= 2 &&
+           f.blend_op >= 0 && f.blend_op <= 1;
+}
+}  // namespace
+
+extern "C" int zs_png_compose_batch_device(zs_ctx *c, int n, const void *const *const *frame_px, const zs_png_frame *const *frames, const int *n_frames,
+                                           const int64_t *width, const int64_t *height, int format, void *const *out, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!frame_px || !frames || !n_frames || !width || !height || !out) return ZS_STREAM_ERROR;
+    if (format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) {
+        c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return ZS_STREAM_ERROR;
+    }
+    const uintptr_t mis = (uintptr_t)(png_expand_bytes(format) - 1);
+    int64_t total_rows = 0, total_frames = 0;
+    for (int i = 0; i < n; i++) {
+        bool ok = frame_px[i] && frames[i] && out[i] && ((uintptr_t)out[i] & mis) == 0 && n_frames[i] >= 1 && width[i] >= 1 && height[i] >= 1 &&
+                  width[i] <= 0x7FFFFFFF && height[i] <= 0x7FFFFFFF;
+        for (int f = 0; ok && f < n_frames[i]; f++)
+            ok = frame_px[i][f] && ((uintptr_t)frame_px[i][f] & mis) == 0 && png_frame_fits(*(const PngFrame *)&frames[i][f], width[i], height[i]);
+        if (!ok) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        total_rows += height[i] * png_compose_row_waves(width[i], format), total_frames += n_frames[i];
+        if (total_rows > 0x7FFFFFFF || total_frames > 0x7FFFFFFF) {  // (the grid is the list of rows, a wave per 64 groups of a row)
+            c->err = "stream error: more than 2^31 - 1 canvas rows (counted once per 64 groups of 16 bytes) or frames in one call (split the batch)";
+            return ZS_STREAM_ERROR;
+        }
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    PngComposeJob job;
+    for (int i = 0; i < n; i++) {
+        job.add(out[i], width[i], height[i], n_frames[i], format);
+        for (int f = 0; f < n_frames[i]; f++) job.add_frame(frame_px[i][f], *(const PngFrame *)&frames[i][f]);
+    }
+    bool no_memory = false;
+    if (!png_compose_run(c, job, format, s, &no_memory)) return no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+    if (c->profiling) {
+        for (double &v : c->stage_ms) v = 0;
+        c->stage_ms[kStPngCompose] = job.ms;
+    }
+    return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
+}
+
+// Files -> composed canvases: the three walks on the host, one upload, KC over the critical chunks and every frame's data
+// chunks (IDAT, or fdAT without its sequence number: gathered per frame), the decode call over all frames of all files as
+// images of their own size, KX into a buffer of the context, KM into out[i].
+extern "C" int zs_png_decode_anim_batch(zs_ctx *c, int n, const void *const *file, const int64_t *file_len, int format, void *const *out,
+                                        const int64_t *out_cap, zs_png_anim *anim, int *status, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!file || !file_len || !out || !out_cap) return ZS_STREAM_ERROR;
+    if (format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) {
+        c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return ZS_STREAM_ERROR;
+    }
+    const int px = png_expand_bytes(format);
+    for (int i = 0; i < n; i++)
+        if (!file[i] || !out[i] || file_len[i] < 0 || out_cap[i] < 0 || ((uintptr_t)out[i] & (uintptr_t)(px - 1)) != 0) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+    struct DataRef {
+        int frame;  // -1: a critical chunk that is checked and not gathered
+        PngChunkRef ref;
+    };
+    struct File {
+        PngFileInfo info;
+        PngFileColors col;
+        PngAnimInfo anim;
+        std::vector<PngFrame> frames;
+        std::vector<DataRef> refs;
+        int frame0 = 0;  // its first frame in the call's list of frames
+    };
+    std::vector<File> fs((size_t)n);
+    std::vector<std::string> why((size_t)n);
+    std::vector<int> st((size_t)n, ZS_OK);
+    size_t blob = 0;
+    int64_t n_spans = 0, rows = 0, canvas_rows = 0, n_fr = 0;
+    char msg[256];
+    for (int i = 0; i < n; i++) {
+        File &F = fs[(size_t)i];
+        const uint8_t *f = (const uint8_t *)file[i];
+        std::vector<PngChunkRef> crit;
+        memset(&F.anim, 0, sizeof F.anim);
+        const bool walked = png_walk_file(f, file_len[i], &F.info, msg, sizeof msg, false, [&](const PngChunkRef &x) { crit.push_back(x); });
+        F.anim.png = F.info;
+        if (!walked || !png_file_colors(f, file_len[i], F.info, &F.col, msg, sizeof msg) ||
+            !png_walk_anim(f, file_len[i], F.info, &F.anim, msg, sizeof msg, [&](int, const PngFrame &fr) { F.frames.push_back(fr); },
+                           [&](int k, const PngChunkRef &x) { F.refs.push_back(DataRef{k, x}); })) {
+            st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = msg;
+        } else {
+            for (const PngChunkRef &x : crit)
+                if (x.type != kPngIDAT || !F.anim.default_is_frame) F.refs.push_back(DataRef{-1, x});
+            for (size_t k = 0; k < F.frames.size() && st[(size_t)i] == ZS_OK; k++) {
+                const PngFrame &fr = F.frames[k];
+                if (fr.data_bytes > kCrcMaxLen || zs_png_idat_layout(fr.width, fr.height, F.info.bits_per_pixel, F.info.interlace, nullptr, nullptr) > kCrcMaxLen) {
+                    snprintf(msg, sizeof msg, "frame %d: the frame or its data is above 2 GiB - 1 KiB", (int)k);
+                    st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = msg;
+                }
+            }
+            const bool too_big = F.info.width > (kCrcMaxLen / px) / F.info.height;  // (a canvas can be larger than every frame: the default image need not be one)
+            const int64_t canvas = too_big ? 0 : F.info.width * F.info.height * px;
+            if (st[(size_t)i] == ZS_OK && (too_big || canvas > INT64_MAX / F.anim.n_frames)) {
+                st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = "the canvases are above what a call can address";
+            } else if (st[(size_t)i] == ZS_OK && out_cap[i] < canvas * F.anim.n_frames) {
+                snprintf(msg, sizeof msg, "the %d canvases need %lld bytes, out_cap is %lld", F.anim.n_frames, (long long)(canvas * F.anim.n_frames), (long long)out_cap[i]);
+                st[(size_t)i] = ZS_BUF_ERROR, why[(size_t)i] = msg;
+            }
+        }
+        if (anim) memcpy(&anim[i], &F.anim, sizeof F.anim);
+        if (st[(size_t)i] != ZS_OK) continue;
+        for (const PngFrame &fr : F.frames) {
+            int64_t r7[kAdam7Passes];
+            (void)zs_png_idat_layout(fr.width, fr.height, F.info.bits_per_pixel, F.info.interlace, nullptr, r7);
+            for (int64_t v : r7) rows += v;
+        }
+        F.frame0 = (int)n_fr;
+        n_fr += (int64_t)F.frames.size();
+        canvas_rows += F.info.height * png_compose_row_waves(F.info.width, format);
+        blob += ((size_t)file_len[i] + 255) & ~(size_t)255;
+        n_spans += (int64_t)F.refs.size();
+    }
+    auto finish = [&](int rc) {
+        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
+        return rc;
+    };
+    auto verdict = [&]() {  // the first failing file's code and message
+        for (int i = 0; i < n; i++)
+            if (st[(size_t)i] != ZS_OK) {
+                c->err = std::string(st[(size_t)i] == ZS_BUF_ERROR ? "buffer error: file " : "data error: file ") + std::to_string(i) + ": " + why[(size_t)i];
+                return finish(st[(size_t)i]);
+            }
+        return finish(ZS_OK);
+    };
+    if (n_spans > 0x3FFFFFFF || rows > 0x7FFFFFFF || canvas_rows > 0x7FFFFFFF || n_fr > 0x3FFFFFFF) {
+        c->err = "stream error: too many chunks, frames or rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (n_spans == 0) return verdict();
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    auto all_fail = [&](int code) {
+        for (int &v : st)
+            if (v == ZS_OK) v = code;
+        return finish(code);
+    };
+    // where every frame of the call has its gathered stream, its raw scanlines and its RGBA pixels (each on a 256-byte boundary)
+    std::vector<size_t> g_at((size_t)n_fr), raw_at((size_t)n_fr), px_at((size_t)n_fr);
+    size_t gather = 0, raw_total = 0, px_total = 0;
+    for (int i = 0; i < n; i++) {
+        if (st[(size_t)i] != ZS_OK) continue;
+        const File &F = fs[(size_t)i];
+        for (size_t k = 0; k < F.frames.size(); k++) {
+            const PngFrame &fr = F.frames[k];
+            const size_t j = (size_t)F.frame0 + k;
+            g_at[j] = gather, gather += ((size_t)fr.data_bytes + 255) & ~(size_t)255;
+            raw_at[j] = raw_total, raw_total += ((size_t)(png_bits_row_bytes(fr.width, F.info.bits_per_pixel) * fr.height) + 255) & ~(size_t)255;
+            px_at[j] = px_total, px_total += ((size_t)(fr.width * fr.height * px) + 255) & ~(size_t)255;
+        }
+    }
+    Crc32Job job;
+    bool no_memory = false;
+    if (!ensure(c, c->png_gather, gather + 256) || !ensure(c, c->png_raw, raw_total + 256) || !ensure(c, c->png_frames, px_total + 256)) return all_fail(ZS_MEM_ERROR);
+    if (!crc32_begin(c, (int)n_spans, blob, &job, &no_memory)) return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    size_t k = 0, b = 0;
+    for (int i = 0; i < n; i++) {
+        if (st[(size_t)i] != ZS_OK) continue;
+        const File &F = fs[(size_t)i];
+        memcpy(job.blob + b, file[i], (size_t)file_len[i]);
+        std::vector<size_t> fill(F.frames.size(), 0);  // bytes of every frame gathered so far
+        for (const DataRef &r : F.refs) {
+            const PngChunkRef &x = r.ref;
+            const uint32_t skip = x.type == kPngfdAT ? 8 : 4;  // the type, and an fdAT's sequence number
+            uint8_t *dst = nullptr;
+            if (r.frame >= 0) {
+                dst = (uint8_t *)c->png_gather.p + g_at[(size_t)F.frame0 + (size_t)r.frame] + fill[(size_t)r.frame];
+                fill[(size_t)r.frame] += (size_t)(x.len + 4 - skip);
+            }
+            job.spans[k++] = Crc32Span{job.d_blob + b + x.at + 4, dst, nullptr, x.len + 4, 0xFFFFFFFFu, skip, 0, 0};
+        }
+        b += ((size_t)file_len[i] + 255) & ~(size_t)255;
+    }
+    if (!crc32_run(c, &job, s)) return all_fail(ZS_STREAM_ERROR);
+    const double crc_ms = job.ms;
+    k = 0;
+    struct Img {
+        int file, frame;
+    };
+    std::vector<Img> d_who;
+    std::vector<const void *> d_idat;
+    std::vector<int64_t> d_len, d_w, d_h;
+    std::vector<int> d_bits, d_il;
+    std::vector<void *> d_out;
+    for (int i = 0; i < n; i++) {
+        if (st[(size_t)i] != ZS_OK) continue;
+        const File &F = fs[(size_t)i];
+        const uint8_t *f = (const uint8_t *)file[i];
+        for (const DataRef &r : F.refs) {
+            const PngChunkRef &x = r.ref;
+            const uint32_t got = job.crc[k++];
+            if (st[(size_t)i] == ZS_OK && got != png_be32(f + x.at + 8 + x.len)) {
+                if (r.frame >= 0) snprintf(msg, sizeof msg, "frame %d: CRC error in %.4s chunk at offset %lld", r.frame, (const char *)f + x.at + 4, (long long)x.at);
+                else snprintf(msg, sizeof msg, "CRC error in %.4s chunk at offset %lld", (const char *)f + x.at + 4, (long long)x.at);
+                st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = msg;
+            }
+        }
+        if (st[(size_t)i] != ZS_OK) continue;
+        for (size_t q = 0; q < F.frames.size(); q++) {
+            const PngFrame &fr = F.frames[q];
+            const size_t j = (size_t)F.frame0 + q;
+            d_who.push_back(Img{i, (int)q}), d_idat.push_back((const uint8_t *)c->png_gather.p + g_at[j]), d_len.push_back(fr.data_bytes);
+            d_w.push_back(fr.width), d_h.push_back(fr.height), d_bits.push_back(F.info.bits_per_pixel), d_il.push_back(F.info.interlace);
+            d_out.push_back((uint8_t *)c->png_raw.p + raw_at[j]);
+        }
+    }
+    if (!d_who.empty()) {
+        std::vector<int> dst_st(d_who.size(), ZS_STREAM_ERROR);
+        const int drc = zs_png_decode_batch_device(c, (int)d_who.size(), d_idat.data(), d_len.data(), d_w.data(), d_h.data(), d_bits.data(), d_il.data(),
+                                                   d_out.data(), dst_st.data(), (void *)s);
+        if (drc != ZS_OK && drc != ZS_DATA_ERROR) return all_fail(drc);
+        const std::string inner = c->err;
+        bool first = true;
+        for (size_t j = 0; j < d_who.size(); j++) {
+            if (dst_st[j] == ZS_OK) continue;
+            // the decode call's message names its first failing image by its place in that call: keep the reason
+            std::string reason = "the frame's stream does not decode";
+            if (first) {
+                const size_t colon = inner.find(": ", inner.find("image "));
+                reason = inner.find("image ") != std::string::npos && colon != std::string::npos ? inner.substr(colon + 2) : inner;
+                first = false;
+            }
+            if (st[(size_t)d_who[j].file] != ZS_OK) continue;  // (the file's first failing frame stays)
+            st[(size_t)d_who[j].file] = dst_st[j];
+            why[(size_t)d_who[j].file] = "frame " + std::to_string(d_who[j].frame) + ": " + reason;
+        }
+    }
+    double expand_ms = 0, compose_ms = 0;
+    PngExpandJob xjob;
+    PngComposeJob mjob;
+    for (int i = 0; i < n; i++) {
+        if (st[(size_t)i] != ZS_OK) continue;
+        const File &F = fs[(size_t)i];
+        mjob.add(out[i], F.info.width, F.info.height, (int)F.frames.size(), format);
+        for (size_t q = 0; q < F.frames.size(); q++) {
+            const PngFrame &fr = F.frames[q];
+            const size_t j = (size_t)F.frame0 + q;
+            uint8_t *pixels = (uint8_t *)c->png_frames.p + px_at[j];
+            xjob.add((const uint8_t *)c->png_raw.p + raw_at[j], pixels, fr.width, fr.height, F.info.bit_depth, F.info.color_type, format, F.col.plte,
+                     F.col.plte_entries, F.col.trns, F.col.trns_len);
+            mjob.add_frame(pixels, fr);
+        }
+    }
+    if (!mjob.anim.empty()) {
+        if (!png_expand_run(c, xjob, format, s, &no_memory) || !png_compose_run(c, mjob, format, s, &no_memory))
+            return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+        if (!hip_stream && hipStreamSynchronize(s) != hipSuccess) return all_fail(ZS_STREAM_ERROR);
+        expand_ms = xjob.ms, compose_ms = mjob.ms;
+    }
+    if (c->profiling) c->stage_ms[kStCrc32] = crc_ms, c->stage_ms[kStPngExpand] = expand_ms, c->stage_ms[kStPngCompose] = compose_ms;
+    return verdict();
 }
 
 // ------------------------------------------------------------------ multi-GPU batch entry points

@@ -727,5 +727,151 @@ inline void png_choose_format(bool opaque, bool gray, bool low8, int sample_dept
     *color_type = ct, *bit_depth = bd;
 }
 
+// ---- composing the frames of an animation (KM, zs_png.hip, and its host model tests/cpp/test_png_compose.cpp) ----
+// Frame k of an animated PNG is a rectangle of RGBA pixels that is drawn onto a canvas; canvas k is what a viewer shows
+// while frame k is up (APNG specification 1.0, "fcTL").  The canvas starts as transparent black.  A pixel is held as
+// png_expand_pack makes it: RGBA8 in the low 32 bits (R lowest), RGBA16 as four uint16, R lowest.
+//   blend SOURCE: the region takes the frame's pixels.
+//   blend OVER, per pixel, M = 255 or 65535, foreground (f, fa), canvas (b, ba): fa == 0 leaves the canvas alone;
+//     fa == M or ba == 0 copies the frame's pixel; otherwise u = fa * M, v = (M - fa) * ba, al = u + v, every colour channel
+//     becomes (f * u + b * v) / al and alpha al / M, both floor divisions (64-bit products at RGBA16).  This is the integer
+//     arithmetic of the specification's sample code.
+//   dispose, after canvas k is written: NONE keeps the canvas; BACKGROUND sets the region to transparent black; PREVIOUS
+//     puts back what the region held before frame k was drawn, and acts as BACKGROUND on frame 0.
+constexpr int kPngComposeGroup = 16;  // canvas bytes a lane carries: 4 pixels of RGBA8, 2 of RGBA16
+
+struct PngComposeFrame {
+    const uint8_t *px;  // height rows of width * png_expand_bytes(format) bytes, aligned to a pixel
+    int32_t x, y, width, height;  // the region: inside the canvas
+    int32_t dispose, blend;
+};
+struct PngComposeAnim {
+    uint8_t *out;  // n_frames canvases of height rows of width * png_expand_bytes(format) bytes, aligned to a pixel
+    int32_t width, height;
+    int32_t frame0, n_frames;  // its frames in the call's list of frames
+};
+
+// waves that share a canvas row: one per 64 groups
+ZS_HD int64_t png_compose_row_waves(int64_t width, int format) {
+    const int64_t n = kPngComposeGroup / png_expand_bytes(format), groups = (width + n - 1) / n;
+    return (groups + 63) / 64;
+}
+
+template <int F>
+ZS_HD uint32_t png_px_channel(uint64_t px, int k) {
+    if constexpr (F == ZS_PNG_FMT_RGBA8) return (uint32_t)(px >> (8 * k)) & 255u;
+    else return (uint32_t)(px >> (16 * k)) & 65535u;
+}
+template <int F>
+ZS_HD uint64_t png_blend_over(uint64_t fg, uint64_t bg) {
+    constexpr uint32_t M = F == ZS_PNG_FMT_RGBA8 ? 255u : 65535u;
+    const uint32_t fa = png_px_channel<F>(fg, 3), ba = png_px_channel<F>(bg, 3);
+    if (fa == 0) return bg;
+    if (fa == M || ba == 0) return fg;
+    const uint32_t u = fa * M, v = (M - fa) * ba, al = u + v;  // (al <= M * M < 2^32)
+    uint32_t c[3];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 3; k++) {
+        if constexpr (F == ZS_PNG_FMT_RGBA8) c[k] = (png_px_channel<F>(fg, k) * u + png_px_channel<F>(bg, k) * v) / al;
+        else c[k] = (uint32_t)(((uint64_t)png_px_channel<F>(fg, k) * u + (uint64_t)png_px_channel<F>(bg, k) * v) / al);
+    }
+    return png_expand_pack<F>(c[0], c[1], c[2], al / M);
+}
+template <int F>
+ZS_HD uint64_t png_compose_blend(int blend, uint64_t fg, uint64_t bg) {
+    return blend == 0 ? fg : png_blend_over<F>(fg, bg);
+}
+// what a pixel of frame k's region holds once the frame's time is up: `shown` is canvas k's value, `before` the value in
+// front of the frame's blend
+ZS_HD uint64_t png_compose_dispose(int dispose, int k, uint64_t shown, uint64_t before) {
+    return dispose == 0 ? shown : dispose == 2 && k > 0 ? before : 0;
+}
+template <int F>
+ZS_HD uint64_t png_compose_load(const uint8_t *p) {
+    if constexpr (F == ZS_PNG_FMT_RGBA8) {
+        uint32_t v;
+        __builtin_memcpy(&v, __builtin_assume_aligned(p, 4), 4);
+        return v;
+    } else {
+        uint64_t v;
+        __builtin_memcpy(&v, __builtin_assume_aligned(p, 8), 8);
+        return v;
+    }
+}
+
+// Pixels [x0, x0 + N) of row y (N = 16 / pixel size; the part of them inside the row) in all of the animation's canvases:
+// what one lane does.  The pixels' current values, and their values in front of the frame at hand, stay in
+// registers through the frames; a frame's pixels are read only where (x, y) falls into its region, the row tested first
+// (uniform over a wave); every canvas's pixels are stored once, as one 16-byte store where the group is whole and its
+// address in that canvas is 16-aligned, pixel by pixel elsewhere.  No canvas byte is read, none is written twice.
+template <int F>
+ZS_HD void png_compose_group(const PngComposeAnim &a, const PngComposeFrame *frames, int64_t y, int64_t x0) {
+    constexpr int P = png_expand_bytes(F), N = kPngComposeGroup / P;
+    const int64_t rb = (int64_t)a.width * P, canvas = rb * a.height;
+    const bool whole = x0 + N <= a.width;
+    uint64_t cur[N], before[N];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < N; j++) cur[j] = 0, before[j] = 0;
+    uint8_t *dst = a.out + y * rb + x0 * P;
+    for (int k = 0; k < a.n_frames; k++, dst += canvas) {
+        const PngComposeFrame fr = frames[a.frame0 + k];  // (a copy: the stores below do not make the compiler read it again)
+        const bool row_in = y >= fr.y && y < (int64_t)fr.y + fr.height;
+        bool in[N];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < N; j++) in[j] = false;
+        if (row_in) {
+            const int64_t fx = x0 - fr.x;  // the group's first column in the frame
+            const uint8_t *src = fr.px + ((y - fr.y) * (int64_t)fr.width + fx) * P;
+            uint64_t fg[N];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int j = 0; j < N; j++) in[j] = fx + j >= 0 && fx + j < fr.width, fg[j] = 0;
+            if (fx >= 0 && fx + N <= fr.width && ((uint64_t)(uintptr_t)src & (kPngComposeGroup - 1)) == 0) {
+                uint64_t v[2];
+                __builtin_memcpy(v, __builtin_assume_aligned(src, kPngComposeGroup), kPngComposeGroup);
+                if constexpr (F == ZS_PNG_FMT_RGBA8) fg[0] = v[0] & 0xFFFFFFFFu, fg[1] = v[0] >> 32, fg[2] = v[1] & 0xFFFFFFFFu, fg[3] = v[1] >> 32;
+                else fg[0] = v[0], fg[1] = v[1];
+            } else {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+                for (int j = 0; j < N; j++)
+                    if (in[j]) fg[j] = png_compose_load<F>(src + j * P);
+            }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int j = 0; j < N; j++)
+                if (in[j]) before[j] = cur[j], cur[j] = png_compose_blend<F>(fr.blend, fg[j], cur[j]);
+        }
+        if (whole && ((uint64_t)(uintptr_t)dst & (kPngComposeGroup - 1)) == 0) {
+            uint64_t v[2];
+            if constexpr (F == ZS_PNG_FMT_RGBA8) v[0] = cur[0] | cur[1] << 32, v[1] = cur[2] | cur[3] << 32;
+            else v[0] = cur[0], v[1] = cur[1];
+            __builtin_memcpy(__builtin_assume_aligned(dst, kPngComposeGroup), v, kPngComposeGroup);
+        } else {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int j = 0; j < N; j++)
+                if (x0 + j < a.width) __builtin_memcpy(__builtin_assume_aligned(dst + j * P, P), &cur[j], P);
+        }
+        if (row_in) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int j = 0; j < N; j++)
+                if (in[j]) cur[j] = png_compose_dispose(fr.dispose, k, cur[j], before[j]);
+        }
+    }
+}
+
 
 }  // namespace zs

@@ -1,4 +1,4 @@
-// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip); KA, KS, KX, KG and KV behind it.  What inflate leaves for
+// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip); KA, KS, KX, KG, KV and KM behind it.  What inflate leaves for
 // an IDAT payload is, per row, a filter-type byte and the filtered bytes; reconstruction reads reconstructed neighbours
 // (left, above, above-left), so it is serial along a row and across rows.  Two kernels:
 //   zs_png_scan_kernel      one workgroup per image over its type bytes: the first invalid one, and the segments
@@ -493,6 +493,31 @@ __global__ __launch_bounds__(256) void zs_png_survey_merge_kernel(const int32_t 
     if (mask) atomicOr(&s_mask, mask);
     __syncthreads();
     png_survey_emit(s_slots, &s_count, &s_pos, s_mask, &out[i]);
+}
+
+// KM: the frames of animations composed into canvases (zs_png.h png_compose_group), one launch a call, shaped like KX.  The
+// grid is the flat list of all animations' canvas rows, every row cut into stretches of 64 groups (256 pixels of RGBA8, 128
+// of RGBA16: png_compose_row_waves), a wave per stretch and four waves a workgroup: a lane takes four (RGBA16: two) pixels of
+// the row.  A lane carries its pixels through frames 0 .. F-1 in registers -- the current value and the value PREVIOUS puts
+// back -- reads a frame's pixels only inside the frame's region (the row test is uniform over the wave; the frame's
+// descriptor is indexed by the uniform frame number and comes through scalar loads) and stores its pixels into every canvas
+// once: 16 bytes where the address in that canvas is 16-aligned, pixel by pixel elsewhere.  The canvases are never read.  No
+// atomics, no LDS, no traffic between waves: no output byte has two writers.  (A wave per whole row, looping over the
+// stretches, left one 1024 x 1024 animation with one wave per SIMD and every frame's load latency in the open: DESIGN.md.)
+constexpr int kComposeWavesPerWg = 4;
+
+template <int F>
+__global__ __launch_bounds__(64 * kComposeWavesPerWg) void zs_png_compose_kernel(const PngComposeAnim *__restrict__ anims, const int32_t *__restrict__ wave_off,
+                                                                                 const PngComposeFrame *__restrict__ frames, int n, int64_t wave0) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    const int64_t t = wave0 + (int64_t)blockIdx.x * kComposeWavesPerWg + w;
+    if (t >= (int64_t)wave_off[n]) return;
+    const int i = __builtin_amdgcn_readfirstlane(png_row_image(wave_off, n, t));  // (the same in every lane: the descriptors come through scalar loads)
+    const PngComposeAnim a = anims[i];
+    constexpr int N = kPngComposeGroup / png_expand_bytes(F);
+    const uint32_t local = (uint32_t)(t - wave_off[i]), per_row = (uint32_t)png_compose_row_waves(a.width, F);
+    const int64_t y = local / per_row, g = (int64_t)(local % per_row) * 64 + lane;
+    if (g * N < a.width) png_compose_group<F>(a, frames, y, g * N);
 }
 
 }  // namespace zs
