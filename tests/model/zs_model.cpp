@@ -318,6 +318,7 @@ static void parse_fast_sweep(Model &m, int64_t &p_out, int &kdone_out, int64_t &
             st.k_fired++;
             m.events.push_back(t);
             st.preins = t + 1;
+            if (fs_event_nil_edge(t, m.rev[(size_t)st.k_fired - 1].base, m.rev[(size_t)st.k_fired].base)) st.nil_pos = t;
             m.ins[(size_t)t + 1] = 1;
             if (m.link[(size_t)t + 1] == 1) {
                 st.dead_pos = t, st.only_pos = t + 1;
@@ -333,7 +334,7 @@ static void parse_fast_sweep(Model &m, int64_t &p_out, int &kdone_out, int64_t &
         for (int64_t q = st.w0; q < hi; q++) {
             // a search whose first candidate lies below w0 looks at final bits only: its result stays (kFsExact), and the
             // sweeps behind it do not search the position again
-            if (q < st.ev_end && (rprev[(size_t)q] & kFsExact) && q != st.dead_pos && q != st.only_pos) {
+            if (q < st.ev_end && (rprev[(size_t)q] & kFsExact) && q != st.dead_pos && q != st.only_pos && q != st.nil_pos) {
                 rcur[(size_t)(q - g0)] = rprev[(size_t)q];
                 skipped++;
                 continue;
@@ -341,7 +342,7 @@ static void parse_fast_sweep(Model &m, int64_t &p_out, int &kdone_out, int64_t &
             const int l0 = m.link[(size_t)q];
             const bool exact = l0 == 0 || q - l0 < st.w0;
             const long v0 = acc.visits;
-            rcur[(size_t)(q - g0)] = fs_search(acc, q, m.lv.chain, m.lv.nice, !search || q == st.dead_pos, search && q == st.only_pos) | (exact ? kFsExact : 0u);
+            rcur[(size_t)(q - g0)] = fs_search(acc, q, m.lv.chain, m.lv.nice, !search || q == st.dead_pos, search && q == st.only_pos, q == st.nil_pos) | (exact ? kFsExact : 0u);
             searched++;
             if (walk_hist.empty()) walk_hist.assign(4 * 64, 0);
             {
@@ -535,6 +536,7 @@ static void parse_fast_rounds(Model &m, int64_t &p_out, int &kdone_out, int64_t 
                     const int64_t t = st.w0;
                     st.k_fired++;
                     st.preins = preins = t + 1;
+                    if (fs_event_nil_edge(t, m.rev[(size_t)st.k_fired - 1].base, m.rev[(size_t)st.k_fired].base)) st.nil_pos = t;
                     ins[(size_t)t + 1] = 1;
                     if (lnk[(size_t)t + 1] == 1) {
                         st.dead_pos = t, st.only_pos = t + 1;
@@ -548,13 +550,13 @@ static void parse_fast_rounds(Model &m, int64_t &p_out, int &kdone_out, int64_t 
                 int64_t hi = std::min<int64_t>(g0 + W, c.b_hi);
                 if (st.trigger >= 0 && st.trigger < hi) hi = st.trigger;
                 for (int64_t q = st.w0; q < hi; q++) {
-                    if (q < st.ev_end && (rprev[(size_t)q] & kFsExact) && q != st.dead_pos && q != st.only_pos) {
+                    if (q < st.ev_end && (rprev[(size_t)q] & kFsExact) && q != st.dead_pos && q != st.only_pos && q != st.nil_pos) {
                         rcur[(size_t)(q - g0)] = rprev[(size_t)q];
                         continue;
                     }
                     const int l0 = lnk[(size_t)q];
                     const bool exact = l0 == 0 || q - l0 < st.w0;
-                    rcur[(size_t)(q - g0)] = fs_search(acc, q, m.lv.chain, m.lv.nice, !search || q == st.dead_pos, search && q == st.only_pos) | (exact ? kFsExact : 0u);
+                    rcur[(size_t)(q - g0)] = fs_search(acc, q, m.lv.chain, m.lv.nice, !search || q == st.dead_pos, search && q == st.only_pos, q == st.nil_pos) | (exact ? kFsExact : 0u);
                 }
                 int64_t t = st.w0, tstar = -1, last_top = -1;
                 std::vector<int64_t> tops;

@@ -52,9 +52,11 @@ ZS_HD int fs_adv(uint32_t r) { return fs_len(r) >= kMinMatch ? fs_len(r) : 1; }
 //                (fs_compress) --, 0 = none within reach
 //   acc.ins(c):  c is in the set (final below the sweep's first loop-top, the guess from there on)
 //   acc.lcp(q, c): common prefix length of the strings at q and c, at most kMaxMatch
-// dead: the search does not happen (refill quirk); only_prev: the search sees just q - 1 (equal-bucket refill).
+// dead: the search does not happen (refill quirk); only_prev: the search sees just q - 1 (equal-bucket refill); nil_edge: q is
+// the loop-top of a read event that slid the window while standing exactly at the slide threshold (fs_event_nil_edge): a first
+// candidate at distance MAX_DIST is window index 0 now, i.e. NIL, so every candidate has to be nearer.
 template <class Acc>
-ZS_HD uint32_t fs_search(const Acc &acc, int64_t q, int max_chain, int nice, bool dead, bool only_prev) {
+ZS_HD uint32_t fs_search(const Acc &acc, int64_t q, int max_chain, int nice, bool dead, bool only_prev, bool nil_edge = false) {
     if (dead) return kFsNone;
     if (only_prev) {
         const int len = acc.lcp(q, q - 1);
@@ -67,7 +69,7 @@ ZS_HD uint32_t fs_search(const Acc &acc, int64_t q, int max_chain, int nice, boo
         if (!l) break;
         c -= l;
         const int64_t d = q - c;
-        if (c < 1 || (found == 0 ? d > kMaxDist : d >= kMaxDist)) break;  // hash_head: <= MAX_DIST; later: cur_match > limit
+        if (c < 1 || (found == 0 && !nil_edge ? d > kMaxDist : d >= kMaxDist)) break;  // hash_head: <= MAX_DIST; later: cur_match > limit
         if (!acc.ins(c)) continue;
         found++;
         const int len = acc.lcp(q, c);
@@ -94,6 +96,14 @@ ZS_HD int fs_compress(const Acc &acc, int64_t c) {
     }
 }
 
+// A read event at loop-top t that slides the window (the base before and after it differ) with t exactly at the slide threshold
+// -- only the event of a Write that ends 65535 bytes into the window can be there, build_read_events -- leaves t at window index
+// MAX_DIST: SlideHash has turned the position at that distance into 0, "none" (Deflate.cs:967-1019; chunk_special_prefix's
+// nil_edge is the same rule for levels 4-9).
+ZS_HD bool fs_event_nil_edge(int64_t t, int64_t base_before, int64_t base_after) {
+    return base_after != base_before && t - base_after == kMaxDist;
+}
+
 // What a loop-top puts into the set: itself, and the inside of its match when that is short (Deflate.Fast.cs:81-104).
 ZS_HD int fs_inserted_span(uint32_t r, int max_lazy) {
     const int len = fs_len(r);
@@ -110,6 +120,7 @@ struct FsState {
     int64_t dead_pos;  // position whose search is dead by the last event, -1
     int64_t only_pos;  // position whose search sees only its predecessor (equal-bucket event), -1
     int64_t ev_end;    // positions below this were searched by the sweep before (their results are there to compare with)
+    int64_t nil_pos = -1;  // the loop-top of an event that slid at the threshold (fs_event_nil_edge), -1
 };
 
 // ---- Rounds over the chunks of a stream (round 4; zs_fast_sweep_kernel in its chunk form, tests/model mode "frounds").

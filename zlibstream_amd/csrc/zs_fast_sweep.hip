@@ -224,7 +224,7 @@ __global__ __launch_bounds__(NT) void zs_fast_sweep_kernel(const StreamDesc *sd,
     const bool aligned = (((uintptr_t)in) & 15) == 0;
     // the state that goes from sweep to sweep, held by every thread (all of it is computed from shared values); positions are
     // below 2^31 (StreamDesc::n)
-    int w0 = E0, nsyms = 0, preins = -1, dead_pos = -1, only_pos = -1, ev_end = 0;
+    int w0 = E0, nsyms = 0, preins = -1, dead_pos = -1, only_pos = -1, nil_pos = -1, ev_end = 0;
     int k_fired = CH ? ck.kfired0 : 0, next_cut = CH ? 0x7FFFFFFF : kBlockSyms - 1;  // (the symbol with this index ends a block, Deflate.cs:910-948; a chunk's symbols get their places later)
     // read event k fires at the first loop-top at or behind the data end before it - 261; the stream's events are its segment table
     // (one Write: window ends; several: Write ends too)
@@ -358,6 +358,7 @@ __global__ __launch_bounds__(NT) void zs_fast_sweep_kernel(const StreamDesc *sd,
             __syncthreads();
             k_fired++;
             preins = w0 + 1;
+            if (fs_event_nil_edge(w0, s.seg_base[k_fired - 1], s.seg_base[k_fired])) nil_pos = w0;
             if (same) dead_pos = w0, only_pos = w0 + 1;
             else dead_pos = w0 + 1, only_pos = -1;
             preins_ev = w0 + 1;
@@ -394,13 +395,13 @@ __global__ __launch_bounds__(NT) void zs_fast_sweep_kernel(const StreamDesc *sd,
         const int slot = q & (RING - 1);
         const uint32_t old = ring[slot];
         const bool dead = !search || q == dead_pos, only_prev = search && q == only_pos;
-        const bool known = q < ev_end && (old & kFsExact) != 0 && !dead && !only_prev;
+        const bool known = q < ev_end && (old & kFsExact) != 0 && !dead && !only_prev && q != nil_pos;
         int best = 2, bdist = 0;
         uint32_t exact = (dead || only_prev) ? kFsExact : 0u;
         {
             const uint64_t scan8 = lds_u64(wb, qi);
             bool walking = act && !dead && !known;
-            int c = qi, rem = chain, maxd = kMaxDist;  // hash_head: <= MAX_DIST; later: cur_match > limit
+            int c = qi, rem = chain, maxd = q == nil_pos ? kMaxDist - 1 : kMaxDist;  // hash_head: <= MAX_DIST (nil_pos: below it); later: cur_match > limit
             if (qi - (int)(wl[qi] & 0x7FFFu) < gi + w0r) exact = kFsExact;  // (no link: 0x7FFF, below anything)
             uint32_t l = gl[q & (RING - 1)];
             if (only_prev) l = 1, rem = 1;                 // the search sees only q - 1 (equal-bucket refill), whatever the set says
