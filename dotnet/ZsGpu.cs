@@ -176,6 +176,19 @@ namespace SixLabors.ZlibStream
                                                                               long* width, long* height, int format, IntPtr* output, IntPtr hipStream);
         [DllImport(Lib)] public static extern int zs_png_decode_anim_batch(IntPtr ctx, int n, IntPtr* file, long* fileLen, int format, IntPtr* output,
                                                                            long* outCap, PngAnim* anim, int* status, IntPtr hipStream);
+        // animated PNG on the way out: canvases -> the frames' regions; rectangles -> tight rows; canvases -> files
+        [DllImport(Lib)] public static extern int zs_png_diff_batch_device(IntPtr ctx, int n, IntPtr* canvases, int* frameCount, long* width, long* height,
+                                                                           int format, PngFrame** framesOut, IntPtr hipStream);
+        [DllImport(Lib)] public static extern int zs_png_crop_batch_device(IntPtr ctx, int n, IntPtr* input, long* inWidth, long* x, long* y, long* width,
+                                                                           long* height, int pixelBytes, IntPtr* output, IntPtr hipStream);
+        [DllImport(Lib)] public static extern long zs_png_anim_bound(long width, long height, int frameCount, int format, int interlace, long idatChunkBytes,
+                                                                     long extraLen);
+        [DllImport(Lib)] public static extern int zs_png_encode_anim_batch_device(IntPtr ctx, int n, IntPtr* canvases, int* frameCount, long* width, long* height,
+                                                                                  int format, int** delayNum, int** delayDen, int* playCount, int* filter,
+                                                                                  int* interlace, IntPtr* extra, long* extraLen, long rowsPerWrite,
+                                                                                  long idatChunkBytes, IntPtr* output, long* outCap, long* outLen, int* status,
+                                                                                  PngFrame** framesOut, int* colorTypeOut, int* bitDepthOut, int level,
+                                                                                  int strategy, int hashVariant, IntPtr hipStream);
         // bytes fed behind a stream's trailer before its end was seen (the engine looks for the end now and then)
         [DllImport(Lib)] public static extern long zs_inflate_surplus(IntPtr s, IntPtr* p);
     }

@@ -582,6 +582,83 @@ ZS_API int zs_png_compose_batch_device(zs_ctx *ctx, int n, const void *const *co
 ZS_API int zs_png_decode_anim_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, int format,
                                     void *const *out, const int64_t *out_cap, zs_png_anim *anim, int *status, void *hip_stream);
 
+/* The frame diff, n animations a call (KD): what an APNG writer needs to know about canvases that lie
+ * in device memory.  canvases[i]: DEVICE pointer to n_frames[i] canvases of height[i] * width[i] * 4 (ZS_PNG_RGBA8) or * 8
+ * (ZS_PNG_RGBA16) bytes back to back, aligned to 4 or 8 -- the layout zs_png_compose_batch_device writes into out[i].
+ * frames_out[i]: HOST array of n_frames[i] entries, of which x, y, width and height are written and dispose_op / blend_op
+ * set to 0 / 0 (NONE / SOURCE); the delay and data fields are left alone.  The rule is exact:
+ *   frame 0 is the whole canvas; frame f >= 1 is the smallest rectangle that holds every pixel whose bytes in canvas f differ
+ *   from canvas f - 1 -- all four channels count, a colour change under alpha 0 counts, at RGBA16 the low byte of a sample
+ *   counts; where no pixel differs, the 1 x 1 rectangle at (0, 0): APNG has no empty frame.
+ * Drawing frame f's rectangle of canvas f with blend SOURCE over canvas f - 1 under dispose NONE gives canvas f byte for byte.
+ * Two launches: a wave per 64 groups of 16 bytes of a canvas row carries its groups through the canvases in registers -- every
+ * canvas is read once -- and writes one record per frame; one workgroup per (animation, frame) folds the records.  No atomics:
+ * the results are the same on every run.  An animation of one frame launches nothing for itself.
+ * Returns ZS_OK, ZS_MEM_ERROR (the descriptors or records do not fit) or, before any device work, ZS_STREAM_ERROR: null
+ * context, n < 0, null arrays or pointers, n_frames[i] < 1, width or height outside 1 .. 2^31 - 1, a bad format, a misaligned
+ * pointer, more than 2^31 - 1 canvas rows (a row counted once per 1024 bytes of it) or frames in one call.  n == 0 is ZS_OK.
+ * Ordered on hip_stream (NULL: the context's); the call waits for the stream twice, for the upload of its descriptors and for
+ * the rectangles.  zs_ctx_stage_ms shows both launches as "png_diff". */
+ZS_API int zs_png_diff_batch_device(zs_ctx *ctx, int n, const void *const *canvases, const int *n_frames, const int64_t *width,
+                                    const int64_t *height, int format, zs_png_frame *const *frames_out, void *hip_stream);
+
+/* Rectangles of images as tight rows, n a call, one launch over the flat list of all output rows.  in[i]: DEVICE pointer to an
+ * image whose rows are in_width[i] * pixel_bytes bytes; the rectangle of width[i] x height[i] pixels at (x[i], y[i]) goes to
+ * out[i] (DEVICE) as height[i] rows of width[i] * pixel_bytes bytes.  pixel_bytes is 4 or 8; in[i] and out[i] are aligned to it
+ * and do not overlap.  The image's height is not an argument: the caller vouches for y + height.  Arrays are HOST arrays.
+ * Errors, ordering and the single wait (for the descriptors' upload) as for zs_png_expand_batch_device; in addition x or y
+ * below 0 and x + width > in_width are ZS_STREAM_ERROR.  n == 0 is ZS_OK.  zs_ctx_stage_ms shows the launch as "png_crop". */
+ZS_API int zs_png_crop_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *in_width, const int64_t *x,
+                                    const int64_t *y, const int64_t *width, const int64_t *height, int pixel_bytes, void *const *out,
+                                    void *hip_stream);
+
+/* Room that zs_png_encode_anim_batch_device never exceeds for one animation, pure host code: every frame taken as the whole
+ * canvas at 32 (ZS_PNG_RGBA8) or 64 bits a pixel -- zs_deflate_bound(zs_png_idat_layout(width, height, 32 or 64, interlace, 0,
+ * 0)) per frame, 12 bytes per IDAT and 16 per fdAT chunk of at most idat_chunk_bytes stream bytes (0: one chunk), 38 per
+ * fcTL, 20 for acTL, 1048 for PLTE + tRNS, extra_len, signature, IHDR and IEND.  For n_frames == 1 it is not below
+ * zs_png_file_bound(..., extra_len + 1048) of the still encoder.  -1 for arguments the encoder refuses: width or height
+ * outside 1 .. 2^31 - 1, n_frames < 1, a bad format or interlace value, idat_chunk_bytes outside 0 .. 2^31 - 1, extra_len < 0,
+ * a canvas above 2 GiB - 1 KiB once filtered, one chunk asked for a stream it cannot hold. */
+ZS_API int64_t zs_png_anim_bound(int64_t width, int64_t height, int n_frames, int format, int interlace, int64_t idat_chunk_bytes,
+                                 int64_t extra_len);
+
+/* Canvases to animated PNG files, n animations a call: the inverse of zs_png_decode_anim_batch, which returns the canvases
+ * byte for byte.  canvases, n_frames, width, height, format: as for zs_png_diff_batch_device.  delay_num / delay_den: HOST
+ * arrays of HOST arrays, n_frames[i] values 0 .. 65535 each, written into the fcTLs as given.  n_plays (HOST): 0 .. 2^31 - 1
+ * per animation.  filter, interlace (may be NULL), extra, extra_len, rows_per_write, idat_chunk_bytes, out, out_cap, out_len,
+ * status, color_type_out, bit_depth_out, level, strategy, hash_variant: as for zs_png_encode_rgba_batch_device, per animation;
+ * filter[i] and interlace[i] apply to each of its frames, and a frame is interlaced as an image of its region's size.
+ * frames_out (may be NULL): HOST array of HOST arrays, n_frames[i] entries that receive what zs_png_anim_info would report for
+ * the file: region, the caller's delays, dispose 0, blend 0, data_bytes, n_chunks.  Steps:
+ *   the survey over an animation's canvases as ONE image of n_frames * height rows, and zs_png_choose_format once per
+ *   animation: all frames share IHDR's pair and the file's PLTE / tRNS, framed on the host as by the still encoder;
+ *   the diff (above); the crop of every frame f >= 1 into a buffer the context owns (frame 0, and a region as wide as the
+ *   canvas, are read in place); the pack over all frames of all animations as images of their regions' sizes with the
+ *   animation's palette -- it holds every colour of every canvas, so a pixel without an entry is an internal error, reported
+ *   as ZS_STREAM_ERROR for that animation with a message that says so; zs_png_idat_interlace_batch_device over all frames;
+ *   the layout: signature, IHDR (the canvas), extra[i], PLTE, tRNS, acTL (n_frames, n_plays), fcTL 0 (the whole canvas at
+ *   (0, 0)), frame 0's IDAT chunks, then per frame an fcTL and its fdAT chunks of at most idat_chunk_bytes stream bytes, fcTL
+ *   and fdAT numbered by one counter from 0, IEND.  Every fcTL has dispose NONE and blend SOURCE.  acTL, fcTL and IEND are
+ *   host bytes with host CRCs; IDAT and fdAT are framed on the device in one CRC-32 launch.
+ * n_frames[i] == 1 writes no acTL and no fcTL: the file is zs_png_encode_rgba_batch_device's for the one canvas, byte for
+ * byte.  zs_png_anim_bound is always enough room; a short out_cap[i] is ZS_BUF_ERROR for that animation only (out_len[i] says
+ * what it needs, nothing is written for it); a failing deflate costs its animation only.  Argument errors are
+ * ZS_STREAM_ERROR before any device work, status and out_len untouched: those of zs_png_diff_batch_device and
+ * zs_png_encode_rgba_batch_device, a delay outside 0 .. 65535, a negative n_plays, n_frames * height above 2^31 - 1, a canvas
+ * above 2 GiB - 1 KiB once filtered at 32 or 64 bits.  Waits: those of zs_png_encode_rgba_batch_device on the frames, and
+ * three more -- two for the diff, one for the crop's descriptors (none where no region is narrower than its canvas) -- and
+ * one for the pack's counts where an animation has a palette.  zs_ctx_stage_ms shows "png_survey", "png_diff", "png_crop",
+ * "png_pack", "crc32_frame" and the deflate stages.
+ * Not done: blend OVER or dispose BACKGROUND / PREVIOUS chosen to shrink files, merging equal
+ * consecutive frames into one longer delay, a default image that is not a frame, a tRNS colour key, anything lossy. */
+ZS_API int zs_png_encode_anim_batch_device(zs_ctx *ctx, int n, const void *const *canvases, const int *n_frames,
+                                           const int64_t *width, const int64_t *height, int format, const int *const *delay_num,
+                                           const int *const *delay_den, const int *n_plays, const int *filter, const int *interlace,
+                                           const void *const *extra, const int64_t *extra_len, int64_t rows_per_write,
+                                           int64_t idat_chunk_bytes, void *const *out, const int64_t *out_cap, int64_t *out_len,
+                                           int *status, zs_png_frame *const *frames_out, int *color_type_out, int *bit_depth_out,
+                                           int level, int strategy, int hash_variant, void *hip_stream);
+
 /* Stage timing of the last *_batch_device call, measured with hipEvents on
  * the stream the kernels ran on.  Enable before the call. */
 /* Counters of a context for tests and measurements (-1: no such counter): "fast_rounds" -- rounds the last call's DeflateFast took

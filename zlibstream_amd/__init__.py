@@ -14,4 +14,5 @@ from .api import (CompressionLevel, CompressionState, CompressionStrategy, Engin
                   png_adam7_split_batch_device, png_idat_interlace_batch_device, png_encode_interlace_batch_device,
                   png_pack_batch_device, png_survey_batch_device, png_choose_format, png_encode_rgba_batch_device,
                   png_anim_info, png_compose_batch_device, png_decode_anim_batch, PNG_DISPOSE_NONE, PNG_DISPOSE_BACKGROUND,
-                  PNG_DISPOSE_PREVIOUS, PNG_BLEND_SOURCE, PNG_BLEND_OVER)
+                  PNG_DISPOSE_PREVIOUS, PNG_BLEND_SOURCE, PNG_BLEND_OVER, png_diff_batch_device, png_crop_batch_device,
+                  png_anim_bound, png_encode_anim_batch_device)

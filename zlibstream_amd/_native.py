@@ -23,6 +23,7 @@ SYMBOLS = [
     "zs_png_adam7_split_batch_device", "zs_png_idat_interlace_batch_device", "zs_png_encode_interlace_batch_device",
     "zs_png_pack_batch_device", "zs_png_survey_batch_device", "zs_png_choose_format", "zs_png_encode_rgba_batch_device",
     "zs_png_anim_info", "zs_png_compose_batch_device", "zs_png_decode_anim_batch",
+    "zs_png_diff_batch_device", "zs_png_crop_batch_device", "zs_png_anim_bound", "zs_png_encode_anim_batch_device",
 ]
 
 
@@ -205,5 +206,15 @@ def lib():
         L.zs_png_compose_batch_device.argtypes = [vp, i32, P(P(vp)), P(P(PngFrame)), P(i32), P(i64), P(i64), i32, P(vp), vp]
         L.zs_png_decode_anim_batch.restype = i32
         L.zs_png_decode_anim_batch.argtypes = [vp, i32, P(vp), P(i64), i32, P(vp), P(i64), P(PngAnim), P(i32), vp]
+    if hasattr(L, "zs_png_diff_batch_device"):  # (an older build selected with ZS_LIB for an A/B run lacks the animated encoder)
+        L.zs_png_diff_batch_device.restype = i32
+        L.zs_png_diff_batch_device.argtypes = [vp, i32, P(vp), P(i32), P(i64), P(i64), i32, P(P(PngFrame)), vp]
+        L.zs_png_crop_batch_device.restype = i32
+        L.zs_png_crop_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(i64), P(i64), P(i64), i32, P(vp), vp]
+        L.zs_png_anim_bound.restype = i64
+        L.zs_png_anim_bound.argtypes = [i64, i64, i32, i32, i32, i64, i64]
+        L.zs_png_encode_anim_batch_device.restype = i32
+        L.zs_png_encode_anim_batch_device.argtypes = [vp, i32, P(vp), P(i32), P(i64), P(i64), i32, P(P(i32)), P(P(i32)), P(i32), P(i32), P(i32), P(vp), P(i64),
+                                                      i64, i64, P(vp), P(i64), P(i64), P(i32), P(P(PngFrame)), P(i32), P(i32), i32, i32, i32, vp]
     _lib = L
     return L

@@ -1118,6 +1118,156 @@ def png_decode_anim_batch(engine, files, out_ptrs, out_caps, format=PNG_RGBA8, s
     return list(status), [_anim_dict(a) for a in anim]
 
 
+def _png_canvases_check(name, canvas_ptrs, n_frames, widths, heights, format):
+    n = len(canvas_ptrs)
+    if not (len(n_frames) == len(widths) == len(heights) == n):
+        raise ValueError(name + ": the argument lists differ in length")
+    if format not in (PNG_RGBA8, PNG_RGBA16):
+        raise ValueError(name + ": format is PNG_RGBA8 or PNG_RGBA16")
+    px = 8 if format == PNG_RGBA16 else 4
+    waves = 0
+    for p, f, w, h in zip(canvas_ptrs, n_frames, widths, heights):
+        if not p or int(p) % px or int(f) < 1 or not 1 <= int(w) <= 0x7FFFFFFF or not 1 <= int(h) <= 0x7FFFFFFF:
+            raise ValueError(name + ": 1 <= width, height <= 2^31 - 1, at least one frame and non-null canvases aligned to a pixel are required")
+        groups = -(-int(w) // (16 // px))  # of 16 bytes in a row; a wave takes 64
+        waves += int(h) * -(-groups // 64)
+    if waves > 0x7FFFFFFF or sum(int(f) for f in n_frames) > 0x7FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 canvas rows (counted once per 1024 bytes) or frames in one call")
+    return px
+
+
+def png_diff_batch_device(engine, canvas_ptrs, n_frames, widths, heights, format=PNG_RGBA8, stream=None):
+    """The frame diff of many device-resident animations in one call (zs_png_diff_batch_device).  canvas_ptrs[i]: device pointer
+    to n_frames[i] canvases of heights[i] * widths[i] * 4 (PNG_RGBA8) or * 8 (PNG_RGBA16) bytes back to back, as
+    png_compose_batch_device writes them.  Returns one list per animation of dicts x, y, width, height, dispose_op (0),
+    blend_op (0): frame 0 is the whole canvas, frame f >= 1 the smallest rectangle that holds every pixel whose bytes differ
+    between canvas f - 1 and canvas f, or 1 x 1 at (0, 0) where none does."""
+    name = "png_diff_batch_device"
+    _png_canvases_check(name, canvas_ptrs, n_frames, widths, heights, format)
+    n = len(canvas_ptrs)
+    if n == 0:
+        return []
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    fr_arrays = [(_native.PngFrame * int(f))() for f in n_frames]
+    rc = _native.lib().zs_png_diff_batch_device(engine.handle, n, VP(*[int(p) for p in canvas_ptrs]), I32(*[int(f) for f in n_frames]),
+                                                I64(*[int(x) for x in widths]), I64(*[int(x) for x in heights]), int(format),
+                                                (ctypes.POINTER(_native.PngFrame) * n)(*[ctypes.cast(a, ctypes.POINTER(_native.PngFrame)) for a in fr_arrays]),
+                                                ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_diff_batch_device failed (%d): %s" % (rc, engine.last_error()))
+    keys = ("x", "y", "width", "height", "dispose_op", "blend_op")
+    return [[{k: int(getattr(f, k)) for k in keys} for f in a] for a in fr_arrays]
+
+
+def png_crop_batch_device(engine, in_ptrs, in_widths, xs, ys, widths, heights, out_ptrs, pixel_bytes=4, stream=None):
+    """Rectangles of device-resident images as tight rows in one launch (zs_png_crop_batch_device): the widths[i] x heights[i]
+    pixels at (xs[i], ys[i]) of an image whose rows hold in_widths[i] pixels of pixel_bytes (4 or 8) bytes go to out_ptrs[i].
+    Pointers are aligned to a pixel and do not overlap; the caller vouches for ys[i] + heights[i]."""
+    name = "png_crop_batch_device"
+    n = len(in_ptrs)
+    if not (len(in_widths) == len(xs) == len(ys) == len(widths) == len(heights) == len(out_ptrs) == n):
+        raise ValueError(name + ": the argument lists differ in length")
+    if pixel_bytes not in (4, 8):
+        raise ValueError(name + ": pixel_bytes is 4 or 8")
+    for p, iw, x, y, w, h, o in zip(in_ptrs, in_widths, xs, ys, widths, heights, out_ptrs):
+        if not p or not o or int(p) % pixel_bytes or int(o) % pixel_bytes:
+            raise ValueError(name + ": non-null device pointers aligned to a pixel are required")
+        if not 1 <= int(iw) <= 0x7FFFFFFF or int(w) < 1 or not 1 <= int(h) <= 0x7FFFFFFF or int(x) < 0 or int(y) < 0 or int(x) + int(w) > int(iw) or \
+                int(y) + int(h) > 0x7FFFFFFF:
+            raise ValueError(name + ": the rectangle lies outside the image's rows")
+    if sum(int(h) for h in heights) > 0x7FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 rows in one call")
+    if n == 0:
+        return
+    VP, I64 = ctypes.c_void_p * n, ctypes.c_int64 * n
+    rc = _native.lib().zs_png_crop_batch_device(engine.handle, n, VP(*[int(p) for p in in_ptrs]), I64(*[int(v) for v in in_widths]), I64(*[int(v) for v in xs]),
+                                                I64(*[int(v) for v in ys]), I64(*[int(v) for v in widths]), I64(*[int(v) for v in heights]), int(pixel_bytes),
+                                                VP(*[int(p) for p in out_ptrs]), ctypes.c_void_p(stream or 0))
+    if rc != 0:
+        raise ValueError("zs_png_crop_batch_device failed (%d): %s" % (rc, engine.last_error()))
+
+
+def png_anim_bound(width, height, n_frames, format=PNG_RGBA8, interlace=0, idat_chunk_bytes=0, extra_len=0):
+    """zs_png_anim_bound (host code, no GPU): room that png_encode_anim_batch_device never exceeds for one animation -- every
+    frame the whole canvas at 32 or 64 bits a pixel.  -1 for arguments the encoder refuses."""
+    args = [int(width), int(height), int(n_frames), int(format), int(interlace), int(idat_chunk_bytes), int(extra_len)]
+    if not all(-(1 << 31) <= a < 1 << 31 for a in args[2:5]) or not all(-(1 << 63) <= a < 1 << 63 for a in args):
+        return -1
+    return int(_native.lib().zs_png_anim_bound(*args))
+
+
+def png_encode_anim_batch_device(engine, canvas_ptrs, n_frames, widths, heights, filters, out_ptrs, out_caps, delays=None, n_plays=None, format=PNG_RGBA8,
+                                 interlace=None, extra=None, rows_per_write=1, idat_chunk_bytes=0, level=6, strategy=0, hash_variant=0, stream=None,
+                                 return_status=False):
+    """Canvases -> animated PNG files for many device-resident animations in one call (zs_png_encode_anim_batch_device): the
+    survey over an animation's canvases, one (colour type, bit depth) pair and one PLTE / tRNS per animation, the frame diff,
+    the crop, the pack and the deflate over all frames, then acTL / fcTL / IDAT / fdAT framing.  canvas_ptrs, n_frames, widths,
+    heights, format: as for png_diff_batch_device.  delays[i]: n_frames[i] pairs (delay_num, delay_den), each 0 .. 65535
+    (None: 1 / 10 for every frame); n_plays[i]: 0 .. 2^31 - 1 (None: 0, for ever).  The rest as for
+    png_encode_rgba_batch_device, per animation.  png_anim_bound(...) is always enough room.  One frame gives the still
+    encoder's file.  png_decode_anim_batch returns the canvases byte for byte.  Returns (lengths, color_types, bit_depths,
+    frames) -- frames[i] one dict per frame, as png_anim_info gives them; return_status: (rc, lengths, statuses, color_types,
+    bit_depths, frames)."""
+    name = "png_encode_anim_batch_device"
+    n = len(canvas_ptrs)
+    if interlace is None:
+        interlace = [0] * n
+    if delays is None:
+        delays = [[(1, 10)] * int(f) for f in n_frames]
+    if n_plays is None:
+        n_plays = [0] * n
+    if not (len(filters) == len(out_ptrs) == len(out_caps) == len(interlace) == len(delays) == len(n_plays) == n) or (extra is not None and len(extra) != n):
+        raise ValueError(name + ": the argument lists differ in length")
+    px = _png_canvases_check(name, canvas_ptrs, n_frames, widths, heights, format)
+    if int(rows_per_write) < 0 or not 0 <= int(idat_chunk_bytes) <= 0x7FFFFFFF:
+        raise ValueError(name + ": rows_per_write >= 0 and 0 <= idat_chunk_bytes <= 2^31 - 1 are required")
+    if not -1 <= int(level) <= 9 or not 0 <= int(strategy) <= 4:
+        raise ValueError(name + ": level -1..9 and strategy 0..4 are required")
+    total_rows = 0
+    for nf, w, h, f, il, o, cap, d, plays in zip(n_frames, widths, heights, filters, interlace, out_ptrs, out_caps, delays, n_plays):
+        if not o or not 0 <= int(f) <= 5 or int(cap) < 0 or int(il) not in (0, 1):
+            raise ValueError(name + ": filter 0..5, interlace 0 or 1, non-null outputs and non-negative capacities are required")
+        if len(d) != int(nf) or any(not 0 <= int(a) <= 65535 or not 0 <= int(b) <= 65535 for a, b in d) or not 0 <= int(plays) <= 0x7FFFFFFF:
+            raise ValueError(name + ": one (delay_num, delay_den) pair of values 0 .. 65535 per frame and 0 <= n_plays <= 2^31 - 1 are required")
+        if int(nf) * int(h) > 0x7FFFFFFF:
+            raise ValueError(name + ": an animation's canvases have more than 2^31 - 1 rows")
+        if int(w) * int(h) * px > _CRC_MAX_LEN:
+            raise ValueError(name + ": a filtered image is above 2 GiB - 1 KiB")
+        total, _, rows = png_idat_layout(w, h, 8 * px, int(il))
+        if total > _CRC_MAX_LEN:
+            raise ValueError(name + ": a filtered image is above 2 GiB - 1 KiB")
+        total_rows += int(nf) * sum(rows)
+    if total_rows > 0x7FFFFFFF or sum(int(f) for f in n_frames) > 0x3FFFFFFF:
+        raise ValueError(name + ": more than 2^31 - 1 rows or 2^30 - 1 frames in one call")
+    if extra is not None:
+        extra = [bytes(x) if x is not None else b"" for x in extra]
+        if not all(_png_chunks_well_formed(x) for x in extra):
+            raise ValueError(name + ": an animation's extra chunks are not a sequence of whole chunks")
+    if n == 0:
+        return (0, [], [], [], [], []) if return_status else ([], [], [], [])
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    PI32, PFR = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_native.PngFrame)
+    out_len, status, ct, bd = I64(), I32(), I32(), I32()
+    num = [(ctypes.c_int * len(d))(*[int(a) for a, _ in d]) for d in delays]
+    den = [(ctypes.c_int * len(d))(*[int(b) for _, b in d]) for d in delays]
+    fr_arrays = [(_native.PngFrame * int(f))() for f in n_frames]
+    x_ptr = VP(*[_host_ptr(x) for x in extra]) if extra is not None else None  # (the bytes objects are read in place: they outlive the call)
+    x_len = I64(*[len(x) for x in extra]) if extra is not None else None
+    rc = _native.lib().zs_png_encode_anim_batch_device(engine.handle, n, VP(*[int(p) for p in canvas_ptrs]), I32(*[int(f) for f in n_frames]),
+                                                       I64(*[int(x) for x in widths]), I64(*[int(x) for x in heights]), int(format),
+                                                       (PI32 * n)(*[ctypes.cast(a, PI32) for a in num]), (PI32 * n)(*[ctypes.cast(a, PI32) for a in den]),
+                                                       I32(*[int(p) for p in n_plays]), I32(*[int(x) for x in filters]), I32(*[int(x) for x in interlace]),
+                                                       x_ptr, x_len, int(rows_per_write), int(idat_chunk_bytes), VP(*[int(p) for p in out_ptrs]),
+                                                       I64(*[int(x) for x in out_caps]), out_len, status, (PFR * n)(*[ctypes.cast(a, PFR) for a in fr_arrays]),
+                                                       ct, bd, int(level), int(strategy), int(hash_variant), ctypes.c_void_p(stream or 0))
+    frames = [[{k: int(getattr(f, k)) for k in _PNG_FRAME_FIELDS} for f in a] for a in fr_arrays]
+    if return_status:
+        return rc, list(out_len), list(status), list(ct), list(bd), frames
+    if rc != 0:
+        raise ZlibStreamException("png encode: " + engine.last_error())
+    return list(out_len), list(ct), list(bd), frames
+
+
 _default_engine = None
 
 

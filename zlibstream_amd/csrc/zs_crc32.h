@@ -116,12 +116,16 @@ inline void crc32_fill_tables(uint32_t *t) {
 // One span of a batch.  src: `len` bytes on the device, any alignment; init: the register the span starts from (~seed).
 // dst (may be null): the span's bytes from byte `skip` on are also copied there, any alignment.  frame (may be null): a
 // PNG chunk is closed around the copy -- big-endian length and `type` at frame, the data at frame + 8 = dst, the
-// big-endian CRC behind it (the finishing launch writes the twelve bytes).
+// big-endian CRC behind it (the finishing launch writes the twelve bytes).  has_prefix: four more bytes, `prefix` big-endian
+// (an fdAT's sequence number), stand between the type and the data -- the length field counts them, the data lies at
+// frame + 12 = dst, and the CRC covers them: the host seeds init with the type and the prefix, as it seeds it with the type
+// alone for a chunk without one.
 struct Crc32Span {
     const uint8_t *src;
     uint8_t *dst, *frame;
     int64_t len;
-    uint32_t init, skip, type, pad;
+    uint32_t init, skip, type, prefix;
+    uint32_t has_prefix, pad;
 };
 ZS_HD int64_t crc32_span_tiles(int64_t len) { return (len + kCrcTile - 1) / kCrcTile; }
 
@@ -155,6 +159,16 @@ constexpr uint32_t png_type(char a, char b, char c, char d) { return (uint32_t)(
 constexpr uint32_t kPngIHDR = png_type('I', 'H', 'D', 'R'), kPngPLTE = png_type('P', 'L', 'T', 'E'), kPngIDAT = png_type('I', 'D', 'A', 'T'),
                    kPngIEND = png_type('I', 'E', 'N', 'D');
 constexpr int64_t kPngMaxChunk = 0x7FFFFFFF;  // a chunk's data length (PNG specification 5.3)
+
+// Closes a chunk around `n` data bytes that are in place: the big-endian length and the type at f, the prefix (if any) behind
+// them, the big-endian CRC behind the data -- twelve bytes, or sixteen.  What the finishing launch of KC does per framed span
+// (zs_crc32.hip), and tests/cpp/test_png_diff.cpp on the host.
+ZS_HD void png_close_chunk(uint8_t *f, uint32_t n, uint32_t type, bool has_prefix, uint32_t prefix, uint32_t crc) {
+    png_put_be32(f, has_prefix ? n + 4 : n);
+    f[4] = (uint8_t)type, f[5] = (uint8_t)(type >> 8), f[6] = (uint8_t)(type >> 16), f[7] = (uint8_t)(type >> 24);
+    if (has_prefix) png_put_be32(f + 8, prefix);
+    png_put_be32(f + (has_prefix ? 12 : 8) + n, crc);
+}
 
 // bytes of the file that holds a zlib stream of idat_len bytes in IDAT chunks of at most idat_chunk_bytes data bytes
 // (0: one chunk; an empty stream still gets one chunk) and extra_len bytes of caller chunks; -1 for bad arguments

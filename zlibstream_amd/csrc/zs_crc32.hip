@@ -160,21 +160,14 @@ __global__ __launch_bounds__(64 * kCrcWaves) void zs_crc32_tile_kernel(const Crc
 }
 
 // One thread per span: the CRC (the register's complement; a span without bytes never met a tile: its register is init),
-// and for a framed span the twelve bytes around its data.
+// and for a framed span the twelve bytes around its data (sixteen with a prefix: zs_crc32.h png_close_chunk).
 __global__ void zs_crc32_finish_kernel(const Crc32Span *__restrict__ spans, int n_spans, const uint32_t *__restrict__ res, uint32_t *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_spans) return;
     const Crc32Span sp = spans[i];
     const uint32_t crc = ~(sp.len > 0 ? res[i] : sp.init);
     out[i] = crc;
-    if (sp.frame) {
-        uint8_t *f = sp.frame;
-        const uint32_t n = (uint32_t)(sp.len - sp.skip);
-        f[0] = (uint8_t)(n >> 24), f[1] = (uint8_t)(n >> 16), f[2] = (uint8_t)(n >> 8), f[3] = (uint8_t)n;
-        f[4] = (uint8_t)sp.type, f[5] = (uint8_t)(sp.type >> 8), f[6] = (uint8_t)(sp.type >> 16), f[7] = (uint8_t)(sp.type >> 24);
-        uint8_t *c = f + 8 + n;
-        c[0] = (uint8_t)(crc >> 24), c[1] = (uint8_t)(crc >> 16), c[2] = (uint8_t)(crc >> 8), c[3] = (uint8_t)crc;
-    }
+    if (sp.frame) png_close_chunk(sp.frame, (uint32_t)(sp.len - sp.skip), sp.type, sp.has_prefix != 0, sp.prefix, crc);
 }
 
 }  // namespace zs

@@ -30,11 +30,11 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStPngCompose, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStPngCompose, kStPngDiff, kStPngCrop, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
                                            "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
-                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey", "png_compose"};
+                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey", "png_compose", "png_diff", "png_crop"};
 
 }  // namespace
 
@@ -72,7 +72,7 @@ struct zs_ctx {
     uint32_t *crc_tab = nullptr;
     DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, tile_bits, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
-        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw, png_simg, png_split, png_gimg, png_vimg, png_vrec, png_packed, png_cimg, png_frames;
+        par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw, png_simg, png_split, png_gimg, png_vimg, png_vrec, png_packed, png_cimg, png_frames, png_dimg, png_drec, png_kimg, png_crop;
     uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
     hipEvent_t ev_crc[2] = {};            // KC and its finishing launch (profiling)
     hipEvent_t ev_expand[2] = {};         // KX (profiling)
@@ -80,6 +80,8 @@ struct zs_ctx {
     hipEvent_t ev_pack[2] = {};           // KG (profiling)
     hipEvent_t ev_survey[2] = {};         // KV, both launches (profiling)
     hipEvent_t ev_compose[2] = {};        // KM (profiling)
+    hipEvent_t ev_diff[2] = {};           // KD, both launches (profiling)
+    hipEvent_t ev_crop[2] = {};           // the crop (profiling)
     bool resume_poisoned = false;  // a resumed run met a read the bulk form does not handle: the caller goes on with the literal engine
     void *pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1441,6 +1443,8 @@ int zs_ctx_create(int device, zs_ctx **out) {
     for (auto &e : c->ev_crc) (void)hipEventCreate(&e);
     for (auto &e : c->ev_expand) (void)hipEventCreate(&e);
     for (auto &e : c->ev_compose) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_diff) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_crop) (void)hipEventCreate(&e);
     for (auto &e : c->ev_split) (void)hipEventCreate(&e);
     for (auto &e : c->ev_pack) (void)hipEventCreate(&e);
     for (auto &e : c->ev_survey) (void)hipEventCreate(&e);
@@ -1509,7 +1513,7 @@ void zs_ctx_destroy(zs_ctx *c) {
     DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->tile_bits, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
-                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw, &c->png_simg, &c->png_split, &c->png_gimg, &c->png_vimg, &c->png_vrec, &c->png_packed, &c->png_cimg, &c->png_frames};
+                      &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw, &c->png_simg, &c->png_split, &c->png_gimg, &c->png_vimg, &c->png_vrec, &c->png_packed, &c->png_cimg, &c->png_frames, &c->png_dimg, &c->png_drec, &c->png_kimg, &c->png_crop};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->crc_tab) (void)hipFree(c->crc_tab);
@@ -1525,6 +1529,10 @@ void zs_ctx_destroy(zs_ctx *c) {
     for (auto &e : c->ev_survey)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_compose)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_diff)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_crop)
         if (e) (void)hipEventDestroy(e);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pin_io) (void)hipHostFree(c->pin_io);
@@ -1597,7 +1605,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
-    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey || s == kStPngCompose) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA), KV (the survey) and KM (the frames of an animation composed)
+    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey || s == kStPngCompose || s == kStPngDiff || s == kStPngCrop) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA), KV (the survey), KM (the frames of an animation composed), KD (the frame diff) and the crop
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine
@@ -2798,9 +2806,13 @@ struct PngPackJob {
     std::vector<uint32_t> tables;
     int64_t rows = 0;
     double ms = 0;  // profiling: the launches
-    void add(const void *in, void *out, int64_t w, int64_t h, int depth, int color, int format, const uint8_t *plte, int entries, const uint8_t *trns, int trns_len) {
+    // share_table >= 0: a palette image takes the table at that offset, made for an earlier image with the same PLTE / tRNS
+    void add(const void *in, void *out, int64_t w, int64_t h, int depth, int color, int format, const uint8_t *plte, int entries, const uint8_t *trns, int trns_len,
+             int32_t share_table = -1) {
         PngPackImg im{(const uint8_t *)in, (uint8_t *)out, (int32_t)w, (int32_t)h, depth, color, format, 0, {0, 0, 0}, 0};
-        if (color == 3) {
+        if (color == 3 && share_table >= 0) {
+            im.pal_off = share_table;
+        } else if (color == 3) {
             im.pal_off = (int32_t)tables.size();
             tables.resize(tables.size() + kPngPackTableWords);
             // (an entry at or beyond 2^depth has no index in the file: it cannot be named, and is left out)
@@ -3519,6 +3531,41 @@ extern "C" int zs_png_encode_interlace_batch_device(zs_ctx *c, int n, const void
                             out_cap, out_len, status, level, strategy, hash_variant, hip_stream);
 }
 
+namespace {
+// What the survey of an image (or of an animation's canvases) decides on the host: the pair, and for a palette image the PLTE
+// in the survey's order and the tRNS up to the last entry below 255 (none when all are 255), framed behind the caller's
+// chunks in `xs`.
+struct PngChosen {
+    int ct = 0, bd = 0, entries = 0, tlen = 0;
+    std::vector<uint8_t> xs, plte, trns;
+};
+bool png_choose_chunks(const zs_png_survey &sv, const void *extra, int64_t extra_len, PngChosen *o) {
+    auto put_chunk = [](std::vector<uint8_t> &to, const char *type, const std::vector<uint8_t> &data) {
+        const size_t at = to.size();
+        to.resize(at + 12 + data.size());
+        png_put_be32(to.data() + at, (uint32_t)data.size());
+        memcpy(to.data() + at + 4, type, 4);
+        if (!data.empty()) memcpy(to.data() + at + 8, data.data(), data.size());
+        png_put_be32(to.data() + at + 8 + data.size(), crc32_bytes_slow(0, to.data() + at + 4, (int64_t)(4 + data.size())));
+    };
+    if (zs_png_choose_format(&sv, &o->ct, &o->bd) != ZS_OK) return false;
+    if (extra && extra_len > 0) o->xs.assign((const uint8_t *)extra, (const uint8_t *)extra + extra_len);
+    if (o->ct != 3) return true;
+    const int m = sv.n_colors;
+    o->entries = m;
+    o->plte.resize(3 * (size_t)m);
+    for (int e = 0; e < m; e++) {
+        memcpy(o->plte.data() + 3 * (size_t)e, sv.colors[e], 3);
+        if (sv.colors[e][3] != 255) o->tlen = e + 1;
+    }
+    o->trns.resize((size_t)o->tlen);
+    for (int e = 0; e < o->tlen; e++) o->trns[(size_t)e] = sv.colors[e][3];
+    put_chunk(o->xs, "PLTE", o->plte);
+    if (o->tlen > 0) put_chunk(o->xs, "tRNS", o->trns);
+    return true;
+}
+}  // namespace
+
 // RGBA pixels -> files: the survey (KV), the choice per image on the host, PLTE and tRNS of the palette images framed on the
 // host behind the caller's chunks, the pack (KG) into a buffer of the context, then the body of the two calls above on that
 // buffer.  Every argument is checked here first, so that nothing the later steps refuse has touched status by then.
@@ -3580,43 +3627,19 @@ extern "C" int zs_png_encode_rgba_batch_device(zs_ctx *c, int n, const void *con
     int rc = zs_png_survey_batch_device(c, n, pixels, width, height, format, sv.data(), (void *)s);
     if (rc != ZS_OK) return all_fail(rc);
     const double survey_ms = c->profiling ? c->stage_ms[kStPngSurvey] : 0;
-    std::vector<int> ct((size_t)n), bd((size_t)n), entries((size_t)n, 0), tlen((size_t)n, 0);
-    std::vector<std::vector<uint8_t>> xs((size_t)n), plte((size_t)n), trns((size_t)n);
-    std::vector<const void *> x_ptr((size_t)n), plte_ptr((size_t)n, nullptr), trns_ptr((size_t)n, nullptr), packed((size_t)n);
+    std::vector<PngChosen> ch((size_t)n);
+    std::vector<int> ct((size_t)n), bd((size_t)n);
+    std::vector<const void *> x_ptr((size_t)n), packed((size_t)n);
     std::vector<int64_t> x_len((size_t)n);
     size_t pack_total = 0;
-    auto put_chunk = [](std::vector<uint8_t> &to, const char *type, const std::vector<uint8_t> &data) {
-        const size_t at = to.size();
-        to.resize(at + 12 + data.size());
-        png_put_be32(to.data() + at, (uint32_t)data.size());
-        memcpy(to.data() + at + 4, type, 4);
-        if (!data.empty()) memcpy(to.data() + at + 8, data.data(), data.size());
-        png_put_be32(to.data() + at + 8 + data.size(), crc32_bytes_slow(0, to.data() + at + 4, (int64_t)(4 + data.size())));
-    };
     for (int i = 0; i < n; i++) {
         const size_t k = (size_t)i;
-        if (zs_png_choose_format(&sv[k], &ct[k], &bd[k]) != ZS_OK) return all_fail(ZS_STREAM_ERROR);  // (unreachable: the survey is our own)
+        if (!png_choose_chunks(sv[k], extra ? extra[i] : nullptr, extra ? extra_len[i] : 0, &ch[k])) return all_fail(ZS_STREAM_ERROR);  // (unreachable: the survey is our own)
+        ct[k] = ch[k].ct, bd[k] = ch[k].bd;
         if (color_type_out) color_type_out[i] = ct[k];
         if (bit_depth_out) bit_depth_out[i] = bd[k];
-        if (extra && extra_len[i] > 0) xs[k].assign((const uint8_t *)extra[i], (const uint8_t *)extra[i] + extra_len[i]);
-        if (ct[k] == 3) {
-            // PLTE in the survey's order; tRNS up to the last entry below 255, none when all are 255
-            const int m = sv[k].n_colors;
-            entries[k] = m;
-            plte[k].resize(3 * (size_t)m);
-            for (int e = 0; e < m; e++) {
-                memcpy(plte[k].data() + 3 * (size_t)e, sv[k].colors[e], 3);
-                if (sv[k].colors[e][3] != 255) tlen[k] = e + 1;
-            }
-            trns[k].resize((size_t)tlen[k]);
-            for (int e = 0; e < tlen[k]; e++) trns[k][(size_t)e] = sv[k].colors[e][3];
-            put_chunk(xs[k], "PLTE", plte[k]);
-            if (tlen[k] > 0) put_chunk(xs[k], "tRNS", trns[k]);
-            plte_ptr[k] = plte[k].data();
-            trns_ptr[k] = tlen[k] > 0 ? trns[k].data() : nullptr;
-        }
-        x_ptr[k] = xs[k].empty() ? nullptr : xs[k].data();
-        x_len[k] = (int64_t)xs[k].size();
+        x_ptr[k] = ch[k].xs.empty() ? nullptr : ch[k].xs.data();
+        x_len[k] = (int64_t)ch[k].xs.size();
         pack_total += ((size_t)(png_bits_row_bytes(width[i], bd[k] * png_channels(ct[k])) * height[i]) + 255) & ~(size_t)255;
     }
     // ---- the pack
@@ -3627,7 +3650,8 @@ extern "C" int zs_png_encode_rgba_batch_device(zs_ctx *c, int n, const void *con
         for (int i = 0; i < n; i++) {
             const size_t k = (size_t)i;
             packed[k] = (uint8_t *)c->png_packed.p + at;
-            job.add(pixels[i], (void *)packed[k], width[i], height[i], bd[k], ct[k], format, (const uint8_t *)plte_ptr[k], entries[k], (const uint8_t *)trns_ptr[k], tlen[k]);
+            job.add(pixels[i], (void *)packed[k], width[i], height[i], bd[k], ct[k], format, ch[k].ct == 3 ? ch[k].plte.data() : nullptr, ch[k].entries,
+                    ch[k].tlen > 0 ? ch[k].trns.data() : nullptr, ch[k].tlen);
             at += ((size_t)(png_bits_row_bytes(width[i], bd[k] * png_channels(ct[k])) * height[i]) + 255) & ~(size_t)255;
         }
     }
@@ -4181,6 +4205,530 @@ extern "C" int zs_png_decode_anim_batch(zs_ctx *c, int n, const void *const *fil
     }
     if (c->profiling) c->stage_ms[kStCrc32] = crc_ms, c->stage_ms[kStPngExpand] = expand_ms, c->stage_ms[kStPngCompose] = compose_ms;
     return verdict();
+}
+
+// ------------------------------------------------------------------ animated PNG on the way out: the frame diff (KD), the crop, the encoder
+namespace {
+constexpr int64_t kDiffSlice = 1 << 25;  // waves a launch, as KM's
+constexpr int64_t kCropSlice = 1 << 25;  // rows a launch, as KX's
+
+struct PngRegion {
+    int64_t x, y, w, h;
+};
+
+// What zs_png_diff_batch_device and the encoder check alike: the canvases of n animations.  *waves: KD's grid.
+bool png_canvases_ok(zs_ctx *c, int n, const void *const *canvases, const int *n_frames, const int64_t *width, const int64_t *height, int format, int64_t *waves) {
+    if (!canvases || !n_frames || !width || !height) return false;
+    if (format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) {
+        c->err = "stream error: format is neither ZS_PNG_RGBA8 nor ZS_PNG_RGBA16";
+        return false;
+    }
+    const uintptr_t mis = (uintptr_t)(png_expand_bytes(format) - 1);
+    int64_t total_waves = 0, total_frames = 0;
+    for (int i = 0; i < n; i++) {
+        if (!canvases[i] || ((uintptr_t)canvases[i] & mis) != 0 || n_frames[i] < 1 || width[i] < 1 || height[i] < 1 || width[i] > 0x7FFFFFFF || height[i] > 0x7FFFFFFF) {
+            c->err = "stream error";
+            return false;
+        }
+        total_waves += height[i] * png_compose_row_waves(width[i], format), total_frames += n_frames[i];
+        if (total_waves > 0x7FFFFFFF || total_frames > 0x7FFFFFFF) {  // (the grid is the list of rows, a wave per 64 groups of a row)
+            c->err = "stream error: more than 2^31 - 1 canvas rows (counted once per 64 groups of 16 bytes) or frames in one call (split the batch)";
+            return false;
+        }
+    }
+    *waves = total_waves;
+    return true;
+}
+
+// KD over the canvases of n animations: regions[i][f] for every frame.  Uploads the descriptors through the staging buffer,
+// runs both launches on `s` and waits for `s` twice: for the upload and the launches, and for the rectangles.  Animations of
+// one frame take no part; a call without any other launches nothing and does not wait.
+bool png_diff_run(zs_ctx *c, int n, const void *const *canvases, const int *n_frames, const int64_t *width, const int64_t *height, int format,
+                  std::vector<std::vector<PngRegion>> &regions, hipStream_t s, bool *no_memory, double *ms) {
+    *no_memory = false, *ms = 0;
+    regions.assign((size_t)n, {});
+    std::vector<PngDiffAnim> anims((size_t)n);
+    std::vector<int32_t> wave_off((size_t)n + 1), pair_off((size_t)n + 1);
+    int64_t waves = 0, pairs = 0, recs = 0;
+    for (int i = 0; i < n; i++) {
+        regions[(size_t)i].assign((size_t)n_frames[i], PngRegion{0, 0, width[i], height[i]});
+        const int64_t w_i = n_frames[i] > 1 ? height[i] * png_compose_row_waves(width[i], format) : 0;
+        anims[(size_t)i] = PngDiffAnim{(const uint8_t *)canvases[i], recs, (int32_t)width[i], (int32_t)height[i], n_frames[i], 0};
+        wave_off[(size_t)i] = (int32_t)waves, pair_off[(size_t)i] = (int32_t)pairs;
+        waves += w_i, pairs += n_frames[i] - 1, recs += w_i * (n_frames[i] - 1);
+    }
+    wave_off[(size_t)n] = (int32_t)waves, pair_off[(size_t)n] = (int32_t)pairs;
+    if (pairs == 0) return true;
+    const size_t b_anim = sizeof(PngDiffAnim) * (size_t)n, b_off = (sizeof(int32_t) * ((size_t)n + 1) + 15) & ~(size_t)15, b_up = b_anim + 2 * b_off,
+                 b_rec = sizeof(PngDiffRec) * (size_t)recs, b_rect = sizeof(PngDiffRect) * (size_t)pairs;
+    if (!ensure(c, c->png_dimg, b_up) || !ensure(c, c->png_drec, b_rec + b_rect) || !ensure_pinned(c, std::max(b_up, b_rect))) {
+        *no_memory = true;
+        return false;
+    }
+    uint8_t *hp = (uint8_t *)c->pinned;
+    memcpy(hp, anims.data(), b_anim);
+    memcpy(hp + b_anim, wave_off.data(), sizeof(int32_t) * ((size_t)n + 1));
+    memcpy(hp + b_anim + b_off, pair_off.data(), sizeof(int32_t) * ((size_t)n + 1));
+    ZS_HIP(c, hipMemcpyAsync(c->png_dimg.p, c->pinned, b_up, hipMemcpyHostToDevice, s));
+    const bool prof = c->profiling;
+    if (prof) (void)hipEventRecord(c->ev_diff[0], s);
+    const PngDiffAnim *d_anim = (const PngDiffAnim *)c->png_dimg.p;
+    const int32_t *d_woff = (const int32_t *)((const uint8_t *)c->png_dimg.p + b_anim), *d_poff = (const int32_t *)((const uint8_t *)c->png_dimg.p + b_anim + b_off);
+    PngDiffRec *d_rec = (PngDiffRec *)c->png_drec.p;
+    PngDiffRect *d_rect = (PngDiffRect *)((uint8_t *)c->png_drec.p + b_rec);  // (8-aligned: a record is 8 bytes)
+    for (int64_t wave0 = 0; wave0 < waves; wave0 += kDiffSlice) {
+        const int64_t m = std::min<int64_t>(kDiffSlice, waves - wave0);
+        const dim3 grid((unsigned)((m + kDiffWavesPerWg - 1) / kDiffWavesPerWg)), block(64 * kDiffWavesPerWg);
+        if (format == ZS_PNG_FMT_RGBA16) hipLaunchKernelGGL(zs_png_diff_kernel<ZS_PNG_FMT_RGBA16>, grid, block, 0, s, d_anim, d_woff, n, wave0, d_rec);
+        else hipLaunchKernelGGL(zs_png_diff_kernel<ZS_PNG_FMT_RGBA8>, grid, block, 0, s, d_anim, d_woff, n, wave0, d_rec);
+        ZS_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(zs_png_diff_merge_kernel, dim3((unsigned)pairs), dim3(256), 0, s, d_anim, d_poff, n, format, (const PngDiffRec *)d_rec, d_rect);
+    ZS_HIP(c, hipGetLastError());
+    if (prof) (void)hipEventRecord(c->ev_diff[1], s);
+    ZS_HIP(c, hipStreamSynchronize(s));  // the upload has left the staging buffer
+    ZS_HIP(c, hipMemcpyAsync(c->pinned, d_rect, b_rect, hipMemcpyDeviceToHost, s));
+    ZS_HIP(c, hipStreamSynchronize(s));
+    if (prof) {
+        float t = 0;
+        (void)hipEventElapsedTime(&t, c->ev_diff[0], c->ev_diff[1]);
+        *ms = t;
+    }
+    const PngDiffRect *rects = (const PngDiffRect *)c->pinned;
+    for (int i = 0; i < n; i++)
+        for (int f = 1; f < n_frames[i]; f++) {
+            PngRegion &r = regions[(size_t)i][(size_t)f];
+            png_diff_finish(rects[(size_t)pair_off[(size_t)i] + (size_t)f - 1], &r.x, &r.y, &r.w, &r.h);
+        }
+    return true;
+}
+
+// The images of one crop launch: descriptors and the row offsets of the flat row list.
+struct PngCropJob {
+    std::vector<PngCropImg> img;
+    std::vector<int32_t> off;
+    int64_t rows = 0;
+    double ms = 0;  // profiling: the launches
+    void add(const void *in, int64_t in_width, int64_t x, int64_t y, int64_t w, int64_t h, int px, void *out) {
+        img.push_back(PngCropImg{(const uint8_t *)in + (y * in_width + x) * px, (uint8_t *)out, in_width * px, (int32_t)w, (int32_t)h});
+        off.push_back((int32_t)rows);
+        rows += h;
+    }
+};
+
+// Uploads the job through the staging buffer and launches the crop on `s`.  Waits for `s` once: for the upload (the staging
+// buffer is the caller's again), or, with profiling on, for the launches.
+bool png_crop_run(zs_ctx *c, PngCropJob &job, int px, hipStream_t s, bool *no_memory) {
+    *no_memory = false;
+    const int m = (int)job.img.size();
+    const size_t b_img = sizeof(PngCropImg) * (size_t)m, b_off = sizeof(int32_t) * ((size_t)m + 1);
+    if (!ensure(c, c->png_kimg, b_img + b_off) || !ensure_pinned(c, b_img + b_off)) {
+        *no_memory = true;
+        return false;
+    }
+    uint8_t *hp = (uint8_t *)c->pinned;
+    memcpy(hp, job.img.data(), b_img);
+    memcpy(hp + b_img, job.off.data(), sizeof(int32_t) * (size_t)m);
+    const int32_t total = (int32_t)job.rows;
+    memcpy(hp + b_img + sizeof(int32_t) * (size_t)m, &total, sizeof total);
+    ZS_HIP(c, hipMemcpyAsync(c->png_kimg.p, c->pinned, b_img + b_off, hipMemcpyHostToDevice, s));
+    const bool prof = c->profiling;
+    if (!prof) ZS_HIP(c, hipStreamSynchronize(s));
+    else (void)hipEventRecord(c->ev_crop[0], s);
+    const PngCropImg *d_img = (const PngCropImg *)c->png_kimg.p;
+    const int32_t *d_off = (const int32_t *)((const uint8_t *)c->png_kimg.p + b_img);
+    for (int64_t row0 = 0; row0 < job.rows; row0 += kCropSlice) {
+        const int64_t rows = std::min<int64_t>(kCropSlice, job.rows - row0);
+        const dim3 grid((unsigned)((rows + kCropRowsPerWg - 1) / kCropRowsPerWg)), block(64 * kCropRowsPerWg);
+        if (px == 8) hipLaunchKernelGGL(zs_png_crop_kernel<8>, grid, block, 0, s, d_img, d_off, m, row0);
+        else hipLaunchKernelGGL(zs_png_crop_kernel<4>, grid, block, 0, s, d_img, d_off, m, row0);
+        ZS_HIP(c, hipGetLastError());
+    }
+    if (prof) {
+        (void)hipEventRecord(c->ev_crop[1], s);
+        ZS_HIP(c, hipStreamSynchronize(s));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev_crop[0], c->ev_crop[1]);
+        job.ms = ms;
+    }
+    return true;
+}
+
+// chunks that hold a frame's stream of z bytes: IDAT, or fdAT, whose four bytes of sequence number count against the chunk
+// limit; *step: stream bytes of every chunk but the last.  -1: one chunk was asked for and cannot hold the stream.
+int64_t png_anim_chunks(int64_t z, int64_t idat_chunk_bytes, bool fdat, int64_t *step) {
+    const int64_t most = kPngMaxChunk - (fdat ? 4 : 0);
+    if (idat_chunk_bytes == 0 && z > most) return -1;
+    *step = idat_chunk_bytes == 0 ? z : std::min(idat_chunk_bytes, most);
+    return z == 0 || idat_chunk_bytes == 0 ? 1 : (z + *step - 1) / *step;
+}
+constexpr int64_t kPngActlBytes = 20, kPngFctlBytes = 38;
+}  // namespace
+
+extern "C" int zs_png_diff_batch_device(zs_ctx *c, int n, const void *const *canvases, const int *n_frames, const int64_t *width, const int64_t *height,
+                                        int format, zs_png_frame *const *frames_out, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    int64_t waves = 0;
+    if (!frames_out || !png_canvases_ok(c, n, canvases, n_frames, width, height, format, &waves)) return ZS_STREAM_ERROR;
+    for (int i = 0; i < n; i++)
+        if (!frames_out[i]) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    std::vector<std::vector<PngRegion>> regions;
+    bool no_memory = false;
+    double ms = 0;
+    if (!png_diff_run(c, n, canvases, n_frames, width, height, format, regions, s, &no_memory, &ms)) return no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+    if (c->profiling) {
+        for (double &v : c->stage_ms) v = 0;
+        c->stage_ms[kStPngDiff] = ms;
+    }
+    for (int i = 0; i < n; i++)
+        for (int f = 0; f < n_frames[i]; f++) {
+            const PngRegion &r = regions[(size_t)i][(size_t)f];
+            zs_png_frame &o = frames_out[i][f];
+            o.x = r.x, o.y = r.y, o.width = r.w, o.height = r.h, o.dispose_op = kPngDisposeNone, o.blend_op = kPngBlendSource;
+        }
+    return ZS_OK;
+}
+
+extern "C" int zs_png_crop_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *in_width, const int64_t *x, const int64_t *y, const int64_t *width,
+                                        const int64_t *height, int pixel_bytes, void *const *out, void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!in || !in_width || !x || !y || !width || !height || !out) return ZS_STREAM_ERROR;
+    if (pixel_bytes != 4 && pixel_bytes != 8) {
+        c->err = "stream error: pixel_bytes is neither 4 nor 8";
+        return ZS_STREAM_ERROR;
+    }
+    const uintptr_t mis = (uintptr_t)(pixel_bytes - 1);
+    int64_t total_rows = 0;
+    for (int i = 0; i < n; i++) {
+        const bool ok = in[i] && out[i] && ((uintptr_t)in[i] & mis) == 0 && ((uintptr_t)out[i] & mis) == 0 && in_width[i] >= 1 && in_width[i] <= 0x7FFFFFFF && width[i] >= 1 &&
+                        height[i] >= 1 && height[i] <= 0x7FFFFFFF && x[i] >= 0 && y[i] >= 0 && y[i] <= 0x7FFFFFFF - height[i] && x[i] <= in_width[i] - width[i];
+        if (!ok) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        total_rows += height[i];
+    }
+    if (total_rows > 0x7FFFFFFF) {  // (the grid is the row list)
+        c->err = "stream error: more than 2^31 - 1 rows in one call (split the batch)";
+        return ZS_STREAM_ERROR;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    PngCropJob job;
+    for (int i = 0; i < n; i++) job.add(in[i], in_width[i], x[i], y[i], width[i], height[i], pixel_bytes, out[i]);
+    bool no_memory = false;
+    if (!png_crop_run(c, job, pixel_bytes, s, &no_memory)) return no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+    if (c->profiling) {
+        for (double &v : c->stage_ms) v = 0;
+        c->stage_ms[kStPngCrop] = job.ms;
+    }
+    return hip_stream ? ZS_OK : (hipStreamSynchronize(s) == hipSuccess ? ZS_OK : ZS_STREAM_ERROR);
+}
+
+extern "C" int64_t zs_png_anim_bound(int64_t width, int64_t height, int n_frames, int format, int interlace, int64_t idat_chunk_bytes, int64_t extra_len) {
+    if (width < 1 || height < 1 || width > 0x7FFFFFFF || height > 0x7FFFFFFF || n_frames < 1 || (format != ZS_PNG_FMT_RGBA8 && format != ZS_PNG_FMT_RGBA16) ||
+        (interlace != 0 && interlace != 1) || idat_chunk_bytes < 0 || idat_chunk_bytes > kPngMaxChunk || extra_len < 0 || extra_len > (int64_t)1 << 60)
+        return -1;
+    const int px = png_expand_bytes(format);
+    if (width * height > kCrcMaxLen / px) return -1;  // (what the encoder refuses: a filtered canvas above 2 GiB - 1 KiB)
+    const int64_t filtered = zs_png_idat_layout(width, height, 8 * px, interlace, nullptr, nullptr);
+    if (filtered > kCrcMaxLen) return -1;
+    const int64_t z = zs_deflate_bound(filtered);
+    int64_t step = 0;
+    const int64_t idats = png_anim_chunks(z, idat_chunk_bytes, false, &step), fdats = n_frames > 1 ? png_anim_chunks(z, idat_chunk_bytes, true, &step) : 0;
+    if (idats < 0 || fdats < 0) return -1;
+    return 8 + 25 + extra_len + 1048 + kPngActlBytes + kPngFctlBytes + z + 12 * idats + (int64_t)(n_frames - 1) * (kPngFctlBytes + z + 16 * fdats) + 12;
+}
+
+// Canvases -> animated files: the survey (KV) over an animation's canvases as one tall image, the choice and PLTE / tRNS per
+// animation, the diff (KD), the crop of every later frame's region into a buffer of the context (a region as wide as the
+// canvas is read in place: its rows lie back to back already), the pack (KG) and the IDAT call over all frames of all
+// animations as images of their regions' sizes, then one KC launch that frames every IDAT and fdAT chunk and places the host's
+// bytes -- signature, IHDR, the caller's chunks, PLTE, tRNS, acTL, every fcTL, IEND -- around them.
+extern "C" int zs_png_encode_anim_batch_device(zs_ctx *c, int n, const void *const *canvases, const int *n_frames, const int64_t *width, const int64_t *height,
+                                               int format, const int *const *delay_num, const int *const *delay_den, const int *n_plays, const int *filter,
+                                               const int *interlace, const void *const *extra, const int64_t *extra_len, int64_t rows_per_write,
+                                               int64_t idat_chunk_bytes, void *const *out, const int64_t *out_cap, int64_t *out_len, int *status,
+                                               zs_png_frame *const *frames_out, int *color_type_out, int *bit_depth_out, int level, int strategy, int hash_variant,
+                                               void *hip_stream) {
+    if (!c || n < 0) return ZS_STREAM_ERROR;
+    if (n == 0) return ZS_OK;
+    if (!delay_num || !delay_den || !n_plays || !filter || !out || !out_cap || !out_len || (extra && !extra_len)) return ZS_STREAM_ERROR;
+    int64_t waves = 0;
+    if (!png_canvases_ok(c, n, canvases, n_frames, width, height, format, &waves)) return ZS_STREAM_ERROR;
+    if (rows_per_write < 0 || idat_chunk_bytes < 0 || idat_chunk_bytes > kPngMaxChunk || level < -1 || level > 9 || strategy < 0 || strategy > 4) {
+        c->err = "stream error";
+        return ZS_STREAM_ERROR;
+    }
+    const int px = png_expand_bytes(format);
+    int64_t total_rows = 0, total_frames = 0;
+    std::vector<int> fr0((size_t)n);  // an animation's first frame in the call's list of frames
+    for (int i = 0; i < n; i++) {
+        const int il = interlace ? interlace[i] : 0;
+        if (il != 0 && il != 1) {
+            c->err = "stream error: interlace is neither 0 nor 1";
+            return ZS_STREAM_ERROR;
+        }
+        if (!out[i] || !delay_num[i] || !delay_den[i] || (frames_out && !frames_out[i]) || filter[i] < 0 || filter[i] > 5 || out_cap[i] < 0 || n_plays[i] < 0) {
+            c->err = "stream error";
+            return ZS_STREAM_ERROR;
+        }
+        for (int f = 0; f < n_frames[i]; f++)
+            if (delay_num[i][f] < 0 || delay_num[i][f] > 65535 || delay_den[i][f] < 0 || delay_den[i][f] > 65535) {
+                c->err = "stream error: a delay is outside 0 .. 65535";
+                return ZS_STREAM_ERROR;
+            }
+        if ((int64_t)n_frames[i] * height[i] > 0x7FFFFFFF) {  // (the survey takes the canvases as one image)
+            c->err = "stream error: an animation's canvases have more than 2^31 - 1 rows";
+            return ZS_STREAM_ERROR;
+        }
+        // (no pair is chosen and no region known yet: the limit is held against a whole canvas as it comes, which no frame exceeds)
+        if (width[i] * height[i] > kCrcMaxLen / px || zs_png_idat_layout(width[i], height[i], 8 * px, il, nullptr, nullptr) > kCrcMaxLen) {
+            c->err = "stream error: a filtered image is above 2 GiB - 1 KiB";
+            return ZS_STREAM_ERROR;
+        }
+        if (extra && (extra_len[i] < 0 || (extra_len[i] > 0 && !extra[i]) || !png_chunks_well_formed((const uint8_t *)extra[i], extra_len[i]))) {
+            c->err = "stream error: the extra chunks of an image are not a sequence of whole chunks";
+            return ZS_STREAM_ERROR;
+        }
+        fr0[(size_t)i] = (int)total_frames;
+        total_rows += (int64_t)n_frames[i] * (il ? adam7_pass_rows(width[i], height[i]) : height[i]), total_frames += n_frames[i];
+        if (total_rows > 0x7FFFFFFF || total_frames > 0x3FFFFFFF) {
+            c->err = "stream error: more than 2^31 - 1 rows or 2^30 - 1 frames in one call (split the batch)";
+            return ZS_STREAM_ERROR;
+        }
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    auto all_fail = [&](int rc) {
+        for (int i = 0; i < n; i++) {
+            out_len[i] = 0;
+            if (status) status[i] = rc;
+        }
+        return rc;
+    };
+    const size_t M = (size_t)total_frames;
+    // ---- the survey over every animation's canvases as one image, and the choice
+    std::vector<zs_png_survey> sv((size_t)n);
+    std::vector<int64_t> tall((size_t)n);
+    for (int i = 0; i < n; i++) tall[(size_t)i] = (int64_t)n_frames[i] * height[i];
+    int rc = zs_png_survey_batch_device(c, n, canvases, width, tall.data(), format, sv.data(), (void *)s);
+    if (rc != ZS_OK) return all_fail(rc);
+    const double survey_ms = c->profiling ? c->stage_ms[kStPngSurvey] : 0;
+    std::vector<PngChosen> ch((size_t)n);
+    bool any_palette = false;
+    for (int i = 0; i < n; i++) {
+        if (!png_choose_chunks(sv[(size_t)i], extra ? extra[i] : nullptr, extra ? extra_len[i] : 0, &ch[(size_t)i])) return all_fail(ZS_STREAM_ERROR);  // (unreachable: the survey is our own)
+        if (color_type_out) color_type_out[i] = ch[(size_t)i].ct;
+        if (bit_depth_out) bit_depth_out[i] = ch[(size_t)i].bd;
+        any_palette = any_palette || ch[(size_t)i].ct == 3;
+    }
+    // ---- the diff
+    std::vector<std::vector<PngRegion>> regions;
+    bool no_memory = false;
+    double diff_ms = 0;
+    if (!png_diff_run(c, n, canvases, n_frames, width, height, format, regions, s, &no_memory, &diff_ms)) return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    // ---- where every frame's pixels are: frame 0 and the regions as wide as the canvas in place, the others cropped
+    std::vector<const void *> f_px(M), f_packed(M);
+    std::vector<void *> f_zs(M);
+    std::vector<int64_t> f_w(M), f_h(M), f_zcap(M), f_zlen(M, 0), f_unmatched(M, 0);
+    std::vector<int> f_bits(M), f_il(M), f_filter(M), f_st(M, ZS_STREAM_ERROR);
+    size_t crop_total = 0, pack_total = 0, z_total = 0;
+    auto round256 = [](int64_t v) { return ((size_t)v + 255) & ~(size_t)255; };
+    for (int i = 0; i < n; i++)
+        for (int f = 0; f < n_frames[i]; f++) {
+            const size_t j = (size_t)fr0[(size_t)i] + (size_t)f;
+            const PngRegion &r = regions[(size_t)i][(size_t)f];
+            const int bits = ch[(size_t)i].bd * png_channels(ch[(size_t)i].ct), il = interlace ? interlace[i] : 0;
+            f_w[j] = r.w, f_h[j] = r.h, f_bits[j] = bits, f_il[j] = il, f_filter[j] = filter[i];
+            f_zcap[j] = zs_deflate_bound(zs_png_idat_layout(r.w, r.h, bits, il, nullptr, nullptr));
+            if (r.w != width[i]) crop_total += round256(r.w * r.h * px);
+            pack_total += round256(png_bits_row_bytes(r.w, bits) * r.h), z_total += round256(f_zcap[j]);
+        }
+    if (!ensure(c, c->png_crop, crop_total + 256) || !ensure(c, c->png_packed, pack_total + 256) || !ensure(c, c->png_zs, z_total + 256)) return all_fail(ZS_MEM_ERROR);
+    PngCropJob kjob;
+    PngPackJob gjob;
+    {
+        size_t k_at = 0, g_at = 0, z_at = 0;
+        for (int i = 0; i < n; i++) {
+            const PngChosen &h = ch[(size_t)i];
+            const int64_t rb = width[i] * px, canvas = rb * height[i];
+            int32_t table = -1;
+            for (int f = 0; f < n_frames[i]; f++) {
+                const size_t j = (size_t)fr0[(size_t)i] + (size_t)f;
+                const PngRegion &r = regions[(size_t)i][(size_t)f];
+                const uint8_t *cv = (const uint8_t *)canvases[i] + (int64_t)f * canvas;
+                if (r.w == width[i]) f_px[j] = cv + r.y * rb;
+                else {
+                    uint8_t *to = (uint8_t *)c->png_crop.p + k_at;
+                    kjob.add(cv, width[i], r.x, r.y, r.w, r.h, px, to);
+                    f_px[j] = to, k_at += round256(r.w * r.h * px);
+                }
+                f_packed[j] = (uint8_t *)c->png_packed.p + g_at, g_at += round256(png_bits_row_bytes(r.w, f_bits[j]) * r.h);
+                f_zs[j] = (uint8_t *)c->png_zs.p + z_at, z_at += round256(f_zcap[j]);
+                gjob.add(f_px[j], (void *)f_packed[j], r.w, r.h, h.bd, h.ct, format, h.plte.data(), h.entries, h.tlen > 0 ? h.trns.data() : nullptr, h.tlen, table);
+                if (h.ct == 3) table = gjob.img.back().pal_off;  // (the animation's frames share its table)
+            }
+        }
+    }
+    if (!kjob.img.empty() && !png_crop_run(c, kjob, px, s, &no_memory)) return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    if (!png_pack_run(c, gjob, format, any_palette ? f_unmatched.data() : nullptr, s, &no_memory)) return all_fail(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    // ---- every frame's stream
+    const int zrc = zs_png_idat_interlace_batch_device(c, (int)M, f_packed.data(), f_w.data(), f_h.data(), f_bits.data(), f_il.data(), f_filter.data(), rows_per_write,
+                                                       f_zs.data(), f_zcap.data(), f_zlen.data(), f_st.data(), level, strategy, hash_variant, (void *)s);
+    auto stages = [&]() {
+        if (c->profiling) c->stage_ms[kStPngSurvey] = survey_ms, c->stage_ms[kStPngDiff] = diff_ms, c->stage_ms[kStPngCrop] = kjob.ms, c->stage_ms[kStPngPack] = gjob.ms;
+    };
+    std::vector<int> st((size_t)n, ZS_OK);
+    rc = zrc;  // (its message stands)
+    auto fail_anim = [&](int i, int code, const std::string &why) {
+        if (st[(size_t)i] == ZS_OK) st[(size_t)i] = code, out_len[i] = 0;
+        if (rc == ZS_OK) rc = code, c->err = why;
+    };
+    auto finish = [&]() {
+        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
+        stages();
+        return rc;
+    };
+    // ---- the layout: which animations fit, and their spans
+    int64_t n_spans = 0;
+    for (int i = 0; i < n; i++) {
+        out_len[i] = 0;
+        int64_t need = 8 + 25 + (int64_t)ch[(size_t)i].xs.size() + (n_frames[i] > 1 ? kPngActlBytes + kPngFctlBytes : 0) + 12, spans = 2;
+        for (int f = 0; f < n_frames[i]; f++) {
+            const size_t j = (size_t)fr0[(size_t)i] + (size_t)f;
+            if (f_unmatched[j] != 0)
+                fail_anim(i, ZS_STREAM_ERROR, "stream error: animation " + std::to_string(i) + ": internal error: " + std::to_string(f_unmatched[j]) + " pixels of frame " +
+                                                  std::to_string(f) + " have no entry in the palette made from the animation's own colours");
+            else if (f_st[j] != ZS_OK) fail_anim(i, f_st[j], "stream error: animation " + std::to_string(i) + ": frame " + std::to_string(f) + ": the deflate failed");
+            int64_t step = 0;
+            const int64_t chunks = png_anim_chunks(f_zlen[j], idat_chunk_bytes, f > 0, &step);
+            if (chunks < 0) {  // (one chunk cannot hold the stream: unreachable below 2 GiB)
+                fail_anim(i, ZS_STREAM_ERROR, "stream error");
+                break;
+            }
+            need += f_zlen[j] + (f > 0 ? kPngFctlBytes + 16 * chunks : 12 * chunks), spans += chunks + (f > 0 ? 1 : 0);
+            if (frames_out) {
+                const PngRegion &r = regions[(size_t)i][(size_t)f];
+                zs_png_frame &o = frames_out[i][f];
+                o.x = r.x, o.y = r.y, o.width = r.w, o.height = r.h, o.delay_num = delay_num[i][f], o.delay_den = delay_den[i][f];
+                o.dispose_op = kPngDisposeNone, o.blend_op = kPngBlendSource, o.data_bytes = f_zlen[j], o.n_chunks = chunks;
+            }
+        }
+        if (st[(size_t)i] != ZS_OK) continue;
+        out_len[i] = need;
+        if (out_cap[i] < need) {
+            st[(size_t)i] = ZS_BUF_ERROR;
+            if (rc == ZS_OK) rc = ZS_BUF_ERROR, c->err = "buffer error";
+            continue;
+        }
+        n_spans += spans;
+    }
+    if (n_spans > 0x3FFFFFFF) {
+        c->err = "stream error: too many IDAT and fdAT chunks in one call";
+        for (int &v : st)
+            if (v == ZS_OK) v = ZS_STREAM_ERROR;
+        rc = ZS_STREAM_ERROR;
+        return finish();
+    }
+    if (n_spans == 0) return finish();
+    size_t x_total = 0;  // the host's bytes of the files: everything but the streams
+    for (int i = 0; i < n; i++)
+        if (st[(size_t)i] == ZS_OK) x_total += 8 + 25 + ch[(size_t)i].xs.size() + (size_t)kPngActlBytes + (size_t)kPngFctlBytes * (size_t)n_frames[i] + 12;
+    Crc32Job job;
+    if (!crc32_begin(c, (int)n_spans, x_total, &job, &no_memory)) {
+        for (int &v : st)
+            if (v == ZS_OK) v = no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+        rc = no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
+        return finish();
+    }
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+    static const uint8_t idat_type[4] = {'I', 'D', 'A', 'T'};
+    const uint32_t idat_init = ~crc32_bytes_slow(0, idat_type, 4);
+    auto put_chunk = [](uint8_t *to, const char *type, const uint8_t *data, uint32_t len) {  // -> the chunk's bytes
+        png_put_be32(to, len);
+        memcpy(to + 4, type, 4);
+        memcpy(to + 8, data, len);
+        png_put_be32(to + 8 + len, crc32_bytes_slow(0, to + 4, 4 + (uint64_t)len));
+        return (int64_t)len + 12;
+    };
+    size_t k = 0, b = 0;
+    for (int i = 0; i < n; i++) {
+        if (st[(size_t)i] != ZS_OK) continue;
+        uint8_t *o = (uint8_t *)out[i];
+        const std::vector<uint8_t> &xs = ch[(size_t)i].xs;
+        uint32_t seq = 0;
+        auto put_fctl = [&](uint8_t *to, int f) {
+            const PngRegion &r = regions[(size_t)i][(size_t)f];
+            uint8_t d[26];
+            png_put_be32(d, seq++), png_put_be32(d + 4, (uint32_t)r.w), png_put_be32(d + 8, (uint32_t)r.h), png_put_be32(d + 12, (uint32_t)r.x), png_put_be32(d + 16, (uint32_t)r.y);
+            d[20] = (uint8_t)(delay_num[i][f] >> 8), d[21] = (uint8_t)delay_num[i][f], d[22] = (uint8_t)(delay_den[i][f] >> 8), d[23] = (uint8_t)delay_den[i][f];
+            d[24] = kPngDisposeNone, d[25] = kPngBlendSource;
+            return put_chunk(to, "fcTL", d, 26);
+        };
+        // signature, IHDR, the caller's chunks, PLTE, tRNS, acTL and frame 0's fcTL: host bytes, placed by a copy span
+        uint8_t *hd = job.blob + b;
+        memcpy(hd, sig, 8);
+        uint8_t ih[13];
+        png_put_be32(ih, (uint32_t)width[i]), png_put_be32(ih + 4, (uint32_t)height[i]);
+        ih[8] = (uint8_t)ch[(size_t)i].bd, ih[9] = (uint8_t)ch[(size_t)i].ct, ih[10] = 0, ih[11] = 0, ih[12] = (uint8_t)(interlace ? interlace[i] : 0);
+        int64_t head = 8 + put_chunk(hd + 8, "IHDR", ih, 13);
+        if (!xs.empty()) memcpy(hd + head, xs.data(), xs.size());
+        head += (int64_t)xs.size();
+        if (n_frames[i] > 1) {
+            uint8_t ac[8];
+            png_put_be32(ac, (uint32_t)n_frames[i]), png_put_be32(ac + 4, (uint32_t)n_plays[i]);
+            head += put_chunk(hd + head, "acTL", ac, 8);
+            head += put_fctl(hd + head, 0);
+        }
+        job.spans[k++] = Crc32Span{job.d_blob + b, o, nullptr, head, 0xFFFFFFFFu, 0, 0, 0};
+        b += (size_t)head;
+        int64_t pos = head;
+        for (int f = 0; f < n_frames[i]; f++) {
+            const size_t j = (size_t)fr0[(size_t)i] + (size_t)f;
+            if (f > 0) {
+                const int64_t len = put_fctl(job.blob + b, f);
+                job.spans[k++] = Crc32Span{job.d_blob + b, o + pos, nullptr, len, 0xFFFFFFFFu, 0, 0, 0};
+                b += (size_t)len, pos += len;
+            }
+            int64_t step = 0, zat = 0;
+            (void)png_anim_chunks(f_zlen[j], idat_chunk_bytes, f > 0, &step);
+            const int64_t zl = f_zlen[j];
+            do {
+                const int64_t len = std::min(step, zl - zat);
+                const uint8_t *src = (const uint8_t *)f_zs[j] + zat;
+                if (f == 0) {
+                    job.spans[k++] = Crc32Span{src, o + pos + 8, o + pos, len, idat_init, 0, kPngIDAT, 0};
+                    pos += 12 + len;
+                } else {  // fdAT: the register starts behind the type and the sequence number
+                    uint8_t tp[8] = {'f', 'd', 'A', 'T'};
+                    png_put_be32(tp + 4, seq);
+                    job.spans[k++] = Crc32Span{src, o + pos + 12, o + pos, len, ~crc32_bytes_slow(0, tp, 8), 0, kPngfdAT, seq, 1, 0};
+                    seq++, pos += 16 + len;
+                }
+                zat += len;
+            } while (zat < zl);
+        }
+        uint8_t *tl = job.blob + b;
+        const int64_t end = put_chunk(tl, "IEND", tl, 0);
+        job.spans[k++] = Crc32Span{job.d_blob + b, o + pos, nullptr, end, 0xFFFFFFFFu, 0, 0, 0};
+        b += (size_t)end;
+    }
+    if (!crc32_run(c, &job, s)) {
+        for (int &v : st)
+            if (v == ZS_OK) v = ZS_STREAM_ERROR;
+        rc = ZS_STREAM_ERROR;
+        return finish();
+    }
+    if (c->profiling) c->stage_ms[kStCrc32] = job.ms;
+    return finish();
 }
 
 // ------------------------------------------------------------------ multi-GPU batch entry points

@@ -873,5 +873,125 @@ ZS_HD void png_compose_group(const PngComposeAnim &a, const PngComposeFrame *fra
     }
 }
 
+// ---- the frame diff (KD, zs_png.hip, and its host model tests/cpp/test_png_diff.cpp): KM's counterpart on the way out ----
+// Frame f >= 1 of an animation that is written from its canvases is the smallest rectangle that holds every pixel whose
+// bytes differ between canvas f - 1 and canvas f; drawn with blend SOURCE under dispose NONE it turns the one into the other.
+// KD has KM's grid: a wave per stretch of 64 groups of a canvas row, a lane per group of 16 bytes, fixed by column.  The lane
+// keeps canvas f - 1's group in registers and loads canvas f's (png_diff_load), so every canvas is read once; whether and
+// where the two differ inside the group is png_diff_group; the wave's __ballot of "differs" gives the first and the last
+// differing lane, and those two lanes' first / last differing pixel close the wave's record for the frame (png_diff_record):
+// the differing columns of one stretch of one row.  A second launch folds a frame's records into its rectangle
+// (png_diff_merge, png_diff_finish).
+struct PngDiffAnim {
+    const uint8_t *in;  // n_frames canvases of height rows of width * png_expand_bytes(format) bytes back to back, aligned to a pixel
+    int64_t rec0;       // its first record: frame f's records are the waves' [rec0 + (f - 1) * waves, + waves)
+    int32_t width, height;
+    int32_t n_frames, pad;
+};
+struct PngDiffRec {
+    int32_t x0, x1;  // the first and the last differing column of the stretch; x0 > x1: none
+};
+struct PngDiffRect {
+    int32_t x0, y0, x1, y1;  // inclusive; x0 > x1: no pixel differs
+};
+ZS_HD PngDiffRec png_diff_none() { return PngDiffRec{0x7FFFFFFF, -1}; }
+ZS_HD PngDiffRect png_diff_empty() { return PngDiffRect{0x7FFFFFFF, 0x7FFFFFFF, -1, -1}; }
+
+// The group of pixels [x0, x0 + N) of a canvas row, `p` its first pixel: one 16-byte load where the group is whole and the
+// address allows, pixel loads elsewhere (a canvas whose size is no multiple of 16 shifts every later canvas's alignment).
+// Pixels beyond the row are zero.  Nothing outside the row is read.
+template <int F>
+ZS_HD void png_diff_load(const uint8_t *p, int64_t x0, int64_t width, uint64_t v[2]) {
+    constexpr int P = png_expand_bytes(F), N = kPngComposeGroup / P;
+    if (x0 + N <= width && ((uint64_t)(uintptr_t)p & (kPngComposeGroup - 1)) == 0) {
+        __builtin_memcpy(v, __builtin_assume_aligned(p, kPngComposeGroup), kPngComposeGroup);
+        return;
+    }
+    v[0] = 0, v[1] = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < N; j++)
+        if (x0 + j < width) {
+            const uint64_t px = png_compose_load<F>(p + j * P);
+            if constexpr (F == ZS_PNG_FMT_RGBA8) v[j >> 1] |= px << (32 * (j & 1));
+            else v[j] = px;
+        }
+}
+
+// Do the two groups differ in any byte, and if so, which are the first and the last differing pixel (0 .. N - 1)?
+template <int F>
+ZS_HD bool png_diff_group(const uint64_t a[2], const uint64_t b[2], int *first, int *last) {
+    const uint64_t d0 = a[0] ^ b[0], d1 = a[1] ^ b[1];
+    if ((d0 | d1) == 0) return false;
+    if constexpr (F == ZS_PNG_FMT_RGBA8) {
+        const uint32_t m = ((uint32_t)d0 != 0 ? 1u : 0u) | ((d0 >> 32) != 0 ? 2u : 0u) | ((uint32_t)d1 != 0 ? 4u : 0u) | ((d1 >> 32) != 0 ? 8u : 0u);
+        *first = __builtin_ctz(m), *last = 31 - __builtin_clz(m);
+    } else {
+        *first = d0 ? 0 : 1, *last = d1 ? 1 : 0;
+    }
+    return true;
+}
+// the first and the last set lane of a wave's ballot (mask != 0)
+ZS_HD int png_diff_first_lane(uint64_t mask) { return __builtin_ctzll(mask); }
+ZS_HD int png_diff_last_lane(uint64_t mask) { return 63 - __builtin_clzll(mask); }
+// The wave's record: lanes lo and hi are the first and the last whose group differs, `first_lo` and `last_hi` what
+// png_diff_group gave those two; g0 is the stretch's first group and n the pixels of a group.
+ZS_HD PngDiffRec png_diff_record(int lo, int hi, int64_t g0, int n, int first_lo, int last_hi) {
+    return PngDiffRec{(int32_t)((g0 + lo) * n + first_lo), (int32_t)((g0 + hi) * n + last_hi)};
+}
+// a record of row y folded into a rectangle; two rectangles folded into one
+ZS_HD PngDiffRect png_diff_merge(PngDiffRect r, PngDiffRec c, int32_t y) {
+    if (c.x0 > c.x1) return r;
+    return PngDiffRect{c.x0 < r.x0 ? c.x0 : r.x0, y < r.y0 ? y : r.y0, c.x1 > r.x1 ? c.x1 : r.x1, y > r.y1 ? y : r.y1};
+}
+ZS_HD PngDiffRect png_diff_union(PngDiffRect a, PngDiffRect b) {
+    return PngDiffRect{a.x0 < b.x0 ? a.x0 : b.x0, a.y0 < b.y0 ? a.y0 : b.y0, a.x1 > b.x1 ? a.x1 : b.x1, a.y1 > b.y1 ? a.y1 : b.y1};
+}
+// ... and the frame's region: APNG has no empty frame, so no difference is the 1 x 1 rectangle at (0, 0)
+ZS_HD void png_diff_finish(PngDiffRect r, int64_t *x, int64_t *y, int64_t *width, int64_t *height) {
+    if (r.x0 > r.x1) *x = 0, *y = 0, *width = 1, *height = 1;
+    else *x = r.x0, *y = r.y0, *width = (int64_t)r.x1 - r.x0 + 1, *height = (int64_t)r.y1 - r.y0 + 1;
+}
+
+// ---- the crop (zs_png.hip zs_png_crop_kernel): a rectangle of an image as tight rows ----
+struct PngCropImg {
+    const uint8_t *in;  // the rectangle's first pixel in the image, aligned to a pixel
+    uint8_t *out;       // height rows of width * P bytes, aligned to a pixel
+    int64_t in_pitch;   // bytes from one image row to the next
+    int32_t width, height;
+};
+// Bytes [b0, b0 + 16) of output row y (`dst` = the row's first byte, `rb` its length; dst + b0 is 16-aligned, and dst is
+// aligned to a pixel of P bytes, so a group holds whole pixels).  A whole group is one 16-byte store, fed by one 16-byte
+// load where source and destination agree modulo 16 and by pixel loads elsewhere; the ragged first and last group of a row
+// go pixel by pixel.  No byte outside the row is touched, in or out.
+template <int P>
+ZS_HD void png_crop_group(const PngCropImg &im, int64_t y, int64_t rb, uint8_t *dst, int64_t b0) {
+    static_assert(P == 4 || P == 8, "a pixel is RGBA8 or RGBA16");
+    const int64_t lo = b0 < 0 ? 0 : b0, hi = b0 + 16 < rb ? b0 + 16 : rb;
+    const uint8_t *src = im.in + y * im.in_pitch;
+    if (lo == b0 && hi == b0 + 16) {
+        uint64_t v[2];
+        if (((uint64_t)(uintptr_t)(src + b0) & 15) == 0) __builtin_memcpy(v, __builtin_assume_aligned(src + b0, 16), 16);
+        else if constexpr (P == 8) {
+            __builtin_memcpy(&v[0], __builtin_assume_aligned(src + b0, 8), 8);
+            __builtin_memcpy(&v[1], __builtin_assume_aligned(src + b0 + 8, 8), 8);
+        } else {
+            uint32_t w[4];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int j = 0; j < 4; j++) __builtin_memcpy(&w[j], __builtin_assume_aligned(src + b0 + 4 * j, 4), 4);
+            v[0] = w[0] | (uint64_t)w[1] << 32, v[1] = w[2] | (uint64_t)w[3] << 32;
+        }
+        __builtin_memcpy(__builtin_assume_aligned(dst + b0, 16), v, 16);
+    } else
+        for (int64_t b = lo; b < hi; b += P) {
+            uint64_t px = 0;
+            __builtin_memcpy(&px, __builtin_assume_aligned(src + b, P), P);
+            __builtin_memcpy(__builtin_assume_aligned(dst + b, P), &px, P);
+        }
+}
+
 
 }  // namespace zs

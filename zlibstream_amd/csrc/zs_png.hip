@@ -1,4 +1,4 @@
-// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip); KA, KS, KX, KG, KV and KM behind it.  What inflate leaves for
+// zs_png.hip -- KU: PNG scanline reconstruction on the device, the inverse of KP (zs_kernels.hip); KA, KS, KX, KG, KV, KM, KD and the crop behind it.  What inflate leaves for
 // an IDAT payload is, per row, a filter-type byte and the filtered bytes; reconstruction reads reconstructed neighbours
 // (left, above, above-left), so it is serial along a row and across rows.  Two kernels:
 //   zs_png_scan_kernel      one workgroup per image over its type bytes: the first invalid one, and the segments
@@ -518,6 +518,92 @@ __global__ __launch_bounds__(64 * kComposeWavesPerWg) void zs_png_compose_kernel
     const uint32_t local = (uint32_t)(t - wave_off[i]), per_row = (uint32_t)png_compose_row_waves(a.width, F);
     const int64_t y = local / per_row, g = (int64_t)(local % per_row) * 64 + lane;
     if (g * N < a.width) png_compose_group<F>(a, frames, y, g * N);
+}
+
+// KD: the frame diff (zs_png.h png_diff_*), KM's counterpart on the way out and on KM's grid: the flat list of all
+// animations' canvas rows, every row cut into stretches of 64 groups of 16 bytes, a wave per stretch, four waves a
+// workgroup.  A lane carries its group through canvases 0 .. F-1 in registers: it loads canvas f's group -- the load of
+// canvas f + 1 is issued before canvas f is compared -- and compares it with canvas f - 1's, so every canvas is read once.
+// Per frame the wave's answer is a __ballot of "my group differs": the first and the last set lane hand over their first and
+// last differing pixel (readlane: the lane numbers are uniform), and lane 0 stores the wave's record into the wave's own slot
+// of the frame.  The frame loop's trip count is uniform over the wave, and every lane stays in it: a lane beyond the row
+// loads nothing and never differs.  No atomics, no LDS, no traffic between waves: no record has two writers.  An animation of
+// one frame has no waves in the list.
+constexpr int kDiffWavesPerWg = 4;
+
+template <int F>
+__global__ __launch_bounds__(64 * kDiffWavesPerWg) void zs_png_diff_kernel(const PngDiffAnim *__restrict__ anims, const int32_t *__restrict__ wave_off, int n,
+                                                                           int64_t wave0, PngDiffRec *__restrict__ recs) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    const int64_t t = wave0 + (int64_t)blockIdx.x * kDiffWavesPerWg + w;
+    if (t >= (int64_t)wave_off[n]) return;
+    const int i = __builtin_amdgcn_readfirstlane(png_row_image(wave_off, n, t));
+    const PngDiffAnim a = anims[i];
+    constexpr int P = png_expand_bytes(F), N = kPngComposeGroup / P;
+    const uint32_t local = (uint32_t)(t - wave_off[i]), per_row = (uint32_t)png_compose_row_waves(a.width, F);
+    const int64_t y = local / per_row, g0 = (int64_t)(local % per_row) * 64, x0 = (g0 + lane) * N;
+    const int64_t rb = (int64_t)a.width * P, canvas = rb * a.height, waves = (int64_t)a.height * per_row;
+    const bool mine = x0 < a.width;
+    const uint8_t *p = a.in + y * rb + x0 * P;
+    uint64_t prev[2] = {0, 0}, next[2] = {0, 0};
+    if (mine) {
+        png_diff_load<F>(p, x0, a.width, prev);
+        png_diff_load<F>(p + canvas, x0, a.width, next);  // (the list holds animations of two frames and more only)
+    }
+    PngDiffRec *out = recs + a.rec0 + local;
+    for (int f = 1; f < a.n_frames; f++, out += waves) {
+        const uint64_t cur[2] = {next[0], next[1]};
+        if (mine && f + 1 < a.n_frames) png_diff_load<F>(p + (int64_t)(f + 1) * canvas, x0, a.width, next);
+        int first = 0, last = 0;
+        const bool differs = mine && png_diff_group<F>(prev, cur, &first, &last);
+        prev[0] = cur[0], prev[1] = cur[1];
+        const uint64_t mask = __ballot(differs);
+        PngDiffRec rec = png_diff_none();
+        if (mask) {  // (uniform)
+            const int lo = png_diff_first_lane(mask), hi = png_diff_last_lane(mask);
+            rec = png_diff_record(lo, hi, g0, N, __builtin_amdgcn_readlane(first, lo), __builtin_amdgcn_readlane(last, hi));
+        }
+        if (lane == 0) *out = rec;
+    }
+}
+
+// ... its second launch: one workgroup per (animation, frame >= 1) folds the frame's records, one per wave of the first
+// launch, into the frame's rectangle.  Minima and maxima only: the result does not depend on the order.
+__global__ __launch_bounds__(256) void zs_png_diff_merge_kernel(const PngDiffAnim *__restrict__ anims, const int32_t *__restrict__ pair_off, int n, int format,
+                                                                const PngDiffRec *__restrict__ recs, PngDiffRect *__restrict__ rects) {
+    __shared__ PngDiffRect s_part[4];
+    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t pair = (int64_t)blockIdx.x;
+    const int i = png_row_image(pair_off, n, pair);
+    const PngDiffAnim a = anims[i];
+    const int64_t per_row = png_compose_row_waves(a.width, format), waves = (int64_t)a.height * per_row;
+    const PngDiffRec *base = recs + a.rec0 + (pair - pair_off[i]) * waves;
+    PngDiffRect r = png_diff_empty();
+    for (int64_t k = tid; k < waves; k += 256) r = png_diff_merge(r, base[k], (int32_t)(k / per_row));
+    for (int o = 32; o > 0; o >>= 1) r = png_diff_union(r, PngDiffRect{__shfl_xor(r.x0, o), __shfl_xor(r.y0, o), __shfl_xor(r.x1, o), __shfl_xor(r.y1, o)});
+    if (lane == 0) s_part[w] = r;
+    __syncthreads();
+    if (tid == 0) rects[pair] = png_diff_union(png_diff_union(s_part[0], s_part[1]), png_diff_union(s_part[2], s_part[3]));
+}
+
+// The crop (zs_png.h png_crop_group): rectangles of images as tight rows, shaped like KX.  The grid is the flat list of all
+// output rows, four rows a workgroup: wave w takes row 4 * block + w, and its lanes the row's address-aligned groups of 16
+// output bytes, 64 at a time -- one full-width store per lane, contiguous over the wave, fed by one 16-byte load where source
+// and destination agree modulo 16 and by pixel loads elsewhere.  No atomics, no LDS: no output byte has two writers.
+constexpr int kCropRowsPerWg = 4;
+
+template <int P>
+__global__ __launch_bounds__(64 * kCropRowsPerWg) void zs_png_crop_kernel(const PngCropImg *__restrict__ imgs, const int32_t *__restrict__ row_off, int n, int64_t row0) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    const int64_t r = row0 + (int64_t)blockIdx.x * kCropRowsPerWg + w;
+    if (r >= (int64_t)row_off[n]) return;
+    const int i = __builtin_amdgcn_readfirstlane(png_row_image(row_off, n, r));
+    const PngCropImg im = imgs[i];
+    const int64_t y = r - row_off[i], rb = (int64_t)im.width * P;
+    uint8_t *dst = im.out + y * rb;
+    const uint64_t addr = (uint64_t)(uintptr_t)dst;
+    const int64_t ng = adam7_row_groups(addr, rb, 16), b0 = adam7_row_b0(addr, 16);
+    for (int64_t g = lane; g < ng; g += 64) png_crop_group<P>(im, y, rb, dst, b0 + g * 16);
 }
 
 }  // namespace zs
