@@ -126,7 +126,15 @@ ZS_API int zs_deflate_batch(zs_ctx *ctx, int n, const void *const *in, const int
  * zlib streams, each decoded completely (what `new ZlibInputStream(src).Read(...)` to the end of the stream
  * yields, ZlibInputStream.cs:133-186).  out_cap[i] must hold the whole output.  status[i] is ZS_STREAM_END on
  * success; ZS_DATA_ERROR / ZS_BUF_ERROR / ZS_NEED_DICT with the reference's message in zs_ctx_last_error
- * otherwise (e.g. "incorrect data check", Inflate.cs:339).  Returns ZS_OK when every stream ended cleanly. */
+ * otherwise (e.g. "incorrect data check", Inflate.cs:339).  Returns ZS_OK when every stream ended cleanly, else the
+ * code of the first failing stream in the caller's order; zs_ctx_last_error is that same stream's message, whichever
+ * of the library's paths decoded it.  A failing stream fails for itself only: its neighbours are complete.
+ * out_len[i] of a failing stream: the bytes of the tokens (a literal, a whole match, a whole stored block) that were
+ * decoded in full before the failure and fitted out_cap[i]; out[i][0 .. out_len[i]) holds them, and they are a prefix
+ * of what the stream would have given.  So 0 for a refused header, the whole output for a bad Adler-32, and for a
+ * truncated stream or a short out_cap[i] (ZS_BUF_ERROR, "buffer error") everything in front of the token that the
+ * input or the room ended in -- never more than out_cap[i].  Bytes of out[i] behind out_len[i], up to out_cap[i], are
+ * unspecified; nothing is written at or behind out[i] + out_cap[i]. */
 ZS_API int zs_inflate_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *in_len, void *const *out,
                                    const int64_t *out_cap, int64_t *out_len, int *status, void *hip_stream);
 ZS_API int zs_inflate_batch(zs_ctx *ctx, int n, const void *const *in, const int64_t *in_len, void *const *out,

@@ -1773,7 +1773,7 @@ const char *const kInfMessages[kInfMsgCount] = {
     "invalid literal/length code", "invalid distance code", "buffer error", "buffer error", "incorrect data check"};
 
 bool run_inflate_seq(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out, const int64_t *out_cap,
-                 int64_t *out_len, int *status, hipStream_t stream, uint32_t *adler_out = nullptr) {
+                 int64_t *out_len, int *status, hipStream_t stream, uint32_t *adler_out = nullptr, int *msg_out = nullptr) {
     std::vector<InfDesc> d((size_t)n);
     for (int i = 0; i < n; i++) d[(size_t)i] = {(const uint8_t *)in[i], (uint8_t *)out[i], in_len[i], out_cap[i]};
     if (!ensure(c, c->inf_desc, sizeof(InfDesc) * (size_t)n) || !ensure(c, c->inf_state, sizeof(InfState) * (size_t)n)) return false;
@@ -1814,6 +1814,7 @@ bool run_inflate_seq(zs_ctx *c, int n, const void *const *in, const int64_t *in_
         out_len[i] = st[(size_t)i].out_len;
         const int code = st[(size_t)i].status;
         if (status) status[i] = code;
+        if (msg_out) msg_out[i] = st[(size_t)i].msg;
         if (code != ZS_STREAM_END) {
             if (all_ok) c->err = kInfMessages[st[(size_t)i].msg];
             all_ok = false;
@@ -1850,7 +1851,7 @@ constexpr int64_t kParMinInput = 1024;
 // Block-parallel path for the streams listed in `idx`; streams it cannot handle are appended to `rest`.
 bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *in, const int64_t *in_len, void *const *out,
                      const int64_t *out_cap, int64_t *out_len, int *status, hipStream_t stream, std::vector<int> &rest,
-                     uint32_t *adler_out = nullptr) {
+                     uint32_t *adler_out = nullptr, int *msg_out = nullptr) {
     const int m = (int)idx.size();
     c->inf_lane_streams = 0;
     c->inf_wave_streams = 0;
@@ -2126,6 +2127,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
         if (adler_out) adler_out[i] = ads[k];
         if (!aok[k]) {
             status[i] = ZS_DATA_ERROR;
+            if (msg_out) msg_out[i] = kInfBadCheck;
             c->err = kInfMessages[kInfBadCheck];
         }
     }
@@ -2137,8 +2139,8 @@ bool run_inflate(zs_ctx *c, int n, const void *const *in, const int64_t *in_len,
     std::vector<int> par, seq;
     static const int64_t par_min = getenv("ZS_INF_PAR_MIN") ? atoll(getenv("ZS_INF_PAR_MIN")) : kParMinInput;
     for (int i = 0; i < n; i++) (in_len[i] >= par_min ? par : seq).push_back(i);
-    std::vector<int> st((size_t)n, 0);
-    if (!run_inflate_par(c, par, in, in_len, out, out_cap, out_len, st.data(), stream, seq, adler_out)) return false;
+    std::vector<int> st((size_t)n, 0), msg((size_t)n, -1);
+    if (!run_inflate_par(c, par, in, in_len, out, out_cap, out_len, st.data(), stream, seq, adler_out, msg.data())) return false;
     bool ok = true;
     for (int i : par)
         if (std::find(seq.begin(), seq.end(), i) == seq.end() && st[(size_t)i] != ZS_STREAM_END) ok = false;
@@ -2147,15 +2149,22 @@ bool run_inflate(zs_ctx *c, int n, const void *const *in, const int64_t *in_len,
         std::vector<const void *> sin((size_t)m);
         std::vector<void *> sout((size_t)m);
         std::vector<int64_t> slen((size_t)m), scap((size_t)m), solen((size_t)m);
-        std::vector<int> sst((size_t)m);
+        std::vector<int> sst((size_t)m), smsg((size_t)m, -1);
         std::vector<uint32_t> sad((size_t)m, 1u);
         for (int j = 0; j < m; j++) sin[(size_t)j] = in[seq[(size_t)j]], sout[(size_t)j] = out[seq[(size_t)j]], slen[(size_t)j] = in_len[seq[(size_t)j]], scap[(size_t)j] = out_cap[seq[(size_t)j]];
-        if (!run_inflate_seq(c, m, sin.data(), slen.data(), sout.data(), scap.data(), solen.data(), sst.data(), stream, sad.data())) ok = false;
+        if (!run_inflate_seq(c, m, sin.data(), slen.data(), sout.data(), scap.data(), solen.data(), sst.data(), stream, sad.data(), smsg.data())) ok = false;
         for (int j = 0; j < m; j++) {
-            out_len[seq[(size_t)j]] = solen[(size_t)j], st[(size_t)seq[(size_t)j]] = sst[(size_t)j];
+            out_len[seq[(size_t)j]] = solen[(size_t)j], st[(size_t)seq[(size_t)j]] = sst[(size_t)j], msg[(size_t)seq[(size_t)j]] = smsg[(size_t)j];
             if (adler_out) adler_out[seq[(size_t)j]] = sad[(size_t)j];
         }
     }
+    // the call's message is that of its first failing stream in the caller's order, as its code is: the block-parallel pass and
+    // the one-wave decoder each leave the message of the first stream that failed with them, and either may come first
+    for (int i = 0; i < n; i++)
+        if (st[(size_t)i] != ZS_STREAM_END) {
+            if (msg[(size_t)i] > 0) c->err = kInfMessages[msg[(size_t)i]];
+            break;
+        }
     if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
     return ok;
 }

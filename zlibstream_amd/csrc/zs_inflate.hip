@@ -336,7 +336,12 @@ __global__ __launch_bounds__(64) void zs_inflate_kernel(const InfDesc *descs, In
                 if (b.bad) INF_FAIL(ZS_BUF_, kInfTruncated);
                 b.fill();
                 uint16_t e = T.lit[b.peek(7)];
-                if (e == kInfEsc || (int)(e & 15) > b.cnt) INF_FAIL(b.cnt < 7 && b.pos >= b.n ? ZS_BUF_ : ZS_DATA_, kInfBadRepeat);
+                if (e == kInfEsc || (int)(e & 15) > b.cnt) {
+                    // as for the literal and distance codes below: bits that ran out inside a code are a truncated stream
+                    // (a code that no symbol has is read to its 15th bit before it is refused)
+                    const bool trunc = b.pos >= b.n && b.cnt < 15;
+                    INF_FAIL(trunc ? ZS_BUF_ : ZS_DATA_, trunc ? kInfTruncated : kInfBadRepeat);
+                }
                 b.drop(e & 15);
                 int sym = e >> 4;
                 if (sym < 16) {
@@ -355,6 +360,7 @@ __global__ __launch_bounds__(64) void zs_inflate_kernel(const InfDesc *descs, In
                     } else {
                         rep = 11 + (int)b.take(7);
                     }
+                    if (b.bad) INF_FAIL(ZS_BUF_, kInfTruncated);  // the repeat count's bits past the end of the input: no count to judge
                     if (idx + rep > nlen + ndist) INF_FAIL(ZS_DATA_, kInfBadRepeat);
                     if (lane < rep) ll[idx + lane] = val;
                     if (lane + 64 < rep) ll[idx + lane + 64] = val;
