@@ -679,7 +679,8 @@ ZS_API int zs_png_encode_anim_batch_device(zs_ctx *ctx, int n, const void *const
  * no tokens: under 4 bits per symbol, or no room for the token buffers); "inf_wave_streams" -- streams of the last inflate call
  * at or above the block-parallel minimum (1 KiB) that the block-parallel pass could not finish and handed to the one-wave decoder
  * (a chain that does not close, a table or list that overflows, a block that reports failure; streams below the minimum go to
- * that decoder without being counted). */
+ * that decoder without being counted); "plan_reused" -- 1 if the last deflate call had the shape of the one before (stream
+ * count, lengths, capacities, level, strategy, hash variant, Write lists) and took its plan instead of planning, 0 if it planned. */
 ZS_API int64_t zs_ctx_counter(const zs_ctx *ctx, const char *name);
 /* (A test hook, not part of the product's surface: declared only where ZS_TESTING is defined.)
  * For the tests: what the parse stage of the last deflate call left for its first stream, copied from the device -- "state"

@@ -113,7 +113,8 @@ class Engine:
         "spec_streams", "spec_fallbacks", "spec_periodic", "spec_wrong_chunks", "png_segments", "inf_lane_streams" (streams of
         the last inflate call whose chain had blocks for the lane decoder: checkpoints and no tokens), "inf_wave_streams"
         (streams of the last inflate call at or above the block-parallel minimum that the block-parallel pass handed to the
-        one-wave decoder; streams below the minimum are not counted)."""
+        one-wave decoder; streams below the minimum are not counted), "plan_reused" (1: the last deflate call had the shape
+        of the one before and took its plan)."""
         return int(self._lib.zs_ctx_counter(self._h, name.encode()))
 
     def stage_ms(self):

@@ -18,6 +18,7 @@
 #include "zs_inflate_tok.hip"
 #include "zs_png.hip"
 #include "zs_crc32.hip"
+#include "zs_plan_key.h"
 
 using namespace zs;
 
@@ -35,6 +36,8 @@ enum Stage {
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
                                            "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
                                            "spec_compact", "png_expand", "png_split", "png_pack", "png_survey", "png_compose", "png_diff", "png_crop"};
+
+struct PlanCache;  // the last deflate call's plan, kept for a same-shaped call (below, ahead of run_pipeline)
 
 }  // namespace
 
@@ -70,7 +73,7 @@ struct zs_ctx {
     hipEvent_t ev[kStCount + 1] = {};
     double stage_ms[kStCount] = {};
     uint32_t *crc_tab = nullptr;
-    DevBuf sd, st, work, wpre, geo, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, tile_bits, pieces, scratch,
+    DevBuf sd, st, work, link, mm, maps, chunk_far, segmap, supmap, seg_entry, seg_symbase, seg_stale, entry, symbase, stale, syms, blk_end, blk_top, blocks, trees, info, tile_bits, pieces, scratch,
         stage_in, stage_out, wr, inf_desc, inf_state, par_ps, par_st, par_work, par_cbits, par_ccnt, par_surv, par_scnt, par_cands, par_tabs, par_toktabs, par_toks, par_ctoks, par_tokstat, par_tails, par_retry, par_fxtab, par_blocks, par_cells,
         par_windows, par_fail, run_syms, run_bits, run_scratch, run_outs, run_fail, adl_tr, adl_res, plan_blk, ins_bits, mm_bak, cut_pos, cut_bkt, win_groups, win_sg, win_maps, win_entries, persist_bak, resume_flag, rle_tiles, own_in, fr_chunks, fr_meta, fr_planes, fr_prov, fr_base, fr_counters, spec_rec, spec_flags, spec_syms, png_img, png_seg, png_ctr, png_fimg, png_scratch, png_a7img, png_inflated, png_passes, crc_desc, crc_res, png_zs, png_gather, png_ximg, png_raw, png_simg, png_split, png_gimg, png_vimg, png_vrec, png_packed, png_cimg, png_frames, png_dimg, png_drec, png_kimg, png_crop;
     uint32_t *crc32_tab = nullptr;        // KC's tables (zs_crc32.h crc32_fill_tables), made at the first CRC-32 call
@@ -93,6 +96,17 @@ struct zs_ctx {
     void *pin_out = nullptr;  // ... and an inflate stream's decoded output (OutBuf)
     size_t pin_out_cap = 0;
     bool pin_out_busy = false;
+    // The plan of the last deflate call (run_pipeline): its host side in `plan`, its descriptors, work-list prefixes and geometry as
+    // they were uploaded in `plan_pin` (pinned; `pinned` is reused inside a call for the verdict and the states), its device side
+    // in `sd` (descriptors, prefixes and geometry back to back) and `work`.  plan_gen counts whatever may have written those:
+    // every buffer that ensure() moves, every call that plans, device_adlers.  The kept plan serves a call only if the count
+    // still is what it was when the plan was kept.
+    PlanCache *plan = nullptr;
+    void *plan_pin = nullptr;
+    size_t plan_pin_cap = 0;
+    uint64_t plan_gen = 0;
+    int plan_reused = 0;  // the last deflate call took the kept plan (zs_ctx_counter)
+    hipEvent_t ev_verdict = nullptr;  // behind the copy of the speculative walk's verdicts: the host waits for it, not for the stream
 };
 
 namespace {
@@ -109,6 +123,7 @@ bool fail(zs_ctx *c, const char *what, hipError_t e) {
 
 bool ensure(zs_ctx *c, DevBuf &b, size_t bytes) {
     if (bytes <= b.cap) return true;
+    c->plan_gen++;  // (a buffer moves: the kept plan's descriptors may point into it)
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
     b.cap = 0;
@@ -128,6 +143,15 @@ bool ensure(zs_ctx *c, DevBuf &b, size_t bytes) {
         }
     }
     b.cap = want;
+    return true;
+}
+bool ensure_plan_pin(zs_ctx *c, size_t bytes) {
+    if (bytes <= c->plan_pin_cap) return true;
+    if (c->plan_pin) (void)hipHostFree(c->plan_pin);
+    c->plan_pin = nullptr;
+    c->plan_pin_cap = 0;
+    ZS_HIP(c, hipHostMalloc(&c->plan_pin, bytes + bytes / 8 + 4096, hipHostMallocDefault));
+    c->plan_pin_cap = bytes + bytes / 8 + 4096;
     return true;
 }
 bool ensure_pinned(zs_ctx *c, size_t bytes) {
@@ -178,6 +202,26 @@ struct Plan {
     std::vector<uint32_t> cl;
     std::vector<BlockRec> plan_blk;                    // level 0: the stored blocks of every stream, stream after stream
     std::vector<int32_t> plan_wr_blk;                  // level 0 under a flush mode: blocks flushed before each Write began
+};
+
+// What a same-shaped call takes over from the call before (zs_plan_key.h): the plan, the places of the work lists in the work
+// array, and what else the launches read of the planning.
+struct PlanCache {
+    PlanKey key, probe;     // the kept plan's key; the current call's
+    Plan pl;
+    bool valid = false;     // pl, plan_pin, sd and work hold a whole plan that was uploaded ...
+    uint64_t gen = 0;       // ... when the context's plan_gen was this
+    // a call that uploaded from plan_pin has not been waited for to its end: set at the upload, cleared behind the call's last
+    // synchronisation -- a call that leaves early (a HIP error, a workspace that does not fit) leaves it set, and the next call plans
+    bool in_flight = false;
+    size_t o[kWorkLists] = {};
+    int64_t link_span = 0;
+    // a plan for the sweeps and for the speculative runs at once (Plan::any_dual) as it was before a call struck one of them
+    bool dual_saved = false;
+    std::vector<StreamDesc> dual_sd;
+    std::vector<FsChunk> dual_fr;
+    int dual_fr_max_n = 0;
+    int64_t dual_n_runs = 0;
 };
 
 template <class T>
@@ -248,6 +292,40 @@ bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len
                 c->err = "flush modes and incremental runs take one stream a call";
                 return false;
             }
+    // A call of the shape of the one before takes its plan (zs_plan_key.h): nothing below down to the descriptor upload depends
+    // on the data.  Left to plan as ever, because what they add to the plan is not the arguments': an incremental run (its
+    // state, the chains it imports), the re-entries of this function (force_seq, force_lit, rounds, a call barred from the
+    // sweeps' rounds), level 0 (the block list on the device) and Writes under a flush mode (the device counts blocks into their
+    // table).  ZS_NO_PLAN_REUSE: every call plans.
+    if (!c->plan) c->plan = new PlanCache();
+    PlanCache &pc = *c->plan;
+    const bool no_rounds_this_call = c->no_rounds_once;
+    c->no_rounds_once = false;
+    c->fast_rounds = 0;
+    c->plan_reused = 0;
+    bool plan_hit = false, plan_keep = false;
+    {
+        bool flush_any = false;
+        std::vector<PlanWritesView> views;
+        std::vector<const PlanWritesView *> view_ptrs;
+        if (any_writes) {
+            views.resize((size_t)n), view_ptrs.assign((size_t)n, nullptr);
+            for (int i = 0; i < n; i++) {
+                const WriteSpec *wr = writes[i];
+                if (!wr) continue;
+                flush_any = flush_any || wr->flushing() || wr->flush.size() != wr->ends.size();
+                views[(size_t)i] = PlanWritesView{wr->ends.data(), wr->flush.data(), wr->ends.size(), wr->chunk, wr->raw};
+                view_ptrs[(size_t)i] = &views[(size_t)i];
+            }
+        }
+        plan_keep = !ro && !rounds && !force_lit && !no_rounds_this_call && force_seq == 0 && level != 0 && !flush_any && !getenv("ZS_NO_PLAN_REUSE");
+        if (plan_keep) {
+            plan_key_fill(pc.probe, n, in_len, out_cap, level, strategy, hash_variant, force_seq, ro != nullptr, rounds, force_lit != nullptr, no_rounds_this_call,
+                          any_writes ? view_ptrs.data() : nullptr, plan_env_read());
+            plan_hit = pc.valid && pc.gen == c->plan_gen && !pc.in_flight && plan_key_equal(pc.key, pc.probe);
+        }
+        if (!plan_hit) pc.valid = false, pc.dual_saved = false, c->plan_gen++;  // (this call writes the buffers the kept plan lives in)
+    }
     // CompressionStrategy.Rle does not look at Write ends: Deflate.Rle.cs leaves a Deflate call as soon as fewer than MAX_MATCH bytes
     // are ahead under NoFlush (:24-38), so every match is measured with a full lookahead whatever the Writes are, and nothing is
     // inserted anywhere.  What a Write end can move is the loop-top at which the window slides -- when it lies within 262 bytes
@@ -294,14 +372,22 @@ bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len
     const int spec_warm = getenv("ZS_SPEC_WARM") ? std::max(0, std::min(4096, atoi(getenv("ZS_SPEC_WARM")))) : kSpecWarm;
     const int64_t spec_min = getenv("ZS_SPEC_MIN") ? std::max<int64_t>(kWindowSize, atoll(getenv("ZS_SPEC_MIN"))) : kSpecMinInput;
     const int spec_corrupt = getenv("ZS_SPEC_CORRUPT") ? atoi(getenv("ZS_SPEC_CORRUPT")) : -1;
+    // (pl and the o_* below are the context's, not this frame's: a re-entry of run_pipeline plans into them again.  Every re-entry
+    // is a `return run_pipeline(...)` -- the outer frame reads none of them afterwards -- and has to stay one.)
+    Plan &pl = pc.pl;
+    size_t &o_clear = pc.o[0], &o_adler = pc.o[1], &o_links = pc.o[2], &o_match = pc.o[3], &o_chunks = pc.o[4], &o_segs = pc.o[5], &o_sups = pc.o[6],
+           &o_blocks = pc.o[7], &o_runs = pc.o[8];
+    // ---- the plan, its workspace and its upload: everything a same-shaped call skips (the body is not indented) ----
+    auto plan_call = [&]() -> bool {
 plan_again:
-    Plan pl;
+    pl = Plan();
     pl.sd.resize((size_t)n);
     // positions per workgroup of the link kernel (each replays 32 Ki positions of warm-up first): long spans for a
     // big batch, shorter ones when that is what it takes to give every CU a workgroup
     int64_t total_len = 0;
     for (int i = 0; i < n; i++) total_len += in_len[i];
     const int64_t link_span = total_len >= (48ll << 20) ? 262144 : total_len >= (24ll << 20) ? 131072 : 65536;
+    pc.link_span = link_span;
     // a speculative run's share of its stream (levels 1-3, image-like data): a run is one wave on one CU, so a batch shorter than
     // 256 runs of 256 KiB is cut finer, down to 64 KiB a run (64 KiB of warm-up in front of each: at most twice the work)
     const int run_chunk = getenv("ZS_FAST_CHUNK") ? std::max(65536, std::min((int)kFastChunk, atoi(getenv("ZS_FAST_CHUNK")) & ~65535))
@@ -532,13 +618,6 @@ plan_again:
         goto plan_again;
     }
     pl.any_dual = allow_dual;
-    c->lit_engine_bytes += pl.lit_bytes;
-    // (a call that runs its batch again -- below: the sweeps after runs that did not verify, a stream moved to the literal engine,
-    // the cut rounds -- counts the plan it ends with, so that a stream adds the same whatever its neighbours made the batch do)
-    auto plan_rerun = [&]() { c->lit_engine_bytes -= pl.lit_bytes; };
-    c->fast_rounds = 0;
-    const bool no_rounds_this_call = c->no_rounds_once;
-    c->no_rounds_once = false;
     if (pl.any_fv && !getenv("ZS_FAST_NO_ROUNDS") && !no_rounds_this_call && !(ro && ro->resume && getenv("ZS_NO_RESUME_ROUNDS"))) {
         // levels 1-3: every stream's parse as rounds over its chunks, all chunks of the batch at once (zs_fast_sweep.h "Rounds"),
         // when that is the shorter way.  One workgroup per stream takes as long as the longest stream at 46 / 35 / 20 MB/s (levels
@@ -604,9 +683,18 @@ plan_again:
     WorkList *const lists[kWorkLists] = {&pl.w_clear, &pl.w_adler, &pl.w_links, &pl.w_match, &pl.w_chunks, &pl.w_segs, &pl.w_sups, &pl.w_blocks, &pl.w_runs};
     for (WorkList *l : lists) l->finish(n);
     // ---- workspace ----
-    size_t n_work = pl.w_clear.size() + pl.w_adler.size() + pl.w_links.size() + pl.w_match.size() + pl.w_chunks.size() +
-                    pl.w_segs.size() + pl.w_sups.size() + pl.w_blocks.size() + pl.w_runs.size();
-    if (!ensure(c, c->sd, sizeof(StreamDesc) * (size_t)n) || !ensure(c, c->st, sizeof(StreamState) * (size_t)n) ||
+    const size_t n_work = pl.w_clear.size() + pl.w_adler.size() + pl.w_links.size() + pl.w_match.size() + pl.w_chunks.size() +
+                          pl.w_segs.size() + pl.w_sups.size() + pl.w_blocks.size() + pl.w_runs.size();
+    // parse-segment tables: [seg_c0 | seg_after | seg_base | seg_S : int32 x n_segs each][seg_cl : int32 x (n_segs + n)]
+    // [cstart : int32 x (n_chunks + n)][head : int32 x n_chunks][cl : u32 x n_cl]
+    const size_t o_segcl = 16 * (size_t)pl.n_segs, o_cstart = o_segcl + 4 * ((size_t)pl.n_segs + (size_t)n),
+                 o_head = o_cstart + 4 * ((size_t)pl.n_chunks + (size_t)n), o_cl = o_head + 4 * (size_t)pl.n_chunks;
+    const size_t geo_bytes = o_cl + 4 * pl.cl.size();
+    // the descriptors, the work lists' prefixes and the tables back to back in one buffer, as they are in the staging area: one
+    // copy brings all three (a same-shaped call sends the descriptors alone)
+    const size_t sd_bytes = sizeof(StreamDesc) * (size_t)n, pre_bytes = 4 * (size_t)kWorkLists * (size_t)(n + 1);
+    const size_t up_bytes = sd_bytes + pre_bytes + geo_bytes;
+    if (!ensure(c, c->sd, up_bytes + 64) || !ensure(c, c->st, sizeof(StreamState) * (size_t)n) ||
         !ensure(c, c->work, sizeof(uint2) * (n_work + 1)) || !ensure(c, c->link, 2 * (size_t)pl.n_pos + 64) ||
         !ensure(c, c->mm, 8 * (size_t)pl.n_pos + 256) ||  // the symbol kernel stages whole 128-byte lines
         !ensure(c, c->maps, 4 * (size_t)(pl.n_chunks + 1) * kSlots) || !ensure(c, c->segmap, 8 * (size_t)(pl.n_segs + 1) * kSlots) ||
@@ -623,16 +711,10 @@ plan_again:
         (pl.n_spec && (!ensure(c, c->spec_rec, 8 * (size_t)pl.n_spec + 64) || !ensure(c, c->spec_flags, 4 * (size_t)n + 64) ||
                        !ensure(c, c->spec_syms, 4 * (size_t)pl.n_spec * (size_t)spec_slab_stride(spec_bits) + 64))))
         return false;
-    // parse-segment tables: [seg_c0 | seg_after | seg_base | seg_S : int32 x n_segs each][seg_cl : int32 x (n_segs + n)]
-    // [cstart : int32 x (n_chunks + n)][head : int32 x n_chunks][cl : u32 x n_cl]
-    const size_t o_segcl = 16 * (size_t)pl.n_segs, o_cstart = o_segcl + 4 * ((size_t)pl.n_segs + (size_t)n),
-                 o_head = o_cstart + 4 * ((size_t)pl.n_chunks + (size_t)n), o_cl = o_head + 4 * (size_t)pl.n_chunks;
-    const size_t geo_bytes = o_cl + 4 * pl.cl.size();
-    if (!ensure(c, c->geo, geo_bytes + 64)) return false;
     for (int i = 0; i < n; i++) {
         StreamDesc &s = pl.sd[(size_t)i];
-        const int32_t *g = (const int32_t *)c->geo.p;
-        const uint8_t *gb = (const uint8_t *)c->geo.p;
+        const uint8_t *gb = (const uint8_t *)c->sd.p + sd_bytes + pre_bytes;
+        const int32_t *g = (const int32_t *)gb;
         s.seg_c0 = g + s.seg_off, s.seg_after = g + pl.n_segs + s.seg_off, s.seg_base = g + 2 * pl.n_segs + s.seg_off;
         s.seg_S = g + 3 * pl.n_segs + s.seg_off;
         s.seg_cl = (const int32_t *)(gb + o_segcl) + s.seg_off + i;
@@ -694,20 +776,17 @@ plan_again:
         ZS_HIP(c, hipMemcpyAsync(c->plan_blk.p, pl.plan_blk.data(), sizeof(BlockRec) * pl.plan_blk.size(), hipMemcpyHostToDevice, stream));
         ZS_HIP(c, hipStreamSynchronize(stream));  // pageable source
     }
-    // ---- upload descriptors and work lists (one pinned staging copy) ----
-    const size_t pre_bytes = 4 * (size_t)kWorkLists * (size_t)(n + 1);
-    size_t up_bytes = sizeof(StreamDesc) * (size_t)n + pre_bytes + geo_bytes + 16;
-    if (!ensure_pinned(c, std::max(up_bytes, sizeof(StreamState) * (size_t)n)) || !ensure(c, c->wpre, pre_bytes + 64)) return false;
-    uint8_t *hp = (uint8_t *)c->pinned;
-    memcpy(hp, pl.sd.data(), sizeof(StreamDesc) * (size_t)n);
-    int32_t *hpre = (int32_t *)(hp + sizeof(StreamDesc) * (size_t)n);
-    size_t o_clear = 0, o_adler, o_links, o_match, o_chunks, o_segs, o_sups, o_blocks, o_runs;
+    // ---- upload descriptors, work lists' prefixes and tables: one copy from the plan's own pinned staging area ----
+    // (the area keeps them after the call: a same-shaped call puts its pointers into the descriptors there and sends those)
+    if (!ensure_pinned(c, std::max(sd_bytes + 16, sizeof(StreamState) * (size_t)n)) || !ensure_plan_pin(c, up_bytes + 16)) return false;
+    uint8_t *hp = (uint8_t *)c->plan_pin;
+    memcpy(hp, pl.sd.data(), sd_bytes);
+    int32_t *hpre = (int32_t *)(hp + sd_bytes);
     WorkOffsets wo;
     {
-        size_t *const offs[kWorkLists] = {&o_clear, &o_adler, &o_links, &o_match, &o_chunks, &o_segs, &o_sups, &o_blocks, &o_runs};
         size_t at = 0;
         for (int l = 0; l < kWorkLists; l++) {
-            *offs[l] = at;
+            pc.o[l] = at;
             wo.off[l] = (uint32_t)at;
             memcpy(hpre + (size_t)l * (size_t)(n + 1), lists[l]->pre.data(), 4 * (size_t)(n + 1));
             at += lists[l]->size();
@@ -715,7 +794,7 @@ plan_again:
         wo.off[kWorkLists] = (uint32_t)at;
     }
     if (geo_bytes) {
-        uint8_t *hg = hp + sizeof(StreamDesc) * (size_t)n + pre_bytes;
+        uint8_t *hg = hp + sd_bytes + pre_bytes;
         if (pl.n_segs) {
             memcpy(hg, pl.seg_c0.data(), 4 * (size_t)pl.n_segs);
             memcpy(hg + 4 * (size_t)pl.n_segs, pl.seg_after.data(), 4 * (size_t)pl.n_segs);
@@ -726,16 +805,40 @@ plan_again:
         memcpy(hg + o_cstart, pl.cstart.data(), 4 * pl.cstart.size());
         if (pl.n_chunks) memcpy(hg + o_head, pl.head.data(), 4 * (size_t)pl.n_chunks);
         if (!pl.cl.empty()) memcpy(hg + o_cl, pl.cl.data(), 4 * pl.cl.size());
-        if (!rounds) ZS_HIP(c, hipMemcpyAsync(c->geo.p, hg, geo_bytes, hipMemcpyHostToDevice, stream));
-    }
-    if (!rounds) ZS_HIP(c, hipMemcpyAsync(c->sd.p, hp, sizeof(StreamDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
-    if (n_work && !rounds) {
-        ZS_HIP(c, hipMemcpyAsync(c->wpre.p, hpre, pre_bytes, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(zs_worklist_kernel, dim3((unsigned)((n_work + 255) / 256)), dim3(256), 0, stream, dev<int32_t>(c->wpre), n, wo,
-                           dev<uint2>(c->work));
     }
     if (!rounds) {
-        // the per-run flags and state in one launch (the link array is not cleared: K1 writes every entry that is read)
+        pc.in_flight = true;
+        ZS_HIP(c, hipMemcpyAsync(c->sd.p, hp, up_bytes, hipMemcpyHostToDevice, stream));
+        if (n_work)
+            hipLaunchKernelGGL(zs_worklist_kernel, dim3((unsigned)((n_work + 255) / 256)), dim3(256), 0, stream,
+                               (const int32_t *)((const uint8_t *)c->sd.p + sd_bytes), n, wo, dev<uint2>(c->work));
+    }
+    return true;
+    };
+    if (plan_hit) {
+        // the kept plan: the caller's pointers into the kept descriptors, and those alone to the device
+        c->plan_reused = 1;
+        if (pc.dual_saved) pl.sd = pc.dual_sd, pl.fr_chunks = pc.dual_fr, pl.fr_max_n = pc.dual_fr_max_n, pl.n_runs = pc.dual_n_runs, pl.any_fv = true;
+        StreamDesc *hd = (StreamDesc *)c->plan_pin;
+        for (int i = 0; i < n; i++) {
+            hd[i].in = pl.sd[(size_t)i].in = (const uint8_t *)in[i];
+            hd[i].out = pl.sd[(size_t)i].out = (uint8_t *)out[i];
+        }
+        pc.in_flight = true;
+        ZS_HIP(c, hipMemcpyAsync(c->sd.p, hd, sizeof(StreamDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
+    } else {
+        if (!plan_call()) return false;
+        if (plan_keep) std::swap(pc.key, pc.probe), pc.valid = true, pc.gen = c->plan_gen;
+    }
+    const int64_t link_span = pc.link_span;
+    c->lit_engine_bytes += pl.lit_bytes;
+    // (a call that runs its batch again -- below: the sweeps after runs that did not verify, a stream moved to the literal engine,
+    // the cut rounds -- counts the plan it ends with, so that a stream adds the same whatever its neighbours made the batch do)
+    auto plan_rerun = [&]() { c->lit_engine_bytes -= pl.lit_bytes; };
+    // The per-run flags and state in one launch (the link array is not cleared: K1 writes every entry that is read).  Launched
+    // behind K1, which reads none of them -- descriptors, its work items, the input -- and is what the chip waits for at the
+    // start of a call; the match kernel is the first to touch a stream's state.
+    auto zero_state = [&]() -> bool {
         ZeroRegions z;
         auto reg = [&](int r, DevBuf &b, size_t bytes) {
             z.p[r] = b.p;
@@ -760,7 +863,8 @@ plan_again:
             if (hi > lo) ZS_HIP(c, hipMemsetAsync(pl.sd[0].ins_bits + lo, 0xFF, (size_t)(hi - lo) * 4, stream));
             ZS_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(pl.sd[0].ins_bits + hi), (int)((1u << (ro->p0 & 31)) - 1u), 1, stream));
         }
-    }
+        return true;
+    };
 
     const StreamDesc *d_sd = dev<StreamDesc>(c->sd);
     StreamState *d_st = dev<StreamState>(c->st);
@@ -890,11 +994,22 @@ plan_again:
         }
         return true;
     };
+    // the engine is left for a later run, or took the block in progress over from one: it needs K5's symbols and block ends
+    const bool tail_late = ro && (!ro->final_run || ro->resume);
+    // Beside the symbol kernel the tails of a few streams are free; those of hundreds are not: 256 tail workgroups of 1024
+    // threads and 133 KiB of LDS each, one per CU, cost the symbol kernel of 256 x 1 MiB 3 ms (6.8 against 3.9), more than
+    // they take alone (0.5).  From 64 streams of 96 KiB or more on the tails run behind the symbols instead (thousands of
+    // small streams are the other way round: 16 rounds of tails, a short symbol kernel -- beside each other 18.9 ms for
+    // 4096 x 32 KiB, one after the other 20.1).
+    // (1024 x 128 KiB: 2.8 ms one after the other, 3.0 side by side; 4096 x 32 KiB: 5.7 against 4.9)
+    const bool tail_serial = !tail_late && n >= 64 && (pl.n_pos / n >= (96 << 10) || getenv("ZS_TAIL_SERIAL")) && !getenv("ZS_TAIL_FORK");
+    bool fork_recorded = false;  // the tail engine's fork has its event already (the speculative path, below)
     if (!rounds) {
     mark(2);
     if (!pl.w_links.empty())
         hipLaunchKernelGGL(zs_links_kernel, dim3((unsigned)pl.w_links.size()), dim3(1024), kLkLds, stream, d_sd, d_work + o_links,
                            dev<uint16_t>(c->link), c->crc_tab, hash_variant, (int)link_span);
+    if (!zero_state()) return false;
     if (ro && ro->resume)
         hipLaunchKernelGGL(zs_import_chains_kernel, dim3(64), dim3(1024), 0, stream, d_sd, 0, dev<uint16_t>(c->link), c->crc_tab, hash_variant, ro->p0);
     if (pl.any_dual) {
@@ -907,6 +1022,8 @@ plan_again:
             ZS_HIP(c, hipStreamSynchronize(stream));
             for (int i = 0; i < n; i++) periodic = periodic && np[(size_t)i] == 0;
         }
+        // (a kept plan keeps both: what is struck here is put back when a same-shaped call takes the plan, whose links decide anew)
+        if (pc.valid && !pc.dual_saved) pc.dual_saved = true, pc.dual_sd = pl.sd, pc.dual_fr = pl.fr_chunks, pc.dual_fr_max_n = pl.fr_max_n, pc.dual_n_runs = pl.n_runs;
         for (int i = 0; i < n; i++) {
             StreamDesc &sk = pl.sd[(size_t)i];
             if (periodic) sk.fv_end = -1, sk.fr_first = 0, sk.fr_n = 0;
@@ -940,7 +1057,22 @@ plan_again:
                            strategy, hash_variant, k5s, dev<int32_t>(c->spec_flags));
         int32_t *hf = (int32_t *)c->pinned;  // (the staging copy's uploads are through by the time the verdicts arrive: same stream)
         ZS_HIP(c, hipMemcpyAsync(hf, c->spec_flags.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
-        ZS_HIP(c, hipStreamSynchronize(stream));
+        ZS_HIP(c, hipEventRecord(c->ev_verdict, stream));
+        // The chip does not wait for the host's look at the verdicts: the compaction of the verified streams' symbols goes in
+        // right behind them.  It is predicated on the device (StreamState::spec_ok, per stream), reads only what the walk and the
+        // verdict kernel left (records, bases, slabs) and writes only verified streams' symbols and block cuts, none of which the
+        // map path of the other streams touches -- so it may run ahead of that path as well as behind it.  The tail engine's
+        // fork keeps its place behind the verdict kernel: its event is recorded here, in front of the compaction (a stream that
+        // takes the maps records it again behind the resolve kernel, below).
+        if (!tail_late && !tail_serial) {
+            ZS_HIP(c, hipEventRecord(c->ev_fork, stream));
+            fork_recorded = true;
+        }
+        if (prof) (void)hipEventRecord(c->ev_spec[2], stream);
+        hipLaunchKernelGGL(zs_spec_compact_kernel, dim3((unsigned)((pl.max_spec_n + 3) / 4), (unsigned)n), dim3(256), 0, stream, d_sd, d_st, k5s,
+                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top));
+        if (prof) (void)hipEventRecord(c->ev_spec[3], stream);
+        ZS_HIP(c, hipEventSynchronize(c->ev_verdict));
         if (prof) (void)hipEventRecord(c->ev_spec[1], stream);
         for (int i = 0; i < n; i++) {
             if (hf[i] == 0) continue;
@@ -1091,17 +1223,8 @@ plan_again:
             hipLaunchKernelGGL(zs_rle_pass_kernel<1>, tg, dim3(256), 0, stream, d_sd, rt, dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), s0);
         });
     }
-    // the engine is left for a later run, or took the block in progress over from one: it needs K5's symbols and block ends
-    const bool tail_late = ro && (!ro->final_run || ro->resume);
-    // Beside the symbol kernel the tails of a few streams are free; those of hundreds are not: 256 tail workgroups of 1024
-    // threads and 133 KiB of LDS each, one per CU, cost the symbol kernel of 256 x 1 MiB 3 ms (6.8 against 3.9), more than
-    // they take alone (0.5).  From 64 streams of 96 KiB or more on the tails run behind the symbols instead (thousands of
-    // small streams are the other way round: 16 rounds of tails, a short symbol kernel -- beside each other 18.9 ms for
-    // 4096 x 32 KiB, one after the other 20.1).
-    // (1024 x 128 KiB: 2.8 ms one after the other, 3.0 side by side; 4096 x 32 KiB: 5.7 against 4.9)
-    const bool tail_serial = !tail_late && n >= 64 && (pl.n_pos / n >= (96 << 10) || getenv("ZS_TAIL_SERIAL")) && !getenv("ZS_TAIL_FORK");
     if (!tail_late && !tail_serial) {
-        ZS_HIP(c, hipEventRecord(c->ev_fork, stream));
+        if (!fork_recorded || need_maps) ZS_HIP(c, hipEventRecord(c->ev_fork, stream));  // (behind the resolve kernel, if it ran)
         ZS_HIP(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
         hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, c->aux, d_sd, d_st, dev<uint16_t>(c->link),
                            dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks),
@@ -1126,12 +1249,7 @@ plan_again:
     // the records and maps of the streams that were given up, nothing zeroes syms / blk_end / blk_top in between, and the map
     // kernels skip the verified streams by StreamState::spec_ok, which the re-entry does not reset either.
     // tests/test_gpu_spec.py test_a_verified_stream_beside_one_in_the_cut_rounds.)
-    if (spec_ok_streams) {
-        if (prof) (void)hipEventRecord(c->ev_spec[2], stream);
-        hipLaunchKernelGGL(zs_spec_compact_kernel, dim3((unsigned)((pl.max_spec_n + 3) / 4), (unsigned)n), dim3(256), 0, stream, d_sd, d_st, k5s,
-                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top));
-        if (prof) (void)hipEventRecord(c->ev_spec[3], stream);
-    }
+    // (the compaction of their symbols went in behind the verdict kernel, above)
     mark(9);
     if (tail_serial)
         hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
@@ -1215,8 +1333,11 @@ plan_again:
     const int trees_threads = pl.w_blocks.size() > 8192 ? 128 : 256;
     if (n >= 64 && !getenv("ZS_NO_LIVE_LIST")) {
         // many streams: the block list rewritten with the blocks that exist in front (zs_live_scan_kernel)
-        hipLaunchKernelGGL(zs_live_scan_kernel, dim3(1), dim3(1024), 0, stream, d_st, n, dev<int32_t>(c->wpre));
-        hipLaunchKernelGGL(zs_live_fill_kernel, dim3((unsigned)((pl.w_blocks.size() + 255) / 256)), dim3(256), 0, stream, dev<int32_t>(c->wpre), n,
+        // (its prefix sum goes where the work lists' prefixes were uploaded: zs_worklist_kernel is through with them, and a call
+        // that takes this plan over does not run it)
+        int32_t *const d_live = (int32_t *)((uint8_t *)c->sd.p + sizeof(StreamDesc) * (size_t)n);
+        hipLaunchKernelGGL(zs_live_scan_kernel, dim3(1), dim3(1024), 0, stream, d_st, n, d_live);
+        hipLaunchKernelGGL(zs_live_fill_kernel, dim3((unsigned)((pl.w_blocks.size() + 255) / 256)), dim3(256), 0, stream, d_live, n,
                            (uint32_t)pl.w_blocks.size(), dev<uint2>(c->work) + o_blocks);
     }
     hipLaunchKernelGGL(zs_trees_kernel, dim3((unsigned)pl.w_blocks.size()), dim3(trees_threads), 0, stream, d_sd, d_st, d_work + o_blocks,
@@ -1245,7 +1366,13 @@ plan_again:
     ZS_HIP(c, hipMemcpyAsync(hst, d_st, sizeof(StreamState) * (size_t)n, hipMemcpyDeviceToHost, stream));
     ht_launched = ht_us();
     ZS_HIP(c, hipStreamSynchronize(stream));
-    if (host_times) fprintf(stderr, "zs: host: plan + uploads %.0f us, all launched at %.0f us, device done at %.0f us\n", ht_plan, ht_launched, ht_us());
+    pc.in_flight = false;
+    // (what this call itself moved behind its plan -- the sweeps' rounds, the Rle tiles: buffers the launches take from the
+    // context, not from the descriptors -- does not cost the plan it has just made)
+    if (pc.valid && !plan_hit) pc.gen = c->plan_gen;
+    if (host_times)
+        fprintf(stderr, "zs: host: plan + uploads %.0f us%s, all launched at %.0f us, device done at %.0f us\n", ht_plan, c->plan_reused ? " (kept plan)" : "", ht_launched,
+                ht_us());
     c->last_op = lv.func == 1 ? 2 : 0;
     if (getenv("ZS_DEBUG_CHAIN") && n == 1) {  // the chain of one position as the kernels saw it (buffer positions)
         const int64_t q0 = atoll(getenv("ZS_DEBUG_CHAIN")) - (ro ? ro->abs_off : 0);
@@ -1288,10 +1415,11 @@ plan_again:
             (void)hipEventElapsedTime(&b, c->ev_spec[0], c->ev_spec[1]);
             (void)hipEventElapsedTime(&m, c->ev_spec[1], c->ev[kStChunkMap + 1]);
             c->stage_ms[kStSpecWalk] = a, c->stage_ms[kStSpecVerify] = b, c->stage_ms[kStChunkMap] = m;
-            // (the compaction is part of the emit_syms interval: this is its own share of it)
+            // (the compaction runs inside the verdict's interval, while the host looks at the verdicts: its own share of it)
             float k = 0;
-            if (spec_ok_streams) (void)hipEventElapsedTime(&k, c->ev_spec[2], c->ev_spec[3]);
+            (void)hipEventElapsedTime(&k, c->ev_spec[2], c->ev_spec[3]);
             c->stage_ms[kStSpecCompact] = k;
+            c->stage_ms[kStSpecVerify] = b > k ? b - k : 0;
         }
     }
     {
@@ -1345,6 +1473,7 @@ plan_again:
 bool device_adlers(zs_ctx *c, int m, const void *const *bufs, const int64_t *lens, const void *const *trailers, uint32_t *adlers,
                    int *ok, hipStream_t stream) {
     if (m <= 0) return true;
+    c->plan_gen++;  // (the descriptors and work items below go where the kept deflate plan has its own)
     std::vector<StreamDesc> sd((size_t)m);
     std::vector<uint2> work;
     int64_t n_pieces = 0;
@@ -1469,7 +1598,8 @@ int zs_ctx_create(int device, zs_ctx **out) {
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_pre0, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_verdict, hipEventDisableTiming) != hipSuccess) {
         zs_ctx_destroy(c);  // releases whatever was created so far
         return ZS_MEM_ERROR;
     }
@@ -1510,7 +1640,7 @@ int zs_ctx_create(int device, zs_ctx **out) {
 void zs_ctx_destroy(zs_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->wpre, &c->geo, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
+    DevBuf *bufs[] = {&c->sd, &c->st, &c->work, &c->link, &c->mm, &c->maps, &c->chunk_far, &c->segmap, &c->supmap, &c->seg_entry, &c->seg_symbase, &c->seg_stale, &c->entry, &c->symbase, &c->stale, &c->syms,
                       &c->blk_end, &c->blk_top, &c->blocks, &c->trees, &c->info, &c->tile_bits, &c->pieces, &c->scratch, &c->stage_in, &c->stage_out, &c->wr, &c->inf_desc, &c->inf_state, &c->par_ps, &c->par_st, &c->par_work, &c->par_cbits, &c->par_ccnt, &c->par_surv, &c->par_scnt,
                       &c->par_cands, &c->par_tabs, &c->par_toktabs, &c->par_toks, &c->par_ctoks, &c->par_tokstat, &c->par_tails, &c->par_retry, &c->par_fxtab, &c->par_blocks, &c->par_cells, &c->par_windows, &c->par_fail, &c->run_syms, &c->run_bits,
                       &c->run_scratch, &c->run_outs, &c->run_fail, &c->adl_tr, &c->adl_res, &c->plan_blk, &c->ins_bits, &c->mm_bak, &c->cut_pos, &c->cut_bkt, &c->win_groups, &c->win_sg, &c->win_maps, &c->win_entries, &c->persist_bak, &c->resume_flag, &c->rle_tiles, &c->own_in, &c->fr_chunks, &c->fr_meta, &c->fr_planes, &c->fr_prov, &c->fr_base, &c->fr_counters, &c->spec_rec, &c->spec_flags, &c->spec_syms, &c->png_img, &c->png_seg, &c->png_ctr, &c->png_fimg, &c->png_scratch, &c->png_a7img, &c->png_inflated, &c->png_passes, &c->crc_desc, &c->crc_res, &c->png_zs, &c->png_gather, &c->png_ximg, &c->png_raw, &c->png_simg, &c->png_split, &c->png_gimg, &c->png_vimg, &c->png_vrec, &c->png_packed, &c->png_cimg, &c->png_frames, &c->png_dimg, &c->png_drec, &c->png_kimg, &c->png_crop};
@@ -1535,6 +1665,9 @@ void zs_ctx_destroy(zs_ctx *c) {
     for (auto &e : c->ev_crop)
         if (e) (void)hipEventDestroy(e);
     if (c->pinned) (void)hipHostFree(c->pinned);
+    if (c->plan_pin) (void)hipHostFree(c->plan_pin);
+    delete c->plan;
+    if (c->ev_verdict) (void)hipEventDestroy(c->ev_verdict);
     if (c->pin_io) (void)hipHostFree(c->pin_io);
     if (c->pin_out) (void)hipHostFree(c->pin_out);
     for (auto &e : c->ev)
@@ -1573,6 +1706,7 @@ int64_t zs_ctx_counter(const zs_ctx *c, const char *name) {
     if (k == "spec_fallbacks") return c->spec_fallbacks;
     if (k == "spec_periodic") return c->spec_periodic;  // ... fallbacks that were never walked (the match kernel's count of RUNS tiles)
     if (k == "spec_wrong_chunks") return c->spec_wrong_chunks;
+    if (k == "plan_reused") return c->plan_reused;  // 1: the last deflate call took the plan of the call before (same shape)
     if (k == "inf_lane_streams") return c->inf_lane_streams;  // streams of the last inflate call with blocks for the lane decoder
     if (k == "inf_wave_streams") return c->inf_wave_streams;  // ... at or above the parallel minimum that run_inflate_par handed to `rest`
     if (k == "png_segments") return c->png_segments;  // segments the last zs_png_unfilter_batch_device call found
