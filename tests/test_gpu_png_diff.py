@@ -172,6 +172,27 @@ def test_the_crop_at_every_pair_of_residues_with_guard_bytes(engine, px):
     assert d_src.cpu().numpy().tobytes() == src.tobytes()
 
 
+def test_a_crop_of_more_rows_than_one_launch_holds(engine):
+    """A launch of the flat-list kernels takes 2^25 rows, so a call of more is several launches, each with its first row: one
+    image a pixel wide and 2^25 + 5 rows high (its rows on both sides of the seam), and a 7 x 9 rectangle of a 16 x 12 image
+    behind it whose rows all lie in the second launch.  About 270 MB of device memory, compared there."""
+    import torch
+    from zlibstream_amd import png_crop_batch_device
+    tall_h, guard = (1 << 25) + 5, 64
+    gen = torch.Generator(device="cuda").manual_seed(5300)
+    tall = torch.randint(0, 256, (tall_h, 1, 4), dtype=torch.uint8, device="cuda", generator=gen)
+    small = torch.randint(0, 256, (12, 16, 4), dtype=torch.uint8, device="cuda", generator=gen)
+    x, y, w, h = 5, 2, 7, 9
+    outs = [torch.full((tall_h * 4 + guard,), 0xEE, dtype=torch.uint8, device="cuda"), torch.full((w * h * 4 + guard,), 0xEE, dtype=torch.uint8, device="cuda")]
+    torch.cuda.synchronize()
+    png_crop_batch_device(engine, [tall.data_ptr(), small.data_ptr()], [1, 16], [0, x], [0, y], [1, w], [tall_h, h], [t.data_ptr() for t in outs], pixel_bytes=4)
+    torch.cuda.synchronize()
+    for i, (out, want) in enumerate(zip(outs, (tall, small[y:y + h, x:x + w]))):
+        n = want.numel()
+        assert torch.equal(out[:n], want.reshape(-1)), "image %d" % i
+        assert bool((out[n:] == 0xEE).all()), "image %d: written behind its rows" % i
+
+
 def test_the_crop_checks_its_arguments(engine):
     import torch
     from zlibstream_amd import _native
