@@ -34,10 +34,11 @@ struct Args {
     PlanEnv env;
 };
 PlanKey key_of(const Args &a) {
-    PlanWritesView v0{a.ends0.data(), a.flush0.data(), a.ends0.size(), a.chunk0, a.raw0};
-    PlanWritesView v1{a.ends1.data(), a.flush1.data(), a.ends1.size(), 512, false};
-    PlanWritesView v2{a.ends2.data(), a.flush2.data(), a.ends2.size(), a.chunk2, a.raw2};
-    const PlanWritesView *ptrs[3] = {&v0, a.stream1_has_writes ? &v1 : nullptr, &v2};
+    WriteSpec v0, v1, v2;
+    v0.ends = a.ends0, v0.flush = a.flush0, v0.chunk = a.chunk0, v0.raw = a.raw0;
+    v1.ends = a.ends1, v1.flush = a.flush1;
+    v2.ends = a.ends2, v2.flush = a.flush2, v2.chunk = a.chunk2, v2.raw = a.raw2;
+    const WriteSpec *ptrs[3] = {&v0, a.stream1_has_writes ? &v1 : nullptr, &v2};
     PlanKey k;
     plan_key_fill(k, a.n, a.in_len.data(), a.out_cap.data(), a.level, a.strategy, a.hash_variant, a.force_seq, a.incremental, a.rounds, a.forced_lit, a.no_rounds,
                   a.with_writes ? ptrs : nullptr, a.env);
@@ -97,16 +98,21 @@ int main() {
         {"env has_fr_ratio", [](Args &a) { a.env.has_fr_ratio = true; }},
         {"env has_fr_chunk", [](Args &a) { a.env.has_fr_chunk = true; }},
         {"env has_fast_chunk", [](Args &a) { a.env.has_fast_chunk = true; }},
+        {"env has_spec_len", [](Args &a) { a.env.has_spec_len = true; }},
+        {"env has_spec_warm", [](Args &a) { a.env.has_spec_warm = true; }},
+        {"env has_spec_min", [](Args &a) { a.env.has_spec_min = true; }},
+        {"env has_fast_min_input", [](Args &a) { a.env.has_fast_min_input = true; }},
         {"env spec_len", [](Args &a) { a.env.spec_len = 512; }},
-        {"env spec_warm", [](Args &a) { a.env.spec_warm = 0; }},
+        {"env spec_warm", [](Args &a) { a.env.spec_warm = 1; }},
         {"env fast_chunk", [](Args &a) { a.env.fast_chunk = 65536; }},
         {"env spec_min", [](Args &a) { a.env.spec_min = 65536; }},
         {"env fr_chunk", [](Args &a) { a.env.fr_chunk = 4096; }},
+        {"env fast_min_input", [](Args &a) { a.env.fast_min_input = 4194304; }},
         {"env fr_ratio", [](Args &a) { a.env.fr_ratio = 0.5; }},
     };
     // (the walk covers the struct: a field added to PlanKey, PlanKeyWrites or PlanEnv changes one of these sizes, and the
     // list above and the equality are then to be extended with it)
-    struct EnvMirror { bool b[12]; int i[3]; int64_t l[2]; double d; };
+    struct EnvMirror { bool b[16]; int i[3]; int64_t l[3]; double d; };
     static_assert(sizeof(PlanEnv) == sizeof(EnvMirror), "PlanEnv has a field this test does not walk");
     struct WritesMirror { bool present, raw; int chunk; std::vector<int64_t> ends; std::vector<uint8_t> flush; };
     static_assert(sizeof(PlanKeyWrites) == sizeof(WritesMirror), "PlanKeyWrites has a field this test does not walk");

@@ -5,7 +5,7 @@ whether a call took the kept plan.  Sizes: 1 MiB + 3 bytes of text at level 6 (t
 (the maps), 300 000 bytes at level 1 (the sweeps), 64 KiB of sparse rows at level 6 (periodic data).
 
 300 000 bytes at level 1 is planned for the sweeps and for the speculative runs at once, and the links decide in every call
-(run_pipeline, allow_dual): the kept plan keeps both.  300 KiB of sparse rows at level 1 is the same plan with the other answer -- and its runs
+(zs_plan.h plan_streams, allow_dual): the kept plan keeps both.  300 KiB of sparse rows at level 1 is the same plan with the other answer -- and its runs
 do not verify, so the batch is run again on one run of the engine per stream (fast_fallbacks): a call that ends in a re-entry of
 the pipeline ends on a plan that is never kept, and its counter is 0 every time."""
 import io
@@ -245,6 +245,46 @@ def test_a_call_that_fails_then_the_same_shape_with_room(eng, texts, want):
     assert eng.counter("plan_reused") == 1  # (a failing call's shape is a shape too)
     (z,), r = _run(eng, [a], 6)
     assert r == 0 and z == want(a, 6)
+
+
+# (switch, value, the texts' shape, bytes of it, level, strategy, Write ends): the smallest shape on which the switch acts.  Every
+# row changes the plan but ZS_FAST_CHUNK=65536, which is what 300 000 bytes get anyway: that row shows the key alone (the value
+# counts as set); tests/cpp/test_plan.cpp takes 262144, which changes the runs
+PLANNER_SWITCHES = [
+    ("ZS_NO_SPEC", "1", "walk", None, 6, 0, None),
+    ("ZS_SPEC_LEN", "512", "walk", None, 6, 0, None),
+    ("ZS_SPEC_MIN", "2097152", "walk", None, 6, 0, None),
+    ("ZS_NO_FAST_VEC", "1", "sweeps", None, 1, 0, None),
+    ("ZS_FAST_NO_ROUNDS", "1", "sweeps", None, 1, 0, None),
+    ("ZS_FR_RATIO", "0", "sweeps", None, 1, 0, None),
+    ("ZS_FR_CHUNK", "4096", "sweeps", None, 1, 0, None),
+    ("ZS_FAST_CHUNK", "65536", "sweeps", None, 1, 0, None),
+    ("ZS_NO_RLE_RUNS", "1", "maps", 70000, 6, 3, None),
+    ("ZS_NO_RLE_MULTI", "1", "maps", 70000, 6, 3, [30000, 70000]),
+    ("ZS_NO_FAST_MULTI", "1", "sweeps", 300000, 1, 0, [81920, 163840, 245760, 300000]),
+]
+
+
+@pytest.mark.parametrize("switch,value,shape,size,level,strategy,ends", PLANNER_SWITCHES, ids=[c[0] for c in PLANNER_SWITCHES])
+def test_a_planner_switch_flipped_between_same_shaped_calls(eng, texts, want, monkeypatch, switch, value, shape, size, level, strategy, ends):
+    """Every switch the planner takes from the key's PlanEnv (zs_plan.h), on the smallest shape where it acts: buffer a, buffer b,
+    the switch set, a, b, the switch unset, a.  A call under another setting plans afresh, the one behind it takes that plan:
+    plan_reused reads 0, 1, 0, 1, 0, and every output is the oracle's.  ZS_NO_FAST_RESUME and ZS_NO_RESUME_ROUNDS act only on
+    the runs of an incremental stream, whose plans are never kept: tests/cpp/test_plan.cpp has them, on the host."""
+    a, b = (d[:size] if size else d for d in texts[shape])
+    expect = {id(a): want(a, level, strategy, ends), id(b): want(b, level, strategy, ends)}
+
+    def call(data, reused):
+        (z,), r = _run(eng, [data], level, strategy=strategy, ends=[ends] if ends else None)
+        assert r == reused and z == expect[id(data)]
+
+    call(a, 0)
+    call(b, 1)
+    monkeypatch.setenv(switch, value)
+    call(a, 0)
+    call(b, 1)
+    monkeypatch.delenv(switch)
+    call(a, 0)
 
 
 def test_the_switch_turns_reuse_off(eng, texts, want, monkeypatch):

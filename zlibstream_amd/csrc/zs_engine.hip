@@ -19,7 +19,7 @@
 #include "zs_inflate_tok.hip"
 #include "zs_png.hip"
 #include "zs_crc32.hip"
-#include "zs_plan_key.h"
+#include "zs_plan.h"
 
 using namespace zs;
 
@@ -169,46 +169,6 @@ bool ensure_pinned(zs_ctx *c, size_t bytes) {
     return true;
 }
 
-// A kernel's work items: (stream, index) for index < count(stream), stream after stream.  The host keeps the running totals
-// (one per stream); the pairs themselves are written on the device (zs_worklist_kernel) -- for a 64 MiB stream they are
-// 46 K pairs, whose making and upload were 0.1 ms of host time per call.
-struct WorkList {
-    std::vector<int32_t> pre;  // pre[i] = items of the streams before i; one more entry = the total
-    void add(int stream, int64_t count) {
-        while ((int)pre.size() <= stream) pre.push_back(pre.empty() ? 0 : pre.back());
-        pre.push_back(pre.back() + (int32_t)count);
-    }
-    void finish(int n) {
-        if (pre.empty()) pre.push_back(0);
-        while ((int)pre.size() <= n) pre.push_back(pre.back());
-    }
-    size_t size() const { return pre.empty() ? 0 : (size_t)pre.back(); }
-    bool empty() const { return size() == 0; }
-};
-constexpr int kWorkLists = 9;
-struct Plan {
-    std::vector<StreamDesc> sd;
-    WorkList w_clear, w_adler, w_links, w_match, w_chunks, w_segs, w_sups, w_blocks, w_runs;
-    int64_t n_pos = 0, n_syms = 0;
-    int64_t n_chunks = 0, n_segs = 0, n_sups = 0, n_blocks = 0, n_pieces = 0, n_runs = 0;
-    int64_t n_spec = 0;  // chunks of the speculative grid, all streams that try the speculative walk
-    int max_spec_n = 0, n_spec_streams = 0;
-    bool any_fv = false, any_rle = false;
-    bool any_dual = false;  // levels 1-3, a few streams below 4 MiB: planned for the sweeps and for the speculative runs, the links decide (zs_fast_probe_kernel)
-    int64_t n_rle_tiles = 0;
-    int64_t lit_bytes = 0;           // input bytes of this plan that only the literal engine parses
-    std::vector<FsChunk> fr_chunks;  // levels 1-3 as rounds over the chunks of the streams (zs_fast_sweep.h "Rounds"); empty: one workgroup per stream
-    size_t fr_prov = 0;              // symbols of room in the chunks' provisional buffer
-    int fr_max_n = 0;                // the most chunks a stream has
-    int64_t n_cuts = 0;     // entries of a cut list (batched cut rounds): one per read boundary
-    // parse-segment tables (zs_core.h build_geometry), all streams: per segment (seg_off order); seg_cl and cstart hold one
-    // entry more per stream (stream i's lists begin at seg_off + i / chunk_off + i); seg_cl's values index `cl`
-    std::vector<int32_t> seg_c0, seg_after, seg_base, seg_S, seg_cl, cstart, head;
-    std::vector<uint32_t> cl;
-    std::vector<BlockRec> plan_blk;                    // level 0: the stored blocks of every stream, stream after stream
-    std::vector<int32_t> plan_wr_blk;                  // level 0 under a flush mode: blocks flushed before each Write began
-};
-
 // What a same-shaped call takes over from the call before (zs_plan_key.h): the plan, the places of the work lists in the work
 // array, and what else the launches read of the planning.
 struct PlanCache {
@@ -219,8 +179,7 @@ struct PlanCache {
     // a call that uploaded from plan_pin has not been waited for to its end: set at the upload, cleared behind the call's last
     // synchronisation -- a call that leaves early (a HIP error, a workspace that does not fit) leaves it set, and the next call plans
     bool in_flight = false;
-    size_t o[kWorkLists] = {};
-    int64_t link_span = 0;
+    PlanLayout lay;         // where the plan's parts lie in sd, work and the Write table
     // a plan for the sweeps and for the speculative runs at once (Plan::any_dual) as it was before a call struck one of them
     bool dual_saved = false;
     std::vector<StreamDesc> dual_sd;
@@ -234,43 +193,43 @@ T *dev(DevBuf &b) {
     return (T *)b.p;
 }
 
-// The Writes of one stream (ZlibOutputStream.WriteCore): cumulative ends, the FlushMode of each, the caller's output
-// chunk size and whether the stream is raw deflate.
-struct WriteSpec {
-    std::vector<int64_t> ends;
-    std::vector<uint8_t> flush;
-    int chunk = 512;
-    bool raw = false;
-    bool flushing() const {
-        for (uint8_t f : flush)
-            if (f) return true;
-        return false;
-    }
+
+// One run of an incremental stream (zs_stream_api.inc; one stream per call): what the planning reads of it (zs_plan.h PlanRun)
+// and what the run gives back.
+struct RunOpts : PlanRun {
+    int64_t end_bits = 0;  // out: stream bit position behind the run's last block or marker
 };
 
-// One run of an incremental stream (zs_stream_api.inc; one stream per call).  final_run == false: the stream goes on after
-// this run's Writes, the engine is left in `persist` (device memory) where Deflate.Compress would return to its caller, and
-// only what is final -- whole blocks and flush markers, complete bytes -- is output.  cont: the run continues from `persist`;
-// the input buffer then holds the stream from position abs_off on (64 KiB already read, then the new bytes) and `writes`
-// holds absolute ends.
-struct RunOpts {
-    bool final_run = true, cont = false;
-    int64_t hist = 0;  // leading bytes of the buffer that earlier runs have parsed (history: up to 64 KiB)
-    LitPersist *persist = nullptr;
-    int64_t abs_off = 0;
-    uint32_t adler_stream = 1, carry_byte = 0;
-    int64_t end_bits = 0;  // out: stream bit position behind the run's last block or marker
-    // cont: the literal engine stops at the first clean loop-top at or behind this stream position (< 0: runs on) ...
-    int64_t stop_abs = -1;
-    // ... and the run behind such a stop goes on from there on the bulk pipeline (`resume`): loop-top p0 with the input read up to
-    // E0, the window at base0, the block in progress begun at start_block -- buffer positions, the buffer beginning at
-    // stream position abs_off -- with start_syms symbols, in the lazy parse's node `slot` of a chunk that begins at p0
-    // at_read: the stream was flushed at p0 (E0 == p0, nothing pending): the run's first pass through the loop reads, like a
-    // stream's first one, and the run begins with a new Deflate call
-    bool resume = false, mid_write = false, at_read = false;
-    int64_t p0 = 0, E0 = 0, base0 = 0, start_block = 0;
-    int slot = 0;
-    uint32_t start_syms = 0;
+// The launch side's switches (DESIGN.md section 8 has the table), read at one place, when a call's DeflateCall is made;
+// the planning's are the PlanEnv of the call's key.  Per call, but for the two the table says are read once per process.
+struct LaunchEnv {
+    bool no_plan_reuse = getenv("ZS_NO_PLAN_REUSE") != nullptr, no_supmap = getenv("ZS_NO_SUPMAP") != nullptr;
+    // (ZS_NO_DEFER: every cut on the stream's own CU; ZS_FORCE_ROUNDS: the rounds from the first cut on -- for the tests)
+    bool no_defer = getenv("ZS_NO_DEFER") != nullptr, force_rounds = getenv("ZS_FORCE_ROUNDS") != nullptr;
+    bool tail_serial = getenv("ZS_TAIL_SERIAL") != nullptr, tail_fork = getenv("ZS_TAIL_FORK") != nullptr, fast_no_probe = getenv("ZS_FAST_NO_PROBE") != nullptr;
+    bool no_whole_runs = getenv("ZS_NO_WHOLE_RUNS") != nullptr, whole_runs = getenv("ZS_WHOLE_RUNS") != nullptr;
+    bool debug = getenv("ZS_DEBUG") != nullptr, debug_cuts = getenv("ZS_DEBUG_CUTS") != nullptr, debug_fa = getenv("ZS_DEBUG_FA") != nullptr;
+    const char *debug_chain = getenv("ZS_DEBUG_CHAIN"), *debug_chain_want = getenv("ZS_DEBUG_CHAIN_WANT");
+    int k5_ahead = getenv("ZS_K5_AHEAD") ? atoi(getenv("ZS_K5_AHEAD")) : 1;  // lines the symbol kernel's helper wave asks for ahead of a lane
+    // ZS_SPEC_CORRUPT=j: chunk j's recorded guess is spoiled (the tests' way to a failed verification)
+    int spec_corrupt = getenv("ZS_SPEC_CORRUPT") ? atoi(getenv("ZS_SPEC_CORRUPT")) : -1;
+    // (once per process) where the host's share of a call goes: stderr, microseconds; K9's workgroups per block
+    static bool host_times() {
+        static const bool v = getenv("ZS_HOST_TIMES") != nullptr;
+        return v;
+    }
+    static const char *eb_tiles() {
+        static const char *const v = getenv("ZS_EB_TILES");
+        return v;
+    }
+};
+// The switches of the sweeps' rounds, the measurements': read once per process, when the first call takes the rounds.
+struct RoundsEnv {
+    int max_rounds = getenv("ZS_FR_MAX_ROUNDS") ? atoi(getenv("ZS_FR_MAX_ROUNDS")) : 0;
+    int range = getenv("ZS_FR_RANGE") ? std::max(1, atoi(getenv("ZS_FR_RANGE"))) : 0;
+    int group = getenv("ZS_FR_GROUP") ? atoi(getenv("ZS_FR_GROUP")) : 4, tail = getenv("ZS_FR_TAIL_RANGE") ? atoi(getenv("ZS_FR_TAIL_RANGE")) : 1;
+    bool no_seed = getenv("ZS_FR_NO_SEED") != nullptr, fixed = getenv("ZS_FR_RANGE_FIXED") != nullptr, dbg = getenv("ZS_DEBUG") != nullptr;
+    double wake = getenv("ZS_FR_WAKE") ? atof(getenv("ZS_FR_WAKE")) : 4.0;
 };
 
 // `writes` (optional): one entry per stream, the Writes of a multi-Write stream (null: the stream is one Write).  A spec whose
@@ -278,18 +237,118 @@ struct RunOpts {
 bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out, const int64_t *out_cap,
                   int64_t *out_len, int *status, int level, int strategy, int hash_variant, hipStream_t stream,
                   const WriteSpec *const *writes = nullptr, int force_seq = 0, RunOpts *ro = nullptr, bool rounds = false,
-                  const std::vector<uint8_t> *force_lit = nullptr) {
-    if (level == -1) level = 6;
+                  const std::vector<uint8_t> *force_lit = nullptr);
+
+enum { kWClear, kWAdler, kWLinks, kWMatch, kWChunks, kWSegs, kWSups, kWBlocks, kWRuns };  // the work lists, in Plan::list's order
+
+// The state of one deflate call: its arguments, its switches, the plan it runs on and what the steps of the pipeline hand
+// each other.  run_pipeline (below the steps) is the sequence.
+struct DeflateCall {
+    zs_ctx *const c;
+    PlanCache &pc;
+    // (pl and lay are the context's, not this call's: a re-entry of run_pipeline plans into them again -- see rerun)
+    Plan &pl;
+    PlanLayout &lay;
+    // run_pipeline's arguments, in its order (level -1 is 6 by now; `writes` with the Rle lists folded once begin() is through)
+    int n;
+    const void *const *in;
+    const int64_t *in_len;
+    void *const *out;
+    const int64_t *out_cap;
+    int64_t *out_len;
+    int *status;
+    int level, strategy, hash_variant;
+    hipStream_t stream;
+    const WriteSpec *const *writes;
+    int force_seq;
+    RunOpts *ro;
+    bool rounds;
+    const std::vector<uint8_t> *force_lit;
+    // (ZS_HOST_TIMES counts from here: the members below are made in this order, so the switches' reads are inside the call's time)
+    const std::chrono::steady_clock::time_point ht0 = std::chrono::steady_clock::now();
     LevelCfg lv = level_cfg(level);
-    static const bool host_times = getenv("ZS_HOST_TIMES") != nullptr;  // (where the host's share of a call goes: stderr, microseconds)
-    const auto ht0 = std::chrono::steady_clock::now();
-    auto ht_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ht0).count(); };
+    PlanEnv penv = plan_env_read();
+    LaunchEnv env;
+    FoldedWrites folded;
+    PlanArgs pa;
+    bool any_writes = false, no_rounds_this_call = false, plan_hit = false, plan_keep = false;
     double ht_plan = 0, ht_launched = 0;
+    const StreamDesc *d_sd = nullptr;
+    StreamState *d_st = nullptr, *hst = nullptr;
+    const uint2 *d_work = nullptr;
+    bool prof = false;
+    K5Spec k5s{};
+    int spec_ok_streams = 0;  // streams whose speculative walk verified: the map kernels skip them (all of them: not launched)
+    bool need_maps = true, spec_ran = false;
+    bool fork_recorded = false;  // the tail engine's fork has its event already (the speculative path)
+    bool tail_late = false, tail_serial = false, use_sup = false;
+    int defer_mode = 0, cut_stride = 0;
+    // a step ran the batch again (rerun): the call is over and `answer` is what it returns; a step that failed leaves both false
+    bool done = false, answer = false;
+
+    double ht_us() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ht0).count(); }
+    const uint2 *work(int list) const { return d_work + lay.work[list]; }
+    void mark(int i) {
+        if (prof) (void)hipEventRecord(c->ev[i], stream);
+    }
+    // The batch once more, on another plan: the sweeps after runs that did not verify (force_seq), a stream moved to the literal
+    // engine (force_lit), the kernels behind the cut rounds (rounds), a call barred from the sweeps' rounds.  It counts the
+    // plan it ends with, so that a stream adds the same to lit_engine_bytes whatever its neighbours made the batch do.
+    // The plan and the work-list offsets belong to the context: the re-entry plans into them, so whoever calls this
+    // returns at once -- `return rerun(...)` -- and nothing of this call reads pl or lay afterwards.  That has to stay so.
+    bool rerun(int force_seq_, bool rounds_, const std::vector<uint8_t> *force_lit_) {
+        c->lit_engine_bytes -= pl.lit_bytes;
+        done = true;
+        return answer = run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq_, ro, rounds_, force_lit_);
+    }
+    void launch_tail(hipStream_t on) {
+        hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, on, d_sd, d_st, dev<uint16_t>(c->link),
+                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks),
+                           dev<uint8_t>(c->scratch), c->crc_tab, lv, strategy, hash_variant, level);
+    }
+    void launch_resolve(int mode, int iter) {
+        hipLaunchKernelGGL(zs_resolve_kernel, dim3((unsigned)n), dim3(1024), kResolveLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
+                           dev<uint2>(c->mm), dev<uint32_t>(c->maps), dev<uint2>(c->segmap),
+                           dev<uint16_t>(c->seg_entry), dev<uint32_t>(c->seg_symbase), dev<uint8_t>(c->stale),
+                           dev<uint8_t>(c->seg_stale), c->crc_tab, lv, strategy, hash_variant, 0x7FFFFFFF, 0x7FFFFFFF,
+                           use_sup ? dev<uint2>(c->supmap) : (const uint2 *)nullptr, dev<uint16_t>(c->chunk_far), mode, dev<int32_t>(c->cut_pos),
+                           dev<uint32_t>(c->cut_bkt), cut_stride, iter);
+    }
+    // few cuts: 128 workgroups each (every 128th position behind the cut); many: fewer, larger ones
+    // (the kernel comes as an argument, not as template parameters of this function: its instantiations then stand where the
+    // rounds name them, and the device code keeps its order)
+    void launch_cuts_repair(decltype(&zs_cuts_repair_kernel<256, 1>) kernel, unsigned gx, int threads, int max_nc, int iter) {
+        hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)std::min(max_nc, 65535), (unsigned)std::min(n, 65535)), dim3((unsigned)threads), kRepairLds, stream,
+                           d_sd, d_st, dev<uint16_t>(c->link), dev<uint2>(c->mm), dev<uint8_t>(c->stale), dev<uint8_t>(c->seg_stale),
+                           dev<uint16_t>(c->chunk_far), c->crc_tab, lv, hash_variant, dev<int32_t>(c->cut_pos), dev<uint32_t>(c->cut_bkt),
+                           cut_stride, iter, n);
+    }
+    bool begin();            // the arguments, the switches, the key: does the call take the kept plan?
+    bool bind_plan();        // the workspace of the plan, and the descriptors' pointers into it
+    bool plan_and_upload();  // everything a same-shaped call skips
+    bool take_kept_plan();
+    void launch_setup();
+    bool zero_state();
+    bool side_work();
+    bool run_cut_rounds();
+    bool front();            // links, match, the speculative walk or the maps, resolve
+    bool spec_walk();
+    bool dual_probe();
+    bool fast_sweeps();      // levels 1-3
+    bool rle_tiles();
+    bool tails_and_symbols();
+    bool spec_runs();
+    bool blocks_and_bits();
+    void debug_dumps();
+    void stage_times();
+    bool finish();           // poisoned streams, streams for the cut rounds, the results
+};
+
+bool DeflateCall::begin() {
     for (int i = 0; i < n; i++) {  // what the caller sees if a HIP call fails before the results are known
         out_len[i] = 0;
         if (status) status[i] = ZS_STREAM_ERROR;
     }
-    bool any_writes = false;
     for (int i = 0; i < n && writes; i++) any_writes = any_writes || writes[i] != nullptr;
     if (any_writes && n > 1)
         for (int i = 0; i < n; i++)
@@ -302,405 +361,30 @@ bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len
     // state, the chains it imports), the re-entries of this function (force_seq, force_lit, rounds, a call barred from the
     // sweeps' rounds), level 0 (the block list on the device) and Writes under a flush mode (the device counts blocks into their
     // table).  ZS_NO_PLAN_REUSE: every call plans.
-    if (!c->plan) c->plan = new PlanCache();
-    PlanCache &pc = *c->plan;
-    const bool no_rounds_this_call = c->no_rounds_once;
+    no_rounds_this_call = c->no_rounds_once;
     c->no_rounds_once = false;
     c->fast_rounds = 0;
     c->plan_reused = 0;
-    bool plan_hit = false, plan_keep = false;
-    {
-        bool flush_any = false;
-        std::vector<PlanWritesView> views;
-        std::vector<const PlanWritesView *> view_ptrs;
-        if (any_writes) {
-            views.resize((size_t)n), view_ptrs.assign((size_t)n, nullptr);
-            for (int i = 0; i < n; i++) {
-                const WriteSpec *wr = writes[i];
-                if (!wr) continue;
-                flush_any = flush_any || wr->flushing() || wr->flush.size() != wr->ends.size();
-                views[(size_t)i] = PlanWritesView{wr->ends.data(), wr->flush.data(), wr->ends.size(), wr->chunk, wr->raw};
-                view_ptrs[(size_t)i] = &views[(size_t)i];
-            }
-        }
-        plan_keep = !ro && !rounds && !force_lit && !no_rounds_this_call && force_seq == 0 && level != 0 && !flush_any && !getenv("ZS_NO_PLAN_REUSE");
-        if (plan_keep) {
-            plan_key_fill(pc.probe, n, in_len, out_cap, level, strategy, hash_variant, force_seq, ro != nullptr, rounds, force_lit != nullptr, no_rounds_this_call,
-                          any_writes ? view_ptrs.data() : nullptr, plan_env_read());
-            plan_hit = pc.valid && pc.gen == c->plan_gen && !pc.in_flight && plan_key_equal(pc.key, pc.probe);
-        }
-        if (!plan_hit) pc.valid = false, pc.dual_saved = false, c->plan_gen++;  // (this call writes the buffers the kept plan lives in)
+    bool flush_any = false;
+    for (int i = 0; i < n && any_writes; i++)
+        if (const WriteSpec *wr = writes[i]) flush_any = flush_any || wr->flushing() || wr->flush.size() != wr->ends.size();
+    plan_keep = !ro && !rounds && !force_lit && !no_rounds_this_call && force_seq == 0 && level != 0 && !flush_any && !env.no_plan_reuse;
+    if (plan_keep) {
+        plan_key_fill(pc.probe, n, in_len, out_cap, level, strategy, hash_variant, force_seq, ro != nullptr, rounds, force_lit != nullptr, no_rounds_this_call,
+                      any_writes ? writes : nullptr, penv);
+        plan_hit = pc.valid && pc.gen == c->plan_gen && !pc.in_flight && plan_key_equal(pc.key, pc.probe);
     }
-    // CompressionStrategy.Rle does not look at Write ends: Deflate.Rle.cs leaves a Deflate call as soon as fewer than MAX_MATCH bytes
-    // are ahead under NoFlush (:24-38), so every match is measured with a full lookahead whatever the Writes are, and nothing is
-    // inserted anywhere.  What a Write end can move is the loop-top at which the window slides -- when it lies within 262 bytes
-    // below a window end -- and with it a block's permission to be stored.  Any other NoFlush schedule is the single Write's
-    // stream (checked against the oracle on random data and schedules, tests/test_oracle.py) and runs as one.
-    std::vector<WriteSpec> rle_one;
-    std::vector<const WriteSpec *> rle_writes;
-    if (any_writes && strategy == kRle && level >= 1 && !ro && !getenv("ZS_NO_RLE_MULTI")) {
-        rle_one.resize((size_t)n);
-        rle_writes.assign(writes, writes + n);
-        for (int i = 0; i < n; i++) {
-            const WriteSpec *wr = writes[i];
-            if (!wr || wr->ends.size() <= 1 || wr->flushing()) continue;
-            bool safe = true;
-            for (size_t k = 0; k + 1 < wr->ends.size() && safe; k++) {
-                const int64_t E = wr->ends[k];
-                safe = !(E >= kWindowSize - kMinLookahead && (E % kWSize) >= kWSize - kMinLookahead);
-            }
-            if (safe) {
-                rle_one[(size_t)i] = *wr;
-                rle_one[(size_t)i].ends.assign(1, in_len[i]);
-                rle_one[(size_t)i].flush.assign(1, 0);
-                rle_writes[(size_t)i] = &rle_one[(size_t)i];
-            }
-        }
-        writes = rle_writes.data();
-    }
-    // Levels 1-3, a few streams of 256 KiB .. 4 MiB: data that is all period (zeros, image rows, a short period) takes the sweeps'
-    // rounds one range a round -- 1 MiB of zeros 57 ms -- and the speculative runs' engine 7; anything else is better off with
-    // the sweeps, and which it is the links tell (zs_fast_probe_kernel).  Such a batch is planned for both; the kernels behind
-    // the link kernel see the one the probe chose.
-    static const int64_t fast_min_input = getenv("ZS_FAST_MIN_INPUT") ? atoll(getenv("ZS_FAST_MIN_INPUT")) : kFastMinPeriodic;
-    // (a batch with a Write list anywhere is not planned for both: its list-less streams take the sweeps -- the same bytes)
-    bool allow_dual = lv.func == 1 && strategy != kRle && strategy != kHuffmanOnly && !any_writes && !ro && !rounds && force_seq == 0 && !force_lit && n <= 16 && !getenv("ZS_NO_FAST_VEC") &&
-                      !getenv("ZS_FAST_NO_ROUNDS");
-    for (int i = 0; i < n && allow_dual; i++) allow_dual = in_len[i] >= fast_min_input && in_len[i] < kFastMinInput;
-    bool dual_broken = false;
-    // The speculative chunk walk.  ZS_NO_SPEC: every stream through the maps; ZS_SPEC_LEN / ZS_SPEC_WARM /
-    // ZS_SPEC_MIN: the chunk length (512, 1024 or 2048), the warm-up and the shortest stream that tries it; ZS_SPEC_CORRUPT=j:
-    // chunk j's recorded guess is spoiled (the tests' way to a failed verification)
-    const bool spec_on = !getenv("ZS_NO_SPEC");
-    const int spec_len_env = getenv("ZS_SPEC_LEN") ? atoi(getenv("ZS_SPEC_LEN")) : 0;
-    const int spec_bits = spec_len_env == 512 ? 9 : spec_len_env == 2048 ? 11 : spec_len_env == 1024 ? 10 : kSpecLenBits;
-    const int spec_warm = getenv("ZS_SPEC_WARM") ? std::max(0, std::min(4096, atoi(getenv("ZS_SPEC_WARM")))) : kSpecWarm;
-    const int64_t spec_min = getenv("ZS_SPEC_MIN") ? std::max<int64_t>(kWindowSize, atoll(getenv("ZS_SPEC_MIN"))) : kSpecMinInput;
-    const int spec_corrupt = getenv("ZS_SPEC_CORRUPT") ? atoi(getenv("ZS_SPEC_CORRUPT")) : -1;
-    // (pl and the o_* below are the context's, not this frame's: a re-entry of run_pipeline plans into them again.  Every re-entry
-    // is a `return run_pipeline(...)` -- the outer frame reads none of them afterwards -- and has to stay one.)
-    Plan &pl = pc.pl;
-    size_t &o_clear = pc.o[0], &o_adler = pc.o[1], &o_links = pc.o[2], &o_match = pc.o[3], &o_chunks = pc.o[4], &o_segs = pc.o[5], &o_sups = pc.o[6],
-           &o_blocks = pc.o[7], &o_runs = pc.o[8];
-    // ---- the plan, its workspace and its upload: everything a same-shaped call skips (the body is not indented) ----
-    auto plan_call = [&]() -> bool {
-plan_again:
-    pl = Plan();
-    pl.sd.resize((size_t)n);
-    // positions per workgroup of the link kernel (each replays 32 Ki positions of warm-up first): long spans for a
-    // big batch, shorter ones when that is what it takes to give every CU a workgroup
-    int64_t total_len = 0;
-    for (int i = 0; i < n; i++) total_len += in_len[i];
-    const int64_t link_span = total_len >= (48ll << 20) ? 262144 : total_len >= (24ll << 20) ? 131072 : 65536;
-    pc.link_span = link_span;
-    // a speculative run's share of its stream (levels 1-3, image-like data): a run is one wave on one CU, so a batch shorter than
-    // 256 runs of 256 KiB is cut finer, down to 64 KiB a run (64 KiB of warm-up in front of each: at most twice the work)
-    const int run_chunk = getenv("ZS_FAST_CHUNK") ? std::max(65536, std::min((int)kFastChunk, atoi(getenv("ZS_FAST_CHUNK")) & ~65535))
-                                                  : (int)std::max<int64_t>(65536, std::min<int64_t>(kFastChunk, ((total_len / 256 + 65535) >> 16) << 16));
-    for (int i = 0; i < n; i++) {
-        StreamDesc &s = pl.sd[(size_t)i];
-        int64_t len = in_len[i];
-        const WriteSpec *const wr = writes ? writes[i] : nullptr;  // this stream's own Writes
-        s.in = (const uint8_t *)in[i];
-        s.out = (uint8_t *)out[i];
-        s.out_cap = out_cap[i];
-        s.n = (int32_t)len;
-        const bool multi = wr && wr->ends.size() > 1;
-        // an incremental run always takes the block-by-block output accounting (its state is carried from run to run)
-        const bool flushing = wr && (wr->flushing() || ro);
-        const bool resume = ro && ro->resume;
-        const bool cont = ro && ro->cont && !resume, final_run = !ro || ro->final_run;
-        // the bulk pipeline takes the NoFlush schedules build_geometry accepts (zs_core.h: any Write sizes but streams written
-        // a few bytes at a time); a stream the resolve kernel flagged (force_lit: a read whose pre-insert hashes bytes behind the
-        // data) and other streams of several Writes run on the literal engine.  Levels 1-3 keep the single Write's events.
-        std::vector<ReadEvent> rev;
-        Geometry geo;
-        const int64_t one_write[1] = {len};
-        const bool real_flush = wr && wr->flushing();
-        const bool lit_forced = force_lit && (*force_lit)[(size_t)i];
-        const std::vector<int64_t> no_ends_;
-        GeoStart gs;
-        if (resume) gs.resume = true, gs.at_read = ro->at_read, gs.p0 = ro->p0, gs.E0 = ro->E0, gs.base0 = ro->base0;
-        // (a flush mode on the run's last Write alone is the tail engine's business: it closes the block there)
-        bool inner_flush = false;
-        if (wr)
-            for (size_t k = 0; k + 1 < wr->flush.size(); k++) inner_flush = inner_flush || wr->flush[k] != 0;
-        const bool slow_ok = lv.func == 2 && strategy != kRle && !cont && !lit_forced && !(multi && inner_flush) &&
-                             build_geometry(len, multi ? wr->ends : no_ends_, geo, gs);
-        // levels 1-3 take several NoFlush Writes too when every read brings a full lookahead and no Write ends where its loop-top
-        // may or may not slide the window (zs_core.h build_read_events: Stream.CopyTo's 81 920-byte Writes do; a Write every few
-        // bytes does not)
-        const bool fast_multi = multi && !inner_flush && !cont && !resume && lv.func == 1 && strategy != kRle && !getenv("ZS_NO_FAST_MULTI") &&
-                                build_read_events(len, wr->ends, rev, true);
-        // levels 1-3 behind a flush (round 5): the run goes on from the suspended engine's chains too -- zs_import_chains_kernel's
-        // links ARE DeflateFast's chains for the history (prev[] names inserted positions only), so with "inserted" for every
-        // position the chains reach, the sweeps start at p0 as they start at 0; one Write, the engine standing at the flush
-        // (several NoFlush Writes behind the flush as well, on the conditions of a stream's several Writes: every read brings a
-        // full lookahead, no Write ends where its loop-top may or may not slide the window)
-        const bool fast_resume = resume && ro->at_read && lv.func == 1 && strategy != kRle && !inner_flush && !lit_forced && !getenv("ZS_NO_FAST_RESUME") &&
-                                 len - ro->p0 >= 2 * kMinLookahead &&
-                                 (multi ? build_read_events(len, wr->ends, rev, true, ro->p0, ro->base0)
-                                        : build_read_events(len, std::vector<int64_t>(one_write, one_write + 1), rev, true, ro->p0, ro->base0));
-        const bool regular = fast_resume ? true : cont ? false : multi ? fast_multi : build_read_events(len, std::vector<int64_t>(one_write, one_write + 1), rev);
-        s.body_end = slow_ok ? (int32_t)geo.body_end : -1;
-        // levels 1-3, one Write: the speculative chunk runs for large streams (they verify on periodic data and are parallel
-        // inside a stream), else -- and when they did not verify (force_seq) -- DeflateFast for the lanes of a wave
-        // (round 5: also the first run of a stream that flushes -- one Write, the flush at its end: the tail engine closes the
-        // block and is left suspended as it is behind the slow levels' bulk runs)
-        const bool fast_one = lv.func == 1 && strategy != kRle && regular && len >= kMinLookahead && !cont && !resume &&
-                              ((!flushing && final_run && !ro && (!multi || fast_multi)) || (ro && (!multi || fast_multi) && !inner_flush && !lit_forced && !getenv("ZS_NO_FAST_RESUME")));
-        // (force_seq: 1 -- the runs did not verify, or the data does not look periodic: the sweeps; 2 -- they did not verify and the
-        // stream is few symbols: one run of the engine for the whole stream, below)
-        // (a run's buffers are 1.7 MB whatever the stream's length: streams below 4 MiB only in batches of a few -- allow_dual)
-        // (HuffmanOnly: nothing is searched, every position a literal -- the sweeps take that at 7 GB/s, the runs' engine symbol by symbol)
-        const bool fast_par = fast_one && !multi && force_seq != 1 && !ro && strategy != kHuffmanOnly &&
-                              (len >= kFastMinInput || allow_dual || (force_seq == 2 && n <= 16 && len >= fast_min_input));
-        if (allow_dual && !fast_par) dual_broken = true;
-        s.fv_end = ((fast_one && (!fast_par || allow_dual) && !getenv("ZS_NO_FAST_VEC")) || fast_resume) ? (int32_t)(len - kMinLookahead) : -1;
-        s.ins_bits = nullptr;
-        if (s.fv_end >= 0) {
-            pl.any_fv = true;
-        }
-        // CompressionStrategy.Rle, one Write: the parse is a function of where the runs of equal bytes begin (zs_rle.h)
-        s.rle_end = -1, s.rle_tile_off = 0;
-        s.fr_first = 0, s.fr_n = 0;
-        if (strategy == kRle && level >= 1 && !multi && !flushing && final_run && !ro && regular && !getenv("ZS_NO_RLE_RUNS")) {
-            s.rle_end = (int32_t)rle_body_end(len);
-            if (s.rle_end >= 0) {
-                pl.any_rle = true;
-                s.rle_tile_off = (int32_t)pl.n_rle_tiles;
-                pl.n_rle_tiles += (s.rle_end + kMaxMatch + 1 + 4095) / 4096;
-            }
-        }
-        s.n_wr = (multi || flushing) ? (int32_t)wr->ends.size() : 1;  // 0: a run without input (Finish alone)
-        s.wr_end = nullptr;
-        s.wr_flush = nullptr, s.wr_blk = nullptr, s.out_chunk = wr ? wr->chunk : 512, s.raw = wr && wr->raw;
-        s.kl = num_refills(len - (resume ? ro->base0 : 0));
-        s.resume = resume && (slow_ok || fast_resume) ? 1 : 0, s.cont_bits = (cont || resume) ? 1 : 0, s.mid_write = (ro && (ro->mid_write || (resume && !ro->at_read))) ? 1 : 0;
-        if (resume && !slow_ok && !fast_resume) {
-            c->err = "the run cannot go on in the bulk pipeline from where the literal engine stopped";
-            return false;
-        }
-        s.start_slot = resume ? ro->slot : 0, s.start_syms = resume ? ro->start_syms : 0, s.base0 = resume ? ro->base0 : 0;
-        s.start_block = resume ? ro->start_block : 0, s.start_pos = resume ? ro->p0 : 0, s.persist_off = resume ? ro->abs_off : 0, s.stop_abs = (ro && cont) ? ro->stop_abs : -1;
-        s.nchunks = s.body_end >= 0 ? geo.nchunks() : 0;
-        s.pos_off = pl.n_pos;
-        pl.n_pos += (len + 64 + 63) & ~63LL;
-        s.sym_off = pl.n_syms;
-        pl.n_syms += len + 64 + (ro ? kLitBufsize : 0);  // a continued run starts with the symbols of the block in progress
-        s.chunk_off = (int32_t)pl.n_chunks;
-        pl.n_chunks += s.nchunks;
-        s.seg_off = (int32_t)pl.n_segs;
-        s.nsegs = 0;
-        s.cut_off = (int32_t)pl.n_cuts, s.cut_cap = 0;
-        s.grid_chunks = 0;
-        if (s.body_end >= 0) {
-            s.grid_chunks = 1;
-            for (size_t k = 1; k + 1 < geo.cstart.size() && s.grid_chunks; k++)
-                if (geo.cstart[k] != (int32_t)((int64_t)k * kChunk - (kMinLookahead - 1))) s.grid_chunks = 0;
-            // ... and the segments those of a single Write's window ends (chunk_ctx's closed form for the chunk -> segment marks)
-            if (geo.cstart.empty() || geo.cstart[0] != 0) s.grid_chunks = 0;
-            for (size_t k = 0; k < geo.head.size() && s.grid_chunks; k++)
-                if (geo.head[k] != ((k >= 32 && ((k - 32) & 15) == 0) ? (int32_t)((k - 32) >> 4) + 2 : 0)) s.grid_chunks = 0;
-            s.cut_cap = (int32_t)(geo.cl.size() + (size_t)geo.nsegs() + 8);
-            pl.n_cuts += s.cut_cap;
-            s.nsegs = geo.nsegs();
-            const int32_t cl0 = (int32_t)pl.cl.size();
-            pl.seg_c0.insert(pl.seg_c0.end(), geo.seg_c0.begin(), geo.seg_c0.end());
-            pl.seg_after.insert(pl.seg_after.end(), geo.seg_after.begin(), geo.seg_after.end());
-            pl.seg_base.insert(pl.seg_base.end(), geo.seg_base.begin(), geo.seg_base.end());
-            pl.seg_S.insert(pl.seg_S.end(), geo.seg_S.begin(), geo.seg_S.end());
-            for (int32_t v : geo.seg_cl) pl.seg_cl.push_back(v + cl0);
-            pl.cl.insert(pl.cl.end(), geo.cl.begin(), geo.cl.end());
-            pl.cstart.insert(pl.cstart.end(), geo.cstart.begin(), geo.cstart.end());
-            pl.head.insert(pl.head.end(), geo.head.begin(), geo.head.end());
-        } else {
-            if (fast_resume) {  // segment 0: the engine as the flush left it -- the data ends at p0, so the first event fires at the run's first loop-top
-                // (an event's trigger is the data end before it - 261, and a negative one means "none": p0 below 261 counts as 261)
-                pl.seg_c0.push_back(0), pl.seg_after.push_back((int32_t)std::max<int64_t>(ro->p0, kMinLookahead - 1)), pl.seg_base.push_back((int32_t)ro->base0);
-                pl.seg_S.push_back(0), pl.seg_cl.push_back((int32_t)pl.cl.size());
-                s.nsegs++;
-            }
-            if (s.fv_end >= 0 || s.rle_end >= 0)  // levels 1-3, Rle: the events of the single Write (the tail engine takes base and data end from them)
-                for (size_t k = 0; k < rev.size(); k++) {
-                    const int64_t at = (k || fast_resume) ? rev[k].at - (s.rle_end >= 0 ? kMaxMatch : kMinLookahead - 1) : 0;  // where the segment starts
-                    if (at > (s.rle_end >= 0 ? s.rle_end : s.fv_end)) break;
-                    pl.seg_c0.push_back(0), pl.seg_after.push_back((int32_t)rev[k].after), pl.seg_base.push_back((int32_t)rev[k].base);
-                    pl.seg_S.push_back(0), pl.seg_cl.push_back((int32_t)pl.cl.size());
-                    s.nsegs++;
-                }
-            pl.seg_cl.push_back((int32_t)pl.cl.size());
-            pl.cstart.push_back(0);
-        }
-        s.seg_c0 = s.seg_after = s.seg_base = s.seg_S = s.seg_cl = nullptr, s.cl = nullptr, s.cstart = nullptr, s.head = nullptr;
-        pl.n_segs += s.nsegs;
-        s.sup_off = (int32_t)pl.n_sups;
-        pl.n_sups += (s.nsegs + kSupSegs - 1) / kSupSegs;
-        // the speculative chunk walk in place of the maps: the slow levels' single Write from a minimum length on (a stream that
-        // does not verify, or whose match tiles say it is periodic, goes to the maps as it always did)
-        s.spec = 0, s.spec_n = 0, s.spec_off = (int32_t)pl.n_spec;
-        bool spec_geo = s.body_end >= 0 && geo.body_end == len - kMinLookahead;
-        if (spec_geo) {
-            // the speculative grid's own closed form (spec_chunk_ctx): segment k >= 1 is the one window end 65536 + 32768 (k - 1),
-            // whatever the 2048-position chunks of the map path look like
-            const int64_t want = 1 + (len > kWindowSize ? (len - kWindowSize - 1) / kWSize + 1 : 0);
-            spec_geo = (int64_t)geo.nsegs() == want && geo.seg_cl.size() == (size_t)want + 1 && geo.seg_cl[0] == 0 && geo.seg_cl[1] == 0;
-            for (int64_t k = 1; k < want && spec_geo; k++)
-                spec_geo = geo.seg_cl[(size_t)k + 1] - geo.seg_cl[(size_t)k] == 1 &&
-                           geo.cl[(size_t)geo.seg_cl[(size_t)k]] == ((uint32_t)(kWindowSize + kWSize * (k - 1)) | kClWindowBit);
-        }
-        if (spec_on && lv.func == 2 && (strategy == kDefault || strategy == kFiltered) && !wr && !ro && !lit_forced && spec_geo && len >= spec_min &&
-            n <= 65535) {
-            s.spec = 1, s.spec_n = (int32_t)((((int64_t)s.body_end + kMinLookahead - 1) >> spec_bits) + 1);
-            pl.n_spec += s.spec_n, pl.n_spec_streams++;
-            pl.max_spec_n = std::max(pl.max_spec_n, (int)s.spec_n);
-        }
-        // levels 1-3, one Write, large enough: speculative chunk runs instead of one sequential engine
-        s.run_chunk = run_chunk;
-        s.fast_runs = fast_par ? (force_seq == 2 ? 1 : (int32_t)((len + run_chunk - 1) / run_chunk)) : 0;
-        s.run_slots = fast_par ? (force_seq == 2 ? (int32_t)((len + 4096) / kFastChunk + 1) : s.fast_runs) : 0;
-        s.run_off = (int32_t)pl.n_runs;
-        pl.n_runs += s.run_slots;
-        pl.w_runs.add(i, s.fast_runs);
-        s.blk_off = (int32_t)pl.n_blocks;
-        // level 0 runs with memLevel 7: a block is flushed every 8191 symbols (only Rle tallies symbols there)
-        s.max_blocks = (int32_t)(level == 0 ? len / 8191 + len / 32506 + 4 : len / kBlockSyms + 2);
-        if (flushing) s.max_blocks += (int32_t)wr->ends.size() + 1;  // every Write under a flush mode closes a block
-        s.plan_blk = nullptr, s.plan_nblk = 0;
-        s.final_run = final_run ? 1 : 0, s.cont = cont ? 1 : 0, s.persist = ro ? ro->persist : nullptr;
-        s.abs_off = (ro && !resume) ? ro->abs_off : 0, s.adler_stream = ro ? ro->adler_stream : 1, s.carry_byte = ro ? ro->carry_byte : 0;
-        if (level == 0 && strategy != kRle && !ro) {
-            // DeflateStored: block boundaries from the sizes alone (zs_core.h plan_stored_blocks); s.plan_blk holds the
-            // offset into the batch's list until the device address is known
-            const size_t first = pl.plan_blk.size();
-            const std::vector<int64_t> no_ends;
-            const std::vector<uint8_t> no_flush;
-            if (flushing) pl.plan_wr_blk.assign(wr->ends.size(), 0);
-            plan_stored_blocks(len, (multi || flushing) ? wr->ends : no_ends, flushing ? wr->flush : no_flush,
-                               [&](int64_t start, int32_t blen, int can_store, int eof) {
-                                   pl.plan_blk.push_back(BlockRec{start, 0, blen, 0, can_store, eof});
-                               },
-                               [&](int w, int nb) {
-                                   if (flushing) pl.plan_wr_blk[(size_t)w] = nb;
-                               });
-            s.plan_nblk = (int32_t)(pl.plan_blk.size() - first);
-            s.plan_blk = (const BlockRec *)(uintptr_t)first;
-            s.max_blocks = s.plan_nblk + 1;
-        }
-        pl.n_blocks += s.max_blocks;
-        s.adler_off = (int32_t)pl.n_pieces;
-        s.n_adler = ro ? 0 : (int32_t)((len + kAdlerPiece - 1) / kAdlerPiece);  // an incremental stream's checksum is its owner's
-        pl.n_pieces += s.n_adler;
-        pl.w_clear.add(i, (s.out_cap + 65535) / 65536);
-        pl.w_adler.add(i, s.n_adler);
-        if (s.body_end >= 0 || s.fast_runs > 0 || s.fv_end >= 0)
-            pl.w_links.add(i, len - 5 > 0 ? (len - 5 + link_span - 1) / link_span : 0);
-        if (s.body_end >= 0) {
-            pl.w_match.add(i, (int64_t)s.body_end / kMatchTile + 1);
-            pl.w_chunks.add(i, s.nchunks);
-            pl.w_segs.add(i, s.nsegs);
-            if (s.nsegs > kSupSegs) pl.w_sups.add(i, (s.nsegs + kSupSegs - 1) / kSupSegs);  // shorter streams are resolved row by row
-        }
-        pl.w_blocks.add(i, s.max_blocks);
-        // what none of the parallel forms takes is the one-wave literal engine's: the whole run, not just its last 261 bytes
-        if (s.body_end < 0 && s.fv_end < 0 && s.rle_end < 0 && s.fast_runs == 0 && s.plan_nblk == 0 && !(level == 0 && strategy != kRle && !ro)) {
-            const int64_t from = resume ? ro->p0 : ro ? ro->hist : 0;
-            pl.lit_bytes += std::max<int64_t>(0, len - from - (kMinLookahead - 1));
-        }
-    }
-    {
-        // the walk's grids are (most chunks of a stream / 64) x streams: one long stream among thousands of short ones would make
-        // them mostly workgroups that return at once, twice per call -- such a batch keeps the maps
-        int64_t need = 0;
-        for (int i = 0; i < n; i++) need += (pl.sd[(size_t)i].spec_n + 63) / 64;
-        if (pl.n_spec && (int64_t)((pl.max_spec_n + 63) / 64) * n > 4 * need + 4096) {
-            for (int i = 0; i < n; i++) pl.sd[(size_t)i].spec = 0, pl.sd[(size_t)i].spec_n = 0, pl.sd[(size_t)i].spec_off = 0;
-            pl.n_spec = 0, pl.max_spec_n = 0, pl.n_spec_streams = 0;
-        }
-    }
-    if (allow_dual && dual_broken) {  // (a stream the fast forms do not take after all: the batch as it always was planned)
-        allow_dual = false, dual_broken = false;
-        goto plan_again;
-    }
-    pl.any_dual = allow_dual;
-    if (pl.any_fv && !getenv("ZS_FAST_NO_ROUNDS") && !no_rounds_this_call && !(ro && ro->resume && getenv("ZS_NO_RESUME_ROUNDS"))) {
-        // levels 1-3: every stream's parse as rounds over its chunks, all chunks of the batch at once (zs_fast_sweep.h "Rounds"),
-        // when that is the shorter way.  One workgroup per stream takes as long as the longest stream at 46 / 35 / 20 MB/s (levels
-        // 1 / 2 / 3 on text; kennedy.xls and ptt5 are slower).  The rounds take the whole batch through the chip at ~3.5 GB/s a few
-        // times over and then wait for the last disturbances to die out -- up to ~16 ms on text, less on anything else, and never
-        // longer than the longest stream takes one workgroup (profiles/r04_fast_batch_shapes.log: 4 x 4 MiB 26 against 88 ms,
-        // 32 x 4 MiB 46 against 91, 32 x 1 MiB 21 against 23, 64 x 1 MiB 26 against 23, 128 x 256 KiB 10 against 6.6 at level 1; at
-        // level 3 the rounds win up to 64 x 1 MiB: 31 against 49).
-        int64_t pos_fv = 0, max_fv = 0;
-        for (int i = 0; i < n; i++)
-            if (pl.sd[(size_t)i].fv_end >= 0) {
-                pos_fv += pl.sd[(size_t)i].fv_end + 1 - pl.sd[(size_t)i].start_pos;
-                max_fv = std::max<int64_t>(max_fv, pl.sd[(size_t)i].fv_end + 1 - pl.sd[(size_t)i].start_pos);
-            }
-        const double t_stream = (double)max_fv / (level >= 3 ? 20e6 : level == 2 ? 35e6 : 46e6);
-        const double t_rounds = std::min(0.016, (double)max_fv / 60e6) + (double)pos_fv / 3.5e9;
-        if (getenv("ZS_FR_RATIO") ? (double)pos_fv <= atof(getenv("ZS_FR_RATIO")) * (double)max_fv : t_rounds < t_stream) {
-            // chunks of 2048 positions or more (a run's fixed cost -- staging 32 K positions of history -- is 15-30 us, a sweep makes
-            // ~390 positions final in 8 us), at most what one staging of the tile covers; between the two, as many chunks as fit
-            // the chip at once: a round of 260 chunks takes the 256 CUs twice as long as one of 250
-            int64_t target = getenv("ZS_FR_CHUNK") ? atoll(getenv("ZS_FR_CHUNK")) : pos_fv / 250;
-            target = target < 2048 ? 2048 : target > kFsChunkMax ? kFsChunkMax : target;
-            bool too_short = false;
-            for (;;) {
-                pl.fr_chunks.clear();
-                pl.fr_max_n = 0;
-                too_short = false;
-                for (int i = 0; i < n; i++) {
-                    StreamDesc &s = pl.sd[(size_t)i];
-                    if (s.fv_end < 0) continue;
-                    s.fr_first = (int32_t)pl.fr_chunks.size();
-                    {
-                        // the stream's read events are its segments (seg_after of event k - 1 = the data end before event k)
-                        const int32_t *after = pl.seg_after.data() + s.seg_off;
-                        // (a resumed run: segment 0 is the engine as the flush left it, event 1 the read at p0 itself)
-                        const bool res = s.resume != 0;
-                        const int64_t shortest = fs_build_chunks(i, (int64_t)s.fv_end, s.nsegs - 1, [&](int k) { return (int64_t)after[k - 1] - (kMinLookahead - 1); }, (int)target, pl.fr_chunks,
-                                                                 res ? 2 : 1, res ? s.start_pos : 0);
-                        if (shortest < kFsMinSpan) too_short = true;  // (Write ends a few hundred bytes apart: more chunks in a chunk's reach than it looks at)
-                    }
-                    s.fr_n = (int32_t)pl.fr_chunks.size() - s.fr_first;
-                    pl.fr_max_n = s.fr_n > pl.fr_max_n ? s.fr_n : pl.fr_max_n;
-                }
-                if (pl.fr_chunks.size() <= 256 || target >= kFsChunkMax || getenv("ZS_FR_CHUNK")) break;
-                target += 128;
-            }
-            if (too_short) {  // one workgroup per stream then
-                pl.fr_chunks.clear();
-                pl.fr_max_n = 0;
-                for (int i = 0; i < n; i++) pl.sd[(size_t)i].fr_first = pl.sd[(size_t)i].fr_n = 0;
-            }
-            for (FsChunk &ck : pl.fr_chunks) {
-                ck.prov_off = (uint32_t)pl.fr_prov;
-                pl.fr_prov += (size_t)(ck.b_hi - ck.b_lo) + kMaxMatch + 64;  // (its loop-tops lie in [b_lo, b_hi + 258))
-            }
-            if (pl.fr_prov > 0xFFFF0000u) {  // (prov_off is 32 bits: a batch beyond ~4 G positions takes one workgroup per stream)
-                pl.fr_chunks.clear();
-                pl.fr_max_n = 0, pl.fr_prov = 0;
-                for (int i = 0; i < n; i++) pl.sd[(size_t)i].fr_first = pl.sd[(size_t)i].fr_n = 0;
-            }
-        }
-    }
-    WorkList *const lists[kWorkLists] = {&pl.w_clear, &pl.w_adler, &pl.w_links, &pl.w_match, &pl.w_chunks, &pl.w_segs, &pl.w_sups, &pl.w_blocks, &pl.w_runs};
-    for (WorkList *l : lists) l->finish(n);
-    // ---- workspace ----
-    const size_t n_work = pl.w_clear.size() + pl.w_adler.size() + pl.w_links.size() + pl.w_match.size() + pl.w_chunks.size() +
-                          pl.w_segs.size() + pl.w_sups.size() + pl.w_blocks.size() + pl.w_runs.size();
-    // parse-segment tables: [seg_c0 | seg_after | seg_base | seg_S : int32 x n_segs each][seg_cl : int32 x (n_segs + n)]
-    // [cstart : int32 x (n_chunks + n)][head : int32 x n_chunks][cl : u32 x n_cl]
-    const size_t o_segcl = 16 * (size_t)pl.n_segs, o_cstart = o_segcl + 4 * ((size_t)pl.n_segs + (size_t)n),
-                 o_head = o_cstart + 4 * ((size_t)pl.n_chunks + (size_t)n), o_cl = o_head + 4 * (size_t)pl.n_chunks;
-    const size_t geo_bytes = o_cl + 4 * pl.cl.size();
-    // the descriptors, the work lists' prefixes and the tables back to back in one buffer, as they are in the staging area: one
-    // copy brings all three (a same-shaped call sends the descriptors alone)
-    const size_t sd_bytes = sizeof(StreamDesc) * (size_t)n, pre_bytes = 4 * (size_t)kWorkLists * (size_t)(n + 1);
-    const size_t up_bytes = sd_bytes + pre_bytes + geo_bytes;
-    if (!ensure(c, c->sd, up_bytes + 64) || !ensure(c, c->st, sizeof(StreamState) * (size_t)n) ||
-        !ensure(c, c->work, sizeof(uint2) * (n_work + 1)) || !ensure(c, c->link, 2 * (size_t)pl.n_pos + 64) ||
+    if (!plan_hit) pc.valid = false, pc.dual_saved = false, c->plan_gen++;  // (this call writes the buffers the kept plan lives in)
+    writes = fold_rle_writes(folded, n, in_len, writes, any_writes, level, strategy, ro != nullptr, penv);
+    pa.n = n, pa.in = in, pa.in_len = in_len, pa.out = out, pa.out_cap = out_cap, pa.level = level, pa.strategy = strategy;
+    pa.writes = writes, pa.force_seq = force_seq, pa.ro = ro, pa.rounds = rounds, pa.force_lit = force_lit, pa.no_rounds = no_rounds_this_call;
+    return true;
+}
+
+bool DeflateCall::bind_plan() {
+    const int spec_bits = plan_spec_bits(penv);
+    if (!ensure(c, c->sd, lay.up_bytes + 64) || !ensure(c, c->st, sizeof(StreamState) * (size_t)n) ||
+        !ensure(c, c->work, sizeof(uint2) * (lay.work[kWorkLists] + 1)) || !ensure(c, c->link, 2 * (size_t)pl.n_pos + 64) ||
         !ensure(c, c->mm, 8 * (size_t)pl.n_pos + 256) ||  // the symbol kernel stages whole 128-byte lines
         !ensure(c, c->maps, 4 * (size_t)(pl.n_chunks + 1) * kSlots) || !ensure(c, c->segmap, 8 * (size_t)(pl.n_segs + 1) * kSlots) ||
         !ensure(c, c->supmap, 8 * (size_t)(pl.n_sups + 1) * kSlots) || !ensure(c, c->chunk_far, 2 * (size_t)pl.n_chunks + 64) ||
@@ -716,66 +400,31 @@ plan_again:
         (pl.n_spec && (!ensure(c, c->spec_rec, 8 * (size_t)pl.n_spec + 64) || !ensure(c, c->spec_flags, 4 * (size_t)n + 64) ||
                        !ensure(c, c->spec_syms, 4 * (size_t)pl.n_spec * (size_t)spec_slab_stride(spec_bits) + 64))))
         return false;
-    for (int i = 0; i < n; i++) {
-        StreamDesc &s = pl.sd[(size_t)i];
-        const uint8_t *gb = (const uint8_t *)c->sd.p + sd_bytes + pre_bytes;
-        const int32_t *g = (const int32_t *)gb;
-        s.seg_c0 = g + s.seg_off, s.seg_after = g + pl.n_segs + s.seg_off, s.seg_base = g + 2 * pl.n_segs + s.seg_off;
-        s.seg_S = g + 3 * pl.n_segs + s.seg_off;
-        s.seg_cl = (const int32_t *)(gb + o_segcl) + s.seg_off + i;
-        s.cstart = (const int32_t *)(gb + o_cstart) + s.chunk_off + i;
-        s.head = (const int32_t *)(gb + o_head) + s.chunk_off;
-        s.cl = (const uint32_t *)(gb + o_cl);
-    }
-    if (pl.any_fv) {
-        // one bit per position (pos_off is a multiple of 64: every stream's bitmap starts on a word)
-        if (!ensure(c, c->ins_bits, (size_t)pl.n_pos / 8 + kFvBitSlack)) return false;
-        for (int i = 0; i < n; i++)
-            if (pl.sd[(size_t)i].fv_end >= 0) pl.sd[(size_t)i].ins_bits = dev<uint32_t>(c->ins_bits) + pl.sd[(size_t)i].pos_off / 32;
-    }
-    if (!pl.plan_blk.empty()) {
-        if (!ensure(c, c->plan_blk, sizeof(BlockRec) * pl.plan_blk.size())) return false;
-        for (int i = 0; i < n; i++)
-            if (pl.sd[(size_t)i].plan_nblk) pl.sd[(size_t)i].plan_blk = dev<BlockRec>(c->plan_blk) + (uintptr_t)pl.sd[(size_t)i].plan_blk;
-    }
+    if (pl.any_fv && !ensure(c, c->ins_bits, (size_t)pl.n_pos / 8 + kFvBitSlack)) return false;
+    if (!pl.plan_blk.empty() && !ensure(c, c->plan_blk, sizeof(BlockRec) * pl.plan_blk.size())) return false;
     if (pl.n_runs &&
         (!ensure(c, c->run_syms, 4 * (size_t)pl.n_runs * kFastRunSyms) || !ensure(c, c->run_bits, 4 * (size_t)pl.n_runs * kFastRunBitWords) ||
          !ensure(c, c->run_scratch, (size_t)pl.n_runs * kFastRunScratch) || !ensure(c, c->run_outs, sizeof(FastRunOut) * (size_t)pl.n_runs) ||
          !ensure(c, c->run_fail, 4 * (size_t)n + 64)))
         return false;
+    if (any_writes && !ensure(c, c->wr, lay.wr_bytes + 64)) return false;
+    plan_bind(pl, lay, pa, c->sd.p, pl.any_fv ? dev<uint32_t>(c->ins_bits) : nullptr, pl.plan_blk.empty() ? nullptr : dev<BlockRec>(c->plan_blk),
+              any_writes ? c->wr.p : nullptr);
+    return true;
+}
+
+bool DeflateCall::plan_and_upload() {
+    if (!plan_streams(pl, pa, penv, c->err)) return false;
+    plan_layout(lay, pl, pa);
+    if (!bind_plan()) return false;
     // rounds: the call goes on behind the batched cut rounds of the call that made it -- same plan, same workspace; nothing
     // is uploaded or zeroed again and the kernels up to the resolve kernel are not run (the descriptors get the pointers
     // into the Write table again: the table itself is on the device already)
-    if (any_writes) {
-        // every stream's block (zs_core.h write_block_bytes), back to back and 8-byte aligned:
-        // [ends: int64 x nw][blocks before each Write: int32 x nw][flush modes: u8 x nw]
-        std::vector<size_t> nws((size_t)n, 0), offs;
-        for (int i = 0; i < n; i++) {
-            const WriteSpec *wr = writes[i];
-            if (wr && (wr->ends.size() > 1 || wr->flushing() || ro)) nws[(size_t)i] = wr->ends.size();
-        }
-        const size_t wr_bytes = layout_write_blocks(nws, offs);
-        if (!ensure(c, c->wr, wr_bytes + 64)) return false;
-        std::vector<uint8_t> hw(rounds ? 0 : wr_bytes + 64, 0);
-        for (int i = 0; i < n; i++) {
-            const WriteSpec *wr = writes[i];
-            const size_t nw = nws[(size_t)i];
-            if (!wr || !(wr->ends.size() > 1 || wr->flushing() || ro)) continue;
-            uint8_t *blk = (uint8_t *)c->wr.p + offs[(size_t)i];
-            pl.sd[(size_t)i].wr_end = (const int64_t *)blk;
-            if (wr->flushing() || ro) {
-                pl.sd[(size_t)i].wr_blk = (int32_t *)(blk + 8 * nw);
-                pl.sd[(size_t)i].wr_flush = blk + 12 * nw;
-            }
-            if (rounds || !nw) continue;
-            memcpy(hw.data() + offs[(size_t)i], wr->ends.data(), sizeof(int64_t) * nw);
-            if (wr->flushing() || ro) memcpy(hw.data() + offs[(size_t)i] + 12 * nw, wr->flush.data(), nw);
-            if (!pl.plan_wr_blk.empty()) memcpy(hw.data() + offs[(size_t)i] + 8 * nw, pl.plan_wr_blk.data(), 4 * nw);  // (a flushing spec: one stream)
-        }
-        if (!rounds && wr_bytes) {
-            ZS_HIP(c, hipMemcpyAsync(c->wr.p, hw.data(), hw.size(), hipMemcpyHostToDevice, stream));
-            ZS_HIP(c, hipStreamSynchronize(stream));  // pageable source
-        }
+    if (any_writes && !rounds && lay.wr_bytes) {
+        std::vector<uint8_t> hw(lay.wr_bytes + 64, 0);
+        plan_stage_writes(hw.data(), pl, lay, pa);
+        ZS_HIP(c, hipMemcpyAsync(c->wr.p, hw.data(), hw.size(), hipMemcpyHostToDevice, stream));
+        ZS_HIP(c, hipStreamSynchronize(stream));  // pageable source
     }
     if (!rounds && !pl.plan_blk.empty()) {
         ZS_HIP(c, hipMemcpyAsync(c->plan_blk.p, pl.plan_blk.data(), sizeof(BlockRec) * pl.plan_blk.size(), hipMemcpyHostToDevice, stream));
@@ -783,332 +432,213 @@ plan_again:
     }
     // ---- upload descriptors, work lists' prefixes and tables: one copy from the plan's own pinned staging area ----
     // (the area keeps them after the call: a same-shaped call puts its pointers into the descriptors there and sends those)
-    if (!ensure_pinned(c, std::max(sd_bytes + 16, sizeof(StreamState) * (size_t)n)) || !ensure_plan_pin(c, up_bytes + 16)) return false;
-    uint8_t *hp = (uint8_t *)c->plan_pin;
-    memcpy(hp, pl.sd.data(), sd_bytes);
-    int32_t *hpre = (int32_t *)(hp + sd_bytes);
-    WorkOffsets wo;
-    {
-        size_t at = 0;
-        for (int l = 0; l < kWorkLists; l++) {
-            pc.o[l] = at;
-            wo.off[l] = (uint32_t)at;
-            memcpy(hpre + (size_t)l * (size_t)(n + 1), lists[l]->pre.data(), 4 * (size_t)(n + 1));
-            at += lists[l]->size();
-        }
-        wo.off[kWorkLists] = (uint32_t)at;
-    }
-    if (geo_bytes) {
-        uint8_t *hg = hp + sd_bytes + pre_bytes;
-        if (pl.n_segs) {
-            memcpy(hg, pl.seg_c0.data(), 4 * (size_t)pl.n_segs);
-            memcpy(hg + 4 * (size_t)pl.n_segs, pl.seg_after.data(), 4 * (size_t)pl.n_segs);
-            memcpy(hg + 8 * (size_t)pl.n_segs, pl.seg_base.data(), 4 * (size_t)pl.n_segs);
-            memcpy(hg + 12 * (size_t)pl.n_segs, pl.seg_S.data(), 4 * (size_t)pl.n_segs);
-        }
-        memcpy(hg + o_segcl, pl.seg_cl.data(), 4 * pl.seg_cl.size());
-        memcpy(hg + o_cstart, pl.cstart.data(), 4 * pl.cstart.size());
-        if (pl.n_chunks) memcpy(hg + o_head, pl.head.data(), 4 * (size_t)pl.n_chunks);
-        if (!pl.cl.empty()) memcpy(hg + o_cl, pl.cl.data(), 4 * pl.cl.size());
-    }
+    if (!ensure_pinned(c, std::max(lay.sd_bytes + 16, sizeof(StreamState) * (size_t)n)) || !ensure_plan_pin(c, lay.up_bytes + 16)) return false;
+    plan_stage((uint8_t *)c->plan_pin, pl, lay, n);
     if (!rounds) {
+        WorkOffsets wo;
+        for (int l = 0; l <= kWorkLists; l++) wo.off[l] = (uint32_t)lay.work[l];
+        const size_t n_work = lay.work[kWorkLists];
         pc.in_flight = true;
-        ZS_HIP(c, hipMemcpyAsync(c->sd.p, hp, up_bytes, hipMemcpyHostToDevice, stream));
+        ZS_HIP(c, hipMemcpyAsync(c->sd.p, c->plan_pin, lay.up_bytes, hipMemcpyHostToDevice, stream));
         if (n_work)
             hipLaunchKernelGGL(zs_worklist_kernel, dim3((unsigned)((n_work + 255) / 256)), dim3(256), 0, stream,
-                               (const int32_t *)((const uint8_t *)c->sd.p + sd_bytes), n, wo, dev<uint2>(c->work));
+                               (const int32_t *)((const uint8_t *)c->sd.p + lay.sd_bytes), n, wo, dev<uint2>(c->work));
     }
+    if (plan_keep) std::swap(pc.key, pc.probe), pc.valid = true, pc.gen = c->plan_gen;
     return true;
-    };
-    if (plan_hit) {
-        // the kept plan: the caller's pointers into the kept descriptors, and those alone to the device
-        c->plan_reused = 1;
-        if (pc.dual_saved) pl.sd = pc.dual_sd, pl.fr_chunks = pc.dual_fr, pl.fr_max_n = pc.dual_fr_max_n, pl.n_runs = pc.dual_n_runs, pl.any_fv = true;
-        StreamDesc *hd = (StreamDesc *)c->plan_pin;
-        for (int i = 0; i < n; i++) {
-            hd[i].in = pl.sd[(size_t)i].in = (const uint8_t *)in[i];
-            hd[i].out = pl.sd[(size_t)i].out = (uint8_t *)out[i];
-        }
-        pc.in_flight = true;
-        ZS_HIP(c, hipMemcpyAsync(c->sd.p, hd, sizeof(StreamDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
-    } else {
-        if (!plan_call()) return false;
-        if (plan_keep) std::swap(pc.key, pc.probe), pc.valid = true, pc.gen = c->plan_gen;
-    }
-    const int64_t link_span = pc.link_span;
-    c->lit_engine_bytes += pl.lit_bytes;
-    // (a call that runs its batch again -- below: the sweeps after runs that did not verify, a stream moved to the literal engine,
-    // the cut rounds -- counts the plan it ends with, so that a stream adds the same whatever its neighbours made the batch do)
-    auto plan_rerun = [&]() { c->lit_engine_bytes -= pl.lit_bytes; };
-    // The per-run flags and state in one launch (the link array is not cleared: K1 writes every entry that is read).  Launched
-    // behind K1, which reads none of them -- descriptors, its work items, the input -- and is what the chip waits for at the
-    // start of a call; the match kernel is the first to touch a stream's state.
-    auto zero_state = [&]() -> bool {
-        ZeroRegions z;
-        auto reg = [&](int r, DevBuf &b, size_t bytes) {
-            z.p[r] = b.p;
-            z.n16[r] = (uint32_t)(((bytes + 15) / 16 < b.cap / 16) ? (bytes + 15) / 16 : b.cap / 16);
-        };
-        reg(0, c->stale, (size_t)pl.n_chunks + 64);
-        reg(1, c->seg_stale, (size_t)pl.n_segs + 64);
-        reg(2, c->st, sizeof(StreamState) * (size_t)n);
-        if (pl.any_fv) reg(3, c->ins_bits, (size_t)pl.n_pos / 8 + kFvBitSlack);
-        else z.p[3] = nullptr, z.n16[3] = 0;
-        uint32_t most = 0;
-        for (int r = 0; r < 4; r++) most = z.n16[r] > most ? z.n16[r] : most;
-        unsigned blocks = (most + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(zs_zero_kernel, dim3(blocks), dim3(256), 0, stream, z);
-        if (ro && ro->resume && pl.sd[0].fv_end >= 0) {
-            // a resumed run at levels 1-3: below p0 the set is what the suspended engine's chains contain -- every position they
-            // reach is in it (and no walk meets another one): all ones
-            // (exactly the bits below p0: the chunk form's commit ORs the run's own bits in)
-            const int64_t lo = std::max<int64_t>(0, ro->p0 - kWSize - 64) / 32, hi = ro->p0 / 32;
-            if (hi > lo) ZS_HIP(c, hipMemsetAsync(pl.sd[0].ins_bits + lo, 0xFF, (size_t)(hi - lo) * 4, stream));
-            ZS_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(pl.sd[0].ins_bits + hi), (int)((1u << (ro->p0 & 31)) - 1u), 1, stream));
-        }
-        return true;
-    };
+}
 
-    const StreamDesc *d_sd = dev<StreamDesc>(c->sd);
-    StreamState *d_st = dev<StreamState>(c->st);
-    const uint2 *d_work = dev<uint2>(c->work);
-    const bool prof = c->profiling;
-    const int k5_ahead = getenv("ZS_K5_AHEAD") ? atoi(getenv("ZS_K5_AHEAD")) : 1;  // lines the symbol kernel's helper wave asks for ahead of a lane
+// the kept plan: the caller's pointers into the kept descriptors, and those alone to the device
+bool DeflateCall::take_kept_plan() {
+    c->plan_reused = 1;
+    if (pc.dual_saved) pl.sd = pc.dual_sd, pl.fr_chunks = pc.dual_fr, pl.fr_max_n = pc.dual_fr_max_n, pl.n_runs = pc.dual_n_runs, pl.any_fv = true;
+    StreamDesc *hd = (StreamDesc *)c->plan_pin;
+    for (int i = 0; i < n; i++) {
+        hd[i].in = pl.sd[(size_t)i].in = (const uint8_t *)in[i];
+        hd[i].out = pl.sd[(size_t)i].out = (uint8_t *)out[i];
+    }
+    pc.in_flight = true;
+    ZS_HIP(c, hipMemcpyAsync(c->sd.p, hd, lay.sd_bytes, hipMemcpyHostToDevice, stream));
+    return true;
+}
+
+void DeflateCall::launch_setup() {
+    c->lit_engine_bytes += pl.lit_bytes;
+    d_sd = dev<StreamDesc>(c->sd), d_st = dev<StreamState>(c->st), d_work = dev<uint2>(c->work);
+    prof = c->profiling;
     c->dbg_blk_off = pl.sd[0].blk_off, c->dbg_chunk_off = pl.sd[0].chunk_off, c->dbg_nchunks = pl.sd[0].nchunks;
     c->dbg_spec_n = pl.sd[0].spec_n, c->dbg_n_spec = pl.n_spec;
-    const K5Spec k5s{dev<uint32_t>(c->spec_rec), dev<uint32_t>(c->spec_rec) + pl.n_spec, spec_bits, spec_warm, spec_corrupt,
-                     dev<uint32_t>(c->spec_syms), spec_slab_stride(spec_bits)};
-    int spec_ok_streams = 0;  // streams whose speculative walk verified: the map kernels skip them (all of them: not launched)
-    bool need_maps = true, spec_ran = false;
+    const int spec_bits = plan_spec_bits(penv);
+    k5s = K5Spec{dev<uint32_t>(c->spec_rec), dev<uint32_t>(c->spec_rec) + pl.n_spec, spec_bits, plan_spec_warm(penv), env.spec_corrupt,
+                 dev<uint32_t>(c->spec_syms), spec_slab_stride(spec_bits)};
     if (!rounds) c->spec_streams = c->spec_fallbacks = c->spec_wrong_chunks = c->spec_periodic = 0;
-    auto mark = [&](int i) {
-        if (prof) (void)hipEventRecord(c->ev[i], stream);
-    };
-    // the output buffers' clearing and the Adler-32 pieces are wanted by the last two kernels only: they run on the second
-    // stream beside the link and match kernels (their stages are reported as 0: 0.015 and 0.03 ms on english64 alone, and
-    // their events are not recorded).  The host enqueues them behind the first launches of the critical path: every call
-    // in front of K1 is ~5 us in which the device waits for the host.
-    ht_plan = ht_us();
-    ZS_HIP(c, hipEventRecord(c->ev_pre0, stream));
-    auto side_work = [&]() -> bool {
-        ZS_HIP(c, hipStreamWaitEvent(c->aux, c->ev_pre0, 0));
-        if (!pl.w_clear.empty())
-            hipLaunchKernelGGL(zs_clear_kernel, dim3((unsigned)pl.w_clear.size()), dim3(256), 0, c->aux, d_sd, d_work + o_clear);
-        if (!pl.w_adler.empty())
-            hipLaunchKernelGGL(zs_adler_kernel, dim3((unsigned)pl.w_adler.size()), dim3(256), 0, c->aux, d_sd, d_work + o_adler,
-                               dev<uint32_t>(c->pieces));
-        ZS_HIP(c, hipEventRecord(c->ev_pre, c->aux));
-        return true;
-    };
-    // (ZS_NO_DEFER: every cut on the stream's own CU; ZS_FORCE_ROUNDS: the rounds from the first cut on -- for the tests)
-    const int cut_budget = getenv("ZS_FORCE_ROUNDS") ? 0 : kCutBudget;
-    const int defer_mode = ((ro || getenv("ZS_NO_DEFER")) ? 0 : 1) | (getenv("ZS_DEBUG_CUTS") ? 0x100 : 0) | (cut_budget << 16);
-    const int cut_stride = (int)pl.n_cuts;
-    const bool use_sup = !pl.w_sups.empty() && !getenv("ZS_NO_SUPMAP");
-    auto launch_resolve = [&](int mode, int iter) {
-        hipLaunchKernelGGL(zs_resolve_kernel, dim3((unsigned)n), dim3(1024), kResolveLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
-                           dev<uint2>(c->mm), dev<uint32_t>(c->maps), dev<uint2>(c->segmap),
-                           dev<uint16_t>(c->seg_entry), dev<uint32_t>(c->seg_symbase), dev<uint8_t>(c->stale),
-                           dev<uint8_t>(c->seg_stale), c->crc_tab, lv, strategy, hash_variant, 0x7FFFFFFF, 0x7FFFFFFF,
-                           use_sup ? dev<uint2>(c->supmap) : (const uint2 *)nullptr, dev<uint16_t>(c->chunk_far), mode, dev<int32_t>(c->cut_pos),
-                           dev<uint32_t>(c->cut_bkt), cut_stride, iter);
-    };
-    // Batched cut rounds, for the streams the resolve kernel has given up (StreamState::deferred = 1: data whose read events
-    // are equal-bucket ones by the dozen -- zeros, runs, zero pages -- or with thousands of positions to walk again behind
-    // each).  Where a cut falls depends on the parse up to it, and the parse on the repairs of the cuts before: one CU doing
-    // cut, repair, cut, repair is what made such streams 30-170 times slower than text.  Instead: a dry pass of the resolve
-    // kernel walks the rest of the stream on the records as they are and collects every cut on its way; the records from the
-    // first cut that differs from the pass before are put back as they were (a copy made when the rounds began) and all
-    // the cuts of the pass are repaired at once over the chip; the maps of the chunks that changed are made again; and so
-    // on until a pass finds the cuts of the pass before -- then the records it walked are the ones those cuts leave, which
-    // is what the one-after-the-other order gives (the first cut never depends on a repair, the second only on the
-    // first's, ...: a pass fixes at least one more cut, in practice nearly all of them).
-    auto run_cut_rounds = [&]() -> bool {
-        // (the records as they are now, and behind them the chunks' largest match distances: what a restore puts back)
-        const size_t far_off = 8 * (size_t)pl.n_pos + 256;
-        if (!ensure(c, c->mm_bak, far_off + 2 * (size_t)pl.n_chunks + 64)) return false;
-        ZS_HIP(c, hipMemcpyAsync(c->mm_bak.p, c->mm.p, 8 * (size_t)pl.n_pos + 256, hipMemcpyDeviceToDevice, stream));
-        ZS_HIP(c, hipMemcpyAsync((uint8_t *)c->mm_bak.p + far_off, c->chunk_far.p, 2 * (size_t)pl.n_chunks + 64, hipMemcpyDeviceToDevice, stream));
-        ZS_HIP(c, hipMemsetAsync(c->cut_pos.p, 0xFF, 8 * (size_t)pl.n_cuts + 64, stream));  // no cut in any slot (the pass before the first)
-        StreamState *hr = (StreamState *)c->pinned;
-        for (int iter = 0;; iter++) {
-            launch_resolve(3 | (defer_mode & 0x100), iter);
-            ZS_HIP(c, hipMemcpyAsync(hr, d_st, sizeof(StreamState) * (size_t)n, hipMemcpyDeviceToHost, stream));
-            ZS_HIP(c, hipStreamSynchronize(stream));
-            bool all_same = true;
-            int max_nc = 0;
-            for (int i = 0; i < n; i++)
-                if (hr[i].deferred == 1 && !hr[i].cuts_same) all_same = false, max_nc = std::max(max_nc, hr[i].nc[iter & 1]);
-            hipLaunchKernelGGL(zs_cuts_apply_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<uint16_t>(c->link), dev<int32_t>(c->cut_pos),
-                               cut_stride, iter);  // (the streams that are through leave the rounds)
-            if (getenv("ZS_DEBUG")) {
-                int nd = 0, nsame = 0;
-                for (int i = 0; i < n; i++) nd += hr[i].deferred == 1, nsame += hr[i].deferred == 1 && hr[i].cuts_same;
-                fprintf(stderr, "zs: cut round %d: %d streams in the rounds, %d settled, most cuts %d, stream 0: %d cuts, first difference at cut %d (position %d)\n", iter,
-                        nd, nsame, max_nc, hr[0].nc[iter & 1], hr[0].cut_diff_idx, hr[0].cut_diff_pos);
-            }
-            if (all_same && getenv("ZS_DEBUG_CUTS")) {  // the cuts the rounds settled on, stream 0
-                const int ncap = hr[0].nc[iter & 1];
-                std::vector<int32_t> cp((size_t)ncap);
-                std::vector<uint32_t> cb((size_t)ncap);
-                (void)hipMemcpy(cp.data(), dev<int32_t>(c->cut_pos) + (size_t)(iter & 1) * (size_t)cut_stride + pl.sd[0].cut_off, 4 * (size_t)ncap, hipMemcpyDeviceToHost);
-                (void)hipMemcpy(cb.data(), dev<uint32_t>(c->cut_bkt) + (size_t)(iter & 1) * (size_t)cut_stride + pl.sd[0].cut_off, 4 * (size_t)ncap, hipMemcpyDeviceToHost);
-                fprintf(stderr, "zs: cuts of stream 0 (slot: position / bucket):");
-                for (int k = 0; k < ncap; k++)
-                    if (cp[(size_t)k] >= 0) fprintf(stderr, " %d: %d / %u", k, cp[(size_t)k], cb[(size_t)k]);
-                fprintf(stderr, "\n");
-            }
-            if (all_same) break;
-            if (iter >= 4096) {
-                c->err = "the cut rounds did not settle";
-                return false;
-            }
-            c->cut_rounds++;
-            if (iter > 0)  // (before the first round's repairs the records are the copy)
-            hipLaunchKernelGGL(zs_cut_restore_kernel, dim3(2048, (unsigned)std::min(n, 65535)), dim3(256), 0, stream, d_sd, d_st, dev<uint2>(c->mm), (const uint2 *)c->mm_bak.p,
-                               dev<uint8_t>(c->stale), dev<uint8_t>(c->seg_stale), dev<uint16_t>(c->chunk_far), (const uint16_t *)((const uint8_t *)c->mm_bak.p + far_off), n);
-            if (max_nc > 0) {
-                // few cuts: 128 workgroups each (every 128th position behind the cut); many: fewer, larger ones
-                if (max_nc <= 64)
-                    hipLaunchKernelGGL((zs_cuts_repair_kernel<256, 1>), dim3(128, (unsigned)max_nc, (unsigned)std::min(n, 65535)), dim3(256), kRepairLds, stream, d_sd, d_st,
-                                       dev<uint16_t>(c->link), dev<uint2>(c->mm), dev<uint8_t>(c->stale), dev<uint8_t>(c->seg_stale),
-                                       dev<uint16_t>(c->chunk_far), c->crc_tab, lv, hash_variant, dev<int32_t>(c->cut_pos), dev<uint32_t>(c->cut_bkt),
-                                       cut_stride, iter, n);
-                else if (max_nc <= 2048)
-                    hipLaunchKernelGGL((zs_cuts_repair_kernel<256, 8>), dim3(16, (unsigned)max_nc, (unsigned)std::min(n, 65535)), dim3(256), kRepairLds, stream, d_sd, d_st,
-                                       dev<uint16_t>(c->link), dev<uint2>(c->mm), dev<uint8_t>(c->stale), dev<uint8_t>(c->seg_stale),
-                                       dev<uint16_t>(c->chunk_far), c->crc_tab, lv, hash_variant, dev<int32_t>(c->cut_pos), dev<uint32_t>(c->cut_bkt),
-                                       cut_stride, iter, n);
-                else
-                    hipLaunchKernelGGL((zs_cuts_repair_kernel<1024, 32>), dim3(1, (unsigned)std::min(max_nc, 65535), (unsigned)std::min(n, 65535)), dim3(1024), kRepairLds, stream, d_sd,
-                                       d_st, dev<uint16_t>(c->link), dev<uint2>(c->mm), dev<uint8_t>(c->stale), dev<uint8_t>(c->seg_stale),
-                                       dev<uint16_t>(c->chunk_far), c->crc_tab, lv, hash_variant, dev<int32_t>(c->cut_pos), dev<uint32_t>(c->cut_bkt),
-                                       cut_stride, iter, n);
-            }
-            hipLaunchKernelGGL(zs_chunkmap_kernel, dim3((unsigned)pl.w_chunks.size()), dim3(512), 0, stream, d_sd, d_work + o_chunks,
-                               dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint32_t>(c->maps), c->crc_tab, lv, strategy,
-                               hash_variant, dev<uint16_t>(c->chunk_far), dev<uint8_t>(c->stale), (const StreamState *)d_st);
-            hipLaunchKernelGGL(zs_segmap_kernel, dim3((unsigned)pl.w_segs.size()), dim3(320), 0, stream, d_sd, d_work + o_segs,
-                               dev<uint32_t>(c->maps), dev<uint2>(c->segmap));
-            ZS_HIP(c, hipMemsetAsync(c->seg_stale.p, 0, (size_t)pl.n_segs + 64, stream));
-            if (use_sup)
-                hipLaunchKernelGGL(zs_supmap_kernel, dim3((unsigned)pl.w_sups.size()), dim3(320), 0, stream, d_sd, d_work + o_sups,
-                                   dev<uint2>(c->segmap), dev<uint8_t>(c->seg_stale), dev<uint2>(c->supmap));
-        }
-        return true;
-    };
+    const int cut_budget = env.force_rounds ? 0 : kCutBudget;
+    defer_mode = ((ro || env.no_defer) ? 0 : 1) | (env.debug_cuts ? 0x100 : 0) | (cut_budget << 16);
+    cut_stride = (int)pl.n_cuts;
+    use_sup = !pl.w_sups.empty() && !env.no_supmap;
     // the engine is left for a later run, or took the block in progress over from one: it needs K5's symbols and block ends
-    const bool tail_late = ro && (!ro->final_run || ro->resume);
+    tail_late = ro && (!ro->final_run || ro->resume);
     // Beside the symbol kernel the tails of a few streams are free; those of hundreds are not: 256 tail workgroups of 1024
     // threads and 133 KiB of LDS each, one per CU, cost the symbol kernel of 256 x 1 MiB 3 ms (6.8 against 3.9), more than
     // they take alone (0.5).  From 64 streams of 96 KiB or more on the tails run behind the symbols instead (thousands of
     // small streams are the other way round: 16 rounds of tails, a short symbol kernel -- beside each other 18.9 ms for
     // 4096 x 32 KiB, one after the other 20.1).
     // (1024 x 128 KiB: 2.8 ms one after the other, 3.0 side by side; 4096 x 32 KiB: 5.7 against 4.9)
-    const bool tail_serial = !tail_late && n >= 64 && (pl.n_pos / n >= (96 << 10) || getenv("ZS_TAIL_SERIAL")) && !getenv("ZS_TAIL_FORK");
-    bool fork_recorded = false;  // the tail engine's fork has its event already (the speculative path, below)
-    if (!rounds) {
+    tail_serial = !tail_late && n >= 64 && (pl.n_pos / n >= (96 << 10) || env.tail_serial) && !env.tail_fork;
+}
+
+// The per-run flags and state in one launch (the link array is not cleared: K1 writes every entry that is read).  Launched
+// behind K1, which reads none of them -- descriptors, its work items, the input -- and is what the chip waits for at the
+// start of a call; the match kernel is the first to touch a stream's state.
+bool DeflateCall::zero_state() {
+    ZeroRegions z;
+    auto reg = [&](int r, DevBuf &b, size_t bytes) {
+        z.p[r] = b.p;
+        z.n16[r] = (uint32_t)(((bytes + 15) / 16 < b.cap / 16) ? (bytes + 15) / 16 : b.cap / 16);
+    };
+    reg(0, c->stale, (size_t)pl.n_chunks + 64);
+    reg(1, c->seg_stale, (size_t)pl.n_segs + 64);
+    reg(2, c->st, sizeof(StreamState) * (size_t)n);
+    if (pl.any_fv) reg(3, c->ins_bits, (size_t)pl.n_pos / 8 + kFvBitSlack);
+    else z.p[3] = nullptr, z.n16[3] = 0;
+    uint32_t most = 0;
+    for (int r = 0; r < 4; r++) most = z.n16[r] > most ? z.n16[r] : most;
+    unsigned blocks = (most + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(zs_zero_kernel, dim3(blocks), dim3(256), 0, stream, z);
+    if (ro && ro->resume && pl.sd[0].fv_end >= 0) {
+        // a resumed run at levels 1-3: below p0 the set is what the suspended engine's chains contain -- every position they
+        // reach is in it (and no walk meets another one): all ones
+        // (exactly the bits below p0: the chunk form's commit ORs the run's own bits in)
+        const int64_t lo = std::max<int64_t>(0, ro->p0 - kWSize - 64) / 32, hi = ro->p0 / 32;
+        if (hi > lo) ZS_HIP(c, hipMemsetAsync(pl.sd[0].ins_bits + lo, 0xFF, (size_t)(hi - lo) * 4, stream));
+        ZS_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(pl.sd[0].ins_bits + hi), (int)((1u << (ro->p0 & 31)) - 1u), 1, stream));
+    }
+    return true;
+}
+
+// the output buffers' clearing and the Adler-32 pieces are wanted by the last two kernels only: they run on the second
+// stream beside the link and match kernels (their stages are reported as 0: 0.015 and 0.03 ms on english64 alone, and
+// their events are not recorded).  The host enqueues them behind the first launches of the critical path: every call
+// in front of K1 is ~5 us in which the device waits for the host.
+bool DeflateCall::side_work() {
+    ZS_HIP(c, hipStreamWaitEvent(c->aux, c->ev_pre0, 0));
+    if (!pl.w_clear.empty())
+        hipLaunchKernelGGL(zs_clear_kernel, dim3((unsigned)pl.w_clear.size()), dim3(256), 0, c->aux, d_sd, work(kWClear));
+    if (!pl.w_adler.empty())
+        hipLaunchKernelGGL(zs_adler_kernel, dim3((unsigned)pl.w_adler.size()), dim3(256), 0, c->aux, d_sd, work(kWAdler),
+                           dev<uint32_t>(c->pieces));
+    ZS_HIP(c, hipEventRecord(c->ev_pre, c->aux));
+    return true;
+}
+
+// Batched cut rounds, for the streams the resolve kernel has given up (StreamState::deferred = 1: data whose read events
+// are equal-bucket ones by the dozen -- zeros, runs, zero pages -- or with thousands of positions to walk again behind
+// each).  Where a cut falls depends on the parse up to it, and the parse on the repairs of the cuts before: one CU doing
+// cut, repair, cut, repair is what made such streams 30-170 times slower than text.  Instead: a dry pass of the resolve
+// kernel walks the rest of the stream on the records as they are and collects every cut on its way; the records from the
+// first cut that differs from the pass before are put back as they were (a copy made when the rounds began) and all
+// the cuts of the pass are repaired at once over the chip; the maps of the chunks that changed are made again; and so
+// on until a pass finds the cuts of the pass before -- then the records it walked are the ones those cuts leave, which
+// is what the one-after-the-other order gives (the first cut never depends on a repair, the second only on the
+// first's, ...: a pass fixes at least one more cut, in practice nearly all of them).
+bool DeflateCall::run_cut_rounds() {
+    // (the records as they are now, and behind them the chunks' largest match distances: what a restore puts back)
+    const size_t far_off = 8 * (size_t)pl.n_pos + 256;
+    if (!ensure(c, c->mm_bak, far_off + 2 * (size_t)pl.n_chunks + 64)) return false;
+    ZS_HIP(c, hipMemcpyAsync(c->mm_bak.p, c->mm.p, 8 * (size_t)pl.n_pos + 256, hipMemcpyDeviceToDevice, stream));
+    ZS_HIP(c, hipMemcpyAsync((uint8_t *)c->mm_bak.p + far_off, c->chunk_far.p, 2 * (size_t)pl.n_chunks + 64, hipMemcpyDeviceToDevice, stream));
+    ZS_HIP(c, hipMemsetAsync(c->cut_pos.p, 0xFF, 8 * (size_t)pl.n_cuts + 64, stream));  // no cut in any slot (the pass before the first)
+    StreamState *hr = (StreamState *)c->pinned;
+    for (int iter = 0;; iter++) {
+        launch_resolve(3 | (defer_mode & 0x100), iter);
+        ZS_HIP(c, hipMemcpyAsync(hr, d_st, sizeof(StreamState) * (size_t)n, hipMemcpyDeviceToHost, stream));
+        ZS_HIP(c, hipStreamSynchronize(stream));
+        bool all_same = true;
+        int max_nc = 0;
+        for (int i = 0; i < n; i++)
+            if (hr[i].deferred == 1 && !hr[i].cuts_same) all_same = false, max_nc = std::max(max_nc, hr[i].nc[iter & 1]);
+        hipLaunchKernelGGL(zs_cuts_apply_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<uint16_t>(c->link), dev<int32_t>(c->cut_pos),
+                           cut_stride, iter);  // (the streams that are through leave the rounds)
+        if (env.debug) {
+            int nd = 0, nsame = 0;
+            for (int i = 0; i < n; i++) nd += hr[i].deferred == 1, nsame += hr[i].deferred == 1 && hr[i].cuts_same;
+            fprintf(stderr, "zs: cut round %d: %d streams in the rounds, %d settled, most cuts %d, stream 0: %d cuts, first difference at cut %d (position %d)\n", iter,
+                    nd, nsame, max_nc, hr[0].nc[iter & 1], hr[0].cut_diff_idx, hr[0].cut_diff_pos);
+        }
+        if (all_same && env.debug_cuts) {  // the cuts the rounds settled on, stream 0
+            const int ncap = hr[0].nc[iter & 1];
+            std::vector<int32_t> cp((size_t)ncap);
+            std::vector<uint32_t> cb((size_t)ncap);
+            (void)hipMemcpy(cp.data(), dev<int32_t>(c->cut_pos) + (size_t)(iter & 1) * (size_t)cut_stride + pl.sd[0].cut_off, 4 * (size_t)ncap, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(cb.data(), dev<uint32_t>(c->cut_bkt) + (size_t)(iter & 1) * (size_t)cut_stride + pl.sd[0].cut_off, 4 * (size_t)ncap, hipMemcpyDeviceToHost);
+            fprintf(stderr, "zs: cuts of stream 0 (slot: position / bucket):");
+            for (int k = 0; k < ncap; k++)
+                if (cp[(size_t)k] >= 0) fprintf(stderr, " %d: %d / %u", k, cp[(size_t)k], cb[(size_t)k]);
+            fprintf(stderr, "\n");
+        }
+        if (all_same) break;
+        if (iter >= 4096) {
+            c->err = "the cut rounds did not settle";
+            return false;
+        }
+        c->cut_rounds++;
+        if (iter > 0)  // (before the first round's repairs the records are the copy)
+        hipLaunchKernelGGL(zs_cut_restore_kernel, dim3(2048, (unsigned)std::min(n, 65535)), dim3(256), 0, stream, d_sd, d_st, dev<uint2>(c->mm), (const uint2 *)c->mm_bak.p,
+                           dev<uint8_t>(c->stale), dev<uint8_t>(c->seg_stale), dev<uint16_t>(c->chunk_far), (const uint16_t *)((const uint8_t *)c->mm_bak.p + far_off), n);
+        if (max_nc > 0) {
+            if (max_nc <= 64) launch_cuts_repair(zs_cuts_repair_kernel<256, 1>, 128, 256, max_nc, iter);
+            else if (max_nc <= 2048) launch_cuts_repair(zs_cuts_repair_kernel<256, 8>, 16, 256, max_nc, iter);
+            else launch_cuts_repair(zs_cuts_repair_kernel<1024, 32>, 1, 1024, max_nc, iter);
+        }
+        hipLaunchKernelGGL(zs_chunkmap_kernel, dim3((unsigned)pl.w_chunks.size()), dim3(512), 0, stream, d_sd, work(kWChunks),
+                           dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint32_t>(c->maps), c->crc_tab, lv, strategy,
+                           hash_variant, dev<uint16_t>(c->chunk_far), dev<uint8_t>(c->stale), (const StreamState *)d_st);
+        hipLaunchKernelGGL(zs_segmap_kernel, dim3((unsigned)pl.w_segs.size()), dim3(320), 0, stream, d_sd, work(kWSegs),
+                           dev<uint32_t>(c->maps), dev<uint2>(c->segmap));
+        ZS_HIP(c, hipMemsetAsync(c->seg_stale.p, 0, (size_t)pl.n_segs + 64, stream));
+        if (use_sup)
+            hipLaunchKernelGGL(zs_supmap_kernel, dim3((unsigned)pl.w_sups.size()), dim3(320), 0, stream, d_sd, work(kWSups),
+                               dev<uint2>(c->segmap), dev<uint8_t>(c->seg_stale), dev<uint2>(c->supmap));
+    }
+    return true;
+}
+
+// The front of the pipeline, which the re-entry behind the cut rounds skips: links, match search, and the parse's entries -- by
+// the speculative walk, or by the maps and the resolve kernel.
+bool DeflateCall::front() {
     mark(2);
     if (!pl.w_links.empty())
-        hipLaunchKernelGGL(zs_links_kernel, dim3((unsigned)pl.w_links.size()), dim3(1024), kLkLds, stream, d_sd, d_work + o_links,
-                           dev<uint16_t>(c->link), c->crc_tab, hash_variant, (int)link_span);
+        hipLaunchKernelGGL(zs_links_kernel, dim3((unsigned)pl.w_links.size()), dim3(1024), kLkLds, stream, d_sd, work(kWLinks),
+                           dev<uint16_t>(c->link), c->crc_tab, hash_variant, (int)pl.link_span);
     if (!zero_state()) return false;
     if (ro && ro->resume)
         hipLaunchKernelGGL(zs_import_chains_kernel, dim3(64), dim3(1024), 0, stream, d_sd, 0, dev<uint16_t>(c->link), c->crc_tab, hash_variant, ro->p0);
-    if (pl.any_dual) {
-        // the links are there: sweeps or speculative runs (above, allow_dual)?  The other plan is struck from the descriptors
-        bool periodic = true;
-        if (!getenv("ZS_FAST_NO_PROBE")) {
-            hipLaunchKernelGGL(zs_fast_probe_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, dev<uint16_t>(c->link), dev<int32_t>(c->run_fail));
-            std::vector<int32_t> np((size_t)n, 0);
-            ZS_HIP(c, hipMemcpyAsync(np.data(), c->run_fail.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
-            ZS_HIP(c, hipStreamSynchronize(stream));
-            for (int i = 0; i < n; i++) periodic = periodic && np[(size_t)i] == 0;
-        }
-        // (a kept plan keeps both: what is struck here is put back when a same-shaped call takes the plan, whose links decide anew)
-        if (pc.valid && !pc.dual_saved) pc.dual_saved = true, pc.dual_sd = pl.sd, pc.dual_fr = pl.fr_chunks, pc.dual_fr_max_n = pl.fr_max_n, pc.dual_n_runs = pl.n_runs;
-        for (int i = 0; i < n; i++) {
-            StreamDesc &sk = pl.sd[(size_t)i];
-            if (periodic) sk.fv_end = -1, sk.fr_first = 0, sk.fr_n = 0;
-            else sk.fast_runs = 0, sk.run_slots = 0;
-        }
-        if (periodic) pl.any_fv = false, pl.fr_chunks.clear(), pl.fr_max_n = 0;
-        else pl.n_runs = 0;
-        memcpy(c->pinned, pl.sd.data(), sizeof(StreamDesc) * (size_t)n);  // (the staging copy's uploads are through: the stream was just waited for)
-        ZS_HIP(c, hipMemcpyAsync(c->sd.p, c->pinned, sizeof(StreamDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
-        if (getenv("ZS_DEBUG")) fprintf(stderr, "zs: %d stream(s) below 4 MiB at level %d: %s\n", n, level, periodic ? "all period, the speculative runs" : "the sweeps");
-    }
+    if (pl.any_dual && !dual_probe()) return false;
     mark(3);
     if (strategy == kHuffmanOnly) {
         // Longest_match is never called (Deflate.Slow.cs:66-71): every position has no match
         ZS_HIP(c, hipMemsetAsync(c->mm.p, 0, 8 * (size_t)pl.n_pos + 64, stream));
     } else if (!pl.w_match.empty())
-        hipLaunchKernelGGL(zs_match_kernel, dim3((unsigned)pl.w_match.size()), dim3(1024), kMatchLds + 16, stream, d_sd, d_work + o_match,
+        hipLaunchKernelGGL(zs_match_kernel, dim3((unsigned)pl.w_match.size()), dim3(1024), kMatchLds + 16, stream, d_sd, work(kWMatch),
                            dev<uint16_t>(c->link), dev<uint2>(c->mm), lv, strategy, d_st);
     mark(4);
     if (!side_work()) return false;
-    // The speculative chunk walk: every chunk of the streams that qualify walked from a guessed entry, the guesses checked
-    // against the exits, one look at the verdicts.  A stream that verified has its chunks' entries and first symbols and what
-    // the resolve kernel would leave; the others -- and the streams that never qualified, with no look at anything -- take the maps.
-    if (pl.n_spec) {
-        spec_ran = true;
-        hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 1>), dim3((unsigned)((pl.max_spec_n + 63) / 64), (unsigned)n), dim3(kK5Threads), 0, stream, d_sd, d_st,
-                           (const uint2 *)nullptr, 0, dev<uint2>(c->mm), dev<uint16_t>(c->link), (const uint16_t *)nullptr, (const uint32_t *)nullptr,
-                           (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
-        if (prof) (void)hipEventRecord(c->ev_spec[0], stream);
-        hipLaunchKernelGGL(zs_spec_verify_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, dev<uint2>(c->mm), dev<uint16_t>(c->link), c->crc_tab, lv,
-                           strategy, hash_variant, k5s, dev<int32_t>(c->spec_flags));
-        int32_t *hf = (int32_t *)c->pinned;  // (the staging copy's uploads are through by the time the verdicts arrive: same stream)
-        ZS_HIP(c, hipMemcpyAsync(hf, c->spec_flags.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
-        ZS_HIP(c, hipEventRecord(c->ev_verdict, stream));
-        // The chip does not wait for the host's look at the verdicts: the compaction of the verified streams' symbols goes in
-        // right behind them.  It is predicated on the device (StreamState::spec_ok, per stream), reads only what the walk and the
-        // verdict kernel left (records, bases, slabs) and writes only verified streams' symbols and block cuts, none of which the
-        // map path of the other streams touches -- so it may run ahead of that path as well as behind it.  The tail engine's
-        // fork keeps its place behind the verdict kernel: its event is recorded here, in front of the compaction (a stream that
-        // takes the maps records it again behind the resolve kernel, below).
-        if (!tail_late && !tail_serial) {
-            ZS_HIP(c, hipEventRecord(c->ev_fork, stream));
-            fork_recorded = true;
-        }
-        if (prof) (void)hipEventRecord(c->ev_spec[2], stream);
-        hipLaunchKernelGGL(zs_spec_compact_kernel, dim3((unsigned)((pl.max_spec_n + 3) / 4), (unsigned)n), dim3(256), 0, stream, d_sd, d_st, k5s,
-                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top));
-        if (prof) (void)hipEventRecord(c->ev_spec[3], stream);
-        ZS_HIP(c, hipEventSynchronize(c->ev_verdict));
-        if (prof) (void)hipEventRecord(c->ev_spec[1], stream);
-        for (int i = 0; i < n; i++) {
-            if (hf[i] == 0) continue;
-            c->spec_streams++;
-            if (hf[i] == 1) spec_ok_streams++;
-            else c->spec_fallbacks++;
-            if (hf[i] == 2) c->spec_periodic++;  // (the verdicts: 1 verified, 2 periodic -- never walked, 3 an event bailed, 4 wrong guesses)
-        }
-        if (spec_ok_streams < c->spec_streams) {  // how many guesses were wrong: the streams' states (a failed attempt is rare)
-            StreamState *hs = (StreamState *)c->pinned;
-            ZS_HIP(c, hipMemcpyAsync(hs, d_st, sizeof(StreamState) * (size_t)n, hipMemcpyDeviceToHost, stream));
-            ZS_HIP(c, hipStreamSynchronize(stream));
-            for (int i = 0; i < n; i++) c->spec_wrong_chunks += hs[i].spec_wrong;
-        }
-        if (getenv("ZS_DEBUG"))
-            fprintf(stderr, "zs: speculative walk: %d streams tried, %d verified, %d wrong guesses (chunks of %d, warm-up %d)\n", c->spec_streams, spec_ok_streams,
-                    c->spec_wrong_chunks, 1 << spec_bits, spec_warm);
-    }
+    if (pl.n_spec && !spec_walk()) return false;
     need_maps = spec_ok_streams < n;
     const StreamState *spec_st = spec_ok_streams ? (const StreamState *)d_st : nullptr;
     if (!pl.w_chunks.empty() && need_maps)
-        hipLaunchKernelGGL(zs_chunkmap_kernel, dim3((unsigned)pl.w_chunks.size()), dim3(512), 0, stream, d_sd, d_work + o_chunks,
+        hipLaunchKernelGGL(zs_chunkmap_kernel, dim3((unsigned)pl.w_chunks.size()), dim3(512), 0, stream, d_sd, work(kWChunks),
                            dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint32_t>(c->maps), c->crc_tab, lv, strategy,
                            hash_variant, dev<uint16_t>(c->chunk_far), (uint8_t *)nullptr, (const StreamState *)nullptr, spec_st);
     mark(5);
     if (!pl.w_segs.empty() && need_maps)
-        hipLaunchKernelGGL(zs_segmap_kernel, dim3((unsigned)pl.w_segs.size()), dim3(320), 0, stream, d_sd, d_work + o_segs,
+        hipLaunchKernelGGL(zs_segmap_kernel, dim3((unsigned)pl.w_segs.size()), dim3(320), 0, stream, d_sd, work(kWSegs),
                            dev<uint32_t>(c->maps), dev<uint2>(c->segmap), spec_st);
     // the segment maps composed 16 at a time, for the resolve kernel's short way through a long stream (ZS_NO_SUPMAP: without)
     if (use_sup && need_maps)
-        hipLaunchKernelGGL(zs_supmap_kernel, dim3((unsigned)pl.w_sups.size()), dim3(320), 0, stream, d_sd, d_work + o_sups,
+        hipLaunchKernelGGL(zs_supmap_kernel, dim3((unsigned)pl.w_sups.size()), dim3(320), 0, stream, d_sd, work(kWSups),
                            dev<uint2>(c->segmap), dev<uint8_t>(c->seg_stale), dev<uint2>(c->supmap), spec_st);
     mark(6);
     // A stream whose refills are equal-bucket ones with positions to walk again by the thousand (zero pages, runs) is not
@@ -1119,135 +649,207 @@ plan_again:
     // synchronisation, which is what a cut's repair takes on one CU at level 6.  64 MiB of short runs: level 9 7.3 s -> 2.0 s,
     // level 6 175 ms inline against 237 in rounds.)
     if (need_maps) launch_resolve(defer_mode, 0);
+    return true;
+}
+
+// A batch planned for the sweeps and for the speculative runs at once (zs_plan.h plan_streams, allow_dual).  The links are
+// there: which is it?  The other plan is struck from the descriptors
+bool DeflateCall::dual_probe() {
+    bool periodic = true;
+    if (!env.fast_no_probe) {
+        hipLaunchKernelGGL(zs_fast_probe_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, dev<uint16_t>(c->link), dev<int32_t>(c->run_fail));
+        std::vector<int32_t> np((size_t)n, 0);
+        ZS_HIP(c, hipMemcpyAsync(np.data(), c->run_fail.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+        ZS_HIP(c, hipStreamSynchronize(stream));
+        for (int i = 0; i < n; i++) periodic = periodic && np[(size_t)i] == 0;
     }
-    mark(7);
-    // fork: the tail engine (sequential, one workgroup per stream) needs only what the resolve kernel left, so it runs
-    // on the second stream beside the symbol kernels
-    if (pl.any_fv) {
-        // window-wide sweeps of a workgroup (zs_fast_sweep.hip), one workgroup per stream
-        constexpr int fs_lds = fs_lds_bytes<1024, kFsTile1>();
-        if (!pl.fr_chunks.empty()) {
-            // rounds over the chunks of the streams: every round one workgroup per chunk, until a round changes nothing
-            const size_t nch = pl.fr_chunks.size(), plane_words = (size_t)pl.n_pos / 32 + kFvBitSlack / 4 + 64;
-            // the switches of the measurements, read once (not per round)
-            static const int env_max_rounds = getenv("ZS_FR_MAX_ROUNDS") ? atoi(getenv("ZS_FR_MAX_ROUNDS")) : 0;
-            static const int env_range = getenv("ZS_FR_RANGE") ? std::max(1, atoi(getenv("ZS_FR_RANGE"))) : 0;
-            static const int env_group = getenv("ZS_FR_GROUP") ? atoi(getenv("ZS_FR_GROUP")) : 4;
-            static const int env_tail = getenv("ZS_FR_TAIL_RANGE") ? atoi(getenv("ZS_FR_TAIL_RANGE")) : 1;
-            static const bool env_no_seed = getenv("ZS_FR_NO_SEED") != nullptr, env_fixed = getenv("ZS_FR_RANGE_FIXED") != nullptr, env_dbg = getenv("ZS_DEBUG") != nullptr;
-            const int max_rounds = env_max_rounds ? env_max_rounds : pl.fr_max_n + 2;  // (chunk r of a stream is the reference's after round r at the latest)
-            if (!ensure(c, c->fr_chunks, nch * sizeof(FsChunk)) || !ensure(c, c->fr_meta, 2 * nch * sizeof(FsMeta)) || !ensure(c, c->fr_planes, 16 * plane_words) ||
-                !ensure(c, c->fr_prov, 4 * pl.fr_prov + 64) || !ensure(c, c->fr_base, 4 * nch + 64) || !ensure(c, c->fr_counters, 4 * ((size_t)max_rounds + 16))) {
-                // no room for the rounds' planes and provisional symbols: one workgroup per stream needs none of them
-                c->err.clear();
-                ZS_HIP(c, hipStreamSynchronize(c->aux));
-                ZS_HIP(c, hipStreamSynchronize(stream));
-                c->no_rounds_once = true;
-                return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, force_lit);
-            }
-            ZS_HIP(c, hipMemcpyAsync(c->fr_chunks.p, pl.fr_chunks.data(), nch * sizeof(FsChunk), hipMemcpyHostToDevice, stream));
-            ZS_HIP(c, hipMemsetAsync(c->fr_counters.p, 0, 4 * ((size_t)max_rounds + 16), stream));
-            // more chunks than CUs: a workgroup takes a range of consecutive chunks in turn, every chunk reading what the chunks before
-            // it in the range have just left -- within a range the parse is sequential, and the rounds only have to settle what
-            // crosses the ranges' ends (1 MiB of text in chunks of 8192: 43 rounds and 27 runs per chunk with ranges of one, 21 and
-            // 11.5 with ranges of four, 6 and 3.5 with ranges of sixteen; tests/model mode frounds)
-            // A round's ranges are chosen from what the round before changed: while most chunks still change, as many ranges as CUs;
-            // once the chunks that will run again fit the chip (a changed chunk wakes the ~4 behind it), one chunk per workgroup --
-            // two active chunks of one range would wait for each other.
-            // (below two chipfuls of chunks ranges of one: the corpus, 336 chunks of 11 files, 13.9 / 19.1 ms against 16.5 / 23.6)
-            const int range_max = env_range ? env_range : nch >= 512 ? (int)((nch + 255) / 256) : 1;
-            FsRounds fr{dev<FsChunk>(c->fr_chunks), dev<FsMeta>(c->fr_meta), dev<uint32_t>(c->fr_planes), dev<uint32_t>(c->fr_prov), dev<uint32_t>(c->fr_counters),
-                        (int64_t)plane_words, (int)nch, 0, env_no_seed ? 1 : 0, range_max};
-            const int group = env_group;  // rounds between two looks at the counter (ranges of one)
-            uint32_t changed = 1;
-            int r = 0;
-            std::string trace;
-            while (r < max_rounds && changed) {
-                const int g_n = fr.range > 1 ? 1 : group;
-                const unsigned n_wg = (unsigned)((nch + (size_t)fr.range - 1) / (size_t)fr.range);
-                for (int g = 0; g < g_n && r < max_rounds; g++, r++) {
-                    fr.round = r;
-                    hipLaunchKernelGGL((zs_fast_sweep_kernel<1024, kFsTile1, true>), dim3(n_wg), dim3(1024), fs_lds, stream, d_sd, d_st, dev<uint16_t>(c->link),
-                                       dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), lv, strategy, fr);
-                }
-                ZS_HIP(c, hipMemcpyAsync(&changed, dev<uint32_t>(c->fr_counters) + (r - 1), 4, hipMemcpyDeviceToHost, stream));
-                ZS_HIP(c, hipStreamSynchronize(stream));
-                if (env_dbg) {
-                    static auto t_last = std::chrono::steady_clock::now();
-                    const auto t_now = std::chrono::steady_clock::now();
-                    char b[64];
-                    snprintf(b, sizeof b, " %u/%d(%.2f)", changed, fr.range, r <= g_n ? 0.0 : std::chrono::duration<double, std::milli>(t_now - t_last).count());
-                    t_last = t_now;
-                    trace += b;
-                }
-                if (!env_fixed) {
-                    static const double env_wake = getenv("ZS_FR_WAKE") ? atof(getenv("ZS_FR_WAKE")) : 4.0;
-                    const size_t awake = std::min<size_t>(nch, (size_t)(env_wake * (double)changed));
-                    const int tail = env_tail;
-                    fr.range = std::min<int>(range_max, std::max<int>(tail, (int)((awake + 255) / 256)));
-                }
-            }
-            c->fast_rounds = r;
-            if (env_dbg) fprintf(stderr, "zs: DeflateFast over %zu chunks of %d streams, up to %d to a workgroup: %d rounds (changed/range:%s)\n", nch, n, range_max, r, trace.c_str());
-            if (changed) {
-                // (cannot happen: chunk r of a stream is the reference's after round r at the latest.  Should it, the batch takes one
-                // workgroup per stream instead of failing the call)
-                ZS_HIP(c, hipStreamSynchronize(c->aux));
-                c->no_rounds_once = true;
-                return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, force_lit);
-            }
-            const FsMeta *mf = dev<FsMeta>(c->fr_meta) + (size_t)((r - 1) & 1) * nch;
-            hipLaunchKernelGGL(zs_fast_commit_scan_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, mf, dev<int32_t>(c->fr_base));
-            hipLaunchKernelGGL(zs_fast_commit_kernel, dim3((unsigned)nch), dim3(256), 0, stream, d_sd, fr, mf, dev<int32_t>(c->fr_base), dev<uint16_t>(c->link),
-                               dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top));
-        } else {
-            hipLaunchKernelGGL((zs_fast_sweep_kernel<1024, kFsTile1, false>), dim3((unsigned)n), dim3(1024), fs_lds, stream, d_sd, d_st, dev<uint16_t>(c->link),
-                               dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), lv, strategy, FsRounds());
+    // (a kept plan keeps both: what is struck here is put back when a same-shaped call takes the plan, whose links decide anew)
+    if (pc.valid && !pc.dual_saved) pc.dual_saved = true, pc.dual_sd = pl.sd, pc.dual_fr = pl.fr_chunks, pc.dual_fr_max_n = pl.fr_max_n, pc.dual_n_runs = pl.n_runs;
+    for (int i = 0; i < n; i++) {
+        StreamDesc &sk = pl.sd[(size_t)i];
+        if (periodic) sk.fv_end = -1, sk.fr_first = 0, sk.fr_n = 0;
+        else sk.fast_runs = 0, sk.run_slots = 0;
+    }
+    if (periodic) pl.any_fv = false, pl.fr_chunks.clear(), pl.fr_max_n = 0;
+    else pl.n_runs = 0;
+    memcpy(c->pinned, pl.sd.data(), sizeof(StreamDesc) * (size_t)n);  // (the staging copy's uploads are through: the stream was just waited for)
+    ZS_HIP(c, hipMemcpyAsync(c->sd.p, c->pinned, sizeof(StreamDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
+    if (env.debug) fprintf(stderr, "zs: %d stream(s) below 4 MiB at level %d: %s\n", n, level, periodic ? "all period, the speculative runs" : "the sweeps");
+    return true;
+}
+
+// The speculative chunk walk: every chunk of the streams that qualify walked from a guessed entry, the guesses checked
+// against the exits, one look at the verdicts.  A stream that verified has its chunks' entries and first symbols and what
+// the resolve kernel would leave; the others -- and the streams that never qualified, with no look at anything -- take the maps.
+bool DeflateCall::spec_walk() {
+    spec_ran = true;
+    hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 1>), dim3((unsigned)((pl.max_spec_n + 63) / 64), (unsigned)n), dim3(kK5Threads), 0, stream, d_sd, d_st,
+                       (const uint2 *)nullptr, 0, dev<uint2>(c->mm), dev<uint16_t>(c->link), (const uint16_t *)nullptr, (const uint32_t *)nullptr,
+                       (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, c->crc_tab, lv, strategy, hash_variant, env.k5_ahead, k5s);
+    if (prof) (void)hipEventRecord(c->ev_spec[0], stream);
+    hipLaunchKernelGGL(zs_spec_verify_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, dev<uint2>(c->mm), dev<uint16_t>(c->link), c->crc_tab, lv,
+                       strategy, hash_variant, k5s, dev<int32_t>(c->spec_flags));
+    int32_t *hf = (int32_t *)c->pinned;  // (the staging copy's uploads are through by the time the verdicts arrive: same stream)
+    ZS_HIP(c, hipMemcpyAsync(hf, c->spec_flags.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+    ZS_HIP(c, hipEventRecord(c->ev_verdict, stream));
+    // The chip does not wait for the host's look at the verdicts: the compaction of the verified streams' symbols goes in
+    // right behind them.  It is predicated on the device (StreamState::spec_ok, per stream), reads only what the walk and the
+    // verdict kernel left (records, bases, slabs) and writes only verified streams' symbols and block cuts, none of which the
+    // map path of the other streams touches -- so it may run ahead of that path as well as behind it.  The tail engine's
+    // fork keeps its place behind the verdict kernel: its event is recorded here, in front of the compaction (a stream that
+    // takes the maps records it again behind the resolve kernel, below).
+    if (!tail_late && !tail_serial) {
+        ZS_HIP(c, hipEventRecord(c->ev_fork, stream));
+        fork_recorded = true;
+    }
+    if (prof) (void)hipEventRecord(c->ev_spec[2], stream);
+    hipLaunchKernelGGL(zs_spec_compact_kernel, dim3((unsigned)((pl.max_spec_n + 3) / 4), (unsigned)n), dim3(256), 0, stream, d_sd, d_st, k5s,
+                       dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top));
+    if (prof) (void)hipEventRecord(c->ev_spec[3], stream);
+    ZS_HIP(c, hipEventSynchronize(c->ev_verdict));
+    if (prof) (void)hipEventRecord(c->ev_spec[1], stream);
+    for (int i = 0; i < n; i++) {
+        if (hf[i] == 0) continue;
+        c->spec_streams++;
+        if (hf[i] == 1) spec_ok_streams++;
+        else c->spec_fallbacks++;
+        if (hf[i] == 2) c->spec_periodic++;  // (the verdicts: 1 verified, 2 periodic -- never walked, 3 an event bailed, 4 wrong guesses)
+    }
+    if (spec_ok_streams < c->spec_streams) {  // how many guesses were wrong: the streams' states (a failed attempt is rare)
+        StreamState *hs = (StreamState *)c->pinned;
+        ZS_HIP(c, hipMemcpyAsync(hs, d_st, sizeof(StreamState) * (size_t)n, hipMemcpyDeviceToHost, stream));
+        ZS_HIP(c, hipStreamSynchronize(stream));
+        for (int i = 0; i < n; i++) c->spec_wrong_chunks += hs[i].spec_wrong;
+    }
+    if (env.debug)
+        fprintf(stderr, "zs: speculative walk: %d streams tried, %d verified, %d wrong guesses (chunks of %d, warm-up %d)\n", c->spec_streams, spec_ok_streams,
+                c->spec_wrong_chunks, 1 << k5s.len_bits, k5s.warm);
+    return true;
+}
+
+// Levels 1-3: window-wide sweeps of a workgroup (zs_fast_sweep.hip), one workgroup per stream or, the plan having chunks,
+// rounds over the chunks of the streams: every round one workgroup per chunk, until a round changes nothing
+bool DeflateCall::fast_sweeps() {
+    constexpr int fs_lds = fs_lds_bytes<1024, kFsTile1>();
+    if (!pl.fr_chunks.empty()) {
+        const size_t nch = pl.fr_chunks.size(), plane_words = (size_t)pl.n_pos / 32 + kFvBitSlack / 4 + 64;
+        static const RoundsEnv re;  // the switches of the measurements, read once (not per round)
+        const int max_rounds = re.max_rounds ? re.max_rounds : pl.fr_max_n + 2;  // (chunk r of a stream is the reference's after round r at the latest)
+        if (!ensure(c, c->fr_chunks, nch * sizeof(FsChunk)) || !ensure(c, c->fr_meta, 2 * nch * sizeof(FsMeta)) || !ensure(c, c->fr_planes, 16 * plane_words) ||
+            !ensure(c, c->fr_prov, 4 * pl.fr_prov + 64) || !ensure(c, c->fr_base, 4 * nch + 64) || !ensure(c, c->fr_counters, 4 * ((size_t)max_rounds + 16))) {
+            // no room for the rounds' planes and provisional symbols: one workgroup per stream needs none of them
+            c->err.clear();
+            ZS_HIP(c, hipStreamSynchronize(c->aux));
+            ZS_HIP(c, hipStreamSynchronize(stream));
+            c->no_rounds_once = true;
+            return rerun(force_seq, false, force_lit);
         }
+        ZS_HIP(c, hipMemcpyAsync(c->fr_chunks.p, pl.fr_chunks.data(), nch * sizeof(FsChunk), hipMemcpyHostToDevice, stream));
+        ZS_HIP(c, hipMemsetAsync(c->fr_counters.p, 0, 4 * ((size_t)max_rounds + 16), stream));
+        // more chunks than CUs: a workgroup takes a range of consecutive chunks in turn, every chunk reading what the chunks before
+        // it in the range have just left -- within a range the parse is sequential, and the rounds only have to settle what
+        // crosses the ranges' ends (1 MiB of text in chunks of 8192: 43 rounds and 27 runs per chunk with ranges of one, 21 and
+        // 11.5 with ranges of four, 6 and 3.5 with ranges of sixteen; tests/model mode frounds)
+        // A round's ranges are chosen from what the round before changed: while most chunks still change, as many ranges as CUs;
+        // once the chunks that will run again fit the chip (a changed chunk wakes the ~4 behind it), one chunk per workgroup --
+        // two active chunks of one range would wait for each other.
+        // (below two chipfuls of chunks ranges of one: the corpus, 336 chunks of 11 files, 13.9 / 19.1 ms against 16.5 / 23.6)
+        const int range_max = re.range ? re.range : nch >= 512 ? (int)((nch + 255) / 256) : 1;
+        FsRounds fr{dev<FsChunk>(c->fr_chunks), dev<FsMeta>(c->fr_meta), dev<uint32_t>(c->fr_planes), dev<uint32_t>(c->fr_prov), dev<uint32_t>(c->fr_counters),
+                    (int64_t)plane_words, (int)nch, 0, re.no_seed ? 1 : 0, range_max};
+        uint32_t changed = 1;
+        int r = 0;
+        std::string trace;
+        while (r < max_rounds && changed) {
+            const int g_n = fr.range > 1 ? 1 : re.group;  // rounds between two looks at the counter (ranges of one)
+            const unsigned n_wg = (unsigned)((nch + (size_t)fr.range - 1) / (size_t)fr.range);
+            for (int g = 0; g < g_n && r < max_rounds; g++, r++) {
+                fr.round = r;
+                hipLaunchKernelGGL((zs_fast_sweep_kernel<1024, kFsTile1, true>), dim3(n_wg), dim3(1024), fs_lds, stream, d_sd, d_st, dev<uint16_t>(c->link),
+                                   dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), lv, strategy, fr);
+            }
+            ZS_HIP(c, hipMemcpyAsync(&changed, dev<uint32_t>(c->fr_counters) + (r - 1), 4, hipMemcpyDeviceToHost, stream));
+            ZS_HIP(c, hipStreamSynchronize(stream));
+            if (re.dbg) {
+                static auto t_last = std::chrono::steady_clock::now();
+                const auto t_now = std::chrono::steady_clock::now();
+                char b[64];
+                snprintf(b, sizeof b, " %u/%d(%.2f)", changed, fr.range, r <= g_n ? 0.0 : std::chrono::duration<double, std::milli>(t_now - t_last).count());
+                t_last = t_now;
+                trace += b;
+            }
+            if (!re.fixed) {
+                const size_t awake = std::min<size_t>(nch, (size_t)(re.wake * (double)changed));
+                fr.range = std::min<int>(range_max, std::max<int>(re.tail, (int)((awake + 255) / 256)));
+            }
+        }
+        c->fast_rounds = r;
+        if (re.dbg) fprintf(stderr, "zs: DeflateFast over %zu chunks of %d streams, up to %d to a workgroup: %d rounds (changed/range:%s)\n", nch, n, range_max, r, trace.c_str());
+        if (changed) {
+            // (cannot happen: chunk r of a stream is the reference's after round r at the latest.  Should it, the batch takes one
+            // workgroup per stream instead of failing the call)
+            ZS_HIP(c, hipStreamSynchronize(c->aux));
+            c->no_rounds_once = true;
+            return rerun(force_seq, false, force_lit);
+        }
+        const FsMeta *mf = dev<FsMeta>(c->fr_meta) + (size_t)((r - 1) & 1) * nch;
+        hipLaunchKernelGGL(zs_fast_commit_scan_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, mf, dev<int32_t>(c->fr_base));
+        hipLaunchKernelGGL(zs_fast_commit_kernel, dim3((unsigned)nch), dim3(256), 0, stream, d_sd, fr, mf, dev<int32_t>(c->fr_base), dev<uint16_t>(c->link),
+                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top));
+    } else {
+        hipLaunchKernelGGL((zs_fast_sweep_kernel<1024, kFsTile1, false>), dim3((unsigned)n), dim3(1024), fs_lds, stream, d_sd, d_st, dev<uint16_t>(c->link),
+                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), lv, strategy, FsRounds());
     }
-    if (pl.any_rle) {
-        // CompressionStrategy.Rle: the body's symbols from the runs of equal bytes (zs_rle.hip), the tail engine behind them
-        const size_t nt = (size_t)pl.n_rle_tiles;
-        if (!ensure(c, c->rle_tiles, 4 * (4 * nt + (size_t)n) + 256)) return false;
-        int32_t *rb = dev<int32_t>(c->rle_tiles);
-        RleTiles rt{rb, rb + nt, rb + 2 * nt, rb + 3 * nt, rb + 4 * nt};
-        int max_tiles = 0;
-        for (int i = 0; i < n; i++)
-            if (pl.sd[(size_t)i].rle_end >= 0) max_tiles = std::max(max_tiles, (pl.sd[(size_t)i].rle_end + kMaxMatch + 1 + 4095) / 4096);
-        // (a grid's y ends at 65 535: the tile kernels take the streams in slices)
-        auto tiles = [&](auto &&launch) {
-            for (int s0 = 0; s0 < n; s0 += 65535) launch(dim3((unsigned)((max_tiles + 3) / 4), (unsigned)std::min(n - s0, 65535)), s0);
-        };
-        tiles([&](dim3 tg, int s0) { hipLaunchKernelGGL(zs_rle_starts_kernel, tg, dim3(256), 0, stream, d_sd, rt, s0); });
-        hipLaunchKernelGGL(zs_rle_scan_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, rt);
-        tiles([&](dim3 tg, int s0) {
-            hipLaunchKernelGGL(zs_rle_pass_kernel<0>, tg, dim3(256), 0, stream, d_sd, rt, dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), s0);
-        });
-        hipLaunchKernelGGL(zs_rle_sums_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, rt);
-        tiles([&](dim3 tg, int s0) {
-            hipLaunchKernelGGL(zs_rle_pass_kernel<1>, tg, dim3(256), 0, stream, d_sd, rt, dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), s0);
-        });
-    }
+    return true;
+}
+
+// CompressionStrategy.Rle: the body's symbols from the runs of equal bytes (zs_rle.hip), the tail engine behind them
+bool DeflateCall::rle_tiles() {
+    const size_t nt = (size_t)pl.n_rle_tiles;
+    if (!ensure(c, c->rle_tiles, 4 * (4 * nt + (size_t)n) + 256)) return false;
+    int32_t *rb = dev<int32_t>(c->rle_tiles);
+    RleTiles rt{rb, rb + nt, rb + 2 * nt, rb + 3 * nt, rb + 4 * nt};
+    int max_tiles = 0;
+    for (int i = 0; i < n; i++)
+        if (pl.sd[(size_t)i].rle_end >= 0) max_tiles = std::max(max_tiles, (pl.sd[(size_t)i].rle_end + kMaxMatch + 1 + 4095) / 4096);
+    // (a grid's y ends at 65 535: the tile kernels take the streams in slices)
+    auto tiles = [&](auto &&launch) {
+        for (int s0 = 0; s0 < n; s0 += 65535) launch(dim3((unsigned)((max_tiles + 3) / 4), (unsigned)std::min(n - s0, 65535)), s0);
+    };
+    tiles([&](dim3 tg, int s0) { hipLaunchKernelGGL(zs_rle_starts_kernel, tg, dim3(256), 0, stream, d_sd, rt, s0); });
+    hipLaunchKernelGGL(zs_rle_scan_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, rt);
+    tiles([&](dim3 tg, int s0) {
+        hipLaunchKernelGGL(zs_rle_pass_kernel<0>, tg, dim3(256), 0, stream, d_sd, rt, dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), s0);
+    });
+    hipLaunchKernelGGL(zs_rle_sums_kernel, dim3((unsigned)n), dim3(1024), 0, stream, d_sd, d_st, rt);
+    tiles([&](dim3 tg, int s0) {
+        hipLaunchKernelGGL(zs_rle_pass_kernel<1>, tg, dim3(256), 0, stream, d_sd, rt, dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), s0);
+    });
+    return true;
+}
+
+// The tail engine and the symbols of the map path.  The fork: the tail engine (sequential, one workgroup per stream) needs only
+// what the resolve kernel left, so it runs on the second stream beside the symbol kernels -- unless the tails are many
+// (tail_serial) or need the symbols (tail_late).
+bool DeflateCall::tails_and_symbols() {
     if (!tail_late && !tail_serial) {
         if (!fork_recorded || need_maps) ZS_HIP(c, hipEventRecord(c->ev_fork, stream));  // (behind the resolve kernel, if it ran)
         ZS_HIP(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-        hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, c->aux, d_sd, d_st, dev<uint16_t>(c->link),
-                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks),
-                           dev<uint8_t>(c->scratch), c->crc_tab, lv, strategy, hash_variant, level);
+        launch_tail(c->aux);
         ZS_HIP(c, hipEventRecord(c->ev_join, c->aux));
     }
     if (!pl.w_segs.empty() && need_maps)
         hipLaunchKernelGGL(zs_expand_kernel, dim3((unsigned)((pl.w_segs.size() + 63) / 64)), dim3(64), 0, stream, d_sd, d_st,
-                           d_work + o_segs, (int)pl.w_segs.size(), dev<uint2>(c->mm), dev<uint16_t>(c->link),
+                           work(kWSegs), (int)pl.w_segs.size(), dev<uint2>(c->mm), dev<uint16_t>(c->link),
                            dev<uint32_t>(c->maps), dev<uint16_t>(c->seg_entry), dev<uint32_t>(c->seg_symbase),
                            dev<uint8_t>(c->stale), dev<uint16_t>(c->entry), dev<uint32_t>(c->symbase), c->crc_tab, lv, strategy,
                            hash_variant);
     mark(8);
     if (!pl.w_chunks.empty() && need_maps)
         hipLaunchKernelGGL((zs_emit_syms_lane_kernel<4, 0>), dim3((unsigned)((pl.w_chunks.size() + 63) / 64)), dim3(kK5Threads), 0, stream, d_sd, d_st,
-                           d_work + o_chunks, (int)pl.w_chunks.size(), dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint16_t>(c->entry),
+                           work(kWChunks), (int)pl.w_chunks.size(), dev<uint2>(c->mm), dev<uint16_t>(c->link), dev<uint16_t>(c->entry),
                            dev<uint32_t>(c->symbase), dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top),
-                           c->crc_tab, lv, strategy, hash_variant, k5_ahead, k5s);
+                           c->crc_tab, lv, strategy, hash_variant, env.k5_ahead, k5s);
     // the streams whose speculative walk verified: their symbols from the walk's slabs to their places, and the block cuts.
     // (In the re-entry behind the batched cut rounds -- `rounds` -- nothing of the speculative path is launched: the verified
     // streams' symbols and block cuts are those of the call's first pass, which ran to its end for them; the rounds touch only
@@ -1256,96 +858,96 @@ plan_again:
     // tests/test_gpu_spec.py test_a_verified_stream_beside_one_in_the_cut_rounds.)
     // (the compaction of their symbols went in behind the verdict kernel, above)
     mark(9);
-    if (tail_serial)
-        hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
-                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks),
-                           dev<uint8_t>(c->scratch), c->crc_tab, lv, strategy, hash_variant, level);
+    if (tail_serial) launch_tail(stream);
     else if (!tail_late) ZS_HIP(c, hipStreamWaitEvent(stream, c->ev_join, 0));
     hipLaunchKernelGGL(zs_body_blocks_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<int32_t>(c->blk_end),
                        dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks), dev<uint32_t>(c->syms));
-    if (tail_late)
-        hipLaunchKernelGGL(zs_tail_kernel, dim3((unsigned)n), dim3(1024), kTailLds, stream, d_sd, d_st, dev<uint16_t>(c->link),
-                           dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks),
-                           dev<uint8_t>(c->scratch), c->crc_tab, lv, strategy, hash_variant, level);
-    if (pl.n_runs) {
-        // DeflateFast by speculative chunk runs; a run whose hand-over state does not verify sends the batch to the
-        // sequential engine (the result is the reference's bytes either way)
-        if (!getenv("ZS_FAST_NO_PROBE") && force_seq == 0 && !pl.any_dual) {
-            // only data that looks periodic is worth the attempt (zs_fast_probe_kernel); anything else goes to the sweeps right away
-            hipLaunchKernelGGL(zs_fast_probe_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, dev<uint16_t>(c->link), dev<int32_t>(c->run_fail));
-            std::vector<int32_t> np((size_t)n, 0);
-            ZS_HIP(c, hipMemcpyAsync(np.data(), c->run_fail.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
-            ZS_HIP(c, hipStreamSynchronize(stream));
-            for (int i = 0; i < n; i++)
-                if (np[(size_t)i]) {
-                    ZS_HIP(c, hipStreamSynchronize(c->aux));  // (the forked passes read the workspace that is about to be reused)
-                    return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, 1, ro, false, force_lit);
-                }
-        }
-        ZS_HIP(c, hipMemsetAsync(c->run_fail.p, 0, 4 * (size_t)n + 64, stream));
-        hipLaunchKernelGGL(zs_fast_run_kernel, dim3((unsigned)pl.w_runs.size()), dim3(1024), kFastRunLds, stream, d_sd, d_work + o_runs,
-                           dev<uint16_t>(c->link), dev<uint32_t>(c->run_syms), dev<uint32_t>(c->run_bits), dev<uint8_t>(c->run_scratch),
-                           dev<FastRunOut>(c->run_outs), c->crc_tab, lv, strategy, hash_variant);
-        hipLaunchKernelGGL(zs_fast_verify_kernel, dim3((unsigned)pl.w_runs.size()), dim3(256), 0, stream, d_sd, d_work + o_runs,
-                           dev<uint32_t>(c->run_bits), dev<FastRunOut>(c->run_outs), dev<int32_t>(c->run_fail));
-        std::vector<int32_t> rfail((size_t)n, 0);
-        ZS_HIP(c, hipMemcpyAsync(rfail.data(), c->run_fail.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+    if (tail_late) launch_tail(stream);
+    return true;
+}
+
+// DeflateFast by speculative chunk runs; a run whose hand-over state does not verify sends the batch to the
+// sequential engine (the result is the reference's bytes either way)
+bool DeflateCall::spec_runs() {
+    if (!env.fast_no_probe && force_seq == 0 && !pl.any_dual) {
+        // only data that looks periodic is worth the attempt (zs_fast_probe_kernel); anything else goes to the sweeps right away
+        hipLaunchKernelGGL(zs_fast_probe_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, dev<uint16_t>(c->link), dev<int32_t>(c->run_fail));
+        std::vector<int32_t> np((size_t)n, 0);
+        ZS_HIP(c, hipMemcpyAsync(np.data(), c->run_fail.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
         ZS_HIP(c, hipStreamSynchronize(stream));
         for (int i = 0; i < n; i++)
-            if (rfail[(size_t)i]) {
-                ZS_HIP(c, hipStreamSynchronize(c->aux));  // the forked tree pass reads the workspace that is about to be reused
-                c->fast_fallbacks++;
-                std::vector<FastRunOut> outs((size_t)pl.n_runs);
-                ZS_HIP(c, hipMemcpy(outs.data(), c->run_outs.p, sizeof(FastRunOut) * outs.size(), hipMemcpyDeviceToHost));
-                if (getenv("ZS_DEBUG"))
-                    for (int j = 0; j < pl.sd[(size_t)i].fast_runs; j++) {
-                        const FastRunOut &o = outs[(size_t)pl.sd[(size_t)i].run_off + j];
-                        fprintf(stderr, "zs: stream %d run %d ok=%d mark=%lld (+%lld syms) end=%lld nsyms=%lld n_ev=%d\n", i, j, o.ok,
-                                (long long)o.mark_pos, (long long)o.mark_nsyms, (long long)o.end_pos, (long long)o.nsyms, o.n_ev);
-                    }
-                // Data whose parse does not fall back into step (a period that is no divisor of anything, zeros, 8 KiB rows): the
-                // rounds settle one range a round on it -- the stream at one workgroup's 46 / 35 / 20 MB/s -- while one run of
-                // the engine over the whole stream costs ~1 us a symbol, and the runs have just counted the symbols: 5 MiB of a
-                // 7-byte period is 20 K matches, 20 ms against 375; ptt5 nine times over is 600 K symbols, 600 ms against 53.  One run per
-                // stream when that is the shorter way for the batch by a margin (both are estimates).
-                double t_engine = 0, t_sweeps = 0;
-                for (int k = 0; k < n; k++) {
-                    const StreamDesc &sk = pl.sd[(size_t)k];
-                    if (sk.fast_runs <= 0) continue;
-                    // (a run's warm-up is a fifth of it: the counts of whole runs, scaled)
-                    int64_t syms = 0, matches = 0;
-                    for (int j = 0; j < sk.fast_runs; j++) syms += outs[(size_t)sk.run_off + j].nsyms, matches += outs[(size_t)sk.run_off + j].n_match;
-                    const double scale = sk.fast_runs > 1 ? 0.8 : 1.0;
-                    const double te = scale * (1.2e-6 * (double)matches + 0.03e-6 * (double)(syms - matches)) + (double)sk.n / 1.5e9;
-                    if (getenv("ZS_DEBUG")) fprintf(stderr, "zs: stream %d: ~%.0f symbols one at a time, ~%.0f in runs of literals, %d bytes\n", k, scale * (double)matches, scale * (double)(syms - matches), sk.n);
-                    t_engine = std::max(t_engine, te);
-                    t_sweeps = std::max(t_sweeps, (double)sk.n / (level >= 3 ? 20e6 : level == 2 ? 35e6 : 46e6));
-                }
-                const int mode = (force_seq == 0 && !getenv("ZS_NO_WHOLE_RUNS") && (getenv("ZS_WHOLE_RUNS") || t_engine < 0.7 * t_sweeps)) ? 2 : 1;
-                if (getenv("ZS_DEBUG")) fprintf(stderr, "zs: the runs did not verify: %s (engine %.1f ms, sweeps up to %.1f ms)\n", mode == 2 ? "one run per stream" : "the sweeps", t_engine * 1e3, t_sweeps * 1e3);
-                return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, mode, ro, false, force_lit);
+            if (np[(size_t)i]) {
+                ZS_HIP(c, hipStreamSynchronize(c->aux));  // (the forked passes read the workspace that is about to be reused)
+                return rerun(1, false, force_lit);
             }
-        hipLaunchKernelGGL(zs_fast_plan_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<FastRunOut>(c->run_outs), n);
-        hipLaunchKernelGGL(zs_fast_stitch_kernel, dim3((unsigned)pl.w_runs.size()), dim3(256), 0, stream, d_sd, d_work + o_runs,
-                           dev<uint32_t>(c->run_syms), dev<FastRunOut>(c->run_outs), dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end),
-                           dev<int32_t>(c->blk_top));
-        hipLaunchKernelGGL(zs_fast_blocks_kernel, dim3((unsigned)n), dim3(64), 0, stream, d_sd, d_st, dev<FastRunOut>(c->run_outs),
-                           dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks), n);
     }
-    mark(10);
+    ZS_HIP(c, hipMemsetAsync(c->run_fail.p, 0, 4 * (size_t)n + 64, stream));
+    hipLaunchKernelGGL(zs_fast_run_kernel, dim3((unsigned)pl.w_runs.size()), dim3(1024), kFastRunLds, stream, d_sd, work(kWRuns),
+                       dev<uint16_t>(c->link), dev<uint32_t>(c->run_syms), dev<uint32_t>(c->run_bits), dev<uint8_t>(c->run_scratch),
+                       dev<FastRunOut>(c->run_outs), c->crc_tab, lv, strategy, hash_variant);
+    hipLaunchKernelGGL(zs_fast_verify_kernel, dim3((unsigned)pl.w_runs.size()), dim3(256), 0, stream, d_sd, work(kWRuns),
+                       dev<uint32_t>(c->run_bits), dev<FastRunOut>(c->run_outs), dev<int32_t>(c->run_fail));
+    std::vector<int32_t> rfail((size_t)n, 0);
+    ZS_HIP(c, hipMemcpyAsync(rfail.data(), c->run_fail.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+    ZS_HIP(c, hipStreamSynchronize(stream));
+    for (int i = 0; i < n; i++)
+        if (rfail[(size_t)i]) {
+            ZS_HIP(c, hipStreamSynchronize(c->aux));  // the forked tree pass reads the workspace that is about to be reused
+            c->fast_fallbacks++;
+            std::vector<FastRunOut> outs((size_t)pl.n_runs);
+            ZS_HIP(c, hipMemcpy(outs.data(), c->run_outs.p, sizeof(FastRunOut) * outs.size(), hipMemcpyDeviceToHost));
+            if (env.debug)
+                for (int j = 0; j < pl.sd[(size_t)i].fast_runs; j++) {
+                    const FastRunOut &o = outs[(size_t)pl.sd[(size_t)i].run_off + j];
+                    fprintf(stderr, "zs: stream %d run %d ok=%d mark=%lld (+%lld syms) end=%lld nsyms=%lld n_ev=%d\n", i, j, o.ok,
+                            (long long)o.mark_pos, (long long)o.mark_nsyms, (long long)o.end_pos, (long long)o.nsyms, o.n_ev);
+                }
+            // Data whose parse does not fall back into step (a period that is no divisor of anything, zeros, 8 KiB rows): the
+            // rounds settle one range a round on it -- the stream at one workgroup's 46 / 35 / 20 MB/s -- while one run of
+            // the engine over the whole stream costs ~1 us a symbol, and the runs have just counted the symbols: 5 MiB of a
+            // 7-byte period is 20 K matches, 20 ms against 375; ptt5 nine times over is 600 K symbols, 600 ms against 53.  One run per
+            // stream when that is the shorter way for the batch by a margin (both are estimates).
+            double t_engine = 0, t_sweeps = 0;
+            for (int k = 0; k < n; k++) {
+                const StreamDesc &sk = pl.sd[(size_t)k];
+                if (sk.fast_runs <= 0) continue;
+                // (a run's warm-up is a fifth of it: the counts of whole runs, scaled)
+                int64_t syms = 0, matches = 0;
+                for (int j = 0; j < sk.fast_runs; j++) syms += outs[(size_t)sk.run_off + j].nsyms, matches += outs[(size_t)sk.run_off + j].n_match;
+                const double scale = sk.fast_runs > 1 ? 0.8 : 1.0;
+                const double te = scale * (1.2e-6 * (double)matches + 0.03e-6 * (double)(syms - matches)) + (double)sk.n / 1.5e9;
+                if (env.debug) fprintf(stderr, "zs: stream %d: ~%.0f symbols one at a time, ~%.0f in runs of literals, %d bytes\n", k, scale * (double)matches, scale * (double)(syms - matches), sk.n);
+                t_engine = std::max(t_engine, te);
+                t_sweeps = std::max(t_sweeps, (double)sk.n / (level >= 3 ? 20e6 : level == 2 ? 35e6 : 46e6));
+            }
+            const int mode = (force_seq == 0 && !env.no_whole_runs && (env.whole_runs || t_engine < 0.7 * t_sweeps)) ? 2 : 1;
+            if (env.debug) fprintf(stderr, "zs: the runs did not verify: %s (engine %.1f ms, sweeps up to %.1f ms)\n", mode == 2 ? "one run per stream" : "the sweeps", t_engine * 1e3, t_sweeps * 1e3);
+            return rerun(mode, false, force_lit);
+        }
+    hipLaunchKernelGGL(zs_fast_plan_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<FastRunOut>(c->run_outs), n);
+    hipLaunchKernelGGL(zs_fast_stitch_kernel, dim3((unsigned)pl.w_runs.size()), dim3(256), 0, stream, d_sd, work(kWRuns),
+                       dev<uint32_t>(c->run_syms), dev<FastRunOut>(c->run_outs), dev<uint32_t>(c->syms), dev<int32_t>(c->blk_end),
+                       dev<int32_t>(c->blk_top));
+    hipLaunchKernelGGL(zs_fast_blocks_kernel, dim3((unsigned)n), dim3(64), 0, stream, d_sd, d_st, dev<FastRunOut>(c->run_outs),
+                       dev<int32_t>(c->blk_end), dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks), n);
+    return true;
+}
+
+// Blocks to bits: the trees, the blocks' places in the output, the bits; then the wait for the streams' states.
+bool DeflateCall::blocks_and_bits() {
     // the tree kernel is one latency chain per block: many small blocks (a batch of small streams) want more resident
     // workgroups, a long stream's 16 Ki-symbol blocks a wider histogram
     const int trees_threads = pl.w_blocks.size() > 8192 ? 128 : 256;
-    if (n >= 64 && !getenv("ZS_NO_LIVE_LIST")) {
+    if (n >= 64 && !penv.no_live_list) {
         // many streams: the block list rewritten with the blocks that exist in front (zs_live_scan_kernel)
         // (its prefix sum goes where the work lists' prefixes were uploaded: zs_worklist_kernel is through with them, and a call
         // that takes this plan over does not run it)
-        int32_t *const d_live = (int32_t *)((uint8_t *)c->sd.p + sizeof(StreamDesc) * (size_t)n);
+        int32_t *const d_live = (int32_t *)((uint8_t *)c->sd.p + lay.sd_bytes);
         hipLaunchKernelGGL(zs_live_scan_kernel, dim3(1), dim3(1024), 0, stream, d_st, n, d_live);
         hipLaunchKernelGGL(zs_live_fill_kernel, dim3((unsigned)((pl.w_blocks.size() + 255) / 256)), dim3(256), 0, stream, d_live, n,
-                           (uint32_t)pl.w_blocks.size(), dev<uint2>(c->work) + o_blocks);
+                           (uint32_t)pl.w_blocks.size(), dev<uint2>(c->work) + lay.work[kWBlocks]);
     }
-    hipLaunchKernelGGL(zs_trees_kernel, dim3((unsigned)pl.w_blocks.size()), dim3(trees_threads), 0, stream, d_sd, d_st, d_work + o_blocks,
+    hipLaunchKernelGGL(zs_trees_kernel, dim3((unsigned)pl.w_blocks.size()), dim3(trees_threads), 0, stream, d_sd, d_st, work(kWBlocks),
                        dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info), dev<int32_t>(c->tile_bits), strategy, level);
     mark(11);
     ZS_HIP(c, hipStreamWaitEvent(stream, c->ev_pre, 0));  // the cleared output and the Adler pieces (second stream, above)
@@ -1360,14 +962,13 @@ plan_again:
         for (int i = 0; i < n; i++) longest = std::max(longest, in_len[i]);
         eb_tiles = (int)std::min<int64_t>(kEbTiles, (longest + 1) / kEbTile + 1);
     }
-    static const char *const eb_env = getenv("ZS_EB_TILES");  // (read once per process)
-    if (eb_env) eb_tiles = std::max(1, std::min(kEbTiles, atoi(eb_env)));
+    if (env.eb_tiles()) eb_tiles = std::max(1, std::min(kEbTiles, atoi(env.eb_tiles())));
     hipLaunchKernelGGL(zs_emit_bits_kernel, dim3((unsigned)pl.w_blocks.size(), (unsigned)(1 + eb_tiles)), dim3(256), 0, stream, d_sd, d_st,
-                       d_work + o_blocks, dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info),
+                       work(kWBlocks), dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info),
                        dev<int32_t>(c->tile_bits));
     mark(13);
     ZS_HIP(c, hipGetLastError());
-    StreamState *hst = (StreamState *)c->pinned;
+    hst = (StreamState *)c->pinned;
     ZS_HIP(c, hipMemcpyAsync(hst, d_st, sizeof(StreamState) * (size_t)n, hipMemcpyDeviceToHost, stream));
     ht_launched = ht_us();
     ZS_HIP(c, hipStreamSynchronize(stream));
@@ -1375,12 +976,16 @@ plan_again:
     // (what this call itself moved behind its plan -- the sweeps' rounds, the Rle tiles: buffers the launches take from the
     // context, not from the descriptors -- does not cost the plan it has just made)
     if (pc.valid && !plan_hit) pc.gen = c->plan_gen;
-    if (host_times)
+    if (env.host_times())
         fprintf(stderr, "zs: host: plan + uploads %.0f us%s, all launched at %.0f us, device done at %.0f us\n", ht_plan, c->plan_reused ? " (kept plan)" : "", ht_launched,
                 ht_us());
     c->last_op = lv.func == 1 ? 2 : 0;
-    if (getenv("ZS_DEBUG_CHAIN") && n == 1) {  // the chain of one position as the kernels saw it (buffer positions)
-        const int64_t q0 = atoll(getenv("ZS_DEBUG_CHAIN")) - (ro ? ro->abs_off : 0);
+    return true;
+}
+
+void DeflateCall::debug_dumps() {
+    if (env.debug_chain && n == 1) {  // the chain of one position as the kernels saw it (buffer positions)
+        const int64_t q0 = atoll(env.debug_chain) - (ro ? ro->abs_off : 0);
         if (q0 > 0 && q0 < in_len[0]) {
             std::vector<uint16_t> lk((size_t)in_len[0]);
             (void)hipMemcpy(lk.data(), dev<uint16_t>(c->link) + pl.sd[0].pos_off, 2 * (size_t)in_len[0], hipMemcpyDeviceToHost);
@@ -1388,7 +993,7 @@ plan_again:
                     pl.sd[0].resume, (long long)pl.sd[0].start_pos, (long long)q0);
             int64_t q = q0;
             int hops = 0;
-            const int64_t want = getenv("ZS_DEBUG_CHAIN_WANT") ? atoll(getenv("ZS_DEBUG_CHAIN_WANT")) - (ro ? ro->abs_off : 0) : -1;
+            const int64_t want = env.debug_chain_want ? atoll(env.debug_chain_want) - (ro ? ro->abs_off : 0) : -1;
             int want_at = -1;
             while (lk[(size_t)q] && hops < 100000) {
                 q -= lk[(size_t)q], hops++;
@@ -1398,7 +1003,7 @@ plan_again:
             fprintf(stderr, " ... %d hops, ends at %lld; position %lld is hop %d\n", hops, (long long)q, (long long)want, want_at);
         }
     }
-    if (getenv("ZS_DEBUG_FA") && writes && writes[0] && pl.sd[0].wr_blk) {  // the flush accounting's inputs: blocks flushed before each Write began
+    if (env.debug_fa && writes && writes[0] && pl.sd[0].wr_blk) {  // the flush accounting's inputs: blocks flushed before each Write began
         const WriteSpec *wr = writes[0];
         const size_t nw = wr->ends.size();
         std::vector<int32_t> wb(nw);
@@ -1408,25 +1013,31 @@ plan_again:
         for (size_t k = 0; k < nw && k < 24; k++) fprintf(stderr, " %d(end %lld, flush %d)", wb[k], (long long)wr->ends[k], wr->flush.empty() ? 0 : wr->flush[k]);
         fprintf(stderr, "\n");
     }
-    if (prof) {
-        for (int i = 0; i < kStCount; i++) {
-            float ms = 0;
-            if (i >= kStLinks && i <= kStEmitBits) (void)hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]);  // clear / adler: beside the others, unmarked
-            c->stage_ms[i] = ms;
-        }
-        if (spec_ran) {  // the speculative walk and its verdict sit between the match kernel and the maps
-            float a = 0, b = 0, m = 0;
-            (void)hipEventElapsedTime(&a, c->ev[kStChunkMap], c->ev_spec[0]);
-            (void)hipEventElapsedTime(&b, c->ev_spec[0], c->ev_spec[1]);
-            (void)hipEventElapsedTime(&m, c->ev_spec[1], c->ev[kStChunkMap + 1]);
-            c->stage_ms[kStSpecWalk] = a, c->stage_ms[kStSpecVerify] = b, c->stage_ms[kStChunkMap] = m;
-            // (the compaction runs inside the verdict's interval, while the host looks at the verdicts: its own share of it)
-            float k = 0;
-            (void)hipEventElapsedTime(&k, c->ev_spec[2], c->ev_spec[3]);
-            c->stage_ms[kStSpecCompact] = k;
-            c->stage_ms[kStSpecVerify] = b > k ? b - k : 0;
-        }
+}
+
+// profiling: the stages' times from the events the steps recorded
+void DeflateCall::stage_times() {
+    for (int i = 0; i < kStCount; i++) {
+        float ms = 0;
+        if (i >= kStLinks && i <= kStEmitBits) (void)hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]);  // clear / adler: beside the others, unmarked
+        c->stage_ms[i] = ms;
     }
+    if (spec_ran) {  // the speculative walk and its verdict sit between the match kernel and the maps
+        float a = 0, b = 0, m = 0;
+        (void)hipEventElapsedTime(&a, c->ev[kStChunkMap], c->ev_spec[0]);
+        (void)hipEventElapsedTime(&b, c->ev_spec[0], c->ev_spec[1]);
+        (void)hipEventElapsedTime(&m, c->ev_spec[1], c->ev[kStChunkMap + 1]);
+        c->stage_ms[kStSpecWalk] = a, c->stage_ms[kStSpecVerify] = b, c->stage_ms[kStChunkMap] = m;
+        // (the compaction runs inside the verdict's interval, while the host looks at the verdicts: its own share of it)
+        float k = 0;
+        (void)hipEventElapsedTime(&k, c->ev_spec[2], c->ev_spec[3]);
+        c->stage_ms[kStSpecCompact] = k;
+        c->stage_ms[kStSpecVerify] = b > k ? b - k : 0;
+    }
+}
+
+// What the streams' states say: a poisoned stream or one for the cut rounds has the batch run again; else the results.
+bool DeflateCall::finish() {
     {
         // a stream whose true path met a read the bulk form does not handle (zs_core.h kMapPoisonBit): the batch again with
         // those streams on the literal engine
@@ -1442,7 +1053,7 @@ plan_again:
                 return false;
             }
             c->lit_fallbacks++;
-            return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, false, &fl);
+            return rerun(force_seq, false, &fl);
         }
     }
     if (!ro && !rounds) {
@@ -1454,7 +1065,7 @@ plan_again:
             ZS_HIP(c, hipStreamSynchronize(c->aux));
             c->round_runs++;
             if (!run_cut_rounds()) return false;
-            return plan_rerun(), run_pipeline(c, n, in, in_len, out, out_cap, out_len, status, level, strategy, hash_variant, stream, writes, force_seq, ro, true, force_lit);
+            return rerun(force_seq, true, force_lit);
         }
     }
     if (ro) ro->end_bits = hst[0].end_bits;
@@ -1470,6 +1081,32 @@ plan_again:
         }
     }
     return all_ok;
+}
+
+// A deflate call, step by step.  A step that fails returns false; one that ran the batch again (DeflateCall::rerun) has the
+// call's answer already.  Nothing here moves a launch, a copy, an event or a synchronisation against another.
+bool run_pipeline(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level,
+                  int strategy, int hash_variant, hipStream_t stream, const WriteSpec *const *writes, int force_seq, RunOpts *ro, bool rounds,
+                  const std::vector<uint8_t> *force_lit) {
+    if (!c->plan) c->plan = new PlanCache();
+    PlanCache &pc = *c->plan;
+    DeflateCall k{c, pc, pc.pl, pc.lay, n, in, in_len, out, out_cap, out_len, status, level == -1 ? 6 : level, strategy, hash_variant, stream, writes, force_seq, ro, rounds, force_lit};
+    if (!k.begin()) return false;
+    if (!(k.plan_hit ? k.take_kept_plan() : k.plan_and_upload())) return false;
+    k.launch_setup();
+    k.ht_plan = k.ht_us();
+    ZS_HIP(c, hipEventRecord(c->ev_pre0, stream));
+    if (!rounds && !k.front()) return false;  // (K1 first: every call in front of it is ~5 us in which the device waits for the host)
+    k.mark(7);
+    if (k.pl.any_fv && (!k.fast_sweeps() || k.done)) return k.answer;
+    if (k.pl.any_rle && !k.rle_tiles()) return false;
+    if (!k.tails_and_symbols()) return false;
+    if (k.pl.n_runs && (!k.spec_runs() || k.done)) return k.answer;
+    k.mark(10);
+    if (!k.blocks_and_bits()) return false;
+    k.debug_dumps();
+    if (k.prof) k.stage_times();
+    return k.finish();
 }
 
 // Adler-32 (seed 1) of m device buffers in one pass: the piece kernel over all of them, one combining workgroup per
