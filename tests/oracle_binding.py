@@ -68,6 +68,35 @@ class Oracle:
             raise RuntimeError("oracle deflate failed")
         return out.raw[:n]
 
+    def trace(self, data, level, strategy, chunks, flushes=None, hash_variant=0):
+        """The stream of compress_writes and the oracle's Fill_window events while it was made: (z, reads, slides) with reads =
+        [(loop-top, bytes read, pre-insert ran, window base)] and slides = [(loop-top, new window base)], absolute positions.
+        on_symbol and on_match stay null: the tokens are read from the stream."""
+        data = bytes(data)
+        chunks = list(chunks) if chunks else [len(data)]
+        reads, slides = [], []
+        READ = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64)
+        SLIDE = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64)
+
+        class Trace(ctypes.Structure):  # zso_trace (oracle/zs_oracle.h)
+            _fields_ = [("on_symbol", ctypes.c_void_p), ("on_read", READ), ("on_slide", SLIDE), ("on_block", ctypes.c_void_p), ("on_match", ctypes.c_void_p),
+                        ("user", ctypes.c_void_p)]
+        on_read = READ(lambda user, at, nread, pre, base: reads.append((at, nread, pre, base)))
+        on_slide = SLIDE(lambda user, at, base: slides.append((at, base)))
+        t = Trace(None, on_read, on_slide, None, None, None)
+        cap = len(data) + len(data) // 8 + 1024 + 64 * len(chunks)
+        out = ctypes.create_string_buffer(cap)
+        arr = (ctypes.c_size_t * len(chunks))(*chunks)
+        fl = (ctypes.c_int * len(chunks))(*(flushes or [0] * len(chunks)))
+        fn = self.L.zso_compress_stream_modes
+        fn.restype = ctypes.c_size_t
+        fn.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                       ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
+        n = fn(data, len(data), arr, len(chunks), level, strategy, 0, fl, hash_variant, out, cap, ctypes.cast(ctypes.pointer(t), ctypes.c_void_p))
+        if n == ctypes.c_size_t(-1).value:
+            raise RuntimeError("oracle deflate failed")
+        return out.raw[:n], reads, slides
+
     def adler32(self, data, seed=1):
         return self.L.zso_adler32(seed, bytes(data), len(data))
 
