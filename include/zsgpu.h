@@ -141,6 +141,81 @@ ZS_API int zs_inflate_batch(zs_ctx *ctx, int n, const void *const *in, const int
                             const int64_t *out_cap, int64_t *out_len, int *status);
 
 /* ------------------------------------------------------------------ */
+/* The three containers of a deflate body: zlib (RFC 1950: 2 header bytes, Adler-32), none (RFC 1951: a ZIP entry, an HTTP
+ * "deflate" body as most servers send it), gzip (RFC 1952: a .gz file, a BGZF block, an HTTP "gzip" body). */
+enum { ZS_WRAP_ZLIB = 0, ZS_WRAP_RAW = 1, ZS_WRAP_GZIP = 2 };
+
+/* zs_inflate_batch_device for streams in container `wrap`; that call is this one with ZS_WRAP_ZLIB and in_used == NULL.
+ * ZS_WRAP_RAW: the first block begins at bit 0 of in[i] and the stream ends with its final block's last bit; there is no
+ *   trailer and no checksum, so a stream that ends with output that fits is ZS_STREAM_END whatever follows it.
+ * ZS_WRAP_GZIP: in[i] holds one gzip member (and whatever follows it).  A header kernel reads the members' headers -- FEXTRA,
+ *   FNAME, FCOMMENT and FHCRC, which is verified --, the inflate kernels decode from the body's offset (in[i] itself is what
+ *   they load from, so an aligned buffer keeps its 16-byte loads), one CRC-32 launch runs over the outputs that decoded and
+ *   gathers the trailers, and the host compares CRC-32 and ISIZE (the output's length mod 2^32).  The call waits for the
+ *   stream once more than the zlib call for the headers, and once for the CRCs.
+ * in_used (HOST array, may be NULL): the bytes of in[i] the stream occupies -- header, body up to a whole byte, trailer --,
+ *   which is where the next ZIP entry or gzip member begins; 0 for a failing stream.
+ * status / out_len / the guard behind out_cap / "a stream fails for itself only": as for zs_inflate_batch_device.  A gzip
+ * member adds zlib's messages for its own errors: "incorrect header check" (the magic), "unknown compression method",
+ * "unknown header flags set", "header crc mismatch", "incorrect data check" (the CRC-32), "incorrect length check" (ISIZE)
+ * -- all ZS_DATA_ERROR, out_len 0 for a header's, the whole output for a trailer's -- and ZS_BUF_ERROR "buffer error" for a
+ * member cut short anywhere, header and trailer included.  ZS_STREAM_ERROR: a wrap outside the three, and what
+ * zs_inflate_batch_device rejects. */
+ZS_API int zs_inflate_wrap_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *in_len, void *const *out,
+                                        const int64_t *out_cap, int64_t *out_len, int64_t *in_used, int *status, int wrap,
+                                        void *hip_stream);
+
+/* Upper bound of what zs_deflate_wrap_batch_device writes for n input bytes: zs_deflate_bound(n) + 0, - 6 or + 12.
+ * -1 for a negative n or a wrap outside the three.  Pure host code. */
+ZS_API int64_t zs_wrap_bound(int64_t n, int wrap);
+
+/* zs_deflate_batch_device into container `wrap`; with ZS_WRAP_ZLIB it is that call.  For the two others the zlib streams
+ * are written into a buffer the context owns (zs_deflate_bound(in_len[i]) each, kept until zs_ctx_destroy) and one framing
+ * launch (KC's span copy) moves bytes [2, L - 4) of every stream that fits to out[i]: the compressed
+ * bytes are read and written once more than by the zlib call.  The body is, bit for bit, the reference's NoHeader stream
+ * (Deflate.cs:235-289, 622-634).  ZS_WRAP_GZIP puts 1f 8b 08 00, MTIME 0, XFL (2 at level 9, 4 at level 1, else 0) and OS
+ * 255 in front, and behind the body the CRC-32 of in[i] -- computed by the same launch -- and in_len[i] mod 2^32.
+ * out_len[i]: the bytes written, or, with status[i] == ZS_BUF_ERROR, the bytes out_cap[i] would have had to hold: nothing
+ * is written for such a stream, the others are complete, and nothing is ever written at or behind out[i] + out_cap[i].
+ * Everything else -- arguments, return value, ZS_STREAM_ERROR -- as for zs_deflate_batch_device; the call waits for the
+ * stream once more than that call. */
+ZS_API int zs_deflate_wrap_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *in_len, void *const *out,
+                                        const int64_t *out_cap, int64_t *out_len, int *status, int level, int strategy,
+                                        int hash_variant, int wrap, void *hip_stream);
+
+/* What the first member of a gzip file says, and for a BGZF file (SAM/BAM specification 4.1: every member carries the
+ * subfield SI1 = 66, SI2 = 67, SLEN = 2 with its own size minus one) what the walk over the members' sizes finds. */
+typedef struct zs_gzip_info {
+    int bgzf;            /* the first member carries the BGZF subfield */
+    int xfl, os;         /* the first member's */
+    uint32_t mtime;
+    int64_t n_members;   /* BGZF: members, the empty end-of-file member included; otherwise -1 (only decoding tells) */
+    int64_t name_off, name_len; /* the first member's FNAME without its terminator; 0 / 0: none */
+    int64_t isize_sum;   /* BGZF: the sum of the members' ISIZE words = the decoded length; otherwise -1 */
+} zs_gzip_info;
+
+/* One file in HOST memory, pure host code, no context and no GPU.  ZS_OK and *info; ZS_DATA_ERROR for a first header that is
+ * not gzip's (magic, method, reserved flags, FHCRC) and for a BGZF file whose walk meets a header it cannot read or a member
+ * without the subfield; ZS_BUF_ERROR for a first header cut short and for a BGZF member whose size points past the end of
+ * the file; ZS_STREAM_ERROR for null pointers or a negative len.  Zero bytes behind the last member are stepped over. */
+ZS_API int zs_gzip_file_info(const void *file, int64_t len, zs_gzip_info *info);
+
+/* gzip files to bytes, n files a call: what gzip(1) gives, the members of a file decoded back to back into out[i] (DEVICE
+ * pointer, out_cap[i] bytes).  file[i] / file_len[i]: whole files in HOST memory; they go to the device in one copy.
+ * A BGZF file is walked on the host by its members' sizes: every member of every such file of the call is one stream of one
+ * zs_inflate_wrap_batch_device launch, its place in out[i] the sum of the ISIZE words in front of it; a member whose decoded
+ * length is not its ISIZE fails its file with "incorrect length check".  The other files go in rounds: round r decodes
+ * member r of every file that still has bytes, from where the member before ended, one inflate call a round.  Zero bytes
+ * behind the last member are accepted; anything else there is "incorrect header check".
+ * out_len[i]: the bytes decoded, for a failing file those of the members in front of the one that failed (BGZF: in front of
+ * the first that failed).  n_members (HOST, may be NULL): members decoded.  status[i] (may be NULL): ZS_OK, or the failing
+ * member's code; a file fails for itself only, and zs_ctx_last_error names the first failing file and the reason.
+ * Returns ZS_OK, the first failing file's code, ZS_MEM_ERROR, or, before any device work, ZS_STREAM_ERROR: null context,
+ * n < 0, null arrays or pointers, a negative length or capacity, a file or capacity above 2 GiB - 1 KiB. */
+ZS_API int zs_gzip_decode_files_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, void *const *out,
+                                      const int64_t *out_cap, int64_t *out_len, int *n_members, int *status, void *hip_stream);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU batch entry points (SURVEY.md 8(b) "zs_deflate_batch(..., device_mask)", 8(e)): the n independent
  * buffers are partitioned over n_ctx contexts -- normally one per GPU of the node, zs_ctx_create(0 .. count-1) --
  * by size (longest-processing-time, zs_partition), each context's share runs on its own host thread through the

@@ -24,6 +24,7 @@ SYMBOLS = [
     "zs_png_pack_batch_device", "zs_png_survey_batch_device", "zs_png_choose_format", "zs_png_encode_rgba_batch_device",
     "zs_png_anim_info", "zs_png_compose_batch_device", "zs_png_decode_anim_batch",
     "zs_png_diff_batch_device", "zs_png_crop_batch_device", "zs_png_anim_bound", "zs_png_encode_anim_batch_device",
+    "zs_wrap_bound", "zs_deflate_wrap_batch_device", "zs_inflate_wrap_batch_device", "zs_gzip_file_info", "zs_gzip_decode_files_batch",
 ]
 
 
@@ -31,6 +32,11 @@ class PngInfo(ctypes.Structure):  # zs_png_info
     _fields_ = [("width", ctypes.c_int64), ("height", ctypes.c_int64), ("bit_depth", ctypes.c_int), ("color_type", ctypes.c_int),
                 ("interlace", ctypes.c_int), ("bits_per_pixel", ctypes.c_int), ("idat_bytes", ctypes.c_int64),
                 ("pixel_bytes", ctypes.c_int64), ("n_idat", ctypes.c_int64)]
+
+
+class GzipInfo(ctypes.Structure):  # zs_gzip_info
+    _fields_ = [("bgzf", ctypes.c_int), ("xfl", ctypes.c_int), ("os", ctypes.c_int), ("mtime", ctypes.c_uint32),
+                ("n_members", ctypes.c_int64), ("name_off", ctypes.c_int64), ("name_len", ctypes.c_int64), ("isize_sum", ctypes.c_int64)]
 
 
 class PngSurvey(ctypes.Structure):  # zs_png_survey
@@ -216,5 +222,16 @@ def lib():
         L.zs_png_encode_anim_batch_device.restype = i32
         L.zs_png_encode_anim_batch_device.argtypes = [vp, i32, P(vp), P(i32), P(i64), P(i64), i32, P(P(i32)), P(P(i32)), P(i32), P(i32), P(i32), P(vp), P(i64),
                                                       i64, i64, P(vp), P(i64), P(i64), P(i32), P(P(PngFrame)), P(i32), P(i32), i32, i32, i32, vp]
+    if hasattr(L, "zs_inflate_wrap_batch_device"):  # (an older build selected with ZS_LIB for an A/B run lacks the containers)
+        L.zs_wrap_bound.restype = i64
+        L.zs_wrap_bound.argtypes = [i64, i32]
+        L.zs_deflate_wrap_batch_device.restype = i32
+        L.zs_deflate_wrap_batch_device.argtypes = batch_args + [i32, vp]
+        L.zs_inflate_wrap_batch_device.restype = i32
+        L.zs_inflate_wrap_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(vp), P(i64), P(i64), P(i64), P(i32), i32, vp]
+        L.zs_gzip_file_info.restype = i32
+        L.zs_gzip_file_info.argtypes = [vp, i64, P(GzipInfo)]
+        L.zs_gzip_decode_files_batch.restype = i32
+        L.zs_gzip_decode_files_batch.argtypes = [vp, i32, P(vp), P(i64), P(vp), P(i64), P(i64), P(i32), P(i32), vp]
     _lib = L
     return L

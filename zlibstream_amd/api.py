@@ -1269,6 +1269,97 @@ def png_encode_anim_batch_device(engine, canvas_ptrs, n_frames, widths, heights,
     return list(out_len), list(ct), list(bd), frames
 
 
+WRAP_ZLIB, WRAP_RAW, WRAP_GZIP = 0, 1, 2  # ZS_WRAP_*: RFC 1950, RFC 1951 (no container), RFC 1952
+
+
+def wrap_bound(n, wrap):
+    """zs_wrap_bound (host code): room that deflate_wrap_batch_device needs for n input bytes in container `wrap`."""
+    r = _native.lib().zs_wrap_bound(int(n), int(wrap))
+    if r < 0:
+        raise ValueError("wrap_bound: a negative length or an unknown container")
+    return r
+
+
+def deflate_wrap_batch_device(engine, in_ptrs, in_lens, out_ptrs, out_caps, wrap, level=6, strategy=0, hash_variant=0, stream=None):
+    """Device-resident buffers into zlib, raw deflate or gzip streams (zs_deflate_wrap_batch_device; WRAP_ZLIB is
+    deflate_batch_device).  Returns (code, lengths, per-stream codes): -5 (ZS_BUF_ERROR) for a stream whose capacity was too
+    small -- its length is then what it needs, nothing is written for it and the others are complete."""
+    n = len(in_ptrs)
+    if not (len(in_lens) == len(out_ptrs) == len(out_caps) == n):
+        raise ValueError("deflate_wrap_batch_device: the argument lists differ in length")
+    if wrap not in (WRAP_ZLIB, WRAP_RAW, WRAP_GZIP):
+        raise ValueError("deflate_wrap_batch_device: an unknown container")
+    if n == 0:
+        return 0, [], []
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    rc = _native.lib().zs_deflate_wrap_batch_device(engine.handle, n, VP(*[int(p) for p in in_ptrs]), I64(*[int(x) for x in in_lens]),
+                                                    VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, status,
+                                                    int(level), int(strategy), int(hash_variant), int(wrap), ctypes.c_void_p(stream or 0))
+    if rc not in (0, -5):
+        raise ZlibStreamException("deflating: " + engine.last_error())
+    return rc, list(out_len), list(status)
+
+
+def inflate_wrap_batch_device(engine, in_ptrs, in_lens, out_ptrs, out_caps, wrap, stream=None):
+    """Device-resident zlib, raw deflate or gzip streams to bytes (zs_inflate_wrap_batch_device).  Nothing is raised for a
+    failing stream: returns (code, output lengths, bytes of input each stream occupies -- 0 for a failing one --, per-stream
+    codes: 1 is ZS_STREAM_END); engine.last_error() is the first failing stream's message."""
+    n = len(in_ptrs)
+    if not (len(in_lens) == len(out_ptrs) == len(out_caps) == n):
+        raise ValueError("inflate_wrap_batch_device: the argument lists differ in length")
+    if wrap not in (WRAP_ZLIB, WRAP_RAW, WRAP_GZIP):
+        raise ValueError("inflate_wrap_batch_device: an unknown container")
+    if n == 0:
+        return 0, [], [], []
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, in_used, status = I64(), I64(), I32()
+    rc = _native.lib().zs_inflate_wrap_batch_device(engine.handle, n, VP(*[int(p) for p in in_ptrs]), I64(*[int(x) for x in in_lens]),
+                                                    VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, in_used,
+                                                    status, int(wrap), ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError("zs_inflate_wrap_batch_device failed: " + engine.last_error())
+    return rc, list(out_len), list(in_used), list(status)
+
+
+_GZIP_INFO_FIELDS = ("bgzf", "xfl", "os", "mtime", "n_members", "name_off", "name_len", "isize_sum")
+
+
+def gzip_file_info(data):
+    """zs_gzip_file_info (host code, no GPU, no engine): a dict of bgzf, xfl, os, mtime, name_off, name_len -- the first
+    member's -- and n_members, isize_sum (both -1 unless the file is BGZF).  ZlibStreamException for a file whose first header
+    is not gzip's or is cut short, and for a BGZF file whose members' sizes do not walk to its end."""
+    data = bytes(data)
+    info = _native.GzipInfo()
+    rc = _native.lib().zs_gzip_file_info(data, len(data), ctypes.byref(info))
+    if rc != 0:
+        raise ZlibStreamException("gzip_file_info: not a whole gzip file (%d)" % rc)
+    return {k: int(getattr(info, k)) for k in _GZIP_INFO_FIELDS}
+
+
+def gzip_decode_files_batch(engine, files, out_ptrs, out_caps, stream=None):
+    """gzip files (bytes objects in host memory) -> their decoded bytes in device buffers, the members of a file back to
+    back, many files a call (zs_gzip_decode_files_batch).  Returns (statuses, lengths, member counts): status 0, or the
+    failing member's code (-3 ZS_DATA_ERROR, -5 ZS_BUF_ERROR); engine.last_error() names the first failing file."""
+    n = len(files)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("gzip_decode_files_batch: the argument lists differ in length")
+    if any(not o or int(cap) < 0 for o, cap in zip(out_ptrs, out_caps)):
+        raise ValueError("gzip_decode_files_batch: non-null device pointers and non-negative capacities are required")
+    if n == 0:
+        return [], [], []
+    files = [bytes(f) for f in files]
+    keep = [ctypes.create_string_buffer(f, len(f)) if f else ctypes.create_string_buffer(1) for f in files]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, members, status = I64(), I32(), I32()
+    rc = _native.lib().zs_gzip_decode_files_batch(engine.handle, n, VP(*[ctypes.addressof(k) for k in keep]), I64(*[len(f) for f in files]),
+                                                  VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, members, status,
+                                                  ctypes.c_void_p(stream or 0))
+    if rc not in (0, -3, -5):
+        raise ValueError("zs_gzip_decode_files_batch failed (%d): %s" % (rc, engine.last_error()))
+    return list(status), list(out_len), list(members)
+
+
 _default_engine = None
 
 

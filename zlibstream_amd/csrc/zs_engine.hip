@@ -1,6 +1,6 @@
 // zs_engine.hip -- host side of the MI355X deflate engine: workspace, kernel
 // pipeline, and the C ABI of include/zsgpu.h (the PNG and CRC-32 calls of it:
-// zs_png_host.inc).  No CPU fallback: without a usable HIP device every
+// zs_png_host.inc; raw deflate, gzip members and gzip files: zs_wrap_host.inc).  No CPU fallback: without a usable HIP device every
 // compressing entry point fails.
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -19,6 +20,7 @@
 #include "zs_inflate_tok.hip"
 #include "zs_png.hip"
 #include "zs_crc32.hip"
+#include "zs_gzip.hip"
 #include "zs_plan.h"
 
 using namespace zs;
@@ -43,7 +45,10 @@ const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "
 enum PngBuf {
     kBufPngImg, kBufPngSeg, kBufPngCtr, kBufPngFimg, kBufPngScratch, kBufPngA7img, kBufPngInflated, kBufPngPasses, kBufCrcDesc, kBufCrcRes, kBufPngZs, kBufPngGather,
     kBufPngXimg, kBufPngRaw, kBufPngSimg, kBufPngSplit, kBufPngGimg, kBufPngVimg, kBufPngVrec, kBufPngPacked, kBufPngCimg, kBufPngFrames, kBufPngDimg, kBufPngDrec,
-    kBufPngKimg, kBufPngCrop, kBufPngCount
+    kBufPngKimg, kBufPngCrop,
+    // the container calls (zs_wrap_host.inc): the members' descriptors and heads, the trailers gathered for the host, the zlib
+    // streams in front of the framing launch, a call's files
+    kBufWrapHead, kBufWrapGather, kBufWrapZs, kBufWrapFiles, kBufPngCount
 };
 
 struct PlanCache;  // the last deflate call's plan, kept for a same-shaped call (below, ahead of run_pipeline)
@@ -1528,11 +1533,28 @@ const char *const kInfMessages[kInfMsgCount] = {
     "oversubscribed dynamic bit lengths tree", "incomplete dynamic bit lengths tree", "oversubscribed literal/length tree",
     "incomplete literal/length tree", "oversubscribed distance tree", "incomplete distance tree", "empty distance tree with lengths",
     "invalid literal/length code", "invalid distance code", "buffer error", "buffer error", "incorrect data check"};
+// the messages of a gzip member's own errors (zlib's, inflate.c), numbered on from the stream's
+const char *const kGzipMessages[kInfMsgAll - kInfMsgCount] = {"unknown header flags set", "header crc mismatch", "incorrect length check"};
+const char *inf_message(int m) { return m < kInfMsgCount ? kInfMessages[m] : kGzipMessages[m - kInfMsgCount]; }
+
+// The container of an inflate call's streams (zs_inflate_wrap_batch_device).  body_off == nullptr: zlib streams.  Otherwise
+// stream i's first block begins at byte body_off[i] and its last block ends it: no Adler-32 is read or computed.  in_used
+// (may be null): the bytes of in[i] up to the stream's end, the Adler-32 included where there is one; 0 for a failing stream.
+struct InfWrap {
+    const int32_t *body_off = nullptr;
+    int64_t *in_used = nullptr;
+    int *msg = nullptr;  // (may be null) InfMsg of every failing stream, 0 for the others
+};
 
 bool run_inflate_seq(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out, const int64_t *out_cap,
-                 int64_t *out_len, int *status, hipStream_t stream, uint32_t *adler_out = nullptr, int *msg_out = nullptr) {
+                 int64_t *out_len, int *status, hipStream_t stream, uint32_t *adler_out = nullptr, int *msg_out = nullptr,
+                 const InfWrap &wrap = InfWrap()) {
+    const bool raw = wrap.body_off != nullptr;
     std::vector<InfDesc> d((size_t)n);
-    for (int i = 0; i < n; i++) d[(size_t)i] = {(const uint8_t *)in[i], (uint8_t *)out[i], in_len[i], out_cap[i]};
+    for (int i = 0; i < n; i++) {
+        d[(size_t)i] = {(const uint8_t *)in[i], (uint8_t *)out[i], in_len[i], out_cap[i]};
+        if (raw) d[(size_t)i].body_off = wrap.body_off[i], d[(size_t)i].raw = 1;
+    }
     if (!ensure(c, c->inf_desc, sizeof(InfDesc) * (size_t)n) || !ensure(c, c->inf_state, sizeof(InfState) * (size_t)n)) return false;
     std::vector<InfState> st((size_t)n);
     ZS_HIP(c, hipMemcpyAsync(c->inf_desc.p, d.data(), sizeof(InfDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
@@ -1557,7 +1579,7 @@ bool run_inflate_seq(zs_ctx *c, int n, const void *const *in, const int64_t *in_
     std::vector<int64_t> alen;
     std::vector<int> aidx;
     for (int i = 0; i < n; i++)
-        if (st[(size_t)i].status == ZS_STREAM_END) abuf.push_back(out[i]), alen.push_back(st[(size_t)i].out_len), aidx.push_back(i);
+        if (st[(size_t)i].status == ZS_STREAM_END && !raw) abuf.push_back(out[i]), alen.push_back(st[(size_t)i].out_len), aidx.push_back(i);
     if (c->inf_probe == nullptr && n == 1) c->inf_used.assign(1, st[0].status == ZS_STREAM_END ? st[0].in_used : 0);
     std::vector<uint32_t> ads(abuf.size(), 1u);
     if (!device_adlers(c, (int)abuf.size(), abuf.data(), alen.data(), nullptr, ads.data(), nullptr, stream)) return false;
@@ -1572,6 +1594,7 @@ bool run_inflate_seq(zs_ctx *c, int n, const void *const *in, const int64_t *in_
         const int code = st[(size_t)i].status;
         if (status) status[i] = code;
         if (msg_out) msg_out[i] = st[(size_t)i].msg;
+        if (wrap.in_used) wrap.in_used[i] = code == ZS_STREAM_END ? st[(size_t)i].in_used : 0;
         if (code != ZS_STREAM_END) {
             if (all_ok) c->err = kInfMessages[st[(size_t)i].msg];
             all_ok = false;
@@ -1608,8 +1631,10 @@ constexpr int64_t kParMinInput = 1024;
 // Block-parallel path for the streams listed in `idx`; streams it cannot handle are appended to `rest`.
 bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *in, const int64_t *in_len, void *const *out,
                      const int64_t *out_cap, int64_t *out_len, int *status, hipStream_t stream, std::vector<int> &rest,
-                     uint32_t *adler_out = nullptr, int *msg_out = nullptr) {
+                     uint32_t *adler_out = nullptr, int *msg_out = nullptr, const InfWrap &wrap = InfWrap()) {
     const int m = (int)idx.size();
+    const bool raw = wrap.body_off != nullptr;
+    const int64_t trailer = raw ? 0 : 4;  // bytes of the stream behind its last block
     c->inf_lane_streams = 0;
     c->inf_wave_streams = 0;
     if (m == 0) return true;
@@ -1628,6 +1653,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
         nblk += p.max_blk;
         p.cell_off = ncells;
         p.fx_off = (int32_t)nfx, p.fx_regions = (int32_t)(in_len[i] * 8 / kFxRegionBits + 1);
+        p.body_off = raw ? wrap.body_off[i] : 2, p.raw = raw ? 1 : 0;
         nfx += p.fx_regions;
         if (c->inf_probe) p.out_cap = (int64_t)0x7FFFFFFF - 1024;  // a probing call decodes nothing: any output size is fine
         else ncells += (out_cap[i] + 63) & ~63LL;
@@ -1866,7 +1892,7 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
         const int i = idx[(size_t)j];
         const ParState &q = st[(size_t)j];
         const int64_t tb = (q.end_bit + 7) >> 3;
-        if (!q.ok || bfail[(size_t)j] || tb + 4 > in_len[i]) {
+        if (!q.ok || bfail[(size_t)j] || tb + trailer > in_len[i]) {
             rest.push_back(i);  // not decodable here, or truncated: the sequential decoder classifies it
             c->inf_wave_streams++;
             continue;
@@ -1874,13 +1900,14 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
         abuf.push_back(out[i]), alen.push_back(q.out_len), atr.push_back((const uint8_t *)in[i] + tb), aidx.push_back(j);
     }
     std::vector<uint32_t> ads(abuf.size(), 1u);
-    std::vector<int> aok(abuf.size(), 0);
-    if (!device_adlers(c, (int)abuf.size(), abuf.data(), alen.data(), atr.data(), ads.data(), aok.data(), stream)) return false;
+    std::vector<int> aok(abuf.size(), raw ? 1 : 0);  // (a stream without an Adler-32 has none to compute or compare)
+    if (!raw && !device_adlers(c, (int)abuf.size(), abuf.data(), alen.data(), atr.data(), ads.data(), aok.data(), stream)) return false;
     for (size_t k = 0; k < aidx.size(); k++) {
         const int j = aidx[k], i = idx[(size_t)j];
         out_len[i] = st[(size_t)j].out_len;
         status[i] = ZS_STREAM_END;
         if (m == 1) c->inf_used.assign(1, ((st[(size_t)j].end_bit + 7) >> 3) + 4);
+        if (wrap.in_used) wrap.in_used[i] = aok[k] ? ((st[(size_t)j].end_bit + 7) >> 3) + trailer : 0;
         if (adler_out) adler_out[i] = ads[k];
         if (!aok[k]) {
             status[i] = ZS_DATA_ERROR;
@@ -1891,13 +1918,18 @@ bool run_inflate_par(zs_ctx *c, const std::vector<int> &idx, const void *const *
     return true;
 }
 
+// One gzip member per in[i] (zs_wrap_host.inc): header kernel, raw inflate from the body's offset, KC, the trailers' compare.
+bool inflate_gzip_members(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out, const int64_t *out_cap,
+                          int64_t *out_len, int64_t *in_used, int *status, int *msg, hipStream_t stream);
+
 bool run_inflate(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out, const int64_t *out_cap,
-                 int64_t *out_len, int *status, hipStream_t stream, uint32_t *adler_out = nullptr) {
+                 int64_t *out_len, int *status, hipStream_t stream, uint32_t *adler_out = nullptr, const InfWrap &wrap = InfWrap()) {
     std::vector<int> par, seq;
     static const int64_t par_min = getenv("ZS_INF_PAR_MIN") ? atoll(getenv("ZS_INF_PAR_MIN")) : kParMinInput;
     for (int i = 0; i < n; i++) (in_len[i] >= par_min ? par : seq).push_back(i);
     std::vector<int> st((size_t)n, 0), msg((size_t)n, -1);
-    if (!run_inflate_par(c, par, in, in_len, out, out_cap, out_len, st.data(), stream, seq, adler_out, msg.data())) return false;
+    if (wrap.in_used) std::fill(wrap.in_used, wrap.in_used + n, (int64_t)0);
+    if (!run_inflate_par(c, par, in, in_len, out, out_cap, out_len, st.data(), stream, seq, adler_out, msg.data(), wrap)) return false;
     bool ok = true;
     for (int i : par)
         if (std::find(seq.begin(), seq.end(), i) == seq.end() && st[(size_t)i] != ZS_STREAM_END) ok = false;
@@ -1909,8 +1941,18 @@ bool run_inflate(zs_ctx *c, int n, const void *const *in, const int64_t *in_len,
         std::vector<int> sst((size_t)m), smsg((size_t)m, -1);
         std::vector<uint32_t> sad((size_t)m, 1u);
         for (int j = 0; j < m; j++) sin[(size_t)j] = in[seq[(size_t)j]], sout[(size_t)j] = out[seq[(size_t)j]], slen[(size_t)j] = in_len[seq[(size_t)j]], scap[(size_t)j] = out_cap[seq[(size_t)j]];
-        if (!run_inflate_seq(c, m, sin.data(), slen.data(), sout.data(), scap.data(), solen.data(), sst.data(), stream, sad.data(), smsg.data())) ok = false;
+        // (the container goes along in the one-wave decoder's order)
+        std::vector<int32_t> sbody;
+        std::vector<int64_t> sused((size_t)m, 0);
+        InfWrap swrap;
+        if (wrap.body_off) {
+            for (int j = 0; j < m; j++) sbody.push_back(wrap.body_off[seq[(size_t)j]]);
+            swrap.body_off = sbody.data();
+        }
+        if (wrap.in_used) swrap.in_used = sused.data();
+        if (!run_inflate_seq(c, m, sin.data(), slen.data(), sout.data(), scap.data(), solen.data(), sst.data(), stream, sad.data(), smsg.data(), swrap)) ok = false;
         for (int j = 0; j < m; j++) {
+            if (wrap.in_used) wrap.in_used[seq[(size_t)j]] = sused[(size_t)j];
             out_len[seq[(size_t)j]] = solen[(size_t)j], st[(size_t)seq[(size_t)j]] = sst[(size_t)j], msg[(size_t)seq[(size_t)j]] = smsg[(size_t)j];
             if (adler_out) adler_out[seq[(size_t)j]] = sad[(size_t)j];
         }
@@ -1923,19 +1965,22 @@ bool run_inflate(zs_ctx *c, int n, const void *const *in, const int64_t *in_len,
             break;
         }
     if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
+    if (wrap.msg)
+        for (int i = 0; i < n; i++) wrap.msg[i] = st[(size_t)i] != ZS_STREAM_END && msg[(size_t)i] > 0 ? msg[(size_t)i] : 0;
     return ok;
 }
 }  // namespace
 
 extern "C" {
 
-int zs_inflate_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out,
-                            const int64_t *out_cap, int64_t *out_len, int *status, void *hip_stream) {
-    if (!c || n < 0) return ZS_STREAM_ERROR;
+int zs_inflate_wrap_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out,
+                                 const int64_t *out_cap, int64_t *out_len, int64_t *in_used, int *status, int wrap, void *hip_stream) {
+    if (!c || n < 0 || wrap < ZS_WRAP_ZLIB || wrap > ZS_WRAP_GZIP) return ZS_STREAM_ERROR;
     if (n == 0) return ZS_OK;
     // what the caller sees if anything fails before the results are known (as run_pipeline does for deflate)
     for (int i = 0; i < n; i++) {
         out_len[i] = 0;
+        if (in_used) in_used[i] = 0;
         if (status) status[i] = ZS_STREAM_ERROR;
     }
     for (int i = 0; i < n; i++)
@@ -1946,12 +1991,26 @@ int zs_inflate_batch_device(zs_ctx *c, int n, const void *const *in, const int64
     if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     std::vector<int> st((size_t)n, ZS_STREAM_ERROR);
-    bool ok = run_inflate(c, n, in, in_len, out, out_cap, out_len, st.data(), s);
+    InfWrap wr;
+    wr.in_used = in_used;
+    std::vector<int32_t> body;
+    bool ok;
+    if (wrap == ZS_WRAP_GZIP) {
+        ok = inflate_gzip_members(c, n, in, in_len, out, out_cap, out_len, in_used, st.data(), nullptr, s);
+    } else {
+        if (wrap == ZS_WRAP_RAW) body.assign((size_t)n, 0), wr.body_off = body.data();
+        ok = run_inflate(c, n, in, in_len, out, out_cap, out_len, st.data(), s, nullptr, wr);
+    }
     if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
     if (ok) return ZS_OK;
     for (int v : st)
         if (v != ZS_STREAM_END) return v == ZS_OK ? ZS_STREAM_ERROR : v;
     return ZS_STREAM_ERROR;
+}
+
+int zs_inflate_batch_device(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out,
+                            const int64_t *out_cap, int64_t *out_len, int *status, void *hip_stream) {
+    return zs_inflate_wrap_batch_device(c, n, in, in_len, out, out_cap, out_len, nullptr, status, ZS_WRAP_ZLIB, hip_stream);
 }
 
 int zs_inflate_batch(zs_ctx *c, int n, const void *const *in, const int64_t *in_len, void *const *out, const int64_t *out_cap,
@@ -1998,6 +2057,7 @@ int zs_inflate_batch(zs_ctx *c, int n, const void *const *in, const int64_t *in_
 }  // extern "C"
 
 #include "zs_png_host.inc"
+#include "zs_wrap_host.inc"
 
 // ------------------------------------------------------------------ multi-GPU batch entry points
 // BASELINE north_star: "independent input buffers shard embarrassingly across the 8 GPUs of one node (no RCCL needed)".

@@ -21,6 +21,9 @@ enum InfMsg {
     kInfTooManySyms, kInfBadRepeat, kInfOverBl, kInfIncompleteBl, kInfOverLit, kInfIncompleteLit, kInfOverDist, kInfIncompleteDist,
     kInfEmptyDist, kInfBadLitCode, kInfBadDistCode, kInfTruncated, kInfOutputFull, kInfBadCheck, kInfMsgCount
 };
+// ... and a gzip member's own, which no kernel of this file reports (zs_gzip.h; the trailer's ISIZE): they number on from the
+// stream's, and the host keeps their texts beside kInfMessages (inf_message)
+enum { kInfBadFlags = kInfMsgCount, kInfBadHeaderCrc, kInfBadLength, kInfMsgAll };
 
 struct InfDesc {
     const uint8_t *in;
@@ -34,6 +37,11 @@ struct InfDesc {
     const uint8_t *hist;
     int64_t start_bit;
     int32_t hist_have, partial;
+    // The container (zs_inflate_wrap_batch_device).  raw == 0: a zlib stream, header at byte 0, Adler-32 behind the last block.
+    // raw != 0: the first block begins at byte body_off -- 0 for a raw deflate stream, behind the header for a gzip member; `in`
+    // stays the member's first byte, so that an aligned buffer keeps its 16-byte loads -- and the stream ends with the last
+    // block's last bit: whatever follows (a gzip trailer, the next member) is the host's to read, InfState::in_used says where.
+    int32_t body_off, raw;
 };
 struct InfState {
     int64_t out_len, in_used;
@@ -260,6 +268,9 @@ __global__ __launch_bounds__(64) void zs_inflate_kernel(const InfDesc *descs, In
         b.pos = d.start_bit >> 3;
         b.fill();
         b.drop((int)(d.start_bit & 7));
+    } else if (d.raw) {  // no zlib header: a block begins at byte body_off
+        b.pos = d.body_off < d.in_len ? d.body_off : d.in_len;
+        good_bits = 8 * b.pos;
     } else {
     b.fill();
     if (d.in_len < 2) INF_FAIL(ZS_BUF_, kInfTruncated);
@@ -441,6 +452,11 @@ __global__ __launch_bounds__(64) void zs_inflate_kernel(const InfDesc *descs, In
     }
     // Adler-32 trailer (Inflate.cs:300-345): compared on the host against the device-computed checksum
     b.drop(b.cnt & 7);
+    if (d.raw) {  // the stream ends with its last block; in_used is the byte behind it
+        if (b.bad) INF_FAIL(ZS_BUF_, kInfTruncated);
+        status = ZS_END_, good_bits = 8 * b.pos - b.cnt, good_out = pos;
+        goto done;
+    }
     b.fill();
     if (b.cnt < 32) INF_FAIL(ZS_BUF_, kInfTruncated);
     {

@@ -14,7 +14,7 @@
 //               kept as tokens (zs_inflate_tok.hip); a block whose tokens found no room -- fewer
 //               than 4 bits per symbol: zeros, sparse rows, image data -- keeps a checkpoint
 //               (bit, output position) per subsequence instead.
-//   C  chain    one wave per stream walks from the real first block (bit 16) through the
+//   C  chain    one wave per stream walks from the real first block (bit 16 of a zlib stream) through the
 //               candidates (end of block i = start of block i+1); blocks the finder cannot
 //               see (stored / fixed) are measured on the spot.  Output offsets follow.
 //   D2 decode   into 16-bit cells: a literal byte, or a marker 0x8000 | i for "byte i of the 32 KiB
@@ -59,7 +59,19 @@ struct ParStream {
     int32_t blk_off, max_blk;     // chain blocks
     int64_t cell_off;             // u16 cells of this stream's output
     int32_t fx_off, fx_regions;   // fixed-code blocks found ahead of the walk (zs_inf_fixed_scan_kernel): the stream's regions in the table
+    // the container, as in InfDesc: the first block begins at byte body_off (2 behind a zlib header, which is checked when raw == 0;
+    // 0 for a raw stream, behind the header for a gzip member), and with raw != 0 nothing of the stream follows its last block
+    int32_t body_off, raw;
 };
+// a stream's first block header, and the fewest bytes a stream with a block has (a zlib stream: header, a block, the Adler-32)
+__device__ __forceinline__ int64_t par_first_bit(const ParStream &s) { return 8 * (int64_t)s.body_off; }
+__device__ __forceinline__ int64_t par_min_len(const ParStream &s) { return (int64_t)s.body_off + (s.raw ? 1 : 4); }
+// zlib header (Inflate.cs:120-170): anything unusual is the one-wave decoder's to classify
+__device__ __forceinline__ bool par_header_ok(const ParStream &s) {
+    if (s.in_len < par_min_len(s)) return false;
+    if (s.raw) return true;
+    return (s.in[0] & 0x0F) == 8 && (s.in[0] >> 4) <= 7 && (((unsigned)s.in[0] << 8) + s.in[1]) % 31 == 0 && !(s.in[1] & 0x20);
+}
 struct ParCand {
     int64_t bit;       // block header bit offset
     int64_t end_bit;   // bit offset after the block's EOB
@@ -573,7 +585,8 @@ __global__ __launch_bounds__(256) void zs_inf_prefilter_kernel(const ParStream *
         m &= ~(sh(4) & sh(5) & sh(6) & sh(7));
         m &= ~(sh(9) & sh(10) & sh(11) & sh(12));
         const int64_t base = byte0 * 8 + j * 32;
-        if (base < 16) m &= ~((1u << (16 - base)) - 1u);         // the zlib header is no block
+        const int64_t first = 8 * (int64_t)s.body_off;           // the container's header is no block
+        if (base < first) m = first - base >= 32 ? 0u : m & ~((1u << (first - base)) - 1u);
         const int64_t last = s.in_len * 8 - 17 - base;            // last offset with 17 header bits inside the stream
         if (last < 31) m = last < 0 ? 0u : m & ((2u << last) - 1u);
         // Second test, one passing offset per trip (a wave goes round as often as its fullest lane needs): the bit-length code
@@ -737,7 +750,7 @@ static_assert(sizeof(InfTables) % 16 == 0 && sizeof(LaneTabs) % 16 == 0 && offse
 // The chain of a stream's blocks without the walk, for the stream whose blocks the finder has all reported (dynamic blocks:
 // everything this library's own deflate writes at levels >= 1 on text): every measured candidate looks up the candidate
 // that starts where it ends (binary search over the sorted header offsets, in LDS), the candidates reachable from the one
-// at bit 16 are marked by pointer doubling (15 rounds for <= 16 Ki candidates), and since a block starts after the one
+// at the stream's first block are marked by pointer doubling (15 rounds for <= 16 Ki candidates), and since a block starts after the one
 // before it, the chain's order is the candidates' order: block numbers and output offsets are prefix sums over the marked
 // ones.  Anything else -- a block the finder did not report, a measure that failed, too many candidates -- leaves
 // nblk = -1 and zs_inf_chain_kernel walks the stream as before.
@@ -757,9 +770,8 @@ __global__ __launch_bounds__(1024) void zs_inf_chain_par_kernel(const ParStream 
     if (!ss.ok) return;
     const int n = ss.ncand, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const ParCand *cd = cands + s.cand_off;
-    bool can = n >= 1 && n <= kChainParMax && s.in_len >= 6 && s.in_len < ((int64_t)1 << 28);
-    // zlib header (Inflate.cs:120-170): anything unusual is the walking kernel's to classify
-    if (can && ((s.in[0] & 0x0F) != 8 || (s.in[0] >> 4) > 7 || (((unsigned)s.in[0] << 8) + s.in[1]) % 31 != 0 || (s.in[1] & 0x20))) can = false;
+    // (anything unusual in the header is the walking kernel's to classify)
+    const bool can = n >= 1 && n <= kChainParMax && s.in_len < ((int64_t)1 << 28) && par_header_ok(s);
     if (!can) {
         if (tid == 0) ss.nblk = -1;
         return;
@@ -786,7 +798,7 @@ __global__ __launch_bounds__(1024) void zs_inf_chain_par_kernel(const ParStream 
         }
         jump[i] = nx;
     }
-    if (tid == 0 && !(bits[0] == 16u && cd[0].ok)) bad = 1;  // the first block starts behind the 2-byte header
+    if (tid == 0 && !(bits[0] == (uint32_t)par_first_bit(s) && cd[0].ok)) bad = 1;  // the first block starts behind the header
     if (bad) sh_fail = 1;
     __syncthreads();
     if (sh_fail) {
@@ -1048,13 +1060,14 @@ __global__ __launch_bounds__(64) void zs_inf_fixed_scan_kernel(const ParStream *
     if (!st[w.x].ok || st[w.x].nblk >= 1) return;  // (no chain to make, or zs_inf_chain_par_kernel has made it)
     // (a stream of fixed blocks begins with one: a stream whose blocks do not chain for another reason -- the empty stored blocks of
     // flush markers -- is not decoded as fixed code on a guess, 3.5 ms per call for nothing)
-    if (s.in_len < 3 || ((s.in[2] >> 1) & 3u) != 1u) return;
+    const int64_t first = par_first_bit(s);
+    if (s.in_len < s.body_off + 1 || ((s.in[s.body_off] >> 1) & 3u) != 1u) return;
     const int64_t nbits = s.in_len * 8, r_lo = (int64_t)w.y * kFxRegionBits, r_hi = r_lo + kFxRegionBits;
     // The guess lies a region's length in front of the region (two or three blocks): a decoder that begins in the middle of a
     // symbol may take bits for an end-of-block code before it is in step -- what follows is then no header -- but the decode
     // from any position ends at a true end-of-block once it is in step, and everything behind that is true.  `pseudo`: pos is a
     // position symbols are decoded from on trust, not a header.
-    int64_t pos = w.y == 0 ? 16 : (r_lo - kFxRegionBits > 16 ? r_lo - kFxRegionBits : 19);
+    int64_t pos = w.y == 0 ? first : (r_lo - kFxRegionBits > first ? r_lo - kFxRegionBits : first + 3);
     bool pseudo = w.y != 0;
     int n = 0;
     for (int budget = 96; budget > 0 && n < kFxEntries && pos < r_hi && pos + 3 <= nbits; budget--) {
@@ -1090,10 +1103,10 @@ __global__ __launch_bounds__(64) void zs_inf_chain_kernel(const ParStream *ps, P
     const ParCand *cd = cands + s.cand_off;
     ParBlock *bl = blocks + s.blk_off;
     const int ncand = ss.ncand;
-    int64_t cur = 16, out = 0;
+    int64_t cur = par_first_bit(s), out = 0;
     int nb = 0, ok = 1, ci = 0;
-    // zlib header (Inflate.cs:120-170): anything unusual goes to the sequential decoder, which reports it
-    if (s.in_len < 6 || (s.in[0] & 0x0F) != 8 || (s.in[0] >> 4) > 7 || (((unsigned)s.in[0] << 8) + s.in[1]) % 31 != 0 || (s.in[1] & 0x20)) ok = 0;
+    // anything unusual in the header goes to the sequential decoder, which reports it
+    if (!par_header_ok(s)) ok = 0;
     InfBits b{s.in, s.in_len, 0, 0, 0, false, L.ibuf, -1};
     // The walk is one dependency chain over the stream's blocks; its candidates come 64 at a time into the lanes'
     // registers (lane l holds candidate cbase + l) and are read with wave-uniform shuffles, so that a step is not a chain

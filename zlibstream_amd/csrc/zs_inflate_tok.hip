@@ -442,7 +442,7 @@ __global__ __launch_bounds__(64) void zs_inf_measure_tok_kernel(const ParStream 
     ParCand &c = cands[s.cand_off + w.y];
     const int lane = threadIdx.x;
     const int64_t cbit = c.bit, nbits = s.in_len * 8;
-    if (!st[w.x].ok || cbit < 16 || cbit + 17 > nbits) {  // (not a header offset of this stream: nothing is read through it)
+    if (!st[w.x].ok || cbit < 8 * (int64_t)s.body_off || cbit + 17 > nbits) {  // (not a header offset of this stream: nothing is read through it)
         if (lane == 0) c.ok = 0;
         return;
     }

@@ -1004,7 +1004,9 @@ bool crc32_begin(zs_ctx *c, int m, size_t blob_bytes, Crc32Job *job, bool *no_me
 }
 
 // Uploads the job, runs KC and the finishing launch and waits for `s` once; the CRCs are in job->crc afterwards.
-bool crc32_run(zs_ctx *c, Crc32Job *job, hipStream_t s) {
+// behind (may be null): work the caller puts on `s` behind the finishing launch and in front of that one wait -- it is given
+// the CRCs' place on the device (a gzip trailer is written from there, zs_wrap_host.inc); false from it fails the job.
+bool crc32_run(zs_ctx *c, Crc32Job *job, hipStream_t s, const std::function<bool(const uint32_t *)> *behind = nullptr) {
     const int m = job->m;
     uint32_t *off = (uint32_t *)((uint8_t *)c->pinned + job->b_sp);
     uint64_t tiles = 0;
@@ -1036,6 +1038,7 @@ bool crc32_run(zs_ctx *c, Crc32Job *job, hipStream_t s) {
     }
     hipLaunchKernelGGL(zs_crc32_finish_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d_sp, m, (const uint32_t *)d_res, d_crc);
     ZS_HIP(c, hipGetLastError());
+    if (behind && !(*behind)(d_crc)) return false;
     if (prof) (void)hipEventRecord(c->ev_png[1], s);
     ZS_HIP(c, hipMemcpyAsync((void *)job->crc, d_crc, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
     ZS_HIP(c, hipStreamSynchronize(s));
