@@ -216,6 +216,98 @@ ZS_API int zs_gzip_decode_files_batch(zs_ctx *ctx, int n, const void *const *fil
                                       const int64_t *out_cap, int64_t *out_len, int *n_members, int *status, void *hip_stream);
 
 /* ------------------------------------------------------------------ */
+/* ZIP archives (PKWARE APPNOTE 6.3; .zip, .docx, .jar, .npz, .whl): whole files decoded on the device, and archives written
+ * there.  The container's rules are zlibstream_amd/csrc/zs_zip.h's:
+ *   - the end record is searched backwards over the last 22 + 65535 bytes; the first signature whose comment length reaches
+ *     exactly the end of the file is taken.  No such record: ZS_DATA_ERROR (ZS_BUF_ERROR for a file under 22 bytes);
+ *   - the ZIP64 end record and the ZIP64 extra field (id 0x0001: size, compressed size, local offset) are read where a field
+ *     is all ones;
+ *   - shift = (place of the end record, or of the ZIP64 one) - cd_len - cd_off: bytes in front of the archive (a
+ *     self-extractor) are added to every offset, as Python's zipfile does; a negative shift is ZS_DATA_ERROR;
+ *   - ZS_DATA_ERROR for the file: "multi-disk archives are not supported" (a disk number other than 0, counts that differ),
+ *     a central record without its signature or reaching out of the directory, records that do not end exactly at
+ *     cd_off + cd_len, a record count that does not match;
+ *   - per entry, the walk going on: flag bit 0, 6 or 13 -- ZS_DATA_ERROR "encrypted entries are not supported"; a method
+ *     outside {0, 8} -- ZS_DATA_ERROR "unsupported compression method"; method 0 with comp_len != len -- ZS_DATA_ERROR
+ *     "incorrect length check"; a local header without its signature or with another name than the central record's --
+ *     ZS_DATA_ERROR "local header mismatch"; a local header or a body that the file ends in -- ZS_BUF_ERROR "buffer error".
+ *     Flag bit 3 (a data descriptor behind the body) is legal and the descriptor is never read: sizes and CRC-32 are the
+ *     central directory's.  The body begins behind the LOCAL header's name and extra field, which may differ from the
+ *     central record's. */
+enum { ZS_ZIP_AUTO = -1, ZS_ZIP_STORED = 0, ZS_ZIP_DEFLATED = 8 };
+
+typedef struct zs_zip_info {
+    int64_t n_entries, total_len;      /* total_len: the sum of the entries' len = what the decode call writes */
+    int64_t cd_off, cd_len, shift;     /* as found, shift applied to cd_off */
+    int64_t comment_off, comment_len;
+    int zip64;                         /* a ZIP64 end record was used */
+} zs_zip_info;
+
+typedef struct zs_zip_entry {
+    int64_t name_off; int name_len;    /* the central directory's copy of the name, in the file */
+    int method, flags;
+    uint32_t crc32;
+    int64_t comp_len, len, local_off, body_off, out_off; /* local_off: shift applied; out_off: sum of len of the entries in front */
+    uint16_t dos_time, dos_date; uint32_t external_attr;
+    int status;                        /* ZS_OK: decodable; else why not (rules above), body_off undefined */
+} zs_zip_entry;
+
+/* One archive in HOST memory, pure host code, no context and no GPU.  ZS_OK, *info and the entries; the file's error (rules
+ * above), with *info as far as the end record gave it; ZS_STREAM_ERROR for null pointers or negative lengths.  entries may be
+ * NULL (entries_cap 0) to ask for the counts only; entries_cap < n_entries: ZS_BUF_ERROR with info filled and the first
+ * entries_cap entries written. */
+ZS_API int zs_zip_file_info(const void *file, int64_t len, zs_zip_info *info, zs_zip_entry *entries, int64_t entries_cap);
+
+/* ZIP archives to their entries' bytes, n archives a call.  file[i] / file_len[i]: whole files in HOST memory; they go to
+ * the device in one copy and are walked on the host.  out[i] (DEVICE pointer, out_cap[i] bytes): entry e of file i lands at
+ * out[i] + out_off[e] (zs_zip_file_info gives the offsets), out_len[i] is total_len.  All deflated entries of all files are
+ * the streams of one raw inflate launch, each with exactly len bytes of room: a body that needs more, or ends with fewer, is
+ * ZS_DATA_ERROR "incorrect length check"; one that ends in front of comp_len is accepted, as zipfile accepts it.  One CRC-32
+ * launch then copies every stored entry into place and checks all entries: ZS_DATA_ERROR "incorrect data check".
+ * out_cap[i] < total_len: ZS_BUF_ERROR for that file, nothing of it is decoded, out_len[i] says what it needs.  total_len or
+ * the file above 2 GiB - 1 KiB: ZS_DATA_ERROR for that file (take the offsets from zs_zip_file_info and call the raw inflate).
+ * entry_status (HOST, may be NULL, as may entry_status[i]): n_entries ints per file, ZS_OK or the entry's code; written only
+ * for a file whose directory was walked and whose out_cap sufficed.  status[i] (may be NULL): ZS_OK, the file's error, or
+ * its first failing entry's code; zs_ctx_last_error names the first failing file, the entry and the reason ("file 1: entry 2:
+ * incorrect data check").  A failing entry's bytes are unspecified, every other entry is complete, and nothing is written
+ * outside [out[i], out[i] + total_len).  Returns ZS_OK, the first failing file's code, ZS_MEM_ERROR, or, before any device
+ * work, ZS_STREAM_ERROR: null context, n < 0, null arrays or pointers, a negative length or capacity.  The call waits for
+ * the stream for the upload, as the inflate call does, and once for the CRCs. */
+ZS_API int zs_zip_decode_files_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, void *const *out,
+                                     const int64_t *out_cap, int64_t *out_len, int *const *entry_status, int *status,
+                                     void *hip_stream);
+
+typedef struct zs_zip_put {
+    const void *data; int64_t len;     /* DEVICE pointer (may be NULL where len is 0), 0 .. 2 GiB - 1 KiB */
+    const char *name; int name_len;    /* HOST bytes, 1 .. 65535, written as given */
+    int method;                        /* ZS_ZIP_AUTO, ZS_ZIP_STORED, ZS_ZIP_DEFLATED */
+    int utf8;                          /* general purpose bit 11 */
+    uint16_t dos_time, dos_date;       /* written as given (0 / 0x0021 = 1980-01-01 00:00 is a sane default) */
+    uint32_t external_attr;            /* "made by" host byte 3 (Unix) when its high 16 bits are non-zero, else 0 */
+} zs_zip_put;
+
+/* Room that zs_zip_encode_batch_device needs for these entries at the most: 22 + per entry 76 + 2 name_len + len, and for
+ * an entry forced to ZS_ZIP_DEFLATED zs_wrap_bound(len, ZS_WRAP_RAW) in place of len.  Pure host code.  -1 for what that
+ * call refuses: n_entries outside 0 .. 65535, a null list, a field of a zs_zip_put out of range, a bound above 2^32 - 1. */
+ZS_API int64_t zs_zip_bound(const zs_zip_put *entries, int n_entries);
+
+/* Entries in device memory to ZIP archives in device memory, n archives a call: archive i holds entries[i][0 .. n_entries[i]).
+ * Its bytes: per entry a local header (version needed 20, or 10 for a stored entry, no extra field, no data descriptor),
+ * the name and the body; the central directory; the end record without a comment.  ZIP64 is not written.
+ * One zs_deflate_batch_device call deflates every entry of every archive that is not ZS_ZIP_STORED or empty, into a buffer the
+ * context owns; a deflated body is, bit for bit, what zs_deflate_wrap_batch_device(..., ZS_WRAP_RAW) writes for the same bytes,
+ * level, strategy and hash variant.  ZS_ZIP_AUTO keeps the stored form when the raw body is not shorter than the data; an
+ * empty entry is always stored.  One framing launch (KC) then copies headers, names, bodies and directories into place and
+ * computes the CRC-32 of every entry's data, and a closing kernel writes each into its local header and central record: the
+ * CRCs never come to the host.  The call waits for the stream once more than the deflate call.
+ * out_len / out_cap / status / the return value: as for zs_deflate_wrap_batch_device -- an archive that does not fit is
+ * ZS_BUF_ERROR, out_len[i] says what it needs, nothing is written for it and the others are complete; zs_zip_bound is always
+ * enough.  ZS_STREAM_ERROR before any device work for what zs_zip_bound answers with -1, and for null arrays or pointers. */
+ZS_API int zs_zip_encode_batch_device(zs_ctx *ctx, int n, const zs_zip_put *const *entries, const int *n_entries,
+                                      void *const *out, const int64_t *out_cap, int64_t *out_len, int *status, int level,
+                                      int strategy, int hash_variant, void *hip_stream);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU batch entry points (SURVEY.md 8(b) "zs_deflate_batch(..., device_mask)", 8(e)): the n independent
  * buffers are partitioned over n_ctx contexts -- normally one per GPU of the node, zs_ctx_create(0 .. count-1) --
  * by size (longest-processing-time, zs_partition), each context's share runs on its own host thread through the

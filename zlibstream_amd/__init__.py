@@ -16,4 +16,5 @@ from .api import (CompressionLevel, CompressionState, CompressionStrategy, Engin
                   png_anim_info, png_compose_batch_device, png_decode_anim_batch, PNG_DISPOSE_NONE, PNG_DISPOSE_BACKGROUND,
                   PNG_DISPOSE_PREVIOUS, PNG_BLEND_SOURCE, PNG_BLEND_OVER, png_diff_batch_device, png_crop_batch_device,
                   png_anim_bound, png_encode_anim_batch_device, WRAP_ZLIB, WRAP_RAW, WRAP_GZIP, wrap_bound,
-                  deflate_wrap_batch_device, inflate_wrap_batch_device, gzip_file_info, gzip_decode_files_batch)
+                  deflate_wrap_batch_device, inflate_wrap_batch_device, gzip_file_info, gzip_decode_files_batch,
+                  ZIP_AUTO, ZIP_STORED, ZIP_DEFLATED, zip_file_info, zip_decode_files_batch, zip_bound, zip_encode_batch_device)

@@ -25,6 +25,7 @@ SYMBOLS = [
     "zs_png_anim_info", "zs_png_compose_batch_device", "zs_png_decode_anim_batch",
     "zs_png_diff_batch_device", "zs_png_crop_batch_device", "zs_png_anim_bound", "zs_png_encode_anim_batch_device",
     "zs_wrap_bound", "zs_deflate_wrap_batch_device", "zs_inflate_wrap_batch_device", "zs_gzip_file_info", "zs_gzip_decode_files_batch",
+    "zs_zip_file_info", "zs_zip_decode_files_batch", "zs_zip_bound", "zs_zip_encode_batch_device",
 ]
 
 
@@ -37,6 +38,24 @@ class PngInfo(ctypes.Structure):  # zs_png_info
 class GzipInfo(ctypes.Structure):  # zs_gzip_info
     _fields_ = [("bgzf", ctypes.c_int), ("xfl", ctypes.c_int), ("os", ctypes.c_int), ("mtime", ctypes.c_uint32),
                 ("n_members", ctypes.c_int64), ("name_off", ctypes.c_int64), ("name_len", ctypes.c_int64), ("isize_sum", ctypes.c_int64)]
+
+
+class ZipInfo(ctypes.Structure):  # zs_zip_info
+    _fields_ = [("n_entries", ctypes.c_int64), ("total_len", ctypes.c_int64), ("cd_off", ctypes.c_int64), ("cd_len", ctypes.c_int64),
+                ("shift", ctypes.c_int64), ("comment_off", ctypes.c_int64), ("comment_len", ctypes.c_int64), ("zip64", ctypes.c_int)]
+
+
+class ZipEntry(ctypes.Structure):  # zs_zip_entry
+    _fields_ = [("name_off", ctypes.c_int64), ("name_len", ctypes.c_int), ("method", ctypes.c_int), ("flags", ctypes.c_int),
+                ("crc32", ctypes.c_uint32), ("comp_len", ctypes.c_int64), ("len", ctypes.c_int64), ("local_off", ctypes.c_int64),
+                ("body_off", ctypes.c_int64), ("out_off", ctypes.c_int64), ("dos_time", ctypes.c_uint16), ("dos_date", ctypes.c_uint16),
+                ("external_attr", ctypes.c_uint32), ("status", ctypes.c_int)]
+
+
+class ZipPut(ctypes.Structure):  # zs_zip_put
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_int64), ("name", ctypes.c_char_p), ("name_len", ctypes.c_int),
+                ("method", ctypes.c_int), ("utf8", ctypes.c_int), ("dos_time", ctypes.c_uint16), ("dos_date", ctypes.c_uint16),
+                ("external_attr", ctypes.c_uint32)]
 
 
 class PngSurvey(ctypes.Structure):  # zs_png_survey
@@ -233,5 +252,14 @@ def lib():
         L.zs_gzip_file_info.argtypes = [vp, i64, P(GzipInfo)]
         L.zs_gzip_decode_files_batch.restype = i32
         L.zs_gzip_decode_files_batch.argtypes = [vp, i32, P(vp), P(i64), P(vp), P(i64), P(i64), P(i32), P(i32), vp]
+    if hasattr(L, "zs_zip_file_info"):
+        L.zs_zip_file_info.restype = i32
+        L.zs_zip_file_info.argtypes = [vp, i64, P(ZipInfo), P(ZipEntry), i64]
+        L.zs_zip_decode_files_batch.restype = i32
+        L.zs_zip_decode_files_batch.argtypes = [vp, i32, P(vp), P(i64), P(vp), P(i64), P(i64), P(P(i32)), P(i32), vp]
+        L.zs_zip_bound.restype = i64
+        L.zs_zip_bound.argtypes = [P(ZipPut), i32]
+        L.zs_zip_encode_batch_device.restype = i32
+        L.zs_zip_encode_batch_device.argtypes = [vp, i32, P(P(ZipPut)), P(i32), P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
     _lib = L
     return L

@@ -1360,6 +1360,126 @@ def gzip_decode_files_batch(engine, files, out_ptrs, out_caps, stream=None):
     return list(status), list(out_len), list(members)
 
 
+ZIP_AUTO, ZIP_STORED, ZIP_DEFLATED = -1, 0, 8  # ZS_ZIP_*: a zs_zip_put's method
+_ZIP_INFO_FIELDS = ("n_entries", "total_len", "cd_off", "cd_len", "shift", "comment_off", "comment_len", "zip64")
+_ZIP_ENTRY_FIELDS = ("name_off", "name_len", "method", "flags", "crc32", "comp_len", "len", "local_off", "body_off", "out_off", "dos_time",
+                     "dos_date", "external_attr", "status")
+
+
+def zip_file_info(data):
+    """zs_zip_file_info (host code, no GPU, no engine): (info dict, [entry dicts]) of one archive -- the fields of zs_zip_info
+    and zs_zip_entry, and per entry "name", the central directory's bytes decoded as UTF-8 where flag bit 11 says so and as
+    cp437 otherwise.  An entry the engine cannot decode has a non-zero "status"; ZlibStreamException for a file whose
+    directory cannot be walked."""
+    data = bytes(data)
+    L = _native.lib()
+    info = _native.ZipInfo()
+    rc = L.zs_zip_file_info(data, len(data), ctypes.byref(info), None, 0)
+    if rc != 0:
+        raise ZlibStreamException("zip_file_info: not a whole ZIP archive (%d)" % rc)
+    n = int(info.n_entries)
+    entries = (_native.ZipEntry * max(n, 1))()
+    rc = L.zs_zip_file_info(data, len(data), ctypes.byref(info), entries, n)
+    if rc != 0:
+        raise ZlibStreamException("zip_file_info: not a whole ZIP archive (%d)" % rc)
+    out = []
+    for e in entries[:n]:
+        d = {k: int(getattr(e, k)) for k in _ZIP_ENTRY_FIELDS}
+        d["name"] = data[d["name_off"]:d["name_off"] + d["name_len"]].decode("utf-8" if d["flags"] & 0x800 else "cp437")
+        out.append(d)
+    return {k: int(getattr(info, k)) for k in _ZIP_INFO_FIELDS}, out
+
+
+def zip_decode_files_batch(engine, files, out_ptrs, out_caps, stream=None):
+    """ZIP archives (bytes objects in host memory) -> their entries' bytes in device buffers, entry e of file i at
+    out_ptrs[i] + out_off[e] (zip_file_info), many archives a call (zs_zip_decode_files_batch).  Returns (code, lengths,
+    per file the list of its entries' codes, per-file codes): a file's code is 0, its own error, or its first failing entry's
+    (-3 ZS_DATA_ERROR, -5 ZS_BUF_ERROR); the list of a file whose directory could not be walked, or whose capacity was too
+    small, is empty.  engine.last_error() names the first failing file, the entry and the reason."""
+    n = len(files)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("zip_decode_files_batch: the argument lists differ in length")
+    if any(not o or int(cap) < 0 for o, cap in zip(out_ptrs, out_caps)):
+        raise ValueError("zip_decode_files_batch: non-null device pointers and non-negative capacities are required")
+    if n == 0:
+        return 0, [], [], []
+    L = _native.lib()
+    files = [bytes(f) for f in files]
+    keep = [ctypes.create_string_buffer(f, len(f)) if f else ctypes.create_string_buffer(1) for f in files]
+    counts = []  # entries whose codes the call writes: none for a file it does not walk or has no room for
+    for f, cap in zip(files, out_caps):
+        info = _native.ZipInfo()
+        walked = len(f) <= _CRC_MAX_LEN and L.zs_zip_file_info(f, len(f), ctypes.byref(info), None, 0) == 0
+        counts.append(int(info.n_entries) if walked and info.total_len <= min(int(cap), _CRC_MAX_LEN) else 0)
+    per_entry = [(ctypes.c_int * max(k, 1))() for k in counts]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    rows = (ctypes.POINTER(ctypes.c_int) * n)(*[ctypes.cast(r, ctypes.POINTER(ctypes.c_int)) for r in per_entry])
+    rc = L.zs_zip_decode_files_batch(engine.handle, n, VP(*[ctypes.addressof(k) for k in keep]), I64(*[len(f) for f in files]),
+                                     VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, rows, status,
+                                     ctypes.c_void_p(stream or 0))
+    if rc not in (0, -3, -5):
+        raise ValueError("zs_zip_decode_files_batch failed (%d): %s" % (rc, engine.last_error()))
+    return rc, list(out_len), [list(per_entry[i][:counts[i]]) for i in range(n)], list(status)
+
+
+def _zip_dos(date_time):
+    y, mo, d, h, mi, s = date_time
+    if not (1980 <= y <= 2107 and 1 <= mo <= 12 and 1 <= d <= 31 and 0 <= h < 24 and 0 <= mi < 60 and 0 <= s < 60):
+        raise ValueError("a ZIP entry's date_time must lie in 1980 .. 2107")
+    return h << 11 | mi << 5 | s >> 1, (y - 1980) << 9 | mo << 5 | d
+
+
+def _zip_puts(entries):
+    """A list of (name bytes, device ptr, len[, method[, utf8[, date_time[, external_attr]]]]) as a zs_zip_put array; date_time
+    is zipfile's (year, month, day, hour, minute, second).  Also returns what keeps the names alive."""
+    puts = (_native.ZipPut * max(len(entries), 1))()
+    keep = []
+    for p, e in zip(puts, entries):
+        name, ptr, length = e[0], e[1], e[2]
+        method, utf8, date_time, attr = (tuple(e[3:]) + (ZIP_AUTO, 0, (1980, 1, 1, 0, 0, 0), 0)[len(e) - 3:])[:4]
+        name = bytes(name)
+        keep.append(name)
+        p.data, p.len, p.name, p.name_len, p.method, p.utf8 = int(ptr) or None, int(length), name, len(name), int(method), int(bool(utf8))
+        p.dos_time, p.dos_date = _zip_dos(date_time)
+        p.external_attr = int(attr) & 0xFFFFFFFF
+    return puts, keep
+
+
+def zip_bound(entries):
+    """zs_zip_bound (host code): room that zip_encode_batch_device needs for one archive of these entries at the most."""
+    puts, keep = _zip_puts(entries)
+    r = _native.lib().zs_zip_bound(puts, len(entries))
+    if r < 0:
+        raise ValueError("zip_bound: more than 65535 entries, a field out of range, or an archive that would need ZIP64")
+    return r
+
+
+def zip_encode_batch_device(engine, archives, out_ptrs, out_caps, level=6, strategy=0, hash_variant=0, stream=None):
+    """Device-resident entries into ZIP archives in device buffers, many archives a call (zs_zip_encode_batch_device).
+    archives: per archive a list of (name bytes, device ptr, len[, method[, utf8[, date_time[, external_attr]]]]), method
+    ZIP_AUTO (the default: deflated unless that is no shorter), ZIP_STORED or ZIP_DEFLATED.  Returns (code, lengths,
+    per-archive codes): -5 (ZS_BUF_ERROR) for an archive whose capacity was too small -- its length is then what it needs,
+    nothing is written for it and the others are complete."""
+    n = len(archives)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("zip_encode_batch_device: the argument lists differ in length")
+    if n == 0:
+        return 0, [], []
+    built = [_zip_puts(a) for a in archives]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    rows = (ctypes.POINTER(_native.ZipPut) * n)(*[ctypes.cast(p, ctypes.POINTER(_native.ZipPut)) for p, _ in built])
+    rc = _native.lib().zs_zip_encode_batch_device(engine.handle if engine is not None else None, n, rows, I32(*[len(a) for a in archives]),
+                                                  VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, status,
+                                                  int(level), int(strategy), int(hash_variant), ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError("zs_zip_encode_batch_device: more than 65535 entries, a field out of range, or an archive that would need ZIP64")
+    if rc not in (0, -5):
+        raise ZlibStreamException("zip encode: " + engine.last_error())
+    return rc, list(out_len), list(status)
+
+
 _default_engine = None
 
 

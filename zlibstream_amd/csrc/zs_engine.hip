@@ -1,6 +1,7 @@
 // zs_engine.hip -- host side of the MI355X deflate engine: workspace, kernel
 // pipeline, and the C ABI of include/zsgpu.h (the PNG and CRC-32 calls of it:
-// zs_png_host.inc; raw deflate, gzip members and gzip files: zs_wrap_host.inc).  No CPU fallback: without a usable HIP device every
+// zs_png_host.inc; raw deflate, gzip members and gzip files: zs_wrap_host.inc; ZIP archives: zs_zip_host.inc).  No CPU fallback:
+// without a usable HIP device every
 // compressing entry point fails.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include "zs_png.hip"
 #include "zs_crc32.hip"
 #include "zs_gzip.hip"
+#include "zs_zip.hip"
 #include "zs_plan.h"
 
 using namespace zs;
@@ -47,8 +49,8 @@ enum PngBuf {
     kBufPngXimg, kBufPngRaw, kBufPngSimg, kBufPngSplit, kBufPngGimg, kBufPngVimg, kBufPngVrec, kBufPngPacked, kBufPngCimg, kBufPngFrames, kBufPngDimg, kBufPngDrec,
     kBufPngKimg, kBufPngCrop,
     // the container calls (zs_wrap_host.inc): the members' descriptors and heads, the trailers gathered for the host, the zlib
-    // streams in front of the framing launch, a call's files
-    kBufWrapHead, kBufWrapGather, kBufWrapZs, kBufWrapFiles, kBufPngCount
+    // streams in front of the framing launch, a call's files; the ZIP writer's zlib streams (zs_zip_host.inc)
+    kBufWrapHead, kBufWrapGather, kBufWrapZs, kBufWrapFiles, kBufZipZs, kBufPngCount
 };
 
 struct PlanCache;  // the last deflate call's plan, kept for a same-shaped call (below, ahead of run_pipeline)
@@ -2058,6 +2060,7 @@ int zs_inflate_batch(zs_ctx *c, int n, const void *const *in, const int64_t *in_
 
 #include "zs_png_host.inc"
 #include "zs_wrap_host.inc"
+#include "zs_zip_host.inc"
 
 // ------------------------------------------------------------------ multi-GPU batch entry points
 // BASELINE north_star: "independent input buffers shard embarrassingly across the 8 GPUs of one node (no RCCL needed)".
