@@ -308,6 +308,117 @@ ZS_API int zs_zip_encode_batch_device(zs_ctx *ctx, int n, const zs_zip_put *cons
                                       int strategy, int hash_variant, void *hip_stream);
 
 /* ------------------------------------------------------------------ */
+/* TIFF files with Deflate compression (TIFF 6.0; compression 8, Adobe's, and 32946, the older code for the same): whole files
+ * decoded on the device, and files written there.  A Deflate TIFF is a batch of independent zlib streams, one per strip or
+ * tile ("chunk" below), with an optional predictor in front.  The container's rules are zlibstream_amd/csrc/zs_tiff.h's:
+ *   - read: classic TIFF (42) and BigTIFF (43), "II" and "MM"; a page is an IFD of the chain (SubIFDs are not followed); tags
+ *     256, 257, 258, 259, 262, 266, 273, 274, 277, 278, 279, 284, 317, 322, 323, 324, 325, 338, 339, their values as BYTE, SHORT,
+ *     LONG or LONG8, with the specification's defaults (RowsPerStrip 2^32 - 1 = one strip);
+ *   - accepted: compression 1 (none), 8, 32946; predictor 1, 2 (horizontal differencing; 8, 16 or 32 bits) and 3 (floating
+ *     point; 32 bits, sample format 3); 1, 2, 4, 8, 16 or 32 bits per sample, the same for all; 1 .. 8 samples per pixel;
+ *     planar configuration 1 (2 with one sample); strips, or tiles whose width and length are multiples of 16;
+ *   - ZS_DATA_ERROR for the file, each with its own message: "not a TIFF file", "an IFD reaches out of the file", a tag's value
+ *     that does, "the IFD chain loops", "no such page", "a required tag is missing" (256, 257, offsets, byte counts, and for
+ *     tiles 322 and 323), offsets or byte counts that are not one per chunk, "unsupported compression method", "unsupported
+ *     predictor", "unsupported planar configuration", "unsupported bits per sample", "unsupported samples per pixel",
+ *     "unsupported fill order" (2), photometric 6 (YCbCr), "invalid strip or tile size", pixels above 2 GiB - 1 KiB;
+ *   - ZS_BUF_ERROR: a file shorter than its header; per chunk, the walk going on, a body that the file ends in.
+ * Photometric, ExtraSamples, SampleFormat and Orientation are reported, not interpreted. */
+typedef struct zs_tiff_info {
+    int64_t n_pages;                   /* IFDs in the chain */
+    int big_endian, bigtiff;
+    int64_t width, height;
+    int bits, spp, sample_format, photometric;
+    int extra_samples, extra_kind;     /* how many, and the first one's kind */
+    int compression, predictor, planar, orientation;
+    int tiled, pad;
+    int64_t chunk_w, chunk_h, n_chunks; /* a tile; or the width and the rows of a strip */
+    int64_t row_bytes, out_len;        /* ceil(width * spp * bits / 8), and height times that = what the decode call writes */
+} zs_tiff_info;
+
+typedef struct zs_tiff_chunk {
+    int64_t off, comp_len;             /* the body in the file */
+    int64_t x, y, w, h;                /* its place in the image, and the part of it that lies inside the image */
+    int status, pad;                   /* ZS_OK, or ZS_BUF_ERROR: the file ends in it (off and comp_len are 0 then) */
+} zs_tiff_chunk;
+
+/* Page `page` of one file in HOST memory, pure host code, no context and no GPU.  ZS_OK, *info and the chunks; the file's
+ * error (rules above), with n_pages and the byte order in *info as far as the walk got; ZS_STREAM_ERROR for null pointers or
+ * negative numbers.  chunks may be NULL (chunks_cap 0) to ask for the counts only; chunks_cap < n_chunks: ZS_BUF_ERROR with
+ * info filled and the first chunks_cap chunks written. */
+ZS_API int zs_tiff_file_info(const void *file, int64_t len, int64_t page, zs_tiff_info *info, zs_tiff_chunk *chunks,
+                             int64_t chunks_cap);
+
+/* The predictor kernels alone (KT), n chunks a call, all pointers DEVICE pointers of any alignment.
+ * Undo: in[i] is a decoded chunk, height[i] rows of ceil(width[i] * spp * bits / 8) bytes, as a TIFF reader has it behind
+ * inflate; out[i] receives its top left out_width[i] x out_height[i] pixels (<= width, height: a tile that hangs over the
+ * image's edge) as rows of ceil(out_width[i] * spp * bits / 8) bytes, samples little-endian.  Predictor 1 copies (and swaps
+ * where big_endian[i], which may be NULL, says the samples lie most significant byte first), 2 sums every row with stride spp
+ * mod 2^bits over the chunk's full width, 3 sums its bytes likewise and gathers the four byte planes, the most significant
+ * first.  Predict is the inverse, and always little-endian: in[i] holds in_width[i] x in_height[i] pixels, out[i] receives
+ * width[i] x height[i], the surplus filled by repeating the last pixel and the last row.
+ * ZS_STREAM_ERROR before any device work: null arrays or pointers, a size outside 1 .. 2^31 - 1, a part larger than its
+ * chunk, bits outside {1, 2, 4, 8, 16, 32}, spp outside 1 .. 8, predictor 2 below 8 bits, predictor 3 at other than 32, more
+ * than 2^31 - 1 rows in the call.  n == 0 is ZS_OK.  With a hip_stream the launches stay in flight on it. */
+ZS_API int zs_tiff_unpredict_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *width,
+                                          const int64_t *height, const int64_t *out_width, const int64_t *out_height,
+                                          const int *bits, const int *spp, const int *predictor, const int *big_endian,
+                                          void *hip_stream);
+ZS_API int zs_tiff_predict_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *in_width,
+                                        const int64_t *in_height, const int64_t *width, const int64_t *height, const int *bits,
+                                        const int *spp, const int *predictor, void *hip_stream);
+
+/* TIFF files to pixels, n files a call.  file[i] / file_len[i]: whole files in HOST memory; they go to the device in one copy
+ * and are walked on the host.  page (HOST, may be NULL: page 0 of every file): the page of file i.  out[i] (DEVICE pointer,
+ * out_cap[i] bytes) receives height rows of row_bytes bytes, samples little-endian, out_len[i] is the page's out_len.
+ * All deflated chunks of all files are the streams of one inflate launch, read from 16-byte-aligned pointers wherever they
+ * lie in their files; their Adler-32s are checked by one more launch ("incorrect data check").  A strip must yield the rows
+ * it has inside the image -- a last strip may also yield all of RowsPerStrip, both exist in the wild --, a tile all of itself:
+ * fewer bytes, or more than the chunk holds, are ZS_DATA_ERROR "incorrect length check".  Strips of a file with predictor 1
+ * whose samples need no swap are inflated straight into out[i]; every other chunk goes through a buffer the context owns and
+ * one launch of the undo kernel, which also takes uncompressed chunks from the uploaded file.
+ * out_cap[i] < out_len: ZS_BUF_ERROR for that file, nothing of it is decoded, out_len[i] says what it needs.  A file above
+ * 2 GiB - 1 KiB: ZS_DATA_ERROR for that file.
+ * chunk_status (HOST, may be NULL, as may chunk_status[i]): n_chunks ints per file, ZS_OK or the chunk's code; written only
+ * for a file whose page was walked and whose out_cap sufficed.  status[i] (may be NULL): ZS_OK, the file's error, or its first
+ * failing chunk's code; zs_ctx_last_error names the first failing file, the chunk and the reason ("file 1: chunk 7: incorrect
+ * data check").  A failing chunk's pixels are unspecified, every other chunk is complete, and nothing is written outside
+ * [out[i], out[i] + out_len).  Returns ZS_OK, the first failing file's code, ZS_MEM_ERROR, or, before any device work,
+ * ZS_STREAM_ERROR: null context, n < 0, null arrays or pointers, a negative length, capacity or page. */
+ZS_API int zs_tiff_decode_files_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, const int64_t *page,
+                                      void *const *out, const int64_t *out_cap, int64_t *out_len, int *const *chunk_status,
+                                      int *status, void *hip_stream);
+
+typedef struct zs_tiff_put {
+    const void *pixels;                /* DEVICE pointer: height rows of ceil(width * spp * bits / 8) bytes, little-endian */
+    int64_t width, height;             /* 1 .. 2^31 - 1, the pixels at most 2 GiB - 1 KiB */
+    int bits, spp;                     /* 1, 2, 4, 8, 16, 32; 1 .. 8 */
+    int sample_format, photometric;    /* tags 339 and 262, written as given (photometric 6 is refused) */
+    int extra_samples, extra_kind;     /* tag 338: how many of the spp samples are extra (0: the tag is left out), and their kind */
+    int predictor, pad;                /* 1, 2 (bits >= 8), 3 (bits 32, sample format 3) */
+    int64_t tile_width, tile_height;   /* multiples of 16; 0 / 0: strips */
+    int64_t rows_per_strip;            /* 0: strips of about 256 KiB of pixels */
+} zs_tiff_put;
+
+/* Room that zs_tiff_encode_batch_device needs for this image at the most: the head (header, IFD, its longer values) and per
+ * chunk zs_deflate_bound(its bytes) + 1.  Pure host code.  -1 for what that call refuses: a null pointer, a field out of range
+ * (above), a bound above 2^32 - 1 (BigTIFF is not written). */
+ZS_API int64_t zs_tiff_bound(const zs_tiff_put *put);
+
+/* Images in device memory to TIFF files in device memory, n files a call: classic little-endian TIFF, one page, compression
+ * 8, planar configuration 1, [header | IFD, tags ascending | the IFD's longer values | the chunks, each at an even offset].
+ * One launch of the forward kernel cuts, pads and predicts every chunk of every image (a last strip is written with the rows
+ * it has), one zs_deflate_batch_device call deflates them all into a buffer the context owns -- a chunk's stream is, bit for
+ * bit, what that call writes for the same predicted bytes, level, strategy and hash variant --, the host builds the heads from
+ * the lengths it returns, and one framing launch (KC's span copy) assembles the files.
+ * out_len / out_cap / status / the return value: as for zs_zip_encode_batch_device -- a file that does not fit is
+ * ZS_BUF_ERROR, out_len[i] says what it needs, nothing is written for it and the others are complete; zs_tiff_bound is always
+ * enough.  ZS_STREAM_ERROR before any device work for what zs_tiff_bound answers with -1, and for null arrays or pointers. */
+ZS_API int zs_tiff_encode_batch_device(zs_ctx *ctx, int n, const zs_tiff_put *puts, void *const *out, const int64_t *out_cap,
+                                       int64_t *out_len, int *status, int level, int strategy, int hash_variant,
+                                       void *hip_stream);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU batch entry points (SURVEY.md 8(b) "zs_deflate_batch(..., device_mask)", 8(e)): the n independent
  * buffers are partitioned over n_ctx contexts -- normally one per GPU of the node, zs_ctx_create(0 .. count-1) --
  * by size (longest-processing-time, zs_partition), each context's share runs on its own host thread through the

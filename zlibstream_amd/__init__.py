@@ -17,4 +17,5 @@ from .api import (CompressionLevel, CompressionState, CompressionStrategy, Engin
                   PNG_DISPOSE_PREVIOUS, PNG_BLEND_SOURCE, PNG_BLEND_OVER, png_diff_batch_device, png_crop_batch_device,
                   png_anim_bound, png_encode_anim_batch_device, WRAP_ZLIB, WRAP_RAW, WRAP_GZIP, wrap_bound,
                   deflate_wrap_batch_device, inflate_wrap_batch_device, gzip_file_info, gzip_decode_files_batch,
-                  ZIP_AUTO, ZIP_STORED, ZIP_DEFLATED, zip_file_info, zip_decode_files_batch, zip_bound, zip_encode_batch_device)
+                  ZIP_AUTO, ZIP_STORED, ZIP_DEFLATED, zip_file_info, zip_decode_files_batch, zip_bound, zip_encode_batch_device,
+                  tiff_file_info, tiff_decode_files, tiff_encode, tiff_bound, tiff_predict, tiff_unpredict)

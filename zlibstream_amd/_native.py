@@ -26,6 +26,8 @@ SYMBOLS = [
     "zs_png_diff_batch_device", "zs_png_crop_batch_device", "zs_png_anim_bound", "zs_png_encode_anim_batch_device",
     "zs_wrap_bound", "zs_deflate_wrap_batch_device", "zs_inflate_wrap_batch_device", "zs_gzip_file_info", "zs_gzip_decode_files_batch",
     "zs_zip_file_info", "zs_zip_decode_files_batch", "zs_zip_bound", "zs_zip_encode_batch_device",
+    "zs_tiff_file_info", "zs_tiff_unpredict_batch_device", "zs_tiff_predict_batch_device", "zs_tiff_decode_files_batch", "zs_tiff_bound",
+    "zs_tiff_encode_batch_device",
 ]
 
 
@@ -56,6 +58,27 @@ class ZipPut(ctypes.Structure):  # zs_zip_put
     _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_int64), ("name", ctypes.c_char_p), ("name_len", ctypes.c_int),
                 ("method", ctypes.c_int), ("utf8", ctypes.c_int), ("dos_time", ctypes.c_uint16), ("dos_date", ctypes.c_uint16),
                 ("external_attr", ctypes.c_uint32)]
+
+
+class TiffInfo(ctypes.Structure):  # zs_tiff_info
+    _fields_ = [("n_pages", ctypes.c_int64), ("big_endian", ctypes.c_int), ("bigtiff", ctypes.c_int), ("width", ctypes.c_int64),
+                ("height", ctypes.c_int64), ("bits", ctypes.c_int), ("spp", ctypes.c_int), ("sample_format", ctypes.c_int),
+                ("photometric", ctypes.c_int), ("extra_samples", ctypes.c_int), ("extra_kind", ctypes.c_int), ("compression", ctypes.c_int),
+                ("predictor", ctypes.c_int), ("planar", ctypes.c_int), ("orientation", ctypes.c_int), ("tiled", ctypes.c_int),
+                ("pad", ctypes.c_int), ("chunk_w", ctypes.c_int64), ("chunk_h", ctypes.c_int64), ("n_chunks", ctypes.c_int64),
+                ("row_bytes", ctypes.c_int64), ("out_len", ctypes.c_int64)]
+
+
+class TiffChunk(ctypes.Structure):  # zs_tiff_chunk
+    _fields_ = [("off", ctypes.c_int64), ("comp_len", ctypes.c_int64), ("x", ctypes.c_int64), ("y", ctypes.c_int64), ("w", ctypes.c_int64),
+                ("h", ctypes.c_int64), ("status", ctypes.c_int), ("pad", ctypes.c_int)]
+
+
+class TiffPut(ctypes.Structure):  # zs_tiff_put
+    _fields_ = [("pixels", ctypes.c_void_p), ("width", ctypes.c_int64), ("height", ctypes.c_int64), ("bits", ctypes.c_int), ("spp", ctypes.c_int),
+                ("sample_format", ctypes.c_int), ("photometric", ctypes.c_int), ("extra_samples", ctypes.c_int), ("extra_kind", ctypes.c_int),
+                ("predictor", ctypes.c_int), ("pad", ctypes.c_int), ("tile_width", ctypes.c_int64), ("tile_height", ctypes.c_int64),
+                ("rows_per_strip", ctypes.c_int64)]
 
 
 class PngSurvey(ctypes.Structure):  # zs_png_survey
@@ -252,6 +275,19 @@ def lib():
         L.zs_gzip_file_info.argtypes = [vp, i64, P(GzipInfo)]
         L.zs_gzip_decode_files_batch.restype = i32
         L.zs_gzip_decode_files_batch.argtypes = [vp, i32, P(vp), P(i64), P(vp), P(i64), P(i64), P(i32), P(i32), vp]
+    if hasattr(L, "zs_tiff_file_info"):
+        L.zs_tiff_file_info.restype = i32
+        L.zs_tiff_file_info.argtypes = [vp, i64, i64, P(TiffInfo), P(TiffChunk), i64]
+        L.zs_tiff_unpredict_batch_device.restype = i32
+        L.zs_tiff_unpredict_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i64), P(i64), P(i64), P(i32), P(i32), P(i32), P(i32), vp]
+        L.zs_tiff_predict_batch_device.restype = i32
+        L.zs_tiff_predict_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i64), P(i64), P(i64), P(i32), P(i32), P(i32), vp]
+        L.zs_tiff_decode_files_batch.restype = i32
+        L.zs_tiff_decode_files_batch.argtypes = [vp, i32, P(vp), P(i64), P(i64), P(vp), P(i64), P(i64), P(P(i32)), P(i32), vp]
+        L.zs_tiff_bound.restype = i64
+        L.zs_tiff_bound.argtypes = [P(TiffPut)]
+        L.zs_tiff_encode_batch_device.restype = i32
+        L.zs_tiff_encode_batch_device.argtypes = [vp, i32, P(TiffPut), P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
     if hasattr(L, "zs_zip_file_info"):
         L.zs_zip_file_info.restype = i32
         L.zs_zip_file_info.argtypes = [vp, i64, P(ZipInfo), P(ZipEntry), i64]

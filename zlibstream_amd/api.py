@@ -1480,6 +1480,147 @@ def zip_encode_batch_device(engine, archives, out_ptrs, out_caps, level=6, strat
     return rc, list(out_len), list(status)
 
 
+_TIFF_INFO_FIELDS = ("n_pages", "big_endian", "bigtiff", "width", "height", "bits", "spp", "sample_format", "photometric", "extra_samples",
+                     "extra_kind", "compression", "predictor", "planar", "orientation", "tiled", "chunk_w", "chunk_h", "n_chunks", "row_bytes",
+                     "out_len")
+_TIFF_CHUNK_FIELDS = ("off", "comp_len", "x", "y", "w", "h", "status")
+_TIFF_PUT_DEFAULTS = {"bits": 8, "spp": 1, "sample_format": 1, "photometric": 1, "extra_samples": 0, "extra_kind": 0, "predictor": 1, "tile_width": 0,
+                      "tile_height": 0, "rows_per_strip": 0}
+
+
+def tiff_file_info(data, page=0):
+    """zs_tiff_file_info (host code, no GPU, no engine): (info dict, [chunk dicts]) of one page of a TIFF file -- the fields of
+    zs_tiff_info and zs_tiff_chunk.  A chunk (a strip or a tile) that the file ends in has a non-zero "status";
+    ZlibStreamException, with the library's code in its text, for a file or a page the library does not read."""
+    data = bytes(data)
+    L = _native.lib()
+    info = _native.TiffInfo()
+    rc = L.zs_tiff_file_info(data, len(data), int(page), ctypes.byref(info), None, 0)
+    if rc != 0:
+        raise ZlibStreamException("tiff_file_info: not a TIFF page this library reads (%d)" % rc)
+    n = int(info.n_chunks)
+    chunks = (_native.TiffChunk * max(n, 1))()
+    rc = L.zs_tiff_file_info(data, len(data), int(page), ctypes.byref(info), chunks, n)
+    if rc != 0:
+        raise ZlibStreamException("tiff_file_info: not a TIFF page this library reads (%d)" % rc)
+    return {k: int(getattr(info, k)) for k in _TIFF_INFO_FIELDS}, [{k: int(getattr(c, k)) for k in _TIFF_CHUNK_FIELDS} for c in chunks[:n]]
+
+
+def tiff_decode_files(engine, files, out_ptrs, out_caps, pages=None, stream=None):
+    """TIFF files (bytes objects in host memory) -> the pixels of one page each in device buffers, rows of row_bytes bytes with
+    little-endian samples, many files a call (zs_tiff_decode_files_batch).  pages: per file the page, None for page 0 of all.
+    Returns (code, lengths, per file the list of its chunks' codes, per-file codes): a file's code is 0, its own error, or its
+    first failing chunk's (-3 ZS_DATA_ERROR, -5 ZS_BUF_ERROR); the list of a file whose page could not be walked, or whose
+    capacity was too small, is empty.  engine.last_error() names the first failing file, the chunk and the reason."""
+    n = len(files)
+    if len(out_ptrs) != n or len(out_caps) != n or (pages is not None and len(pages) != n):
+        raise ValueError("tiff_decode_files: the argument lists differ in length")
+    if any(not o or int(cap) < 0 for o, cap in zip(out_ptrs, out_caps)) or (pages is not None and any(int(p) < 0 for p in pages)):
+        raise ValueError("tiff_decode_files: non-null device pointers and non-negative capacities and pages are required")
+    if n == 0:
+        return 0, [], [], []
+    L = _native.lib()
+    files = [bytes(f) for f in files]
+    keep = [ctypes.create_string_buffer(f, len(f)) if f else ctypes.create_string_buffer(1) for f in files]
+    counts = []  # chunks whose codes the call writes: none for a file it does not walk or has no room for
+    for i, (f, cap) in enumerate(zip(files, out_caps)):
+        info = _native.TiffInfo()
+        walked = len(f) <= _CRC_MAX_LEN and L.zs_tiff_file_info(f, len(f), int(pages[i]) if pages is not None else 0, ctypes.byref(info), None, 0) == 0
+        counts.append(int(info.n_chunks) if walked and info.out_len <= int(cap) else 0)
+    per_chunk = [(ctypes.c_int * max(k, 1))() for k in counts]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    rows = (ctypes.POINTER(ctypes.c_int) * n)(*[ctypes.cast(r, ctypes.POINTER(ctypes.c_int)) for r in per_chunk])
+    rc = L.zs_tiff_decode_files_batch(engine.handle if engine is not None else None, n, VP(*[ctypes.addressof(k) for k in keep]), I64(*[len(f) for f in files]),
+                                      I64(*[int(p) for p in pages]) if pages is not None else None, VP(*[int(p) for p in out_ptrs]),
+                                      I64(*[int(x) for x in out_caps]), out_len, rows, status, ctypes.c_void_p(stream or 0))
+    if rc not in (0, 2, -3, -5):
+        raise ValueError("zs_tiff_decode_files_batch failed (%d): %s" % (rc, engine.last_error() if engine is not None else "no engine"))
+    return rc, list(out_len), [list(per_chunk[i][:counts[i]]) for i in range(n)], list(status)
+
+
+def _tiff_put(image, p=None):
+    """A dict of pixels (device pointer), width, height and, where they differ from _TIFF_PUT_DEFAULTS, the other fields of a
+    zs_tiff_put."""
+    p = p if p is not None else _native.TiffPut()
+    unknown = set(image) - set(_TIFF_PUT_DEFAULTS) - {"pixels", "width", "height"}
+    if unknown:
+        raise ValueError("a TIFF image has no field %s" % sorted(unknown))
+    p.pixels, p.width, p.height = int(image["pixels"]) or None, int(image["width"]), int(image["height"])
+    for k, v in _TIFF_PUT_DEFAULTS.items():
+        setattr(p, k, int(image.get(k, v)))
+    return p
+
+
+def tiff_bound(image):
+    """zs_tiff_bound (host code): room that tiff_encode needs for this image (a dict, see tiff_encode) at the most."""
+    r = _native.lib().zs_tiff_bound(ctypes.byref(_tiff_put(image)))
+    if r < 0:
+        raise ValueError("tiff_bound: a field out of range, or a file that would need BigTIFF")
+    return r
+
+
+def tiff_encode(engine, images, out_ptrs, out_caps, level=6, strategy=0, hash_variant=0, stream=None):
+    """Device-resident images into Deflate TIFF files in device buffers, many files a call (zs_tiff_encode_batch_device).
+    images: per file a dict of pixels (device pointer: height rows of ceil(width * spp * bits / 8) bytes, little-endian), width,
+    height and optionally bits (8), spp (1), sample_format (1), photometric (1), extra_samples (0), extra_kind (0), predictor
+    (1; 2 horizontal, 3 floating point), tile_width and tile_height (0: strips), rows_per_strip (0: about 256 KiB a strip).
+    Returns (code, lengths, per-file codes): -5 (ZS_BUF_ERROR) for a file whose capacity was too small -- its length is then
+    what it needs, nothing is written for it and the others are complete."""
+    n = len(images)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("tiff_encode: the argument lists differ in length")
+    if n == 0:
+        return 0, [], []
+    puts = (_native.TiffPut * n)()
+    for p, im in zip(puts, images):
+        _tiff_put(im, p)
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    rc = _native.lib().zs_tiff_encode_batch_device(engine.handle if engine is not None else None, n, puts, VP(*[int(p) for p in out_ptrs]),
+                                                   I64(*[int(x) for x in out_caps]), out_len, status, int(level), int(strategy), int(hash_variant),
+                                                   ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError("zs_tiff_encode_batch_device: a field out of range, or a file that would need BigTIFF")
+    if rc not in (0, -5):
+        raise ZlibStreamException("tiff encode: " + engine.last_error())
+    return rc, list(out_len), list(status)
+
+
+def _tiff_kernel_call(fn, name, engine, in_ptrs, out_ptrs, lists, stream):
+    n = len(in_ptrs)
+    if len(out_ptrs) != n or any(len(x) != n for x in lists if x is not None):
+        raise ValueError(name + ": the argument lists differ in length")
+    if n == 0:
+        return
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    args = [(I64 if k < 4 else I32)(*[int(v) for v in x]) if x is not None else None for k, x in enumerate(lists)]
+    rc = fn(engine.handle if engine is not None else None, n, VP(*[int(p) for p in in_ptrs]), VP(*[int(p) for p in out_ptrs]), *args,
+            ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError(name + ": " + ((engine.last_error() if engine is not None else "") or "stream error"))
+    if rc != 0:
+        raise ZlibStreamException("%s failed (%d): %s" % (name, rc, engine.last_error()))
+
+
+def tiff_unpredict(engine, in_ptrs, out_ptrs, widths, heights, bits, spp, predictors, out_widths=None, out_heights=None, big_endian=None, stream=None):
+    """Decoded TIFF chunks -> pixels (zs_tiff_unpredict_batch_device, the undo kernel alone): chunk i of widths[i] x heights[i]
+    pixels at in_ptrs[i], its top left out_widths[i] x out_heights[i] (default: all of it) to out_ptrs[i], predictor 1, 2 or 3
+    undone and big-endian samples swapped.  Device pointers of any alignment."""
+    ow, oh = out_widths if out_widths is not None else widths, out_heights if out_heights is not None else heights
+    _tiff_kernel_call(_native.lib().zs_tiff_unpredict_batch_device, "tiff_unpredict", engine, in_ptrs, out_ptrs,
+                      [widths, heights, ow, oh, bits, spp, predictors, big_endian], stream)
+
+
+def tiff_predict(engine, in_ptrs, out_ptrs, in_widths, in_heights, bits, spp, predictors, widths=None, heights=None, stream=None):
+    """Pixels -> predicted TIFF chunks (zs_tiff_predict_batch_device, the forward kernel alone): in_widths[i] x in_heights[i]
+    pixels at in_ptrs[i] into a chunk of widths[i] x heights[i] (default: the same) at out_ptrs[i], the surplus filled by
+    repeating the last pixel and row, then differenced (2) or split into byte planes and differenced (3)."""
+    w, h = widths if widths is not None else in_widths, heights if heights is not None else in_heights
+    _tiff_kernel_call(_native.lib().zs_tiff_predict_batch_device, "tiff_predict", engine, in_ptrs, out_ptrs,
+                      [in_widths, in_heights, w, h, bits, spp, predictors], stream)
+
+
 _default_engine = None
 
 
