@@ -1022,8 +1022,9 @@ ZS_API const char *zs_last_message(const zs_deflate_stream *s);
  *   (the reader has run out of input for now: ZlibInputStream.ReadCore behind a writer's flush) decodes what the bytes so
  *   far hold in complete blocks -- a flush ends on a block boundary (Deflate.cs:583-613), so everything the writer flushed
  *   is delivered -- and the stream goes on piece by piece from there with the next input; so does a stream that is fed 64
- *   MiB without a call for output (bounded host memory for a stream of any length).  ZS_STREAM_END comes with the last
- *   byte.  total_in is the stream's length with its trailer; bytes behind the trailer that the call which met the end
+ *   MiB without a call for output (bounded host memory for a stream of any length).  A block is complete when its last
+ *   bit has arrived; the final block only when the four trailer bytes behind it have, so it is held back until then
+ *   (tests/inflate_stream_cases.py states the rule and pins it).  ZS_STREAM_END comes with the last byte.  total_in is the stream's length with its trailer; bytes behind the trailer that the call which met the end
  *   brought are left to the caller (*avail_in), as the managed engine leaves them; bytes behind it from earlier calls
  *   (the end is only looked for now and then) are kept: zs_inflate_surplus.  A call without input that has nothing new to
  *   give is ZS_BUF_ERROR (Inflate.Decompress's "no progress"); corrupt data gives ZS_DATA_ERROR with the reference's

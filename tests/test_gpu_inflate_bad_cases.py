@@ -221,8 +221,10 @@ def test_caps_sweep_in_one_batch(engine, oracle):
 
 @pytest.mark.parametrize("name", [n for n in bc.NAMES if bc.META[n][2] == "behind_100k" and bc.case(n)[2] != bc.ZS_STREAM_END])
 def test_rejected_behind_100k_through_zlib_input_stream(engine, name):
-    """Read 70 000 bytes at a time: the piece-wise path.  The exception carries the message, and what read() returned before
-    it is a prefix of the plaintext."""
+    """Read 70 000 bytes at a time.  With a BytesIO underneath the mirror feeds the whole stream before the first decode: the
+    end of a malformed stream is not found, so the one call without input decodes it as a first piece that holds everything
+    (no piece is resumed here; tests/test_gpu_inflate_stream.py does that).  The exception carries the message, and what
+    read() returned before it is a prefix of the plaintext."""
     _, z, _, message, _, prefix = bc.case(name)
     s = ZlibInputStream(io.BytesIO(z), engine=engine)
     got = bytearray()

@@ -57,7 +57,10 @@ def test_built_streams_in_one_batch(engine, order):
 
 @pytest.mark.parametrize("name", [n for n in db.case_names() if n == "all_codes" or n.startswith(("empties_", "nested_"))])
 def test_built_stream_through_zlib_input_stream(engine, name):
-    """Read 70 000 bytes at a time: the probing calls run finder, measure and chain on prefixes of the stream."""
+    """Read 70 000 bytes at a time.  With a BytesIO underneath the mirror feeds the whole stream, 8 KiB a call, before the
+    first decode: a stream above 1 MiB has its end looked for on a prefix on the way (finder, measure and chain), and the
+    call without input then decodes the whole stream at once -- nothing here is decoded piece by piece
+    (tests/test_gpu_inflate_stream.py does that)."""
     _, z, plain, _ = db.case(name)
     s = ZlibInputStream(io.BytesIO(z), engine=engine)
     got = bytearray()
