@@ -419,6 +419,135 @@ ZS_API int zs_tiff_encode_batch_device(zs_ctx *ctx, int n, const zs_tiff_put *pu
                                        void *hip_stream);
 
 /* ------------------------------------------------------------------ */
+/* OpenEXR files with ZIP / ZIPS compression: whole files decoded on the device into channel planes, and files written there.
+ * Such a file is a batch of independent zlib streams, one per chunk of 1 (ZIPS) or 16 (ZIP) scanlines or per tile, with a
+ * byte predictor over the whole chunk in front.  No third-party reader was at hand when this was written: the rules below,
+ * which zlibstream_amd/csrc/zs_exr.h implements, are what the tests pin.
+ *   File head.  Bytes 0-3 are 76 2F 31 01; bytes 4-7 a little-endian version word whose low byte must be 2.  Bit 0x200: single
+ *     part, tiled.  Bit 0x400: long names, up to 255 bytes, otherwise 31.  Bit 0x800 (deep data), bit 0x1000 (multi-part) and
+ *     every other bit are refused.  All integers and samples in the file are little-endian.
+ *   Header.  Attributes: name\0 type\0 int32 size, then size bytes; a single \0 where a name would start ends the list.  Read:
+ *     `channels` (chlist), `compression` (compression, 1 byte), `dataWindow` (box2i: xMin, yMin, xMax, yMax as int32,
+ *     inclusive, negative values allowed), `lineOrder` (lineOrder, 1 byte: 0 increasing, 1 decreasing, 2 random, tiles only),
+ *     with 0x200 `tiles` (tiledesc: uint32 xSize, uint32 ySize, a mode byte whose low nibble is 0 ONE_LEVEL, 1 MIPMAP,
+ *     2 RIPMAP); `displayWindow` (box2i) is reported when present; every other attribute is stepped over.
+ *   Channel list.  Per channel name\0, int32 type (0 UINT 4 bytes, 1 HALF 2 bytes, 2 FLOAT 4 bytes), uint8 pLinear, 3 reserved
+ *     bytes, int32 xSampling, int32 ySampling; a \0 ends the list.  The file's layout order is the list's order (writers sort
+ *     byte-wise, so RGBA lies as A, B, G, R; the reader does not demand it).
+ *   Compression.  0 none, 2 ZIPS (1 line a chunk), 3 ZIP (16 lines a chunk); every other value (RLE 1, PIZ 4, PXR24 5, B44 6,
+ *     B44A 7, DWAA 8, DWAB 9) is "unsupported compression method".
+ *   Offset table.  Directly behind the header, one uint64 absolute file offset per chunk.  Scanlines: n = ceil(H / L), entry k
+ *     is the chunk whose first line is yMin + k L whatever the line order (decreasing order only changes where the bodies
+ *     lie).  ONE_LEVEL tiles: n = ceil(W / tx) ceil(H / ty), entry tileY * nx + tileX.
+ *   Chunk.  Scanlines: int32 y, int32 dataSize, data.  Tiles: int32 tileX, tileY, levelX, levelY, int32 dataSize, data.  The
+ *     coordinates must match the table slot.  The chunk's raw bytes U: for each row, for each channel in list order, w samples
+ *     -- w the image's width or the part of the tile inside the data window; edge tiles and a last scanline chunk hold only
+ *     the pixels and rows they have.  dataSize == U: the bytes lie raw (always so under compression 0; also what a writer
+ *     does when zlib did not shrink the chunk).  dataSize < U: a zlib stream that must inflate to exactly U bytes t[0 .. U),
+ *     which are undone in two steps: t[i] = (t[i-1] + t[i] - 128) mod 256 for i >= 1, then raw[2k] = t[k], raw[2k+1] = t[h+k]
+ *     with h = (U + 1) / 2.  (Raw 01 02 03 04 05 is split 01 03 05 02 04 and stored 01 82 82 7D 82.)
+ *   ZS_DATA_ERROR for the file, each with its own message: "not an OpenEXR file", an unsupported version, deep data,
+ *     multi-part, other flag bits, "the header reaches out of the file", a name longer than the flags allow, an attribute
+ *     whose size disagrees with its type (for the five read), "a required attribute is missing", an empty or inverted data
+ *     window, no channels or more than 64, "unsupported pixel type", "unsupported channel sampling" (any sampling != 1),
+ *     "unsupported level mode" (MIPMAP, RIPMAP), tile size 0, line order 2 on scanlines, "the offset table reaches out of the
+ *     file", pixels above 2 GiB - 1 KiB.  Per chunk, the walk going on: "a chunk's coordinates do not match its place",
+ *     "invalid chunk size" (dataSize > U or < 0).
+ *   ZS_BUF_ERROR: a file shorter than 8 bytes; per chunk, the walk going on, an offset or body that the file ends in.
+ * Output layout: channel-planar, the layout a tensor wants and the only one that holds mixed types.  Plane c is H rows of W
+ * samples, little-endian, at plane_off[c]: the running sum of the planes' bytes, rounded up to 16; out_len is the end of the
+ * last plane; the padding bytes between planes are never written.
+ * Out of scope: tiles, decreasing order and long names on the write side; mip / rip levels; multi-part and deep files;
+ * sampled channels; every codec but zlib; interleaved (H, W, C) output; the dotnet shim has no binding for these calls. */
+typedef struct zs_exr_info {
+    int32_t data_window[4], display_window[4];  /* xMin, yMin, xMax, yMax */
+    int64_t width, height;
+    int n_channels, compression, line_order, tiled;
+    int has_display_window, long_names;
+    int64_t tile_w, tile_h;             /* 0 for scanline files */
+    int64_t lines_per_chunk, n_chunks;  /* 1 or 16, or a tile's height */
+    int64_t out_len;                    /* what the decode call writes into */
+} zs_exr_info;
+
+typedef struct zs_exr_channel {
+    char name[256];
+    int type, sample_bytes;             /* 0 UINT, 1 HALF, 2 FLOAT; 4, 2, 4 */
+    int64_t plane_off;
+} zs_exr_channel;
+
+typedef struct zs_exr_chunk {
+    int64_t off, data_len, raw_len;     /* the data behind the chunk's header in the file (dataSize bytes), and U */
+    int64_t x, y, w, h;                 /* its place, counted from the data window's corner */
+    int status, pad;                    /* ZS_OK, ZS_BUF_ERROR or ZS_DATA_ERROR (rules above; off and data_len are 0 then) */
+} zs_exr_chunk;
+
+/* One file in HOST memory, pure host code, no context and no GPU.  ZS_OK, *info, the channels and the chunks; the file's error
+ * (rules above) with *info as far as the walk got; ZS_STREAM_ERROR for null pointers or negative numbers.  channels and chunks
+ * may be NULL (cap 0) to ask for the counts only; a cap below the count: ZS_BUF_ERROR with info filled and the first cap
+ * entries written. */
+ZS_API int zs_exr_file_info(const void *file, int64_t len, zs_exr_info *info, zs_exr_channel *channels, int64_t channels_cap,
+                            zs_exr_chunk *chunks, int64_t chunks_cap);
+
+/* The predictor kernels alone (KE), n chunks a call, DEVICE pointers of any alignment, len[i] in
+ * 1 .. 2^31 - 1, contiguous in, contiguous out.  Undo: in[i] holds a chunk's inflated bytes t, out[i] receives its raw bytes
+ * (both steps above).  Predict is the inverse.  ZS_STREAM_ERROR before any device work for null arrays or pointers or a length
+ * out of range.  n == 0 is ZS_OK.  With a hip_stream the launches stay in flight on it. */
+ZS_API int zs_exr_unpredict_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *len,
+                                         void *hip_stream);
+ZS_API int zs_exr_predict_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *len,
+                                       void *hip_stream);
+
+/* OpenEXR files to channel planes, n files a call.  file[i] / file_len[i]: whole files in HOST memory; they go to the device
+ * in one copy and are walked on the host.  out[i] (DEVICE pointer, out_cap[i] bytes) receives the planes (layout above),
+ * out_len[i] is the file's out_len.  All zlib chunks of all files are the streams of one inflate launch, read from
+ * 16-byte-aligned pointers wherever they lie in their files, into a buffer the context owns; their Adler-32s are checked by
+ * one more launch ("incorrect data check"); a stream that yields fewer or more than U bytes is ZS_DATA_ERROR "incorrect length
+ * check".  One launch of the undo kernel over all chunks then writes the planes; chunks that lie raw come from the uploaded
+ * file and take the same launch with both steps off.
+ * out_cap[i] < out_len: ZS_BUF_ERROR for that file, nothing of it is decoded, out_len[i] says what it needs.  A file above
+ * 2 GiB - 1 KiB: ZS_DATA_ERROR for that file.
+ * chunk_status (HOST, may be NULL, as may chunk_status[i]): n_chunks ints per file, ZS_OK or the chunk's code; written only
+ * for a file whose header was walked and whose out_cap sufficed.  status[i] (may be NULL): ZS_OK, the file's error, or its
+ * first failing chunk's code; zs_ctx_last_error names the first failing file, the chunk and the reason ("file 1: chunk 7:
+ * incorrect data check").  A failing chunk's pixels are unspecified, every other chunk is complete, and nothing is written
+ * outside [out[i], out[i] + out_len).  Returns ZS_OK, the first failing file's code, ZS_MEM_ERROR, or, before any device work,
+ * ZS_STREAM_ERROR: null context, n < 0, null arrays or pointers, a negative length or capacity. */
+ZS_API int zs_exr_decode_files_batch(zs_ctx *ctx, int n, const void *const *file, const int64_t *file_len, void *const *out,
+                                     const int64_t *out_cap, int64_t *out_len, int *const *chunk_status, int *status,
+                                     void *hip_stream);
+
+typedef struct zs_exr_put {
+    const void *planes;                 /* DEVICE pointer: the channel planes, layout above */
+    int64_t width, height;              /* 1 .. 2^31 - 1, the planes at most 2 GiB - 1 KiB */
+    int32_t x_min, y_min;               /* the data window's corner; the display window is written equal to the data window */
+    int n_channels, compression;        /* 1 .. 64; 0, 2 (ZIPS) or 3 (ZIP) */
+    const char *const *names;           /* HOST: n_channels names of 1 .. 31 bytes, sorted byte-wise, none twice */
+    const int *types;                   /* HOST: 0 UINT, 1 HALF, 2 FLOAT */
+    const void *extra;                  /* HOST, may be NULL: attributes the caller has encoded, copied verbatim behind the others */
+    int64_t extra_len;
+} zs_exr_put;
+
+/* Room that zs_exr_encode_batch_device needs for this image at the most: the head, the offset table, and per chunk its eight
+ * bytes of header and its raw bytes (a chunk that zlib does not shrink is stored raw).  Pure host code.  -1 for what that
+ * call refuses: a null pointer, a field out of range, names that are unsorted, repeated, empty or longer than 31 bytes. */
+ZS_API int64_t zs_exr_bound(const zs_exr_put *put);
+
+/* Channel planes in device memory to OpenEXR files in device memory, n files a call: single-part scanline files, version word
+ * 02 00 00 00, increasing Y, the attributes channels, compression, dataWindow, displayWindow, lineOrder, pixelAspectRatio 1.0,
+ * screenWindowCenter (0, 0), screenWindowWidth 1.0 and the extras, in this order.  One launch of the forward kernel gathers,
+ * splits and differences every chunk, one zs_deflate_batch_device call deflates them all into a buffer the context owns -- a
+ * deflated chunk is, bit for bit, what that call writes for the same predicted bytes, level, strategy and hash variant --,
+ * the host reads the lengths, a chunk whose stream is not shorter than its raw bytes is stored raw (a second, small forward
+ * launch with both steps off, for those chunks only), the host builds head, offset table and chunk headers, and one framing
+ * launch (KC's span copy) assembles the files.
+ * out_len / out_cap / status / the return value: as for zs_tiff_encode_batch_device -- a file that does not fit is
+ * ZS_BUF_ERROR, out_len[i] says what it needs, nothing is written for it and the others are complete; zs_exr_bound is always
+ * enough.  ZS_STREAM_ERROR before any device work for what zs_exr_bound answers with -1, and for null arrays or pointers. */
+ZS_API int zs_exr_encode_batch_device(zs_ctx *ctx, int n, const zs_exr_put *puts, void *const *out, const int64_t *out_cap,
+                                      int64_t *out_len, int *status, int level, int strategy, int hash_variant,
+                                      void *hip_stream);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU batch entry points (SURVEY.md 8(b) "zs_deflate_batch(..., device_mask)", 8(e)): the n independent
  * buffers are partitioned over n_ctx contexts -- normally one per GPU of the node, zs_ctx_create(0 .. count-1) --
  * by size (longest-processing-time, zs_partition), each context's share runs on its own host thread through the

@@ -28,6 +28,8 @@ SYMBOLS = [
     "zs_zip_file_info", "zs_zip_decode_files_batch", "zs_zip_bound", "zs_zip_encode_batch_device",
     "zs_tiff_file_info", "zs_tiff_unpredict_batch_device", "zs_tiff_predict_batch_device", "zs_tiff_decode_files_batch", "zs_tiff_bound",
     "zs_tiff_encode_batch_device",
+    "zs_exr_file_info", "zs_exr_unpredict_batch_device", "zs_exr_predict_batch_device", "zs_exr_decode_files_batch", "zs_exr_bound",
+    "zs_exr_encode_batch_device",
 ]
 
 
@@ -79,6 +81,28 @@ class TiffPut(ctypes.Structure):  # zs_tiff_put
                 ("sample_format", ctypes.c_int), ("photometric", ctypes.c_int), ("extra_samples", ctypes.c_int), ("extra_kind", ctypes.c_int),
                 ("predictor", ctypes.c_int), ("pad", ctypes.c_int), ("tile_width", ctypes.c_int64), ("tile_height", ctypes.c_int64),
                 ("rows_per_strip", ctypes.c_int64)]
+
+
+class ExrInfo(ctypes.Structure):  # zs_exr_info
+    _fields_ = [("data_window", ctypes.c_int32 * 4), ("display_window", ctypes.c_int32 * 4), ("width", ctypes.c_int64), ("height", ctypes.c_int64),
+                ("n_channels", ctypes.c_int), ("compression", ctypes.c_int), ("line_order", ctypes.c_int), ("tiled", ctypes.c_int),
+                ("has_display_window", ctypes.c_int), ("long_names", ctypes.c_int), ("tile_w", ctypes.c_int64), ("tile_h", ctypes.c_int64),
+                ("lines_per_chunk", ctypes.c_int64), ("n_chunks", ctypes.c_int64), ("out_len", ctypes.c_int64)]
+
+
+class ExrChannel(ctypes.Structure):  # zs_exr_channel
+    _fields_ = [("name", ctypes.c_char * 256), ("type", ctypes.c_int), ("sample_bytes", ctypes.c_int), ("plane_off", ctypes.c_int64)]
+
+
+class ExrChunk(ctypes.Structure):  # zs_exr_chunk
+    _fields_ = [("off", ctypes.c_int64), ("data_len", ctypes.c_int64), ("raw_len", ctypes.c_int64), ("x", ctypes.c_int64), ("y", ctypes.c_int64),
+                ("w", ctypes.c_int64), ("h", ctypes.c_int64), ("status", ctypes.c_int), ("pad", ctypes.c_int)]
+
+
+class ExrPut(ctypes.Structure):  # zs_exr_put
+    _fields_ = [("planes", ctypes.c_void_p), ("width", ctypes.c_int64), ("height", ctypes.c_int64), ("x_min", ctypes.c_int32), ("y_min", ctypes.c_int32),
+                ("n_channels", ctypes.c_int), ("compression", ctypes.c_int), ("names", ctypes.POINTER(ctypes.c_char_p)),
+                ("types", ctypes.POINTER(ctypes.c_int)), ("extra", ctypes.c_char_p), ("extra_len", ctypes.c_int64)]
 
 
 class PngSurvey(ctypes.Structure):  # zs_png_survey
@@ -288,6 +312,19 @@ def lib():
         L.zs_tiff_bound.argtypes = [P(TiffPut)]
         L.zs_tiff_encode_batch_device.restype = i32
         L.zs_tiff_encode_batch_device.argtypes = [vp, i32, P(TiffPut), P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
+    if hasattr(L, "zs_exr_file_info"):
+        L.zs_exr_file_info.restype = i32
+        L.zs_exr_file_info.argtypes = [vp, i64, P(ExrInfo), P(ExrChannel), i64, P(ExrChunk), i64]
+        L.zs_exr_unpredict_batch_device.restype = i32
+        L.zs_exr_unpredict_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), vp]
+        L.zs_exr_predict_batch_device.restype = i32
+        L.zs_exr_predict_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), vp]
+        L.zs_exr_decode_files_batch.restype = i32
+        L.zs_exr_decode_files_batch.argtypes = [vp, i32, P(vp), P(i64), P(vp), P(i64), P(i64), P(P(i32)), P(i32), vp]
+        L.zs_exr_bound.restype = i64
+        L.zs_exr_bound.argtypes = [P(ExrPut)]
+        L.zs_exr_encode_batch_device.restype = i32
+        L.zs_exr_encode_batch_device.argtypes = [vp, i32, P(ExrPut), P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
     if hasattr(L, "zs_zip_file_info"):
         L.zs_zip_file_info.restype = i32
         L.zs_zip_file_info.argtypes = [vp, i64, P(ZipInfo), P(ZipEntry), i64]

@@ -1621,6 +1621,151 @@ def tiff_predict(engine, in_ptrs, out_ptrs, in_widths, in_heights, bits, spp, pr
                       [in_widths, in_heights, w, h, bits, spp, predictors], stream)
 
 
+_EXR_INFO_FIELDS = ("width", "height", "n_channels", "compression", "line_order", "tiled", "has_display_window", "long_names", "tile_w", "tile_h",
+                    "lines_per_chunk", "n_chunks", "out_len")
+_EXR_CHUNK_FIELDS = ("off", "data_len", "raw_len", "x", "y", "w", "h", "status")
+EXR_UINT, EXR_HALF, EXR_FLOAT = 0, 1, 2
+
+
+def exr_file_info(data):
+    """zs_exr_file_info (host code, no GPU, no engine): (info dict, [channel dicts], [chunk dicts]) of an OpenEXR file -- the
+    fields of zs_exr_info (the windows as 4-tuples xMin, yMin, xMax, yMax; display_window None where the file has none),
+    zs_exr_channel and zs_exr_chunk.  A chunk that the file ends in, or whose header is wrong, has a non-zero "status";
+    ZlibStreamException, with the library's code in its text, for a file the library does not read."""
+    data = bytes(data)
+    L = _native.lib()
+    info = _native.ExrInfo()
+    rc = L.zs_exr_file_info(data, len(data), ctypes.byref(info), None, 0, None, 0)
+    if rc != 0:
+        raise ZlibStreamException("exr_file_info: not an OpenEXR file this library reads (%d)" % rc)
+    nc, n = int(info.n_channels), int(info.n_chunks)
+    channels, chunks = (_native.ExrChannel * max(nc, 1))(), (_native.ExrChunk * max(n, 1))()
+    rc = L.zs_exr_file_info(data, len(data), ctypes.byref(info), channels, nc, chunks, n)
+    if rc != 0:
+        raise ZlibStreamException("exr_file_info: not an OpenEXR file this library reads (%d)" % rc)
+    out = {k: int(getattr(info, k)) for k in _EXR_INFO_FIELDS}
+    out["data_window"] = tuple(int(v) for v in info.data_window)
+    out["display_window"] = tuple(int(v) for v in info.display_window) if info.has_display_window else None
+    return (out, [{"name": c.name.decode("latin-1"), "type": int(c.type), "sample_bytes": int(c.sample_bytes), "plane_off": int(c.plane_off)} for c in channels[:nc]],
+            [{k: int(getattr(c, k)) for k in _EXR_CHUNK_FIELDS} for c in chunks[:n]])
+
+
+def exr_decode_files(engine, files, out_ptrs, out_caps, stream=None):
+    """OpenEXR files (bytes objects in host memory) -> their channel planes in device buffers (plane c at plane_off[c], H rows
+    of W little-endian samples), many files a call (zs_exr_decode_files_batch).  Returns (code, lengths, per file the list of
+    its chunks' codes, per-file codes): a file's code is 0, its own error, or its first failing chunk's (-3 ZS_DATA_ERROR,
+    -5 ZS_BUF_ERROR); the list of a file whose header could not be walked, or whose capacity was too small, is empty.
+    engine.last_error() names the first failing file, the chunk and the reason."""
+    n = len(files)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("exr_decode_files: the argument lists differ in length")
+    if any(not o or int(cap) < 0 for o, cap in zip(out_ptrs, out_caps)):
+        raise ValueError("exr_decode_files: non-null device pointers and non-negative capacities are required")
+    if n == 0:
+        return 0, [], [], []
+    L = _native.lib()
+    files = [bytes(f) for f in files]
+    keep = [ctypes.create_string_buffer(f, len(f)) if f else ctypes.create_string_buffer(1) for f in files]
+    counts = []  # chunks whose codes the call writes: none for a file it does not walk or has no room for
+    for f, cap in zip(files, out_caps):
+        info = _native.ExrInfo()
+        walked = len(f) <= _CRC_MAX_LEN and L.zs_exr_file_info(f, len(f), ctypes.byref(info), None, 0, None, 0) == 0
+        counts.append(int(info.n_chunks) if walked and info.out_len <= int(cap) else 0)
+    per_chunk = [(ctypes.c_int * max(k, 1))() for k in counts]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    rows = (ctypes.POINTER(ctypes.c_int) * n)(*[ctypes.cast(r, ctypes.POINTER(ctypes.c_int)) for r in per_chunk])
+    rc = L.zs_exr_decode_files_batch(engine.handle if engine is not None else None, n, VP(*[ctypes.addressof(k) for k in keep]), I64(*[len(f) for f in files]),
+                                     VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len, rows, status, ctypes.c_void_p(stream or 0))
+    if rc not in (0, 2, -3, -5):
+        raise ValueError("zs_exr_decode_files_batch failed (%d): %s" % (rc, engine.last_error() if engine is not None else "no engine"))
+    return rc, list(out_len), [list(per_chunk[i][:counts[i]]) for i in range(n)], list(status)
+
+
+def _exr_put(image, p=None):
+    """A dict of planes (device pointer), width, height, channels (a list of (name, type) pairs) and optionally x_min, y_min
+    (0), compression (3) and extra (bytes) as a zs_exr_put; the arrays it points to hang on the struct."""
+    p = p if p is not None else _native.ExrPut()
+    unknown = set(image) - {"planes", "width", "height", "channels", "x_min", "y_min", "compression", "extra"}
+    if unknown:
+        raise ValueError("an OpenEXR image has no field %s" % sorted(unknown))
+    channels = list(image["channels"])
+    names = [c[0].encode("latin-1") if isinstance(c[0], str) else bytes(c[0]) for c in channels]
+    extra = bytes(image.get("extra", b""))
+    p._names = (ctypes.c_char_p * max(len(names), 1))(*names)
+    p._types = (ctypes.c_int * max(len(names), 1))(*[int(c[1]) for c in channels])
+    p._extra = ctypes.create_string_buffer(extra, len(extra)) if extra else None
+    p.planes, p.width, p.height = int(image["planes"]) or None, int(image["width"]), int(image["height"])
+    p.x_min, p.y_min, p.n_channels, p.compression = int(image.get("x_min", 0)), int(image.get("y_min", 0)), len(names), int(image.get("compression", 3))
+    p.names, p.types = p._names, p._types
+    p.extra, p.extra_len = ctypes.cast(p._extra, ctypes.c_char_p) if extra else None, len(extra)
+    return p
+
+
+def exr_bound(image):
+    """zs_exr_bound (host code): room that exr_encode needs for this image (a dict, see exr_encode) at the most."""
+    r = _native.lib().zs_exr_bound(ctypes.byref(_exr_put(image)))
+    if r < 0:
+        raise ValueError("exr_bound: a field out of range, or channel names that are unsorted, repeated, empty or longer than 31 bytes")
+    return r
+
+
+def exr_encode(engine, images, out_ptrs, out_caps, level=6, strategy=0, hash_variant=0, stream=None):
+    """Device-resident channel planes into OpenEXR files in device buffers, many files a call (zs_exr_encode_batch_device).
+    images: per file a dict of planes (device pointer: plane c at the running sum of the planes' bytes rounded up to 16, H rows
+    of W little-endian samples), width, height, channels (a list of (name, type) pairs sorted byte-wise by name; type 0 UINT,
+    1 HALF, 2 FLOAT) and optionally x_min, y_min (0), compression (3 ZIP; 2 ZIPS, 0 none) and extra (encoded attributes).
+    Returns (code, lengths, per-file codes): -5 (ZS_BUF_ERROR) for a file whose capacity was too small -- its length is then
+    what it needs, nothing is written for it and the others are complete."""
+    n = len(images)
+    if len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("exr_encode: the argument lists differ in length")
+    if n == 0:
+        return 0, [], []
+    puts = (_native.ExrPut * n)()
+    keep = []  # (an array's element is a copy each time it is read: the arrays of names and types are held here)
+    for k, im in enumerate(images):
+        q = _exr_put(im)
+        keep.append(q)
+        ctypes.memmove(ctypes.byref(puts, k * ctypes.sizeof(_native.ExrPut)), ctypes.byref(q), ctypes.sizeof(_native.ExrPut))
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    out_len, status = I64(), I32()
+    rc = _native.lib().zs_exr_encode_batch_device(engine.handle if engine is not None else None, n, puts, VP(*[int(p) for p in out_ptrs]),
+                                                  I64(*[int(x) for x in out_caps]), out_len, status, int(level), int(strategy), int(hash_variant),
+                                                  ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError("zs_exr_encode_batch_device: a field out of range, or channel names that are unsorted, repeated, empty or longer than 31 bytes")
+    if rc not in (0, -5):
+        raise ZlibStreamException("exr encode: " + engine.last_error())
+    return rc, list(out_len), list(status)
+
+
+def _exr_kernel_call(fn, name, engine, in_ptrs, out_ptrs, lens, stream):
+    n = len(in_ptrs)
+    if len(out_ptrs) != n or len(lens) != n:
+        raise ValueError(name + ": the argument lists differ in length")
+    if n == 0:
+        return
+    VP, I64 = ctypes.c_void_p * n, ctypes.c_int64 * n
+    rc = fn(engine.handle if engine is not None else None, n, VP(*[int(p) for p in in_ptrs]), VP(*[int(p) for p in out_ptrs]), I64(*[int(v) for v in lens]),
+            ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError(name + ": " + ((engine.last_error() if engine is not None else "") or "stream error"))
+    if rc != 0:
+        raise ZlibStreamException("%s failed (%d): %s" % (name, rc, engine.last_error()))
+
+
+def exr_unpredict(engine, in_ptrs, out_ptrs, lens, stream=None):
+    """Inflated OpenEXR chunks -> their raw bytes (zs_exr_unpredict_batch_device, the undo kernel alone): the running byte sum
+    over the whole chunk, then the two halves interleaved.  Device pointers of any alignment, lens[i] in 1 .. 2^31 - 1."""
+    _exr_kernel_call(_native.lib().zs_exr_unpredict_batch_device, "exr_unpredict", engine, in_ptrs, out_ptrs, lens, stream)
+
+
+def exr_predict(engine, in_ptrs, out_ptrs, lens, stream=None):
+    """Raw chunk bytes -> what an OpenEXR writer hands to zlib (zs_exr_predict_batch_device, the forward kernel alone)."""
+    _exr_kernel_call(_native.lib().zs_exr_predict_batch_device, "exr_predict", engine, in_ptrs, out_ptrs, lens, stream)
+
+
 _default_engine = None
 
 

@@ -1,6 +1,6 @@
 // zs_engine.hip -- host side of the MI355X deflate engine: workspace, kernel
 // pipeline, and the C ABI of include/zsgpu.h (the PNG and CRC-32 calls of it:
-// zs_png_host.inc; raw deflate, gzip members and gzip files: zs_wrap_host.inc; ZIP archives: zs_zip_host.inc; TIFF files: zs_tiff_host.inc).  No CPU fallback:
+// zs_png_host.inc; raw deflate, gzip members and gzip files: zs_wrap_host.inc; ZIP archives: zs_zip_host.inc; TIFF files: zs_tiff_host.inc; OpenEXR files: zs_exr_host.inc).  No CPU fallback:
 // without a usable HIP device every
 // compressing entry point fails.
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@
 #include "zs_gzip.hip"
 #include "zs_zip.hip"
 #include "zs_tiff.hip"
+#include "zs_exr.hip"
 #include "zs_plan.h"
 
 using namespace zs;
@@ -52,8 +53,9 @@ enum PngBuf {
     // the container calls (zs_wrap_host.inc): the members' descriptors and heads, the trailers gathered for the host, the zlib
     // streams in front of the framing launch, a call's files; the ZIP writer's zlib streams (zs_zip_host.inc); the TIFF calls'
     // chunks between inflate or deflate and the predictor kernel, that kernel's descriptors, the writer's zlib streams
-    // (zs_tiff_host.inc)
-    kBufWrapHead, kBufWrapGather, kBufWrapZs, kBufWrapFiles, kBufZipZs, kBufTiffChunks, kBufTiffDesc, kBufTiffZs, kBufPngCount
+    // (zs_tiff_host.inc); the same three of the OpenEXR calls, and KE's segment sums (zs_exr_host.inc)
+    kBufWrapHead, kBufWrapGather, kBufWrapZs, kBufWrapFiles, kBufZipZs, kBufTiffChunks, kBufTiffDesc, kBufTiffZs, kBufExrChunks, kBufExrDesc, kBufExrZs, kBufExrSegs,
+    kBufPngCount
 };
 
 struct PlanCache;  // the last deflate call's plan, kept for a same-shaped call (below, ahead of run_pipeline)
@@ -2065,6 +2067,7 @@ int zs_inflate_batch(zs_ctx *c, int n, const void *const *in, const int64_t *in_
 #include "zs_wrap_host.inc"
 #include "zs_zip_host.inc"
 #include "zs_tiff_host.inc"
+#include "zs_exr_host.inc"
 
 // ------------------------------------------------------------------ multi-GPU batch entry points
 // BASELINE north_star: "independent input buffers shard embarrassingly across the 8 GPUs of one node (no RCCL needed)".
