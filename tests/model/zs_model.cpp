@@ -960,7 +960,10 @@ static void run_tail(Model &m, int64_t p, int kind, uint32_t pend, int k_done, i
     m.wr_blk.assign(m.wr_end.size(), 0);
     if (m.flush_mode) e.wr_flush = m.wr_flush.data(), e.wr_blk = m.wr_blk.data();
     size_t body_syms = m.syms.size();
-    m.syms.resize(body_syms + 2 * kMinLookahead + 600 + (m.body_end < 0 ? (size_t)m.n : 0));
+    // the tail's symbols, one per position at the most: behind the other bodies the tail is a lookahead or two long; behind
+    // the Rle body it begins at rle_body_end's H, which lies up to kRleTailMax = 1302 positions in front of the end (zs_rle.h)
+    const size_t tail_room = m.strategy == kRle ? (size_t)kRleTailMax + 64 : 2 * kMinLookahead + 600;
+    m.syms.resize(body_syms + tail_room + (m.body_end < 0 ? (size_t)m.n : 0));
     e.syms = m.syms.data();
     e.nsyms = (int64_t)body_syms;
     size_t body_blocks = m.blocks.size();

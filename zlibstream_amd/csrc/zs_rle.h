@@ -61,4 +61,9 @@ inline int64_t rle_body_end(int64_t n) {
     return h >= 4096 ? h : -1;
 }
 
+// The longest tail a hand-over leaves: rle_body_end starts at n - 3 * kMinLookahead and moves at most once -- the triggers lie
+// kWSize apart -- from no further than t + kMaxMatch - 1 down to t - kMaxMatch - 1.  The tail engine emits at most one symbol per
+// position from H on: 786 + 516 = 1302.
+constexpr int64_t kRleTailMax = 3 * kMinLookahead + 2 * kMaxMatch;
+
 }  // namespace zs
