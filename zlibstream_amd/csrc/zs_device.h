@@ -178,6 +178,10 @@ struct StreamState {
     // whether every chunk's guessed entry was its predecessor's exit (the kernels of the map path then skip the stream), and
     // the chunks whose guess was wrong
     int32_t spec_run_tiles, spec_ok, spec_wrong;
+    // the split back end (zs_kernels.hip stream_body_blocks): part 0 of the offsets kernel leaves the stream bit position
+    // behind the finished blocks, and whether one of them is a stored block the reference cannot send, for part 1
+    int32_t body_bad;
+    int64_t body_bits;
 };
 // A speculative chunk's record: bits 0..8 the guessed entry slot, 9..17 the exit slot (relative to the next chunk's start, as
 // map_exit is), 18..29 the symbols of the chunk from the guess, bit 30: an event on the path is K4's business (kMapEqualBit /

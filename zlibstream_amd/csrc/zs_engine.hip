@@ -38,11 +38,11 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStPngCompose, kStPngDiff, kStPngCrop, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStPngCompose, kStPngDiff, kStPngCrop, kStPart1, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
                                            "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
-                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey", "png_compose", "png_diff", "png_crop"};
+                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey", "png_compose", "png_diff", "png_crop", "part1_chain"};
 
 // The context's device buffers of the PNG and CRC-32 calls (zs_png_host.inc), by what they hold: descriptors of a kernel
 // (..img, kBufCrcDesc), its records or results, or an intermediate of a call built from several kernels.
@@ -68,6 +68,9 @@ struct zs_ctx {
     hipStream_t aux = nullptr;  // second stream: tree building of the finished blocks runs beside the tail engine
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pre0 = nullptr, ev_pre = nullptr;
     hipEvent_t ev_spec[4] = {};           // the speculative walk and its verdict; the compaction of its symbols (profiling)
+    // the split back end: the symbols in place (main stream), the finished blocks placed (main stream); profiling: the part-1
+    // chain on the second stream, from behind the tail engine to its last launch
+    hipEvent_t ev_syms = nullptr, ev_part0 = nullptr, ev_part1[2] = {};
     std::string err;
     bool profiling = false;
     int fast_fallbacks = 0;  // speculative DeflateFast batches that had to be redone sequentially
@@ -220,6 +223,7 @@ struct LaunchEnv {
     bool no_defer = getenv("ZS_NO_DEFER") != nullptr, force_rounds = getenv("ZS_FORCE_ROUNDS") != nullptr;
     bool tail_serial = getenv("ZS_TAIL_SERIAL") != nullptr, tail_fork = getenv("ZS_TAIL_FORK") != nullptr, fast_no_probe = getenv("ZS_FAST_NO_PROBE") != nullptr;
     bool no_whole_runs = getenv("ZS_NO_WHOLE_RUNS") != nullptr, whole_runs = getenv("ZS_WHOLE_RUNS") != nullptr;
+    bool no_split_backend = getenv("ZS_NO_SPLIT_BACKEND") != nullptr;  // the finished blocks wait for the tail engine like the rest
     bool debug = getenv("ZS_DEBUG") != nullptr, debug_cuts = getenv("ZS_DEBUG_CUTS") != nullptr, debug_fa = getenv("ZS_DEBUG_FA") != nullptr;
     const char *debug_chain = getenv("ZS_DEBUG_CHAIN"), *debug_chain_want = getenv("ZS_DEBUG_CHAIN_WANT");
     int k5_ahead = getenv("ZS_K5_AHEAD") ? atoi(getenv("ZS_K5_AHEAD")) : 1;  // lines the symbol kernel's helper wave asks for ahead of a lane
@@ -294,6 +298,7 @@ struct DeflateCall {
     bool need_maps = true, spec_ran = false;
     bool fork_recorded = false;  // the tail engine's fork has its event already (the speculative path)
     bool tail_late = false, tail_serial = false, use_sup = false;
+    bool split = false;  // the finished blocks go through K5b, K7, K8 and K9 beside the tail engine (tails_and_symbols)
     int defer_mode = 0, cut_stride = 0;
     // a step ran the batch again (rerun): the call is over and `answer` is what it returns; a step that failed leaves both false
     bool done = false, answer = false;
@@ -844,11 +849,27 @@ bool DeflateCall::rle_tiles() {
 // what the resolve kernel left, so it runs on the second stream beside the symbol kernels -- unless the tails are many
 // (tail_serial) or need the symbols (tail_late).
 bool DeflateCall::tails_and_symbols() {
+    // The split back end (zs_kernels.hip stream_body_blocks): with the tail engine forked, the blocks that end inside the body
+    // go through K5b, K7, K8 and K9 on the main stream while it runs, and only what it writes follows behind it on the second
+    // stream.  Not where the block list is rewritten for the blocks that exist (blocks_and_bits: that needs the tail engine's
+    // count), not beside the speculative runs of levels 1-3 (their blocks are made on the main stream, behind this step), and
+    // not where no stream is long enough for a finished block (a symbol is at least a byte): those calls keep their order.
+    // Nor a call with a stream on the map path: K4b and K5 run beside the tail engine there and take longer than it does (one
+    // chunk's chain in K5 is 0.38 ms), so nothing waits for it and the second set of launches is only a cost (0.04 ms of a
+    // 64 KiB stream's 1.01; profiles/split_backend.md).  What splits: streams that all verified on the speculative walk, whose
+    // compaction is 0.05 ms against the tail engine's 0.26, and the paths that put no kernel beside it (levels 1-3, Rle).
+    const bool beside_k5 = need_maps && (!pl.w_segs.empty() || !pl.w_chunks.empty());
+    if (!tail_late && !tail_serial && (n < 64 || penv.no_live_list) && !env.no_split_backend && pl.n_runs == 0 && !beside_k5) {
+        int64_t longest = 0;
+        for (int i = 0; i < n; i++) longest = std::max(longest, in_len[i]);
+        split = longest >= kBlockSyms;
+    }
     if (!tail_late && !tail_serial) {
         if (!fork_recorded || need_maps) ZS_HIP(c, hipEventRecord(c->ev_fork, stream));  // (behind the resolve kernel, if it ran)
         ZS_HIP(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
         launch_tail(c->aux);
-        ZS_HIP(c, hipEventRecord(c->ev_join, c->aux));
+        if (split && prof) (void)hipEventRecord(c->ev_part1[0], c->aux);
+        if (!split) ZS_HIP(c, hipEventRecord(c->ev_join, c->aux));
     }
     if (!pl.w_segs.empty() && need_maps)
         hipLaunchKernelGGL(zs_expand_kernel, dim3((unsigned)((pl.w_segs.size() + 63) / 64)), dim3(64), 0, stream, d_sd, d_st,
@@ -870,10 +891,21 @@ bool DeflateCall::tails_and_symbols() {
     // tests/test_gpu_spec.py test_a_verified_stream_beside_one_in_the_cut_rounds.)
     // (the compaction of their symbols went in behind the verdict kernel, above)
     mark(9);
+    auto body_blocks = [&](hipStream_t on, int part) {
+        hipLaunchKernelGGL(zs_body_blocks_kernel, dim3((unsigned)n), dim3(256), 0, on, d_sd, d_st, dev<int32_t>(c->blk_end),
+                           dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks), dev<uint32_t>(c->syms), part);
+    };
+    if (split) {
+        // (part 1 of a stream that does not split reads the symbols the main stream has just placed)
+        ZS_HIP(c, hipEventRecord(c->ev_syms, stream));
+        body_blocks(stream, kPartBody);
+        ZS_HIP(c, hipStreamWaitEvent(c->aux, c->ev_syms, 0));
+        body_blocks(c->aux, kPartRest);
+        return true;
+    }
     if (tail_serial) launch_tail(stream);
     else if (!tail_late) ZS_HIP(c, hipStreamWaitEvent(stream, c->ev_join, 0));
-    hipLaunchKernelGGL(zs_body_blocks_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<int32_t>(c->blk_end),
-                       dev<int32_t>(c->blk_top), dev<BlockRec>(c->blocks), dev<uint32_t>(c->syms));
+    body_blocks(stream, kPartAll);
     if (tail_late) launch_tail(stream);
     return true;
 }
@@ -959,13 +991,20 @@ bool DeflateCall::blocks_and_bits() {
         hipLaunchKernelGGL(zs_live_fill_kernel, dim3((unsigned)((pl.w_blocks.size() + 255) / 256)), dim3(256), 0, stream, d_live, n,
                            (uint32_t)pl.w_blocks.size(), dev<uint2>(c->work) + lay.work[kWBlocks]);
     }
-    hipLaunchKernelGGL(zs_trees_kernel, dim3((unsigned)pl.w_blocks.size()), dim3(trees_threads), 0, stream, d_sd, d_st, work(kWBlocks),
-                       dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info), dev<int32_t>(c->tile_bits), strategy, level);
+    auto trees = [&](hipStream_t on, int part) {
+        hipLaunchKernelGGL(zs_trees_kernel, dim3((unsigned)pl.w_blocks.size()), dim3(trees_threads), 0, on, d_sd, d_st, work(kWBlocks), dev<uint32_t>(c->syms),
+                           dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info), dev<int32_t>(c->tile_bits), strategy, level, part);
+    };
+    auto offsets = [&](hipStream_t on, int part) {
+        hipLaunchKernelGGL(zs_offsets_kernel, dim3((unsigned)n), dim3(256), 0, on, d_sd, d_st, dev<BlockRec>(c->blocks), dev<BlockInfo>(c->info),
+                           dev<TreeWork>(c->trees), dev<uint32_t>(c->pieces), level, n, part);
+    };
+    trees(stream, split ? kPartBody : kPartAll);
     mark(11);
     ZS_HIP(c, hipStreamWaitEvent(stream, c->ev_pre, 0));  // the cleared output and the Adler pieces (second stream, above)
-    hipLaunchKernelGGL(zs_offsets_kernel, dim3((unsigned)n), dim3(256), 0, stream, d_sd, d_st, dev<BlockRec>(c->blocks),
-                       dev<BlockInfo>(c->info), dev<TreeWork>(c->trees), dev<uint32_t>(c->pieces), level, n);
+    offsets(stream, split ? kPartBody : kPartAll);
     mark(12);
+    if (split) ZS_HIP(c, hipEventRecord(c->ev_part0, stream));  // the finished blocks are placed: part 1 goes on from their end
     // one workgroup for a block's header and one for each of its tiles of symbols, whose bit counts the tree kernel left
     // (a workgroup takes every eb_tiles-th tile: any number covers them all); a symbol is at least one input byte
     int eb_tiles = kEbTiles;
@@ -975,10 +1014,23 @@ bool DeflateCall::blocks_and_bits() {
         eb_tiles = (int)std::min<int64_t>(kEbTiles, (longest + 1) / kEbTile + 1);
     }
     if (env.eb_tiles()) eb_tiles = std::max(1, std::min(kEbTiles, atoi(env.eb_tiles())));
-    hipLaunchKernelGGL(zs_emit_bits_kernel, dim3((unsigned)pl.w_blocks.size(), (unsigned)(1 + eb_tiles)), dim3(256), 0, stream, d_sd, d_st,
-                       work(kWBlocks), dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info),
-                       dev<int32_t>(c->tile_bits));
+    auto emit_bits = [&](hipStream_t on, int part) {
+        hipLaunchKernelGGL(zs_emit_bits_kernel, dim3((unsigned)pl.w_blocks.size(), (unsigned)(1 + eb_tiles)), dim3(256), 0, on, d_sd, d_st, work(kWBlocks),
+                           dev<uint32_t>(c->syms), dev<BlockRec>(c->blocks), dev<TreeWork>(c->trees), dev<BlockInfo>(c->info), dev<int32_t>(c->tile_bits), part);
+    };
+    emit_bits(stream, split ? kPartBody : kPartAll);
     mark(13);
+    if (split) {
+        // behind the tail engine and part 1 of K5b (tails_and_symbols): what the tail engine wrote, and every stream that does
+        // not split.  The parts of a stream meet in shared output words through atomicOr, like the parts of a block.
+        trees(c->aux, kPartRest);
+        ZS_HIP(c, hipStreamWaitEvent(c->aux, c->ev_part0, 0));
+        offsets(c->aux, kPartRest);
+        emit_bits(c->aux, kPartRest);
+        if (prof) (void)hipEventRecord(c->ev_part1[1], c->aux);
+        ZS_HIP(c, hipEventRecord(c->ev_join, c->aux));
+        ZS_HIP(c, hipStreamWaitEvent(stream, c->ev_join, 0));
+    }
     ZS_HIP(c, hipGetLastError());
     hst = (StreamState *)c->pinned;
     ZS_HIP(c, hipMemcpyAsync(hst, d_st, sizeof(StreamState) * (size_t)n, hipMemcpyDeviceToHost, stream));
@@ -1033,6 +1085,13 @@ void DeflateCall::stage_times() {
         float ms = 0;
         if (i >= kStLinks && i <= kStEmitBits) (void)hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]);  // clear / adler: beside the others, unmarked
         c->stage_ms[i] = ms;
+    }
+    if (split) {
+        // the back end split: trees, offsets and emit_bits above are the part-0 launches, this is the chain behind the tail
+        // engine on the second stream, beside them -- the stages of such a call do not sum to its path
+        float p1 = 0;
+        (void)hipEventElapsedTime(&p1, c->ev_part1[0], c->ev_part1[1]);
+        c->stage_ms[kStPart1] = p1;
     }
     if (spec_ran) {  // the speculative walk and its verdict sit between the match kernel and the maps
         float a = 0, b = 0, m = 0;
@@ -1223,6 +1282,7 @@ int zs_ctx_create(int device, zs_ctx **out) {
     }
     for (auto &e : c->ev) (void)hipEventCreate(&e);
     for (auto &e : c->ev_spec) (void)hipEventCreate(&e);
+    for (auto &e : c->ev_part1) (void)hipEventCreate(&e);
     for (auto &e : c->ev_png) (void)hipEventCreate(&e);
     {
         // the link kernel relies on the LDS applying the lanes of one DS_MSKOR_RTN_B32 in lane order: check it here
@@ -1246,6 +1306,8 @@ int zs_ctx_create(int device, zs_ctx **out) {
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_pre0, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_syms, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_part0, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_verdict, hipEventDisableTiming) != hipSuccess) {
         zs_ctx_destroy(c);  // releases whatever was created so far
         return ZS_MEM_ERROR;
@@ -1313,6 +1375,10 @@ void zs_ctx_destroy(zs_ctx *c) {
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_pre0) (void)hipEventDestroy(c->ev_pre0);
     if (c->ev_pre) (void)hipEventDestroy(c->ev_pre);
+    if (c->ev_syms) (void)hipEventDestroy(c->ev_syms);
+    if (c->ev_part0) (void)hipEventDestroy(c->ev_part0);
+    for (auto &e : c->ev_part1)
+        if (e) (void)hipEventDestroy(e);
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1374,7 +1440,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
-    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey || s == kStPngCompose || s == kStPngDiff || s == kStPngCrop) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA), KV (the survey), KM (the frames of an animation composed), KD (the frame diff) and the crop
+    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey || s == kStPngCompose || s == kStPngDiff || s == kStPngCrop || s == kStPart1) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA), KV (the survey), KM (the frames of an animation composed), KD (the frame diff), the crop, and the part-1 chain of a deflate call whose back end splits
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine

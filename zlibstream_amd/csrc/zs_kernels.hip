@@ -2366,19 +2366,40 @@ __global__ __launch_bounds__(256) void zs_spec_compact_kernel(const StreamDesc *
     blk_top[s.blk_off + bi] = (int32_t)spec_sym_top(start, odd);
 }
 
+// ------------------------------------------------------------------ the split back end (K5b, K7, K8, K9)
+// A block that ends inside the body has its symbols and its blk_end / blk_top entries as soon as the symbols are in place;
+// the tail engine, one workgroup on the second stream, writes symbols from body_syms on, BlockRecs from body_syms / kBlockSyms
+// on and StreamState::nsyms / nblocks, nothing else.  A call that splits (zs_engine.hip DeflateCall::split) launches
+// each of the four kernels twice: part 0 on the main stream beside the tail engine, for the finished blocks of the streams
+// that split; part 1 behind the tail engine, for everything else.  A call that does not split launches them once, for all.
+// Part 0 reads nothing the tail engine writes: not nblocks, nsyms or status, no BlockRec from the bound on.
+enum { kPartAll = -1, kPartBody = 0, kPartRest = 1 };
+// The blocks of the stream that are part 0's: [0, bound); part 1 (and kPartAll) takes [bound, nblocks).  0 for a stream that
+// does not split: one that ends its blocks any other way than with the tail engine's eof block behind a plain body (a flush
+// mode, a Write list, a run of an incremental stream, the runs of levels 1-3, level 0's planned blocks, the cut rounds).
+__device__ __forceinline__ int stream_body_blocks(int part, const StreamDesc &s, const StreamState &ss) {
+    if (part == kPartAll) return 0;
+    const bool splits = s.wr_flush == nullptr && s.n_wr <= 1 && s.final_run && !s.resume && !s.cont && !s.cont_bits && s.fast_runs == 0 &&
+                        s.plan_nblk == 0 && !ss.deferred;
+    return splits ? (int)(ss.body_syms / kBlockSyms) : 0;
+}
+
 // ------------------------------------------------------------------ K5b
 // The block cuts recorded by K5 become BlockRec entries (the blocks that end inside the bulk parse).
 __global__ __launch_bounds__(256) void zs_body_blocks_kernel(const StreamDesc *sd, const StreamState *st, const int32_t *blk_end,
-                                                             const int32_t *blk_top, BlockRec *blocks, uint32_t *syms) {
+                                                             const int32_t *blk_top, BlockRec *blocks, uint32_t *syms, int part) {
     const StreamDesc s = sd[blockIdx.x];
     if (s.fast_runs > 0 || st[blockIdx.x].deferred) return;
+    const int nb0 = stream_body_blocks(part, s, st[blockIdx.x]);
+    if (part == kPartBody && nb0 == 0) return;
     if (s.resume)  // the symbols of the block the run took over in the middle: in front of the run's own
         for (uint32_t i = threadIdx.x; i < s.start_syms; i += blockDim.x) syms[s.sym_off + i] = s.persist->syms[i];
     const int nb_body = (int)(st[blockIdx.x].body_syms / kBlockSyms);
     BlockRec *blk = blocks + s.blk_off;
     // start = end of the previous block; stored blocks are allowed only while blockStart has not slid out of the
     // window (Deflate.cs:953)
-    for (int i = threadIdx.x; i < nb_body; i += blockDim.x) {
+    // (a stream that splits: part 0 makes them, part 1 finds them made)
+    for (int i = threadIdx.x; i < (part == kPartRest && nb0 > 0 ? 0 : nb_body); i += blockDim.x) {
         int64_t start = i ? blk_end[s.blk_off + i - 1] : (s.resume ? s.start_block : 0);
         int64_t end = blk_end[s.blk_off + i];
         BlockRec r;
@@ -2391,6 +2412,7 @@ __global__ __launch_bounds__(256) void zs_body_blocks_kernel(const StreamDesc *s
         r.eof = 0;
         blk[i] = r;
     }
+    if (part == kPartBody) return;  // (the fix-up below reads the tail engine's record)
     // Writes that began inside the body (every Write is a Deflate call of its own, and under a flush mode the chunk accounting
     // counts them: zs_core.h FlushAcct): Write w begins at the first loop-top that finds its predecessor's data short
     // (>= end - 261), so the blocks flushed before it are those whose last symbol came at a loop-top below that.  The Writes
@@ -3231,7 +3253,7 @@ typedef u32x4 __attribute__((aligned(4))) u32x4a4;
 typedef u32x4 __attribute__((aligned(8))) u32x4a8;
 __global__ __launch_bounds__(256) void zs_trees_kernel(const StreamDesc *sd, const StreamState *st, const uint2 *work,
                                                        const uint32_t *syms, const BlockRec *blocks, TreeWork *trees,
-                                                       BlockInfo *info, int32_t *tile_bits, int strategy, int level) {
+                                                       BlockInfo *info, int32_t *tile_bits, int strategy, int level, int part) {
     __shared__ __attribute__((aligned(16))) TreeWork tw;
     __shared__ SideTree sw;
     __shared__ uint32_t hl[kLCodes], hd[kDCodes];
@@ -3247,7 +3269,8 @@ __global__ __launch_bounds__(256) void zs_trees_kernel(const StreamDesc *sd, con
     if (w.x == kNoWork || st[w.x].deferred) return;
     const StreamDesc s = sd[w.x];
     const int b = (int)w.y;
-    if (b >= st[w.x].nblocks) return;
+    const int nb0 = stream_body_blocks(part, s, st[w.x]);
+    if (part == kPartBody ? b >= nb0 : (b < nb0 || b >= st[w.x].nblocks)) return;
     const BlockRec r = blocks[s.blk_off + b];
     if (level == 0 && r.nsyms == 0 && s.plan_nblk > 0) {
         // DeflateStored tallies nothing and level 0 skips the tree comparison (Trees.cs:601-620): stored while the block
@@ -3443,7 +3466,7 @@ struct OrBitsAt {  // FlushAcct's put: OR into the zeroed stream, never past the
 };
 __global__ __launch_bounds__(256) void zs_offsets_kernel(const StreamDesc *sd, StreamState *st, const BlockRec *blocks,
                                                          BlockInfo *info, const TreeWork *trees, const uint32_t *adler_pieces,
-                                                         int level, int nstreams) {
+                                                         int level, int nstreams, int part) {
     __shared__ int32_t sh_type[1024], sh_bits[1024], sh_len[1024], sh_eof[1024];
     __shared__ int64_t sh_start[1024];
     __shared__ uint32_t ad_v[256];
@@ -3458,13 +3481,18 @@ __global__ __launch_bounds__(256) void zs_offsets_kernel(const StreamDesc *sd, S
     if (st[si].deferred) return;
     const StreamDesc s = sd[si];
     StreamState &ss = st[si];
-    const int nb = ss.nblocks;
+    // the split back end: part 0 places the finished blocks of a stream that splits and leaves the bit position behind them
+    // (and whether one of them cannot be sent) for part 1, which goes on from there and alone ends the stream
+    const int nb0 = stream_body_blocks(part, s, ss);
+    if (part == kPartBody && nb0 == 0) return;
+    const int nb = part == kPartBody ? nb0 : ss.nblocks;
+    const int nb_first = part == kPartBody ? 0 : nb0;
     LitPersist *ps = s.persist;
     // a run that continues an incremental stream starts where the run before stopped: `bit_base` is the stream bit position
     // of this run's out[0], whose low bits (the stream's last, incomplete byte) come with the descriptor
-    const int64_t start_bits = s.cont_bits ? ps->fa.bits : 16;
+    const int64_t start_bits = s.cont_bits ? ps->fa.bits : nb_first > 0 ? ss.body_bits : 16;
     const int64_t bit_base = s.cont_bits ? (start_bits & ~7LL) : 0;
-    if (threadIdx.x == 0) sh_pos = start_bits, sh_bad = 0;
+    if (threadIdx.x == 0) sh_pos = start_bits, sh_bad = nb_first > 0 ? ss.body_bad : 0;
     const OrBitsAt fa_put{s.out, s.out_cap, bit_base};
     if (flushing) {
         if (s.cont_bits) fa = ps->fa;
@@ -3475,7 +3503,7 @@ __global__ __launch_bounds__(256) void zs_offsets_kernel(const StreamDesc *sd, S
     }
     if (threadIdx.x == 0 && s.cont_bits && s.out_cap > 0) s.out[0] = (uint8_t)s.carry_byte;
     __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
+    for (int b0 = nb_first; b0 < nb; b0 += 1024) {
         int cnt = nb - b0 < 1024 ? nb - b0 : 1024;
         for (int i = threadIdx.x; i < cnt; i += 256) {
             const BlockInfo bi = info[s.blk_off + b0 + i];
@@ -3550,6 +3578,19 @@ __global__ __launch_bounds__(256) void zs_offsets_kernel(const StreamDesc *sd, S
         for (int i = threadIdx.x; i < cnt; i += 256) info[s.blk_off + b0 + i].bit_start = sh_start[i] - bit_base;
         __syncthreads();
     }
+    if (part == kPartBody) {
+        if (threadIdx.x == 0) {
+            ss.body_bits = sh_pos, ss.body_bad = sh_bad;
+            // the zlib header, in front of K9's part 0 as ever: the first block's bits share its word (a stream that splits
+            // starts at out[0]; one whose output turns out too small is reported by part 1 and its bytes are nobody's)
+            if (s.out_cap >= 2) {
+                const unsigned hdr = zlib_header(level);
+                s.out[0] = (uint8_t)(hdr >> 8);
+                s.out[1] = (uint8_t)hdr;
+            }
+        }
+        return;
+    }
     // Adler-32 of the whole input: tree combine of the 64 KiB pieces (adler_combine is associative)
     uint32_t acc = 1;   // adler of the empty string
     uint64_t acc_len = 0;
@@ -3598,7 +3639,7 @@ __global__ __launch_bounds__(256) void zs_offsets_kernel(const StreamDesc *sd, S
         return;
     }
     ss.status = 0;
-    if (!s.cont_bits) {
+    if (!s.cont_bits && nb_first == 0) {  // (part 0 has sent it for a stream whose finished blocks it placed)
         unsigned hdr = zlib_header(level);
         s.out[0] = (uint8_t)(hdr >> 8);
         s.out[1] = (uint8_t)hdr;
@@ -3657,7 +3698,7 @@ struct LdsBitPut {
 #endif
 __global__ __launch_bounds__(256) void zs_emit_bits_kernel(const StreamDesc *sd, const StreamState *st, const uint2 *work,
                                                            const uint32_t *syms, const BlockRec *blocks, const TreeWork *trees,
-                                                           const BlockInfo *info, const int32_t *tile_bits) {
+                                                           const BlockInfo *info, const int32_t *tile_bits, int split_part) {
     __shared__ uint32_t lt[kLCodes], dt[kDCodes];
     __shared__ uint32_t obuf[kEbWords];
     __shared__ uint32_t wsum[4];
@@ -3669,9 +3710,19 @@ __global__ __launch_bounds__(256) void zs_emit_bits_kernel(const StreamDesc *sd,
     if (w.x == kNoWork || st[w.x].deferred) return;
     const StreamDesc s = sd[w.x];
     const int b = (int)w.y;
-    if (b >= st[w.x].nblocks || st[w.x].status != 0) return;
+    const int nb0 = stream_body_blocks(split_part, s, st[w.x]);
+    if (split_part == kPartBody ? b >= nb0 : (b >= st[w.x].nblocks || st[w.x].status != 0)) return;
     const BlockRec r = blocks[s.blk_off + b];
     const BlockInfo bi = info[s.blk_off + b];
+    if (b < nb0) {
+        // A finished block of a stream that splits.  Part 0 runs before the offsets kernel has said whether the output is large
+        // enough (status, above: part 1's to read), so it sends the block only where everything a part may touch -- the block's
+        // last byte and the 12 bytes of slack OrBitsAt allows for -- lies inside the caller's capacity; the others are part 1's,
+        // by the same test, once the status is known.
+        const int64_t end_byte = bi.type == 0 ? ((bi.bit_start + 3 + 7) >> 3) + 4 + r.stored_len : (bi.bit_start + bi.bits + 7) >> 3;
+        const bool fits = end_byte + 12 <= s.out_cap;
+        if (fits != (split_part == kPartBody)) return;
+    }
     uint8_t *out = s.out;
     const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
     const int part = (int)blockIdx.y, ntl = (int)gridDim.y - 1;
