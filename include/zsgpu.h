@@ -548,6 +548,104 @@ ZS_API int zs_exr_encode_batch_device(zs_ctx *ctx, int n, const zs_exr_put *puts
                                       void *hip_stream);
 
 /* ------------------------------------------------------------------ */
+/* Chunked N-dimensional arrays: the chunks of an HDF5 / NetCDF-4 dataset with the shuffle and deflate filters, and of a
+ * Zarr v2 array with the `zlib` or `gzip` compressor and the `shuffle` filter, which are byte for byte the same thing.  No
+ * file format is walked: the caller gives the geometry and the chunks (h5py read_direct_chunk / write_direct_chunk, a Zarr
+ * store's values).  The rules, which tests/chunk_cases.py models and the tests pin:
+ *   An array has rank 1..8, shape[d] >= 1, chunk[d] >= 1, elements of elem_size 1..16 bytes in C order (last axis fastest).
+ *   grid[d] = ceil(shape[d] / chunk[d]); chunk c is the C-order index of its grid coordinates (Zarr's key i.j.k, HDF5's
+ *   chunk offset divided by the chunk dims).
+ *   A decoded chunk has E = prod(chunk[d]) elements, chunk_bytes = E * elem_size bytes, always: edge chunks are full-sized
+ *   and padded.  Chunk element q (C order over chunk[]) of grid cell p is array element p[d] * chunk[d] + q[d]; it exists
+ *   when that index is below shape[d] on every axis.  The others are padding: ignored when reading, written as `fill` (one
+ *   element of elem_size bytes) when writing.
+ *   Shuffle (H5Zshuffle, numcodecs Shuffle): byte j of element e lies at j * E + e of the chunk.  On a bare buffer of any
+ *   length (the two stand-alone calls) count = len / elem_size, and the len % elem_size leftover bytes are copied unchanged
+ *   behind the planes, which is HDF5's rule.
+ *   wrap: ZS_WRAP_ZLIB is HDF5 deflate and numcodecs Zlib, ZS_WRAP_GZIP numcodecs GZip; ZS_WRAP_RAW is accepted too.
+ *   Per-chunk flags: ZS_CHUNK_STORED -- the bytes are not compressed (HDF5's filter-mask bit of an optional deflate that did
+ *   not shrink; a Zarr array with compressor null); ZS_CHUNK_UNSHUFFLED -- the filter-mask bit of the shuffle filter;
+ *   ZS_CHUNK_SKIP (read side) -- this chunk was not fetched: its region is left alone; ZS_CHUNK_ABSENT (write side) -- the
+ *   chunk was not written.  A chunk with a null pointer and no SKIP flag is missing: its region reads as `fill`.
+ * Out of scope: Fortran order and big-endian dtypes; the filters delta, scale-offset, bitshuffle, Fletcher-32, szip and
+ * N-bit; Blosc, LZ4 and Zstd; Zarr v3 and sharding; reading HDF5 files themselves; object and variable-length dtypes. */
+enum { ZS_CHUNK_STORED = 1, ZS_CHUNK_UNSHUFFLED = 2, ZS_CHUNK_SKIP = 4, ZS_CHUNK_ABSENT = 8 };
+enum { ZS_CHUNKS_SKIP_FILL = 1, ZS_CHUNKS_ALLOW_STORED = 2 };
+
+typedef struct zs_chunk_grid {
+    int rank;          /* 1..8 */
+    int elem_size;     /* 1..16 */
+    int64_t shape[8];  /* entries behind rank are not read */
+    int64_t chunk[8];
+    int shuffle;       /* 0 or 1: the chunks' bytes are shuffled (elem_size 1: the same bytes either way) */
+    int wrap;          /* ZS_WRAP_* of the compressed chunks */
+    uint8_t fill[16];  /* one element; bytes behind elem_size are not read */
+} zs_chunk_grid;
+
+typedef struct zs_chunk_ref {
+    const void *data; /* HOST memory; NULL: the chunk is missing (or, with ZS_CHUNK_SKIP, was not fetched) */
+    int64_t len;
+    int flags;        /* ZS_CHUNK_STORED | ZS_CHUNK_UNSHUFFLED | ZS_CHUNK_SKIP */
+} zs_chunk_ref;
+
+/* n_chunks, chunk_bytes and array_bytes of a grid (each pointer may be NULL).  Pure host code.  ZS_STREAM_ERROR for a grid
+ * that breaks a rule above -- rank, elem_size, an extent below 1, shuffle outside 0 / 1, wrap outside the three -- and for
+ * products that leave int64. */
+ZS_API int zs_chunk_grid_info(const zs_chunk_grid *grid, int64_t *n_chunks, int64_t *chunk_bytes, int64_t *array_bytes);
+
+/* Chunks in host memory to arrays in device memory, n arrays a call.  chunks[i]: n_chunks(i) records in chunk order; out[i]:
+ * DEVICE memory with array_bytes(i) of room.  One upload of all chunk bytes, one zs_inflate_wrap_batch_device call over all
+ * compressed chunks of all arrays (one per container where the arrays of a call differ in `wrap`) into a buffer the context
+ * owns -- exactly chunk_bytes of room per chunk, on 256-byte boundaries --, then one launch of the place kernel (KN,
+ * DESIGN.md section 4) over the chunks that are whole: unshuffle and placement fused, STORED chunks read from the upload,
+ * missing chunks written as `fill`.
+ * A chunk fails for itself only: its code goes to chunk_status[i][c] (HOST arrays of n_chunks(i) ints; chunk_status or any
+ * chunk_status[i] may be NULL), its region of out[i] is left untouched, its neighbours are complete.  Reasons: inflate's own
+ * errors with their messages; ZS_BUF_ERROR "buffer error" for a stream that holds more than chunk_bytes; ZS_DATA_ERROR
+ * "incorrect chunk length" for a stream that ends short of chunk_bytes and for a STORED chunk whose len != chunk_bytes.
+ * status[i] (may be NULL): the first failing chunk's code, or ZS_OK; ZS_BUF_ERROR with nothing written for an array whose
+ * out_cap[i] < array_bytes(i).  Nothing is ever written at or behind out[i] + out_cap[i].  Returns the first failing array's
+ * code; zs_ctx_last_error names the array, the chunk and the reason ("array 1: chunk 7: incorrect data check").
+ * ZS_STREAM_ERROR before any device work: null arguments, a bad grid, a negative length, a chunk_bytes or len above
+ * 2 GiB - 1 KiB, more than 2^31 - 1 items (stretches of rows, zs_chunk.h) in the call.
+ * The call waits for the stream for the upload, inside the inflate call, and for the place kernel's descriptors; with a
+ * caller's hip_stream the place launch is left in flight on it. */
+ZS_API int zs_chunks_decode_batch(zs_ctx *ctx, int n, const zs_chunk_grid *grids, const zs_chunk_ref *const *chunks, void *const *out,
+                                  const int64_t *out_cap, int *const *chunk_status, int *status, void *hip_stream);
+
+/* Room that zs_chunks_encode_batch_device needs for this array at the most: n_chunks * zs_wrap_bound(chunk_bytes, wrap).
+ * Pure host code.  -1 for a bad grid and for a result that leaves int64. */
+ZS_API int64_t zs_chunks_bound(const zs_chunk_grid *grid);
+
+/* Arrays in device memory to their chunks in device memory, n arrays a call.  in[i]: the array; out[i] receives the chunks
+ * back to back in chunk order: chunk c lies at out[i] + chunk_off[i][c] and has chunk_len[i][c] bytes, with
+ * chunk_flags[i][c] (HOST arrays of n_chunks(i) entries; chunk_flags or any chunk_flags[i] may be NULL).  One launch of the
+ * gather kernel (KN) reads every chunk's clipped region, pads it with `fill` and writes it, shuffled or not, into a buffer
+ * the context owns; one deflate call over all chunks writes the streams into a second one -- a compressed chunk is, bit for
+ * bit, what zs_deflate_wrap_batch_device writes for the same bytes, level, strategy, hash variant and wrap --; the host reads
+ * the lengths, and one launch of KC's span copy moves the chunks into place (the pattern of zs_zip_encode_batch_device).
+ * options & ZS_CHUNKS_SKIP_FILL: a survey launch (records per item, a folding launch, one more wait) finds the chunks whose
+ *   existing elements all equal `fill`; such a chunk is not written: chunk_len 0, flag ZS_CHUNK_ABSENT, left out of gather
+ *   and deflate.
+ * options & ZS_CHUNKS_ALLOW_STORED: a chunk whose stream is not shorter than chunk_bytes is written as its (shuffled) bytes
+ *   with flag ZS_CHUNK_STORED, HDF5's rule for an optional filter.  Without it every chunk is a stream, Zarr's rule.
+ * An array whose out_cap[i] is short is left out: status[i] ZS_BUF_ERROR, out_len[i] what it needs, nothing written; the
+ * others are complete, and zs_chunks_bound is always enough.  Returns the first failing array's code.  ZS_STREAM_ERROR
+ * before any device work as for zs_chunks_decode_batch, and for unknown options. */
+ZS_API int zs_chunks_encode_batch_device(zs_ctx *ctx, int n, const zs_chunk_grid *grids, const void *const *in, void *const *out,
+                                         const int64_t *out_cap, int64_t *out_len, int64_t *const *chunk_off,
+                                         int64_t *const *chunk_len, int *const *chunk_flags, int *status, int level, int strategy,
+                                         int hash_variant, int options, void *hip_stream);
+
+/* The shuffle filter alone on n device buffers (KN's gather and place kernels on a one-chunk, one-row array): out[i] =
+ * the elem_size[i] planes of in[i]'s len[i] / elem_size[i] elements, the leftover bytes behind them; and the inverse.  in[i]
+ * and out[i] must not overlap; any alignment; len[i] in 0 .. 2^31 - 1, elem_size[i] in 1..16. */
+ZS_API int zs_shuffle_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *len,
+                                   const int *elem_size, void *hip_stream);
+ZS_API int zs_unshuffle_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *len,
+                                     const int *elem_size, void *hip_stream);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU batch entry points (SURVEY.md 8(b) "zs_deflate_batch(..., device_mask)", 8(e)): the n independent
  * buffers are partitioned over n_ctx contexts -- normally one per GPU of the node, zs_ctx_create(0 .. count-1) --
  * by size (longest-processing-time, zs_partition), each context's share runs on its own host thread through the

@@ -19,4 +19,6 @@ from .api import (CompressionLevel, CompressionState, CompressionStrategy, Engin
                   deflate_wrap_batch_device, inflate_wrap_batch_device, gzip_file_info, gzip_decode_files_batch,
                   ZIP_AUTO, ZIP_STORED, ZIP_DEFLATED, zip_file_info, zip_decode_files_batch, zip_bound, zip_encode_batch_device,
                   tiff_file_info, tiff_decode_files, tiff_encode, tiff_bound, tiff_predict, tiff_unpredict,
-                  exr_file_info, exr_decode_files, exr_encode, exr_bound, exr_predict, exr_unpredict)
+                  exr_file_info, exr_decode_files, exr_encode, exr_bound, exr_predict, exr_unpredict,
+                  CHUNK_STORED, CHUNK_UNSHUFFLED, CHUNK_SKIP, CHUNK_ABSENT, chunk_grid_info, chunks_decode, chunks_encode, chunks_bound,
+                  shuffle, unshuffle, zarr_v2_grid)

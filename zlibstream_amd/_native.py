@@ -30,6 +30,8 @@ SYMBOLS = [
     "zs_tiff_encode_batch_device",
     "zs_exr_file_info", "zs_exr_unpredict_batch_device", "zs_exr_predict_batch_device", "zs_exr_decode_files_batch", "zs_exr_bound",
     "zs_exr_encode_batch_device",
+    "zs_chunk_grid_info", "zs_chunks_decode_batch", "zs_chunks_bound", "zs_chunks_encode_batch_device", "zs_shuffle_batch_device",
+    "zs_unshuffle_batch_device",
 ]
 
 
@@ -103,6 +105,15 @@ class ExrPut(ctypes.Structure):  # zs_exr_put
     _fields_ = [("planes", ctypes.c_void_p), ("width", ctypes.c_int64), ("height", ctypes.c_int64), ("x_min", ctypes.c_int32), ("y_min", ctypes.c_int32),
                 ("n_channels", ctypes.c_int), ("compression", ctypes.c_int), ("names", ctypes.POINTER(ctypes.c_char_p)),
                 ("types", ctypes.POINTER(ctypes.c_int)), ("extra", ctypes.c_char_p), ("extra_len", ctypes.c_int64)]
+
+
+class ChunkGrid(ctypes.Structure):  # zs_chunk_grid
+    _fields_ = [("rank", ctypes.c_int), ("elem_size", ctypes.c_int), ("shape", ctypes.c_int64 * 8), ("chunk", ctypes.c_int64 * 8),
+                ("shuffle", ctypes.c_int), ("wrap", ctypes.c_int), ("fill", ctypes.c_uint8 * 16)]
+
+
+class ChunkRef(ctypes.Structure):  # zs_chunk_ref
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_int64), ("flags", ctypes.c_int)]
 
 
 class PngSurvey(ctypes.Structure):  # zs_png_survey
@@ -325,6 +336,20 @@ def lib():
         L.zs_exr_bound.argtypes = [P(ExrPut)]
         L.zs_exr_encode_batch_device.restype = i32
         L.zs_exr_encode_batch_device.argtypes = [vp, i32, P(ExrPut), P(vp), P(i64), P(i64), P(i32), i32, i32, i32, vp]
+    if hasattr(L, "zs_chunks_decode_batch"):
+        L.zs_chunk_grid_info.restype = i32
+        L.zs_chunk_grid_info.argtypes = [P(ChunkGrid), P(i64), P(i64), P(i64)]
+        L.zs_chunks_decode_batch.restype = i32
+        L.zs_chunks_decode_batch.argtypes = [vp, i32, P(ChunkGrid), P(P(ChunkRef)), P(vp), P(i64), P(P(i32)), P(i32), vp]
+        L.zs_chunks_bound.restype = i64
+        L.zs_chunks_bound.argtypes = [P(ChunkGrid)]
+        L.zs_chunks_encode_batch_device.restype = i32
+        L.zs_chunks_encode_batch_device.argtypes = [vp, i32, P(ChunkGrid), P(vp), P(vp), P(i64), P(i64), P(P(i64)), P(P(i64)), P(P(i32)), P(i32), i32, i32,
+                                                    i32, i32, vp]
+        L.zs_shuffle_batch_device.restype = i32
+        L.zs_shuffle_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i32), vp]
+        L.zs_unshuffle_batch_device.restype = i32
+        L.zs_unshuffle_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i32), vp]
     if hasattr(L, "zs_zip_file_info"):
         L.zs_zip_file_info.restype = i32
         L.zs_zip_file_info.argtypes = [vp, i64, P(ZipInfo), P(ZipEntry), i64]

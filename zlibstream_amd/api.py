@@ -1766,6 +1766,210 @@ def exr_predict(engine, in_ptrs, out_ptrs, lens, stream=None):
     _exr_kernel_call(_native.lib().zs_exr_predict_batch_device, "exr_predict", engine, in_ptrs, out_ptrs, lens, stream)
 
 
+CHUNK_STORED, CHUNK_UNSHUFFLED, CHUNK_SKIP, CHUNK_ABSENT = 1, 2, 4, 8  # ZS_CHUNK_*
+_GRID_KEYS = {"shape", "chunks", "elem_size", "shuffle", "wrap", "fill", "stored", "level", "dtype"}
+
+
+def _chunk_grid(grid, g=None):
+    """A dict of shape, chunks, elem_size and optionally shuffle (False), wrap (WRAP_ZLIB) and fill (zeros; bytes of one element)
+    as a zs_chunk_grid.  The keys stored, level and dtype, which zarr_v2_grid adds, are the caller's to read."""
+    g = g if g is not None else _native.ChunkGrid()
+    unknown = set(grid) - _GRID_KEYS
+    if unknown:
+        raise ValueError("a chunk grid has no field %s" % sorted(unknown))
+    shape, chunks = [int(v) for v in grid["shape"]], [int(v) for v in grid["chunks"]]
+    if len(shape) != len(chunks):
+        raise ValueError("a chunk grid's shape and chunks differ in length")
+    g.rank, g.elem_size = len(shape), int(grid["elem_size"])
+    for d in range(min(len(shape), 8)):
+        g.shape[d], g.chunk[d] = shape[d], chunks[d]
+    g.shuffle, g.wrap = int(bool(grid.get("shuffle", False))), int(grid.get("wrap", WRAP_ZLIB))
+    fill = bytes(grid.get("fill", b"") or b"")
+    if fill and len(fill) != g.elem_size:
+        raise ValueError("a chunk grid's fill is one element of elem_size bytes")
+    for j, b in enumerate(fill[:16]):
+        g.fill[j] = b
+    return g
+
+
+def _chunk_grids(grids):
+    arr = (_native.ChunkGrid * max(len(grids), 1))()
+    for k, grid in enumerate(grids):
+        _chunk_grid(grid, arr[k])
+    return arr
+
+
+def chunk_grid_info(grid):
+    """zs_chunk_grid_info (host code): (n_chunks, chunk_bytes, array_bytes) of a grid (a dict, see chunks_decode).  ValueError
+    for a grid that breaks a rule of include/zsgpu.h: rank 1..8, elem_size 1..16, extents of at least 1, products within int64."""
+    n, cb, ab = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    if _native.lib().zs_chunk_grid_info(ctypes.byref(_chunk_grid(grid)), ctypes.byref(n), ctypes.byref(cb), ctypes.byref(ab)) != 0:
+        raise ValueError("chunk_grid_info: rank, elem_size, an extent, shuffle or wrap out of range, or a product that leaves int64")
+    return n.value, cb.value, ab.value
+
+
+def chunks_bound(grid):
+    """zs_chunks_bound (host code): room that chunks_encode needs for this array at the most."""
+    r = _native.lib().zs_chunks_bound(ctypes.byref(_chunk_grid(grid)))
+    if r < 0:
+        raise ValueError("chunks_bound: a grid out of range")
+    return r
+
+
+def chunks_decode(engine, grids, chunks, out_ptrs, out_caps, stream=None):
+    """The chunks of HDF5 / NetCDF-4 datasets or Zarr v2 arrays (host bytes) -> the arrays in device buffers, many arrays a call
+    (zs_chunks_decode_batch).  grids: per array a dict of shape, chunks, elem_size, shuffle, wrap and fill (zarr_v2_grid makes
+    one from a .zarray document).  chunks: per array its n_chunks entries in chunk order (C order over the grid: Zarr's key
+    i.j.k) -- bytes, None for a missing chunk (it reads as fill), or a pair (bytes or None, flags) with CHUNK_STORED,
+    CHUNK_UNSHUFFLED (HDF5's filter mask) or CHUNK_SKIP (not fetched: the region is left alone); in a grid with stored set every
+    chunk is CHUNK_STORED.  Returns (code, per array the list of its chunks' codes, per-array codes): a chunk fails for itself
+    only, its region untouched; the list of an array whose capacity was too small (-5) is empty.  engine.last_error() names the
+    first failing array, the chunk and the reason."""
+    n = len(grids)
+    if len(chunks) != n or len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("chunks_decode: the argument lists differ in length")
+    if n == 0:
+        return 0, [], []
+    L = _native.lib()
+    garr = _chunk_grids(grids)
+    keep, refs, counts = [], [], []
+    for i, (grid, entries) in enumerate(zip(grids, chunks)):
+        n_chunks, _, array_bytes = chunk_grid_info(grid)
+        if len(entries) != n_chunks:
+            raise ValueError("chunks_decode: array %d has %d chunks, %d were given" % (i, n_chunks, len(entries)))
+        r = (_native.ChunkRef * n_chunks)()
+        for k, e in enumerate(entries):
+            data, flags = e if isinstance(e, tuple) else (e, 0)
+            if grid.get("stored"):
+                flags |= CHUNK_STORED
+            if data is not None:
+                data = bytes(data)
+                buf = ctypes.create_string_buffer(data, len(data)) if data else ctypes.create_string_buffer(1)
+                keep.append(buf)
+                r[k].data, r[k].len = ctypes.addressof(buf), len(data)
+            r[k].flags = int(flags)
+        refs.append(r)
+        counts.append(n_chunks if int(out_caps[i]) >= array_bytes else 0)
+    per_chunk = [(ctypes.c_int * max(k, 1))() for k in counts]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    status = I32()
+    rows = (ctypes.POINTER(ctypes.c_int) * n)(*[ctypes.cast(r, ctypes.POINTER(ctypes.c_int)) for r in per_chunk])
+    ref_rows = (ctypes.POINTER(_native.ChunkRef) * n)(*[ctypes.cast(r, ctypes.POINTER(_native.ChunkRef)) for r in refs])
+    rc = L.zs_chunks_decode_batch(engine.handle if engine is not None else None, n, garr, ref_rows, VP(*[int(p) for p in out_ptrs]),
+                                  I64(*[int(x) for x in out_caps]), rows, status, ctypes.c_void_p(stream or 0))
+    if rc not in (0, 2, -3, -5):
+        raise ValueError("zs_chunks_decode_batch failed (%d): %s" % (rc, (engine.last_error() if engine is not None else "") or "stream error"))
+    return rc, [list(per_chunk[i][:counts[i]]) for i in range(n)], list(status)
+
+
+def chunks_encode(engine, grids, in_ptrs, out_ptrs, out_caps, level=6, strategy=0, hash_variant=0, skip_fill=False, allow_stored=False, stream=None):
+    """Device-resident arrays -> their chunks in device buffers, many arrays a call (zs_chunks_encode_batch_device): shuffled
+    where the grid says so, deflated into the grid's container, back to back in chunk order.  skip_fill: a chunk whose existing
+    elements all equal fill is not written (CHUNK_ABSENT, length 0).  allow_stored: a chunk whose stream is not shorter than
+    its bytes is written as those (CHUNK_STORED), HDF5's rule; without it every chunk is a stream, Zarr's.  Returns (code,
+    lengths, per array the list of its chunks' (offset, length, flags), per-array codes): -5 (ZS_BUF_ERROR) for an array whose
+    capacity was too small -- its length is then what it needs and nothing is written for it."""
+    n = len(grids)
+    if len(in_ptrs) != n or len(out_ptrs) != n or len(out_caps) != n:
+        raise ValueError("chunks_encode: the argument lists differ in length")
+    if n == 0:
+        return 0, [], [], []
+    counts = [chunk_grid_info(g)[0] for g in grids]
+    offs, lens, flags = [(ctypes.c_int64 * k)() for k in counts], [(ctypes.c_int64 * k)() for k in counts], [(ctypes.c_int * k)() for k in counts]
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)
+    out_len, status = I64(), I32()
+    rc = _native.lib().zs_chunks_encode_batch_device(engine.handle if engine is not None else None, n, _chunk_grids(grids), VP(*[int(p) for p in in_ptrs]),
+                                                     VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len,
+                                                     (P64 * n)(*[ctypes.cast(a, P64) for a in offs]), (P64 * n)(*[ctypes.cast(a, P64) for a in lens]),
+                                                     (P32 * n)(*[ctypes.cast(a, P32) for a in flags]), status, int(level), int(strategy), int(hash_variant),
+                                                     (1 if skip_fill else 0) | (2 if allow_stored else 0), ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError("zs_chunks_encode_batch_device: " + ((engine.last_error() if engine is not None else "") or "stream error"))
+    if rc not in (0, -5):
+        raise ZlibStreamException("chunks encode: " + engine.last_error())
+    return rc, list(out_len), [list(zip(offs[i], lens[i], flags[i])) for i in range(n)], list(status)
+
+
+def _shuffle_call(fn, name, engine, in_ptrs, out_ptrs, lens, elem_sizes, stream):
+    n = len(in_ptrs)
+    if len(out_ptrs) != n or len(lens) != n or len(elem_sizes) != n:
+        raise ValueError(name + ": the argument lists differ in length")
+    if n == 0:
+        return
+    VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    rc = fn(engine.handle if engine is not None else None, n, VP(*[int(p) for p in in_ptrs]), VP(*[int(p) for p in out_ptrs]), I64(*[int(v) for v in lens]),
+            I32(*[int(v) for v in elem_sizes]), ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError(name + ": " + ((engine.last_error() if engine is not None else "") or "stream error"))
+    if rc != 0:
+        raise ZlibStreamException("%s failed (%d): %s" % (name, rc, engine.last_error()))
+
+
+def shuffle(engine, in_ptrs, out_ptrs, lens, elem_sizes, stream=None):
+    """The shuffle filter of HDF5 and numcodecs on device buffers (zs_shuffle_batch_device): byte j of element e to
+    j * count + e, count = len // elem_size, the leftover bytes copied behind the planes.  Any alignment, no overlap."""
+    _shuffle_call(_native.lib().zs_shuffle_batch_device, "shuffle", engine, in_ptrs, out_ptrs, lens, elem_sizes, stream)
+
+
+def unshuffle(engine, in_ptrs, out_ptrs, lens, elem_sizes, stream=None):
+    """The inverse of shuffle (zs_unshuffle_batch_device)."""
+    _shuffle_call(_native.lib().zs_unshuffle_batch_device, "unshuffle", engine, in_ptrs, out_ptrs, lens, elem_sizes, stream)
+
+
+def zarr_v2_grid(zarray_json):
+    """A Zarr v2 .zarray document (str, bytes or the parsed dict) as a grid dict for chunks_decode / chunks_encode.  Pure Python.
+    Accepted: zarr_format 2, order "C", a little-endian or single-byte dtype of at most 16 bytes, compressor null, zlib or gzip,
+    filters empty or one shuffle whose elementsize is the itemsize; fill_value goes through numpy.  ValueError naming the field
+    for anything else.  The dict also has stored (compressor null: every chunk is its plain bytes), level and dtype."""
+    import json
+
+    import numpy as np
+    doc = zarray_json if isinstance(zarray_json, dict) else json.loads(zarray_json.decode() if isinstance(zarray_json, (bytes, bytearray)) else zarray_json)
+
+    def bad(field, why):
+        return ValueError("zarr_v2_grid: %s: %s" % (field, why))
+    if doc.get("zarr_format") != 2:
+        raise bad("zarr_format", "only 2 is read")
+    if doc.get("order") != "C":
+        raise bad("order", "only C order is read")
+    spec = doc.get("dtype")
+    if not isinstance(spec, str) or len(spec) < 2 or spec[0] not in "<|>":
+        raise bad("dtype", "a simple dtype string is required")
+    try:
+        dt = np.dtype(spec)
+    except TypeError:
+        raise bad("dtype", "not a dtype numpy knows")
+    if dt.kind in "OUV" or dt.itemsize < 1 or dt.itemsize > 16 or (spec[0] == ">" and dt.itemsize > 1):
+        raise bad("dtype", "a little-endian or single-byte fixed-size dtype of at most 16 bytes is required")
+    lists = {}
+    for field in ("shape", "chunks"):
+        v = doc.get(field)
+        if not isinstance(v, list) or not 1 <= len(v) <= 8 or any(not isinstance(x, int) or isinstance(x, bool) or x < 1 for x in v):
+            raise bad(field, "1 to 8 extents of at least 1 are required")
+        lists[field] = tuple(v)
+    if len(lists["shape"]) != len(lists["chunks"]):
+        raise bad("chunks", "as many extents as the shape has are required")
+    comp = doc.get("compressor")
+    if comp is None:
+        wrap, level = WRAP_ZLIB, None
+    elif isinstance(comp, dict) and comp.get("id") in ("zlib", "gzip"):
+        wrap, level = (WRAP_ZLIB if comp["id"] == "zlib" else WRAP_GZIP), comp.get("level")
+    else:
+        raise bad("compressor", "only null, zlib and gzip are read")
+    filters = doc.get("filters") or []
+    if not isinstance(filters, list) or len(filters) > 1 or (filters and not (isinstance(filters[0], dict) and filters[0].get("id") == "shuffle" and
+                                                                                filters[0].get("elementsize", 4) == dt.itemsize)):
+        raise bad("filters", "only one shuffle filter whose elementsize is the itemsize is read")
+    fv = doc.get("fill_value")
+    try:
+        fill = bytes(dt.itemsize) if fv is None else np.array(fv).astype(dt).reshape(()).tobytes()
+    except (TypeError, ValueError):
+        raise bad("fill_value", "not a value of the dtype")
+    return {"shape": lists["shape"], "chunks": lists["chunks"], "elem_size": dt.itemsize, "shuffle": bool(filters), "wrap": wrap, "fill": fill,
+            "stored": comp is None, "level": level, "dtype": spec}
+
+
 _default_engine = None
 
 

@@ -1,6 +1,6 @@
 // zs_engine.hip -- host side of the MI355X deflate engine: workspace, kernel
 // pipeline, and the C ABI of include/zsgpu.h (the PNG and CRC-32 calls of it:
-// zs_png_host.inc; raw deflate, gzip members and gzip files: zs_wrap_host.inc; ZIP archives: zs_zip_host.inc; TIFF files: zs_tiff_host.inc; OpenEXR files: zs_exr_host.inc).  No CPU fallback:
+// zs_png_host.inc; raw deflate, gzip members and gzip files: zs_wrap_host.inc; ZIP archives: zs_zip_host.inc; TIFF files: zs_tiff_host.inc; OpenEXR files: zs_exr_host.inc; chunked arrays: zs_chunk_host.inc).  No CPU fallback:
 // without a usable HIP device every
 // compressing entry point fails.
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "zs_zip.hip"
 #include "zs_tiff.hip"
 #include "zs_exr.hip"
+#include "zs_chunk.hip"
 #include "zs_plan.h"
 
 using namespace zs;
@@ -38,11 +39,11 @@ struct DevBuf {
 
 enum Stage {
     kStClear, kStAdler, kStLinks, kStMatch, kStChunkMap, kStSegMap, kStResolve, kStExpand, kStEmitSyms, kStTail, kStTrees,
-    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStPngCompose, kStPngDiff, kStPngCrop, kStPart1, kStCount
+    kStOffsets, kStEmitBits, kStSpecWalk, kStSpecVerify, kStCrc32, kStSpecCompact, kStPngExpand, kStPngSplit, kStPngPack, kStPngSurvey, kStPngCompose, kStPngDiff, kStPngCrop, kStPart1, kStChunk, kStCount
 };
 const char *const kStageNames[kStCount] = {"clear", "adler", "links", "match", "chunkmap", "segmap", "resolve", "expand",
                                            "emit_syms", "tail", "trees", "offsets", "emit_bits", "spec_walk", "spec_verify", "crc32_frame",
-                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey", "png_compose", "png_diff", "png_crop", "part1_chain"};
+                                           "spec_compact", "png_expand", "png_split", "png_pack", "png_survey", "png_compose", "png_diff", "png_crop", "part1_chain", "chunk_kn"};
 
 // The context's device buffers of the PNG and CRC-32 calls (zs_png_host.inc), by what they hold: descriptors of a kernel
 // (..img, kBufCrcDesc), its records or results, or an intermediate of a call built from several kernels.
@@ -53,8 +54,11 @@ enum PngBuf {
     // the container calls (zs_wrap_host.inc): the members' descriptors and heads, the trailers gathered for the host, the zlib
     // streams in front of the framing launch, a call's files; the ZIP writer's zlib streams (zs_zip_host.inc); the TIFF calls'
     // chunks between inflate or deflate and the predictor kernel, that kernel's descriptors, the writer's zlib streams
-    // (zs_tiff_host.inc); the same three of the OpenEXR calls, and KE's segment sums (zs_exr_host.inc)
+    // (zs_tiff_host.inc); the same three of the OpenEXR calls, and KE's segment sums (zs_exr_host.inc); of the chunked-array
+    // calls KN's descriptors, the chunks between inflate or deflate and KN, the writer's streams, the survey's records
+    // (zs_chunk_host.inc)
     kBufWrapHead, kBufWrapGather, kBufWrapZs, kBufWrapFiles, kBufZipZs, kBufTiffChunks, kBufTiffDesc, kBufTiffZs, kBufExrChunks, kBufExrDesc, kBufExrZs, kBufExrSegs,
+    kBufChunkDesc, kBufChunkData, kBufChunkZs, kBufChunkRec,
     kBufPngCount
 };
 
@@ -1440,7 +1444,7 @@ int64_t zs_ctx_debug_read(zs_ctx *c, const char *name, void *out, int64_t cap) {
 
 const char *zs_ctx_stage_name(const zs_ctx *c, int s) {
     static const char *const inf_names[6] = {"inf_find", "inf_measure", "inf_chain", "inf_decode", "inf_windows", "inf_resolve"};
-    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey || s == kStPngCompose || s == kStPngDiff || s == kStPngCrop || s == kStPart1) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA), KV (the survey), KM (the frames of an animation composed), KD (the frame diff), the crop, and the part-1 chain of a deflate call whose back end splits
+    if (s == kStCrc32 || s == kStSpecCompact || s == kStPngExpand || s == kStPngSplit || s == kStPngPack || s == kStPngSurvey || s == kStPngCompose || s == kStPngDiff || s == kStPngCrop || s == kStPart1 || s == kStChunk) return kStageNames[s];  // appended stages keep their names whatever the last call was: KC (the CRC-32 calls, the framing of PNG files, the check and gather of their chunks), KSc (the speculative walk's compaction), KX (the expansion to RGBA), KS (the Adam7 split), KG (the pack from RGBA), KV (the survey), KM (the frames of an animation composed), KD (the frame diff), the crop, the part-1 chain of a deflate call whose back end splits, and KN (the chunked-array kernels)
     if (c && c->last_op == 1) return s >= 0 && s < 6 ? inf_names[s] : "";
     // levels 1-3: DeflateFast for the lanes of a wave runs where the lazy parse has its expand stage, and the speculative
     // chunk runs (run / verify / stitch) are timed with the tail engine
@@ -2134,6 +2138,7 @@ int zs_inflate_batch(zs_ctx *c, int n, const void *const *in, const int64_t *in_
 #include "zs_zip_host.inc"
 #include "zs_tiff_host.inc"
 #include "zs_exr_host.inc"
+#include "zs_chunk_host.inc"
 
 // ------------------------------------------------------------------ multi-GPU batch entry points
 // BASELINE north_star: "independent input buffers shard embarrassingly across the 8 GPUs of one node (no RCCL needed)".
