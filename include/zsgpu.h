@@ -567,8 +567,11 @@ ZS_API int zs_exr_encode_batch_device(zs_ctx *ctx, int n, const zs_exr_put *puts
  *   not shrink; a Zarr array with compressor null); ZS_CHUNK_UNSHUFFLED -- the filter-mask bit of the shuffle filter;
  *   ZS_CHUNK_SKIP (read side) -- this chunk was not fetched: its region is left alone; ZS_CHUNK_ABSENT (write side) -- the
  *   chunk was not written.  A chunk with a null pointer and no SKIP flag is missing: its region reads as `fill`.
- * Out of scope: Fortran order and big-endian dtypes; the filters delta, scale-offset, bitshuffle, Fletcher-32, szip and
- * N-bit; Blosc, LZ4 and Zstd; Zarr v3 and sharding; reading HDF5 files themselves; object and variable-length dtypes. */
+ * Three more filters go through the _filters_ calls further down (zs_chunk_filters): Fletcher-32, delta and big-endian elements.
+ * Out of scope: Fortran order; the filters scale-offset, bitshuffle, szip and N-bit; Blosc, LZ4 and Zstd; Zarr v3 and
+ * sharding; Delta on floating-point dtypes and Delta whose astype differs from its dtype; numcodecs Fletcher32 as a Zarr
+ * filter (its checksum sits inside the compressed stream); the byte-swapped checksum that HDF5 also accepts for files written
+ * before 1.6.3; reading HDF5 files themselves; object and variable-length dtypes. */
 enum { ZS_CHUNK_STORED = 1, ZS_CHUNK_UNSHUFFLED = 2, ZS_CHUNK_SKIP = 4, ZS_CHUNK_ABSENT = 8 };
 enum { ZS_CHUNKS_SKIP_FILL = 1, ZS_CHUNKS_ALLOW_STORED = 2 };
 
@@ -644,6 +647,73 @@ ZS_API int zs_shuffle_batch_device(zs_ctx *ctx, int n, const void *const *in, vo
                                    const int *elem_size, void *hip_stream);
 ZS_API int zs_unshuffle_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *len,
                                      const int *elem_size, void *hip_stream);
+
+/* Fletcher-32, the delta filter and big-endian elements: one zs_chunk_filters per array beside its zs_chunk_grid.  With every
+ * field 0 the two _filters_ calls are the calls above: the same bytes, codes and messages.  The rules, which
+ * tests/chunk_filter_cases.py models and the tests pin:
+ *   byte_order 0 (little) or 1 (big).  The array on the device is always little-endian.  With 1 the chunks hold every
+ *     element with its bytes reversed, and `fill`, given in the array's little-endian form, is written reversed into
+ *     padding.  elem_size 1, 2, 4 or 8 (at 1 nothing changes); any other elem_size with byte_order 1 is ZS_STREAM_ERROR from
+ *     the grid check.  With shuffle, plane j of a chunk is byte elem_size - 1 - j of the little-endian element.
+ *   delta 0 or 1 (numcodecs Delta with astype equal to dtype, an integer dtype): elem_size 1, 2, 4 or 8, any other
+ *     ZS_STREAM_ERROR.  Over the whole padded chunk of E elements in C order, wrapping on unsigned values of elem_size bytes:
+ *     enc[0] = x[0], enc[k] = x[k] - x[k-1].  Encode order is delta, byte order, shuffle, deflate, and decode the inverse: with
+ *     byte_order 1 the differences themselves are stored big-endian, as numcodecs does for Delta(dtype='>i4').  A STORED
+ *     chunk still carries delta.
+ *   fletcher32 0 or 1 (HDF5's last filter, fletcher32=True in h5py, NetCDF-4's checksum switch): computed over the chunk's
+ *     bytes as they are stored -- the compressed stream, or the STORED bytes -- and appended as four little-endian bytes;
+ *     len and chunk_len include them.  The checksum is H5_checksum_fletcher32: over the big-endian 16-bit words of the bytes
+ *     (an odd last byte is a word with a zero low byte), s1 the sum of the words and s2 the sum of the running s1, each
+ *     modulo 65535 with a residue of 0 reading as 0xffff unless every word is zero; (s2 << 16) | s1.
+ *   reserved must be 0; a field outside its values is ZS_STREAM_ERROR.
+ * Read side: a chunk with fletcher32 whose len < 4 is ZS_DATA_ERROR "incorrect chunk length", one whose checksum differs
+ * ZS_DATA_ERROR "incorrect chunk checksum"; either fails for itself only and is not handed to inflate.  One launch of the
+ * checksum kernel (KL) runs over all chunks where they lie behind the upload, and the host compares with the four bytes it
+ * holds.  A chunk with delta goes from the inflate buffer (or the upload) through the delta kernels (KI: tile sums, a scan of
+ * them, the tiles again), whose load side unshuffles and reverses, into a buffer of plain little-endian elements that the
+ * place kernel takes; without delta the place kernel itself reverses.
+ * Write side: gather with `fill`, delta (KI's encode kernel, which writes the byte order and the planes; without delta the
+ * gather kernel does), deflate, the stored-or-stream choice and the span copy as above, then one KL launch over the placed
+ * chunks whose fold writes the four bytes behind each. */
+typedef struct zs_chunk_filters {
+    int delta;      /* 0 or 1 */
+    int byte_order; /* 0 little, 1 big */
+    int fletcher32; /* 0 or 1 */
+    int reserved;   /* must be 0 */
+} zs_chunk_filters;
+
+#define ZS_FLETCHER32_TILE 16384 /* bytes of a span that one wave sums (KL) */
+#define ZS_DELTA_TILE 4096       /* elements of a buffer that one wave differences or sums (KI) */
+
+/* zs_chunks_decode_batch with filters[i] for array i (n of them, not NULL). */
+ZS_API int zs_chunks_decode_filters_batch(zs_ctx *ctx, int n, const zs_chunk_grid *grids, const zs_chunk_filters *filters,
+                                          const zs_chunk_ref *const *chunks, void *const *out, const int64_t *out_cap,
+                                          int *const *chunk_status, int *status, void *hip_stream);
+
+/* zs_chunks_encode_batch_device with filters[i] for array i.  zs_chunks_filters_bound is always enough. */
+ZS_API int zs_chunks_encode_filters_batch_device(zs_ctx *ctx, int n, const zs_chunk_grid *grids, const zs_chunk_filters *filters,
+                                                 const void *const *in, void *const *out, const int64_t *out_cap, int64_t *out_len,
+                                                 int64_t *const *chunk_off, int64_t *const *chunk_len, int *const *chunk_flags,
+                                                 int *status, int level, int strategy, int hash_variant, int options,
+                                                 void *hip_stream);
+
+/* zs_chunks_bound(grid) + 4 * n_chunks with fletcher32.  Pure host code.  -1 for a bad grid, a bad pair of grid and filters
+ * (rules above), a null pointer and a result that leaves int64. */
+ZS_API int64_t zs_chunks_filters_bound(const zs_chunk_grid *grid, const zs_chunk_filters *filters);
+
+/* Fletcher-32 (rules above) of n spans in DEVICE memory, any address, len[i] in 0 .. 2^31 - 1, into out (HOST, n words).  One
+ * launch over the ZS_FLETCHER32_TILE-byte tiles of all spans and one that folds a span's tiles; the call waits for the
+ * results. */
+ZS_API int zs_fletcher32_batch_device(zs_ctx *ctx, int n, const void *const *in, const int64_t *len, uint32_t *out,
+                                      void *hip_stream);
+
+/* The delta filter alone on n device buffers of little-endian elements: count = len[i] / elem_size[i] elements, the
+ * len % elem_size leftover bytes copied unchanged; elem_size[i] 1, 2, 4 or 8, len[i] in 0 .. 2^31 - 1, any alignment; in[i]
+ * and out[i] must not overlap. */
+ZS_API int zs_delta_encode_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *len,
+                                        const int *elem_size, void *hip_stream);
+ZS_API int zs_delta_decode_batch_device(zs_ctx *ctx, int n, const void *const *in, void *const *out, const int64_t *len,
+                                        const int *elem_size, void *hip_stream);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU batch entry points (SURVEY.md 8(b) "zs_deflate_batch(..., device_mask)", 8(e)): the n independent

@@ -21,4 +21,5 @@ from .api import (CompressionLevel, CompressionState, CompressionStrategy, Engin
                   tiff_file_info, tiff_decode_files, tiff_encode, tiff_bound, tiff_predict, tiff_unpredict,
                   exr_file_info, exr_decode_files, exr_encode, exr_bound, exr_predict, exr_unpredict,
                   CHUNK_STORED, CHUNK_UNSHUFFLED, CHUNK_SKIP, CHUNK_ABSENT, chunk_grid_info, chunks_decode, chunks_encode, chunks_bound,
-                  shuffle, unshuffle, zarr_v2_grid)
+                  shuffle, unshuffle, zarr_v2_grid, FLETCHER32_TILE, DELTA_TILE, chunks_filters_bound, fletcher32, delta_encode,
+                  delta_decode, zarr_v2_filters)

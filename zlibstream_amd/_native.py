@@ -32,6 +32,8 @@ SYMBOLS = [
     "zs_exr_encode_batch_device",
     "zs_chunk_grid_info", "zs_chunks_decode_batch", "zs_chunks_bound", "zs_chunks_encode_batch_device", "zs_shuffle_batch_device",
     "zs_unshuffle_batch_device",
+    "zs_chunks_decode_filters_batch", "zs_chunks_encode_filters_batch_device", "zs_chunks_filters_bound", "zs_fletcher32_batch_device",
+    "zs_delta_encode_batch_device", "zs_delta_decode_batch_device",
 ]
 
 
@@ -110,6 +112,10 @@ class ExrPut(ctypes.Structure):  # zs_exr_put
 class ChunkGrid(ctypes.Structure):  # zs_chunk_grid
     _fields_ = [("rank", ctypes.c_int), ("elem_size", ctypes.c_int), ("shape", ctypes.c_int64 * 8), ("chunk", ctypes.c_int64 * 8),
                 ("shuffle", ctypes.c_int), ("wrap", ctypes.c_int), ("fill", ctypes.c_uint8 * 16)]
+
+
+class ChunkFilters(ctypes.Structure):  # zs_chunk_filters
+    _fields_ = [("delta", ctypes.c_int), ("byte_order", ctypes.c_int), ("fletcher32", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
 class ChunkRef(ctypes.Structure):  # zs_chunk_ref
@@ -350,6 +356,20 @@ def lib():
         L.zs_shuffle_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i32), vp]
         L.zs_unshuffle_batch_device.restype = i32
         L.zs_unshuffle_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i32), vp]
+    if hasattr(L, "zs_chunks_decode_filters_batch"):
+        L.zs_chunks_decode_filters_batch.restype = i32
+        L.zs_chunks_decode_filters_batch.argtypes = [vp, i32, P(ChunkGrid), P(ChunkFilters), P(P(ChunkRef)), P(vp), P(i64), P(P(i32)), P(i32), vp]
+        L.zs_chunks_encode_filters_batch_device.restype = i32
+        L.zs_chunks_encode_filters_batch_device.argtypes = [vp, i32, P(ChunkGrid), P(ChunkFilters), P(vp), P(vp), P(i64), P(i64), P(P(i64)), P(P(i64)), P(P(i32)),
+                                                            P(i32), i32, i32, i32, i32, vp]
+        L.zs_chunks_filters_bound.restype = i64
+        L.zs_chunks_filters_bound.argtypes = [P(ChunkGrid), P(ChunkFilters)]
+        L.zs_fletcher32_batch_device.restype = i32
+        L.zs_fletcher32_batch_device.argtypes = [vp, i32, P(vp), P(i64), P(ctypes.c_uint32), vp]
+        L.zs_delta_encode_batch_device.restype = i32
+        L.zs_delta_encode_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i32), vp]
+        L.zs_delta_decode_batch_device.restype = i32
+        L.zs_delta_decode_batch_device.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i32), vp]
     if hasattr(L, "zs_zip_file_info"):
         L.zs_zip_file_info.restype = i32
         L.zs_zip_file_info.argtypes = [vp, i64, P(ZipInfo), P(ZipEntry), i64]

@@ -1816,7 +1816,35 @@ def chunks_bound(grid):
     return r
 
 
-def chunks_decode(engine, grids, chunks, out_ptrs, out_caps, stream=None):
+FLETCHER32_TILE, DELTA_TILE = 16384, 4096  # ZS_FLETCHER32_TILE (bytes), ZS_DELTA_TILE (elements)
+_FILTER_KEYS = ("delta", "byte_order", "fletcher32", "reserved")
+
+
+def _chunk_filters(filters, n):
+    """Per array a dict of delta, byte_order (0 little, 1 big) and fletcher32, each 0 / 1 or a bool and 0 when left out, as
+    zs_chunk_filters."""
+    if len(filters) != n:
+        raise ValueError("the filters and the grids differ in length")
+    arr = (_native.ChunkFilters * max(n, 1))()
+    for k, f in enumerate(filters):
+        unknown = set(f) - set(_FILTER_KEYS)
+        if unknown:
+            raise ValueError("chunk filters have no field %s" % sorted(unknown))
+        for key in _FILTER_KEYS:
+            setattr(arr[k], key, int(f.get(key, 0)))
+    return arr
+
+
+def chunks_filters_bound(grid, filters):
+    """zs_chunks_filters_bound (host code): chunks_bound(grid) and four more bytes a chunk with fletcher32.  ValueError for a
+    grid or a pair of grid and filters out of range (delta or big-endian elements of other than 1, 2, 4 or 8 bytes)."""
+    r = _native.lib().zs_chunks_filters_bound(ctypes.byref(_chunk_grid(grid)), _chunk_filters([filters], 1))
+    if r < 0:
+        raise ValueError("chunks_filters_bound: a grid or its filters out of range")
+    return r
+
+
+def chunks_decode(engine, grids, chunks, out_ptrs, out_caps, stream=None, filters=None):
     """The chunks of HDF5 / NetCDF-4 datasets or Zarr v2 arrays (host bytes) -> the arrays in device buffers, many arrays a call
     (zs_chunks_decode_batch).  grids: per array a dict of shape, chunks, elem_size, shuffle, wrap and fill (zarr_v2_grid makes
     one from a .zarray document).  chunks: per array its n_chunks entries in chunk order (C order over the grid: Zarr's key
@@ -1824,7 +1852,8 @@ def chunks_decode(engine, grids, chunks, out_ptrs, out_caps, stream=None):
     CHUNK_UNSHUFFLED (HDF5's filter mask) or CHUNK_SKIP (not fetched: the region is left alone); in a grid with stored set every
     chunk is CHUNK_STORED.  Returns (code, per array the list of its chunks' codes, per-array codes): a chunk fails for itself
     only, its region untouched; the list of an array whose capacity was too small (-5) is empty.  engine.last_error() names the
-    first failing array, the chunk and the reason."""
+    first failing array, the chunk and the reason.  filters (zs_chunks_decode_filters_batch): per array a dict of delta,
+    byte_order and fletcher32 (zarr_v2_filters makes one); a chunk with fletcher32 ends in its four checksum bytes."""
     n = len(grids)
     if len(chunks) != n or len(out_ptrs) != n or len(out_caps) != n:
         raise ValueError("chunks_decode: the argument lists differ in length")
@@ -1855,20 +1884,25 @@ def chunks_decode(engine, grids, chunks, out_ptrs, out_caps, stream=None):
     status = I32()
     rows = (ctypes.POINTER(ctypes.c_int) * n)(*[ctypes.cast(r, ctypes.POINTER(ctypes.c_int)) for r in per_chunk])
     ref_rows = (ctypes.POINTER(_native.ChunkRef) * n)(*[ctypes.cast(r, ctypes.POINTER(_native.ChunkRef)) for r in refs])
-    rc = L.zs_chunks_decode_batch(engine.handle if engine is not None else None, n, garr, ref_rows, VP(*[int(p) for p in out_ptrs]),
-                                  I64(*[int(x) for x in out_caps]), rows, status, ctypes.c_void_p(stream or 0))
+    args = (ref_rows, VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), rows, status, ctypes.c_void_p(stream or 0))
+    if filters is None:
+        rc = L.zs_chunks_decode_batch(engine.handle if engine is not None else None, n, garr, *args)
+    else:
+        rc = L.zs_chunks_decode_filters_batch(engine.handle if engine is not None else None, n, garr, _chunk_filters(filters, n), *args)
     if rc not in (0, 2, -3, -5):
         raise ValueError("zs_chunks_decode_batch failed (%d): %s" % (rc, (engine.last_error() if engine is not None else "") or "stream error"))
     return rc, [list(per_chunk[i][:counts[i]]) for i in range(n)], list(status)
 
 
-def chunks_encode(engine, grids, in_ptrs, out_ptrs, out_caps, level=6, strategy=0, hash_variant=0, skip_fill=False, allow_stored=False, stream=None):
+def chunks_encode(engine, grids, in_ptrs, out_ptrs, out_caps, level=6, strategy=0, hash_variant=0, skip_fill=False, allow_stored=False, stream=None, filters=None):
     """Device-resident arrays -> their chunks in device buffers, many arrays a call (zs_chunks_encode_batch_device): shuffled
     where the grid says so, deflated into the grid's container, back to back in chunk order.  skip_fill: a chunk whose existing
     elements all equal fill is not written (CHUNK_ABSENT, length 0).  allow_stored: a chunk whose stream is not shorter than
     its bytes is written as those (CHUNK_STORED), HDF5's rule; without it every chunk is a stream, Zarr's.  Returns (code,
     lengths, per array the list of its chunks' (offset, length, flags), per-array codes): -5 (ZS_BUF_ERROR) for an array whose
-    capacity was too small -- its length is then what it needs and nothing is written for it."""
+    capacity was too small -- its length is then what it needs and nothing is written for it.  filters
+    (zs_chunks_encode_filters_batch_device): per array a dict of delta, byte_order and fletcher32; the lengths then include the
+    four checksum bytes of a chunk with fletcher32, and chunks_filters_bound is the room."""
     n = len(grids)
     if len(in_ptrs) != n or len(out_ptrs) != n or len(out_caps) != n:
         raise ValueError("chunks_encode: the argument lists differ in length")
@@ -1879,11 +1913,14 @@ def chunks_encode(engine, grids, in_ptrs, out_ptrs, out_caps, level=6, strategy=
     VP, I64, I32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
     P64, P32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)
     out_len, status = I64(), I32()
-    rc = _native.lib().zs_chunks_encode_batch_device(engine.handle if engine is not None else None, n, _chunk_grids(grids), VP(*[int(p) for p in in_ptrs]),
-                                                     VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len,
-                                                     (P64 * n)(*[ctypes.cast(a, P64) for a in offs]), (P64 * n)(*[ctypes.cast(a, P64) for a in lens]),
-                                                     (P32 * n)(*[ctypes.cast(a, P32) for a in flags]), status, int(level), int(strategy), int(hash_variant),
-                                                     (1 if skip_fill else 0) | (2 if allow_stored else 0), ctypes.c_void_p(stream or 0))
+    args = (VP(*[int(p) for p in in_ptrs]), VP(*[int(p) for p in out_ptrs]), I64(*[int(x) for x in out_caps]), out_len,
+            (P64 * n)(*[ctypes.cast(a, P64) for a in offs]), (P64 * n)(*[ctypes.cast(a, P64) for a in lens]),
+            (P32 * n)(*[ctypes.cast(a, P32) for a in flags]), status, int(level), int(strategy), int(hash_variant),
+            (1 if skip_fill else 0) | (2 if allow_stored else 0), ctypes.c_void_p(stream or 0))
+    if filters is None:
+        rc = _native.lib().zs_chunks_encode_batch_device(engine.handle if engine is not None else None, n, _chunk_grids(grids), *args)
+    else:
+        rc = _native.lib().zs_chunks_encode_filters_batch_device(engine.handle if engine is not None else None, n, _chunk_grids(grids), _chunk_filters(filters, n), *args)
     if rc == -2:
         raise ValueError("zs_chunks_encode_batch_device: " + ((engine.last_error() if engine is not None else "") or "stream error"))
     if rc not in (0, -5):
@@ -1915,6 +1952,77 @@ def shuffle(engine, in_ptrs, out_ptrs, lens, elem_sizes, stream=None):
 def unshuffle(engine, in_ptrs, out_ptrs, lens, elem_sizes, stream=None):
     """The inverse of shuffle (zs_unshuffle_batch_device)."""
     _shuffle_call(_native.lib().zs_unshuffle_batch_device, "unshuffle", engine, in_ptrs, out_ptrs, lens, elem_sizes, stream)
+
+
+def fletcher32(engine, ptrs, lens, stream=None):
+    """HDF5's Fletcher-32 of device buffers (zs_fletcher32_batch_device): a list of 32-bit checksums.  Any address, lens[i] in
+    0 .. 2^31 - 1."""
+    n = len(ptrs)
+    if len(lens) != n:
+        raise ValueError("fletcher32: the argument lists differ in length")
+    if n == 0:
+        return []
+    out = (ctypes.c_uint32 * n)()
+    rc = _native.lib().zs_fletcher32_batch_device(engine.handle if engine is not None else None, n, (ctypes.c_void_p * n)(*[int(p) for p in ptrs]),
+                                                  (ctypes.c_int64 * n)(*[int(v) for v in lens]), out, ctypes.c_void_p(stream or 0))
+    if rc == -2:
+        raise ValueError("fletcher32: " + ((engine.last_error() if engine is not None else "") or "stream error"))
+    if rc != 0:
+        raise ZlibStreamException("fletcher32 failed (%d): %s" % (rc, engine.last_error()))
+    return list(out)
+
+
+def delta_encode(engine, in_ptrs, out_ptrs, lens, elem_sizes, stream=None):
+    """numcodecs Delta on device buffers of little-endian elements of 1, 2, 4 or 8 bytes (zs_delta_encode_batch_device):
+    out[0] = in[0], out[k] = in[k] - in[k-1], wrapping; the len % elem_size leftover bytes copied.  Any alignment, no overlap."""
+    _shuffle_call(_native.lib().zs_delta_encode_batch_device, "delta_encode", engine, in_ptrs, out_ptrs, lens, elem_sizes, stream)
+
+
+def delta_decode(engine, in_ptrs, out_ptrs, lens, elem_sizes, stream=None):
+    """The inverse of delta_encode, a prefix sum (zs_delta_decode_batch_device)."""
+    _shuffle_call(_native.lib().zs_delta_decode_batch_device, "delta_decode", engine, in_ptrs, out_ptrs, lens, elem_sizes, stream)
+
+
+def zarr_v2_filters(zarray_json):
+    """A Zarr v2 .zarray document as (grid, filters) for chunks_decode / chunks_encode with filters=.  Beyond zarr_v2_grid it
+    accepts big-endian dtypes of 2, 4 and 8 bytes (fill stays in the array's little-endian form) and, in front of the optional
+    shuffle, one {"id": "delta", "dtype": D, "astype": D} whose dtype and astype (which may be left out) are the array's dtype, an
+    integer of 1, 2, 4 or 8 bytes.  ValueError naming the key for anything else."""
+    import json
+
+    import numpy as np
+    doc = zarray_json if isinstance(zarray_json, dict) else json.loads(zarray_json.decode() if isinstance(zarray_json, (bytes, bytearray)) else zarray_json)
+
+    def bad(field, why):
+        return ValueError("zarr_v2_filters: %s: %s" % (field, why))
+    spec, doc = doc.get("dtype"), dict(doc)
+    big = False
+    if isinstance(spec, str) and len(spec) >= 2 and spec[0] == ">":
+        try:
+            big = np.dtype(spec).itemsize > 1
+        except TypeError:
+            raise bad("dtype", "not a dtype numpy knows")
+        if big and (np.dtype(spec).itemsize not in (2, 4, 8) or np.dtype(spec).kind in "OUVS"):
+            raise bad("dtype", "a big-endian dtype of 2, 4 or 8 bytes is required")
+        doc["dtype"] = "<" + spec[1:]
+    filters = doc.get("filters") or []
+    delta = False
+    if isinstance(filters, list) and filters and isinstance(filters[0], dict) and filters[0].get("id") == "delta":
+        f = filters[0]
+        try:
+            dt = np.dtype(spec)
+            same = np.dtype(f.get("dtype")) == dt and np.dtype(f.get("astype", f.get("dtype"))) == dt and set(f) <= {"id", "dtype", "astype"}
+        except TypeError:
+            same = False
+        if not isinstance(spec, str) or not same or dt.kind not in "iu" or dt.itemsize not in (1, 2, 4, 8):
+            raise bad("filters", "a delta filter whose dtype and astype are the array's integer dtype of 1, 2, 4 or 8 bytes is required")
+        delta, doc["filters"] = True, filters[1:]
+    try:
+        grid = zarr_v2_grid(doc)
+    except ValueError as e:
+        raise ValueError(str(e).replace("zarr_v2_grid:", "zarr_v2_filters:", 1))
+    grid["dtype"] = spec
+    return grid, {"delta": int(delta), "byte_order": int(big), "fletcher32": 0}
 
 
 def zarr_v2_grid(zarray_json):

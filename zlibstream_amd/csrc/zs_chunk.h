@@ -8,6 +8,8 @@
 // elements in the chunk, clipped to shape[rank-1] in the array, contiguous in both.  A row is cut into stretches of
 // 256 * unit elements, a wave's work: four passes of 64 lanes x `unit` elements (16, 4 or 1 by the length of a row, so that a
 // short row is still many lanes' work).
+// Behind KN's steps: the rules of zs_chunk_filters, Fletcher-32 in closed form with its per-lane step and combine rule, and the
+// per-lane steps of the delta filter; tests/cpp/test_chunk_filters.cpp runs those on the host.
 #pragma once
 
 #include <cstdint>
@@ -22,7 +24,8 @@ constexpr int64_t kChunkMaxBytes = 0x7FFFFFFF - 1024;  // a chunk, in one call o
 constexpr int kChunkPasses = 4;                        // passes of the wave over a stretch
 
 enum { kChunkStored = 1, kChunkUnshuffled = 2, kChunkSkip = 4, kChunkAbsent = 8 };  // ZS_CHUNK_*
-enum { kJobPlain = 1, kJobFill = 2 };  // a job's bytes are not shuffled; it has none: its region is `fill`
+// a job's bytes are not shuffled; it has none: its region is `fill`; its elements (of 2, 4 or 8 bytes) lie big-endian in the chunk
+enum { kJobPlain = 1, kJobFill = 2, kJobSwap = 4 };
 
 struct ChunkGrid {  // zs_chunk_grid
     int32_t rank, elem_size;
@@ -192,12 +195,13 @@ ZS_HD uint32_t chunk_byte(const uint32_t *w, int b) { return (w[b >> 2] >> (8 * 
 
 // ---- a lane's unit of U whole elements of ES bytes: U bytes of each plane (16: one 16-byte load a plane) interleaved in
 // registers and written as U * ES contiguous bytes, 16 at a time; and the inverse
+// (swap: the chunk's elements are big-endian -- plane j holds byte ES - 1 - j of the little-endian element)
 template <int ES, int U>
-ZS_HD void chunk_place_unit(const uint8_t *planes, int64_t E, uint8_t *out) {
+ZS_HD void chunk_place_unit(const uint8_t *planes, int64_t E, uint8_t *out, bool swap = false) {
     constexpr int W = U / 4;
     uint32_t in[ES][W], o[ES * W];
 #pragma unroll
-    for (int j = 0; j < ES; j++) chunk_ld_words<W>(planes + j * E, in[j]);
+    for (int j = 0; j < ES; j++) chunk_ld_words<W>(planes + (swap ? ES - 1 - j : j) * E, in[j]);
 #pragma unroll
     for (int k = 0; k < ES * W; k++) {
         uint32_t v = 0;
@@ -208,7 +212,7 @@ ZS_HD void chunk_place_unit(const uint8_t *planes, int64_t E, uint8_t *out) {
     chunk_st_words<ES * W>(out, o);
 }
 template <int ES, int U>
-ZS_HD void chunk_gather_unit(const uint8_t *in, uint8_t *planes, int64_t E) {
+ZS_HD void chunk_gather_unit(const uint8_t *in, uint8_t *planes, int64_t E, bool swap = false) {
     constexpr int W = U / 4;
     uint32_t a[ES * W], o[W];
     chunk_ld_words<ES * W>(in, a);
@@ -221,42 +225,42 @@ ZS_HD void chunk_gather_unit(const uint8_t *in, uint8_t *planes, int64_t E) {
             for (int b = 0; b < 4; b++) v |= chunk_byte(a, (4 * k + b) * ES + j) << (8 * b);
             o[k] = v;
         }
-        chunk_st_words<W>(planes + j * E, o);
+        chunk_st_words<W>(planes + (swap ? ES - 1 - j : j) * E, o);
     }
 }
 
 // ---- a lane's share of a stretch of n elements: every 64th unit from its own on; the unit that the stretch ends in, byte by byte
 template <int ES, int U>
-ZS_HD void chunk_place_stretch(const uint8_t *planes, int64_t E, uint8_t *out, int n, int lane) {
+ZS_HD void chunk_place_stretch(const uint8_t *planes, int64_t E, uint8_t *out, int n, int lane, bool swap = false) {
     for (int e = lane * U; e < n; e += 64 * U) {
         if (e + U <= n) {
-            chunk_place_unit<ES, U>(planes + e, E, out + (int64_t)e * ES);
+            chunk_place_unit<ES, U>(planes + e, E, out + (int64_t)e * ES, swap);
         } else {
             for (int i = e; i < n; i++)
-                for (int j = 0; j < ES; j++) out[(int64_t)i * ES + j] = planes[j * E + i];
+                for (int j = 0; j < ES; j++) out[(int64_t)i * ES + j] = planes[(swap ? ES - 1 - j : j) * E + i];
         }
     }
 }
 // (first n_exist elements from the array, the others `fill`)
 template <int ES, int U>
-ZS_HD void chunk_gather_stretch(const uint8_t *in, uint8_t *planes, int64_t E, int n, int n_exist, const uint8_t *fill, int lane) {
+ZS_HD void chunk_gather_stretch(const uint8_t *in, uint8_t *planes, int64_t E, int n, int n_exist, const uint8_t *fill, int lane, bool swap = false) {
     for (int e = lane * U; e < n; e += 64 * U) {
         if (e + U <= n_exist) {
-            chunk_gather_unit<ES, U>(in + (int64_t)e * ES, planes + e, E);
+            chunk_gather_unit<ES, U>(in + (int64_t)e * ES, planes + e, E, swap);
         } else {
             for (int i = e; i < n && i < e + U; i++)
-                for (int j = 0; j < ES; j++) planes[j * E + i] = i < n_exist ? in[(int64_t)i * ES + j] : fill[j];
+                for (int j = 0; j < ES; j++) planes[(swap ? ES - 1 - j : j) * E + i] = i < n_exist ? in[(int64_t)i * ES + j] : fill[j];
         }
     }
 }
 // any element size, an element a lane and pass
-ZS_HD void chunk_place_stretch_any(const uint8_t *planes, int64_t E, int es, uint8_t *out, int n, int lane) {
+ZS_HD void chunk_place_stretch_any(const uint8_t *planes, int64_t E, int es, uint8_t *out, int n, int lane, bool swap = false) {
     for (int i = lane; i < n; i += 64)
-        for (int j = 0; j < es; j++) out[(int64_t)i * es + j] = planes[j * E + i];
+        for (int j = 0; j < es; j++) out[(int64_t)i * es + j] = planes[(swap ? es - 1 - j : j) * E + i];
 }
-ZS_HD void chunk_gather_stretch_any(const uint8_t *in, uint8_t *planes, int64_t E, int es, int n, int n_exist, const uint8_t *fill, int lane) {
+ZS_HD void chunk_gather_stretch_any(const uint8_t *in, uint8_t *planes, int64_t E, int es, int n, int n_exist, const uint8_t *fill, int lane, bool swap = false) {
     for (int i = lane; i < n; i += 64)
-        for (int j = 0; j < es; j++) planes[j * E + i] = i < n_exist ? in[(int64_t)i * es + j] : fill[j];
+        for (int j = 0; j < es; j++) planes[(swap ? es - 1 - j : j) * E + i] = i < n_exist ? in[(int64_t)i * es + j] : fill[j];
 }
 
 // 16 bytes of the fill pattern from byte b of a run of elements on
@@ -269,18 +273,38 @@ ZS_HD void chunk_fill16(const uint8_t *fill, int es, int b, uint32_t w[4]) {
         j = j + 1 == es ? 0 : j + 1;
     }
 }
-// ---- the plain forms, over the bytes of a stretch, 16 a lane and pass: bytes [0, n_copy) copied, [n_copy, n) the fill pattern
-ZS_HD void chunk_copy_fill_stretch(const uint8_t *in, uint8_t *out, int n, int n_copy, const uint8_t *fill, int es, int lane) {
+// 16 bytes that hold whole elements of es = 2, 4 or 8 bytes, every element's bytes reversed
+ZS_HD void chunk_swap16(uint32_t w[4], int es) {
+    if (es == 2) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = ((w[k] & 0x00FF00FFu) << 8) | ((w[k] >> 8) & 0x00FF00FFu);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = __builtin_bswap32(w[k]);
+        if (es == 8) {
+            uint32_t t = w[0];
+            w[0] = w[1], w[1] = t, t = w[2], w[2] = w[3], w[3] = t;
+        }
+    }
+}
+// ---- the plain forms, over the bytes of a stretch, 16 a lane and pass: bytes [0, n_copy) copied, [n_copy, n) the fill pattern;
+// swap (es 2, 4 or 8; the stretch and n_copy are whole elements): every element written with its bytes reversed
+ZS_HD void chunk_copy_fill_stretch(const uint8_t *in, uint8_t *out, int n, int n_copy, const uint8_t *fill, int es, int lane, bool swap = false) {
     for (int b = lane * 16; b < n; b += 64 * 16) {
         uint32_t w[4];
         if (b + 16 <= n_copy) {
             chunk_ld16(in + b, w);
+            if (swap) chunk_swap16(w, es);
             chunk_st16(out + b, w);
         } else if (b >= n_copy && b + 16 <= n) {
             chunk_fill16(fill, es, b, w);
+            if (swap) chunk_swap16(w, es);
             chunk_st16(out + b, w);
         } else {
-            for (int i = b; i < n && i < b + 16; i++) out[i] = i < n_copy ? in[i] : fill[i % es];
+            for (int i = b; i < n && i < b + 16; i++) {
+                const int k = swap ? i - i % es + (es - 1 - i % es) : i;  // the byte of the little-endian side that lands at i
+                out[i] = i < n_copy ? in[k] : fill[k % es];
+            }
         }
     }
 }
@@ -309,20 +333,21 @@ ZS_HD bool chunk_is_fill_stretch(const uint8_t *in, int n, const uint8_t *fill, 
 ZS_HD void chunk_place_item(const ChunkGeom &g, const ChunkJob &jb, int64_t q, int lane) {
     const ChunkItem it = chunk_item(g, jb.ext, false, q);
     uint8_t *out = jb.arr + it.a_off * g.es;
+    const bool swap = (jb.flags & kJobSwap) != 0;
     if (jb.flags & kJobFill) {
         chunk_copy_fill_stretch(out, out, it.n * g.es, 0, g.fill, g.es, lane);
     } else if (jb.flags & kJobPlain) {
-        chunk_copy_fill_stretch(jb.chunk + it.c_off * g.es, out, it.n * g.es, it.n * g.es, g.fill, g.es, lane);
+        chunk_copy_fill_stretch(jb.chunk + it.c_off * g.es, out, it.n * g.es, it.n * g.es, g.fill, g.es, lane, swap);
     } else {
         const uint8_t *planes = jb.chunk + it.c_off;
         if (g.unit == 1 || !(g.es == 2 || g.es == 4 || g.es == 8)) {
-            chunk_place_stretch_any(planes, g.E, g.es, out, it.n, lane);
+            chunk_place_stretch_any(planes, g.E, g.es, out, it.n, lane, swap);
         } else if (g.es == 2) {
-            ZS_CHUNK_UNITS(chunk_place_stretch, 2, planes, g.E, out, it.n, lane);
+            ZS_CHUNK_UNITS(chunk_place_stretch, 2, planes, g.E, out, it.n, lane, swap);
         } else if (g.es == 4) {
-            ZS_CHUNK_UNITS(chunk_place_stretch, 4, planes, g.E, out, it.n, lane);
+            ZS_CHUNK_UNITS(chunk_place_stretch, 4, planes, g.E, out, it.n, lane, swap);
         } else {
-            ZS_CHUNK_UNITS(chunk_place_stretch, 8, planes, g.E, out, it.n, lane);
+            ZS_CHUNK_UNITS(chunk_place_stretch, 8, planes, g.E, out, it.n, lane, swap);
         }
     }
 }
@@ -330,18 +355,19 @@ ZS_HD void chunk_place_item(const ChunkGeom &g, const ChunkJob &jb, int64_t q, i
 ZS_HD void chunk_gather_item(const ChunkGeom &g, const ChunkJob &jb, int64_t q, int lane) {
     const ChunkItem it = chunk_item(g, jb.ext, true, q);
     const uint8_t *in = jb.arr + it.a_off * g.es;
+    const bool swap = (jb.flags & kJobSwap) != 0;
     if (jb.flags & kJobPlain) {
-        chunk_copy_fill_stretch(in, jb.chunk + it.c_off * g.es, it.n * g.es, it.n_exist * g.es, g.fill, g.es, lane);
+        chunk_copy_fill_stretch(in, jb.chunk + it.c_off * g.es, it.n * g.es, it.n_exist * g.es, g.fill, g.es, lane, swap);
     } else {
         uint8_t *planes = jb.chunk + it.c_off;
         if (g.unit == 1 || !(g.es == 2 || g.es == 4 || g.es == 8)) {
-            chunk_gather_stretch_any(in, planes, g.E, g.es, it.n, it.n_exist, g.fill, lane);
+            chunk_gather_stretch_any(in, planes, g.E, g.es, it.n, it.n_exist, g.fill, lane, swap);
         } else if (g.es == 2) {
-            ZS_CHUNK_UNITS(chunk_gather_stretch, 2, in, planes, g.E, it.n, it.n_exist, g.fill, lane);
+            ZS_CHUNK_UNITS(chunk_gather_stretch, 2, in, planes, g.E, it.n, it.n_exist, g.fill, lane, swap);
         } else if (g.es == 4) {
-            ZS_CHUNK_UNITS(chunk_gather_stretch, 4, in, planes, g.E, it.n, it.n_exist, g.fill, lane);
+            ZS_CHUNK_UNITS(chunk_gather_stretch, 4, in, planes, g.E, it.n, it.n_exist, g.fill, lane, swap);
         } else {
-            ZS_CHUNK_UNITS(chunk_gather_stretch, 8, in, planes, g.E, it.n, it.n_exist, g.fill, lane);
+            ZS_CHUNK_UNITS(chunk_gather_stretch, 8, in, planes, g.E, it.n, it.n_exist, g.fill, lane, swap);
         }
     }
 }
@@ -349,6 +375,187 @@ ZS_HD void chunk_gather_item(const ChunkGeom &g, const ChunkJob &jb, int64_t q, 
 ZS_HD bool chunk_survey_item(const ChunkGeom &g, const ChunkJob &jb, int64_t q, int lane) {
     const ChunkItem it = chunk_item(g, jb.ext, false, q);
     return chunk_is_fill_stretch(jb.arr + it.a_off * g.es, it.n * g.es, g.fill, g.es, lane);
+}
+
+// ================================================================== the filters beside shuffle (zs_chunk_filters)
+struct ChunkFilters {  // zs_chunk_filters
+    int32_t delta, byte_order, fletcher32, reserved;
+};
+// every field 0 or 1, reserved 0; delta and big-endian elements need an element of 1, 2, 4 or 8 bytes
+ZS_HD bool chunk_filters_check(int elem_size, const ChunkFilters &f) {
+    if (f.delta < 0 || f.delta > 1 || f.byte_order < 0 || f.byte_order > 1 || f.fletcher32 < 0 || f.fletcher32 > 1 || f.reserved != 0) return false;
+    const bool pow2 = elem_size == 1 || elem_size == 2 || elem_size == 4 || elem_size == 8;
+    return pow2 || !(f.delta || f.byte_order);
+}
+
+// ---- Fletcher-32 as HDF5 computes it (H5_checksum_fletcher32), in closed form: over the big-endian 16-bit words w_0 .. w_(N-1)
+// of the bytes (an odd last byte is a word with a zero low byte), s1 = sum w_i and s2 = sum (N - i) w_i, both modulo 65535, a
+// residue of 0 reading as 0xffff unless every word is zero.  A tile's pair (a1, a2) over its own n words, followed by m more
+// words with the pair (b1, b2), combines to (a1 + b1, a2 + m a1 + b2).
+constexpr int kFletTile = 16384;  // bytes of a tile (even: every tile but a span's last is whole words)
+struct FletSum {
+    uint32_t a1, a2, nz, pad;  // both below 65535; whether a byte of the words was not zero
+};
+struct FletSpan {
+    const uint8_t *src;
+    uint8_t *dst;  // where the four bytes of the checksum go, little-endian (may be null)
+    int64_t len;
+};
+ZS_HD FletSum fletcher_combine(const FletSum &a, const FletSum &b, int64_t m_words) {
+    FletSum r;
+    r.a1 = (a.a1 + b.a1) % 65535u;
+    r.a2 = (uint32_t)(((uint64_t)a.a2 + (uint64_t)(m_words % 65535) * a.a1 + b.a2) % 65535u);
+    r.nz = a.nz | b.nz, r.pad = 0;
+    return r;
+}
+ZS_HD uint32_t fletcher_finish(const FletSum &s) {
+    const uint32_t s1 = s.a1 ? s.a1 : (s.nz ? 0xFFFFu : 0u), s2 = s.a2 ? s.a2 : (s.nz ? 0xFFFFu : 0u);
+    return (s2 << 16) | s1;
+}
+ZS_HD int64_t fletcher_tiles(int64_t len) { return (len + kFletTile - 1) / kFletTile; }
+
+// One 16-byte word of a tile as a lane meets it: byte i of it is byte p0 + i of the tile (p0 = 16 m - h may be negative in the
+// tile's first word; bytes outside [0, len) do not count).  Adds the word's share of (sum w, sum (n - index) w) over the tile's
+// n words to A1, A2: at most 2^20 and 2^34 a word, so a lane's 64-bit sums hold any tile.
+ZS_HD void fletcher_word(const uint32_t w[4], int p0, int len, int n, uint64_t *A1, uint64_t *A2) {
+    const int odd = p0 & 1, wi0 = (p0 - odd) / 2;  // the word index of byte p0's word (p0 - odd is even, also below 0)
+    const bool full = p0 >= 0 && p0 + 16 <= len;
+    uint32_t S = 0, T = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        uint32_t v = chunk_byte(w, i) << (((i ^ odd) & 1) ? 0 : 8);
+        if (!full && (p0 + i < 0 || p0 + i >= len)) v = 0;
+        S += v, T += (uint32_t)((i + odd) >> 1) * v;
+    }
+    *A1 += S;
+    *A2 += (uint64_t)((int64_t)(n - wi0) * (int64_t)S - (int64_t)T);  // (every byte that counts has an index below n)
+}
+// a lane's share of a tile of len bytes that begins h bytes into the aligned word `base` points at: words lane, lane + 64, ...
+ZS_HD void fletcher_tile_lane(const uint8_t *base, int h, int len, int lane, uint64_t *A1, uint64_t *A2) {
+    const int n = (len + 1) / 2, words = (h + len + 15) >> 4;
+    for (int m = lane; m < words; m += 64) {
+        uint32_t w[4];
+        chunk_ld16(base + 16 * (int64_t)m, w);
+        fletcher_word(w, 16 * m - h, len, n, A1, A2);
+    }
+}
+
+// ---- delta (numcodecs Delta over the whole padded chunk): enc[0] = x[0], enc[k] = x[k] - x[k-1], wrapping on elem_size bytes
+constexpr int kDeltaUnit = 16, kDeltaPasses = 4;
+constexpr int kDeltaTile = 64 * kDeltaUnit * kDeltaPasses;  // elements of a tile, a wave's work
+enum { kDeltaShuffled = 1, kDeltaSwap = 2 };                // of a job's chunk side: in planes; elements big-endian
+struct DeltaJob {
+    const uint8_t *in;
+    uint8_t *out;
+    int64_t E;                 // elements
+    int32_t es, flags, left;   // left: bytes behind the elements, copied unchanged (a bare buffer's len % elem_size)
+    int32_t pad;
+};
+ZS_HD int64_t delta_tiles(int64_t E, int left) { return E ? (E + kDeltaTile - 1) / kDeltaTile : (left ? 1 : 0); }
+
+// cnt <= 16 elements from element e on, as little-endian values: of a chunk side (flags: in planes of E bytes, plane j byte j of
+// the stored element; big-endian) or, flags 0, of plain little-endian elements
+template <int ES>
+ZS_HD void delta_load(const uint8_t *p, int64_t E, int flags, int64_t e, int cnt, uint64_t x[kDeltaUnit]) {
+    const bool sh = (flags & kDeltaShuffled) && ES > 1, swap = (flags & kDeltaSwap) && ES > 1;
+#pragma unroll
+    for (int k = 0; k < kDeltaUnit; k++) x[k] = 0;
+    if (cnt == kDeltaUnit && sh) {
+#pragma unroll
+        for (int j = 0; j < ES; j++) {
+            uint32_t w[4];
+            chunk_ld16(p + (int64_t)(swap ? ES - 1 - j : j) * E + e, w);
+#pragma unroll
+            for (int k = 0; k < kDeltaUnit; k++) x[k] |= (uint64_t)chunk_byte(w, k) << (8 * j);
+        }
+    } else if (cnt == kDeltaUnit) {
+        uint32_t w[4 * ES];
+        chunk_ld_words<4 * ES>(p + e * ES, w);
+#pragma unroll
+        for (int k = 0; k < kDeltaUnit; k++)
+#pragma unroll
+            for (int j = 0; j < ES; j++) x[k] |= (uint64_t)chunk_byte(w, k * ES + (swap ? ES - 1 - j : j)) << (8 * j);
+    } else {
+        for (int k = 0; k < cnt; k++)
+            for (int j = 0; j < ES; j++) {
+                const int sj = swap ? ES - 1 - j : j;
+                x[k] |= (uint64_t)(sh ? p[(int64_t)sj * E + e + k] : p[(e + k) * ES + sj]) << (8 * j);
+            }
+    }
+}
+template <int ES>
+ZS_HD void delta_store(uint8_t *p, int64_t E, int flags, int64_t e, int cnt, const uint64_t x[kDeltaUnit]) {
+    const bool sh = (flags & kDeltaShuffled) && ES > 1, swap = (flags & kDeltaSwap) && ES > 1;
+    if (cnt == kDeltaUnit && sh) {
+#pragma unroll
+        for (int j = 0; j < ES; j++) {
+            uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < kDeltaUnit; k++) w[k >> 2] |= (uint32_t)((x[k] >> (8 * j)) & 255u) << (8 * (k & 3));
+            chunk_st16(p + (int64_t)(swap ? ES - 1 - j : j) * E + e, w);
+        }
+    } else if (cnt == kDeltaUnit) {
+        uint32_t w[4 * ES];
+#pragma unroll
+        for (int i = 0; i < 4 * ES; i++) w[i] = 0;
+#pragma unroll
+        for (int k = 0; k < kDeltaUnit; k++)
+#pragma unroll
+            for (int j = 0; j < ES; j++) {
+                const int b = k * ES + (swap ? ES - 1 - j : j);
+                w[b >> 2] |= (uint32_t)((x[k] >> (8 * j)) & 255u) << (8 * (b & 3));
+            }
+        chunk_st_words<4 * ES>(p + e * ES, w);
+    } else {
+        for (int k = 0; k < cnt; k++)
+            for (int j = 0; j < ES; j++) {
+                const int sj = swap ? ES - 1 - j : j;
+                (sh ? p[(int64_t)sj * E + e + k] : p[(e + k) * ES + sj]) = (uint8_t)(x[k] >> (8 * j));
+            }
+    }
+}
+// the elements of pass `pass` of tile t that lane `lane` holds: from *e on, 0 .. 16 of them
+ZS_HD int delta_lane_span(int64_t E, int64_t t, int pass, int lane, int64_t *e) {
+    *e = t * kDeltaTile + ((int64_t)pass * 64 + lane) * kDeltaUnit;
+    const int64_t left = E - *e;
+    return left <= 0 ? 0 : left < kDeltaUnit ? (int)left : kDeltaUnit;
+}
+// encode, one lane's elements of one pass: x[k] - x[k-1] from the plain elements of jb.in into jb.out's chunk side
+template <int ES>
+ZS_HD void delta_encode_lane(const DeltaJob &jb, int64_t t, int pass, int lane) {
+    int64_t e;
+    const int cnt = delta_lane_span(jb.E, t, pass, lane, &e);
+    if (cnt == 0) return;
+    uint64_t x[kDeltaUnit], d[kDeltaUnit], prev = 0;
+    delta_load<ES>(jb.in, jb.E, 0, e, cnt, x);
+    if (e > 0)
+        for (int j = 0; j < ES; j++) prev |= (uint64_t)jb.in[(e - 1) * ES + j] << (8 * j);
+#pragma unroll
+    for (int k = 0; k < kDeltaUnit; k++) d[k] = x[k] - (k ? x[k - 1] : prev);
+    delta_store<ES>(jb.out, jb.E, jb.flags, e, cnt, d);
+}
+// decode: a lane's elements of one pass from the chunk side, and their sum (pass 1 needs no more) ...
+template <int ES>
+ZS_HD uint64_t delta_decode_load(const DeltaJob &jb, int64_t t, int pass, int lane, uint64_t x[kDeltaUnit], int64_t *e, int *cnt) {
+    *cnt = delta_lane_span(jb.E, t, pass, lane, e);
+    uint64_t sum = 0;
+    if (*cnt == 0) return 0;
+    delta_load<ES>(jb.in, jb.E, jb.flags, *e, *cnt, x);
+#pragma unroll
+    for (int k = 0; k < kDeltaUnit; k++) sum += x[k];  // (elements behind cnt are 0)
+    return sum;
+}
+// ... and, pass 2, its running sums from `before` (everything in front of the lane's first element) on, written plain
+template <int ES>
+ZS_HD void delta_decode_store(const DeltaJob &jb, int64_t e, int cnt, uint64_t x[kDeltaUnit], uint64_t before) {
+    if (cnt == 0) return;
+#pragma unroll
+    for (int k = 0; k < kDeltaUnit; k++) before += x[k], x[k] = before;
+    delta_store<ES>(jb.out, jb.E, 0, e, cnt, x);
+}
+// the bytes behind the elements, by the lanes of the job's last tile
+ZS_HD void delta_copy_left(const DeltaJob &jb, int64_t t, int lane) {
+    if (t + 1 == delta_tiles(jb.E, jb.left) && lane < jb.left) jb.out[jb.E * jb.es + lane] = jb.in[jb.E * jb.es + lane];
 }
 
 }  // namespace zs

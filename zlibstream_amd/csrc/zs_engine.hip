@@ -55,10 +55,10 @@ enum PngBuf {
     // streams in front of the framing launch, a call's files; the ZIP writer's zlib streams (zs_zip_host.inc); the TIFF calls'
     // chunks between inflate or deflate and the predictor kernel, that kernel's descriptors, the writer's zlib streams
     // (zs_tiff_host.inc); the same three of the OpenEXR calls, and KE's segment sums (zs_exr_host.inc); of the chunked-array
-    // calls KN's descriptors, the chunks between inflate or deflate and KN, the writer's streams, the survey's records
-    // (zs_chunk_host.inc)
+    // calls KN's descriptors, the chunks between inflate or deflate and KN, the writer's streams, the survey's records, the
+    // chunks between the delta kernels and KN or deflate, the tile records of KL and tile sums of KI (zs_chunk_host.inc)
     kBufWrapHead, kBufWrapGather, kBufWrapZs, kBufWrapFiles, kBufZipZs, kBufTiffChunks, kBufTiffDesc, kBufTiffZs, kBufExrChunks, kBufExrDesc, kBufExrZs, kBufExrSegs,
-    kBufChunkDesc, kBufChunkData, kBufChunkZs, kBufChunkRec,
+    kBufChunkDesc, kBufChunkData, kBufChunkZs, kBufChunkRec, kBufChunkDelta, kBufChunkAux,
     kBufPngCount
 };
 
