@@ -1,8 +1,8 @@
 // zs_chunk_host.inc -- host side of the chunked-array calls of include/zsgpu.h: the chunks of HDF5 / NetCDF-4 datasets and
 // Zarr v2 arrays (shuffle in front of deflate) from host memory decoded on the device into arrays, arrays that lie there
-// written as chunks, and the shuffle filter alone.  Part of zs_engine.hip's translation unit, behind zs_wrap_host.inc, whose
-// container calls it calls; the flat-list runner (png_run_list) and the KC job runner (Crc32Job) are zs_png_host.inc's; the
-// geometry is zs_chunk.h's, the kernels (KN) zs_chunk.hip's.  The two array calls take a zs_chunk_filters per array
+// written as chunks, and the shuffle filter alone.  Part of zs_engine.hip's translation unit, behind zs_parts_host.inc, whose gate,
+// staging and roll-up of the codes it takes (zs_parts.h), and zs_wrap_host.inc, whose container calls it calls; the
+// flat-list runner (png_run_list) and the KC job runner (Crc32Job) are zs_png_host.inc's; the geometry is zs_chunk.h's, the kernels (KN) zs_chunk.hip's.  The two array calls take a zs_chunk_filters per array
 // (Fletcher-32, delta, big-endian elements; null: none, the calls without filters); KL and KI are zs_chunk.hip's too, and the
 // checksum and the delta filter are calls of their own as well.
 
@@ -48,7 +48,7 @@ bool chunk_run(zs_ctx *c, ChunkSet &set, ChunkMode mode, hipStream_t s, bool *no
     const int m = (int)set.jobs.size();
     if (m == 0) return true;
     if (!chunk_items_ok(c, set.items.total)) return false;
-    const size_t n_rec = ((size_t)set.items.total + 255) & ~(size_t)255;
+    const size_t n_rec = pad256((size_t)set.items.total);
     if (mode == kChunkSurvey && !ensure(c, c->png[kBufChunkRec], n_rec + (size_t)m)) {
         *no_memory = true;
         return false;
@@ -274,11 +274,17 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
         size_t up, buf;  // its bytes in the upload; its place in the context's buffer (a stream's)
         int64_t len;     // its bytes without the checksum
     };
-    std::vector<int> st((size_t)n, ZS_OK);
-    std::vector<std::vector<int>> cst((size_t)n);
-    std::vector<std::vector<std::string>> cwhy((size_t)n);
+    CallGate gate(n, status);
+    PartCodes pc(gate.st);
     std::vector<Ref> streams[3], stored, missing;
-    size_t up_total = 0, buf_total = 0;
+    StageLayout up(kChunkMaxBytes);  // the chunks that are uploaded, in the walk's order ...
+    std::vector<const void *> up_ptr;  // ... and their bytes
+    std::vector<int64_t> up_len;
+    auto upload = [&](const zs_chunk_ref &r) {
+        up_ptr.push_back(r.data), up_len.push_back(r.len);
+        return up.add(r.len);
+    };
+    size_t buf_total = 0;
     int64_t items = 0;
     for (int i = 0; i < n; i++) {
         if (!chunks[i] || !out[i] || out_cap[i] < 0) {
@@ -288,8 +294,8 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
         const ChunkDims &d = dims[(size_t)i];
         const ChunkGeom geom = chunk_geom((const ChunkGrid &)grids[i]);
         const bool fits = out_cap[i] >= d.array_bytes;
-        if (!fits) st[(size_t)i] = ZS_BUF_ERROR;
-        else cst[(size_t)i].assign((size_t)d.n_chunks, ZS_OK), cwhy[(size_t)i].resize((size_t)d.n_chunks);
+        if (!fits) pc.fail_file(i, ZS_BUF_ERROR, "buffer error");
+        else pc.open_parts(i, (size_t)d.n_chunks);
         for (int64_t k = 0; k < d.n_chunks; k++) {
             const zs_chunk_ref &r = chunks[i][k];
             if (r.len < 0 || r.len > kChunkMaxBytes || (r.flags & ~(kChunkStored | kChunkUnshuffled | kChunkSkip))) {
@@ -302,19 +308,15 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
             int32_t ext[kChunkMaxRank];
             if (!r.data) {
                 missing.push_back(ref);
-            } else if (r.len < tail) {
-                cst[(size_t)i][(size_t)k] = ZS_DATA_ERROR, cwhy[(size_t)i][(size_t)k] = "incorrect chunk length";
+            } else if (r.len < tail || ((r.flags & kChunkStored) && ref.len != d.chunk_bytes)) {
+                pc.fail_part(i, k, ZS_DATA_ERROR, "incorrect chunk length");
                 continue;
             } else if (r.flags & kChunkStored) {
-                if (ref.len != d.chunk_bytes) {
-                    cst[(size_t)i][(size_t)k] = ZS_DATA_ERROR, cwhy[(size_t)i][(size_t)k] = "incorrect chunk length";
-                    continue;
-                }
-                ref.up = up_total, up_total += ((size_t)r.len + 255) & ~(size_t)255;
+                ref.up = upload(r);
                 stored.push_back(ref);
             } else {
-                ref.up = up_total, up_total += ((size_t)r.len + 255) & ~(size_t)255;
-                ref.buf = buf_total, buf_total += ((size_t)d.chunk_bytes + 255) & ~(size_t)255;
+                ref.up = upload(r);
+                ref.buf = buf_total, buf_total += pad256((size_t)d.chunk_bytes);
                 streams[grids[i].wrap].push_back(ref);
             }
             (void)chunk_place_of((const ChunkGrid &)grids[i], k, ext);
@@ -322,29 +324,12 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
         }
     }
     if (!chunk_items_ok(c, items)) return ZS_STREAM_ERROR;
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
+    if (!gate.open(c, hip_stream, nullptr)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
     // ---- the chunks' bytes, one copy
-    if (!ensure(c, c->png[kBufWrapFiles], up_total + 256) || !ensure(c, c->png[kBufChunkData], buf_total + 256) || !ensure_pinned(c, up_total + 256)) return fail_all(ZS_MEM_ERROR);
-    uint8_t *d_up = (uint8_t *)c->png[kBufWrapFiles].p, *d_buf = (uint8_t *)c->png[kBufChunkData].p;
-    auto stage = [&](const std::vector<Ref> &refs) {
-        for (const Ref &r : refs) {
-            const zs_chunk_ref &ch = chunks[r.array][r.chunk];
-            if (ch.len) memcpy((uint8_t *)c->pinned + r.up, ch.data, (size_t)ch.len);
-        }
-    };
-    stage(stored);
-    for (const std::vector<Ref> &g : streams) stage(g);
-    if (up_total && hipMemcpyAsync(d_up, c->pinned, up_total, hipMemcpyHostToDevice, s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);
-    if (hipStreamSynchronize(s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);  // (the inflate call below takes the pinned buffer)
+    if (!ensure(c, c->png[kBufChunkData], buf_total + 256)) return gate.fail_all(ZS_MEM_ERROR);
+    uint8_t *d_up = nullptr, *d_buf = (uint8_t *)c->png[kBufChunkData].p;
+    if (const int rc = stage_files(c, up, up_ptr.data(), up_len.data(), s, &d_up)) return gate.fail_all(rc);
     // ---- Fletcher-32: one KL job over every chunk that carries one, as it lies behind the upload; the host compares with the
     // four bytes it holds, and a chunk that differs goes no further
     bool no_memory = false;
@@ -357,7 +342,7 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
                 if (filt(r.array).fletcher32) spans.push_back(FletSpan{d_up + r.up, nullptr, r.len});
         if (!spans.empty()) {
             std::vector<uint32_t> sums(spans.size());
-            if (!fletcher_run(c, spans, s, &no_memory, &ms_part, sums.data())) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+            if (!fletcher_run(c, spans, s, &no_memory, &ms_part, sums.data())) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
             ms_filters += ms_part;
             size_t q = 0;
             for (std::vector<Ref> *l : lists) {
@@ -367,7 +352,7 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
                         const uint8_t *t = (const uint8_t *)chunks[r.array][r.chunk].data + r.len;
                         const uint32_t want = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
                         if (sums[q++] != want) {
-                            cst[(size_t)r.array][(size_t)r.chunk] = ZS_DATA_ERROR, cwhy[(size_t)r.array][(size_t)r.chunk] = "incorrect chunk checksum";
+                            pc.fail_part(r.array, r.chunk, ZS_DATA_ERROR, "incorrect chunk checksum");
                             continue;
                         }
                     }
@@ -379,6 +364,7 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
     }
     // ---- one inflate call over all compressed chunks (one per container in use), each into exactly chunk_bytes of room
     const std::string before = c->err;
+    std::string first_err[3];  // per container: the message of the inflate call's first failing stream
     std::vector<double> inf_ms;
     ChunkSet set;
     std::vector<int> geom_of((size_t)n, -1);
@@ -407,14 +393,14 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
         bool first = true;  // the call's message is its first failing stream's
         for (int j = 0; j < m; j++) {
             const Ref &r = refs[(size_t)j];
-            if (sst[(size_t)j] == ZS_STREAM_ERROR || sst[(size_t)j] == ZS_OK || sst[(size_t)j] == ZS_MEM_ERROR) return fail_all(sst[(size_t)j] == ZS_MEM_ERROR ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
-            int &code = cst[(size_t)r.array][(size_t)r.chunk];
-            std::string &why = cwhy[(size_t)r.array][(size_t)r.chunk];
+            // (zs_inflate_wrap_batch_device, unlike run_inflate under inflate_parts, reports a call that ran out of memory per stream)
+            if (sst[(size_t)j] == ZS_STREAM_ERROR || sst[(size_t)j] == ZS_OK || sst[(size_t)j] == ZS_MEM_ERROR) return gate.fail_all(sst[(size_t)j] == ZS_MEM_ERROR ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
             if (sst[(size_t)j] != ZS_STREAM_END) {
-                code = sst[(size_t)j], why = first ? c->err : std::string(code == ZS_BUF_ERROR ? "buffer error" : "data error");
+                if (first) first_err[wrap] = c->err;
+                pc.fail_part(r.array, r.chunk, sst[(size_t)j], first ? first_err[wrap].c_str() : sst[(size_t)j] == ZS_BUF_ERROR ? "buffer error" : "data error");
                 first = false;
             } else if (olen[(size_t)j] != scap[(size_t)j]) {
-                code = ZS_DATA_ERROR, why = "incorrect chunk length";
+                pc.fail_part(r.array, r.chunk, ZS_DATA_ERROR, "incorrect chunk length");
             } else {
                 const zs_chunk_ref &ch = chunks[r.array][r.chunk];
                 place(r, (const uint8_t *)sout[(size_t)j], chunk_plain(grids[r.array], ch.flags) ? kJobPlain : 0);
@@ -429,8 +415,8 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
     {
         size_t delta_total = 0;
         for (const Whole &w : whole)
-            if (filt(w.r.array).delta && !(w.flags & kJobFill)) delta_total += ((size_t)dims[(size_t)w.r.array].chunk_bytes + 255) & ~(size_t)255;
-        if (delta_total && !ensure(c, c->png[kBufChunkDelta], delta_total + 256)) return fail_all(ZS_MEM_ERROR);
+            if (filt(w.r.array).delta && !(w.flags & kJobFill)) delta_total += pad256((size_t)dims[(size_t)w.r.array].chunk_bytes);
+        if (delta_total && !ensure(c, c->png[kBufChunkDelta], delta_total + 256)) return gate.fail_all(ZS_MEM_ERROR);
         uint8_t *d_delta = (uint8_t *)c->png[kBufChunkDelta].p;
         std::vector<DeltaJob> jobs;
         size_t at = 0;
@@ -444,10 +430,10 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
             }
             const int64_t cb = dims[(size_t)w.r.array].chunk_bytes;
             jobs.push_back(DeltaJob{w.bytes, d_delta + at, cb / g.elem_size, g.elem_size, ((w.flags & kJobPlain) ? 0 : kDeltaShuffled) | (swap ? kDeltaSwap : 0), 0, 0});
-            w.bytes = d_delta + at, w.flags = kJobPlain, at += ((size_t)cb + 255) & ~(size_t)255;
+            w.bytes = d_delta + at, w.flags = kJobPlain, at += pad256((size_t)cb);
         }
         ms_part = 0;
-        if (!delta_run(c, jobs, true, s, &no_memory, &ms_part)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+        if (!delta_run(c, jobs, true, s, &no_memory, &ms_part)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
         ms_filters += ms_part;
     }
     for (const Whole &w : whole) {
@@ -456,38 +442,14 @@ int chunks_decode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
         set.chunk(g, geom_of[(size_t)w.r.array], w.r.chunk, w.bytes, out[w.r.array], w.flags);
     }
     double ms = 0;
-    if (!chunk_run(c, set, kChunkPlace, s, &no_memory, &ms)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    if (!chunk_run(c, set, kChunkPlace, s, &no_memory, &ms)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
     ms += ms_filters;
-    if (png_done(hip_stream, s) != ZS_OK) return fail_all(ZS_STREAM_ERROR);
+    if (png_done(hip_stream, s) != ZS_OK) return gate.fail_all(ZS_STREAM_ERROR);
     if (c->profiling) {
         if (inf_ms.empty()) png_set_stage(c, kStChunk, ms);
         else std::copy(inf_ms.begin(), inf_ms.end(), c->stage_ms), c->stage_ms[kStChunk] = ms;
     }
-    // ---- the codes: an array's is its first failing chunk's, the call's its first failing array's
-    std::vector<std::string> why((size_t)n);
-    for (int i = 0; i < n; i++) {
-        if (st[(size_t)i] != ZS_OK) {
-            why[(size_t)i] = "buffer error";
-            continue;
-        }
-        if (chunk_status && chunk_status[i]) memcpy(chunk_status[i], cst[(size_t)i].data(), sizeof(int) * cst[(size_t)i].size());
-        for (size_t k = 0; k < cst[(size_t)i].size(); k++)
-            if (cst[(size_t)i][k] != ZS_OK) {
-                char head[48];
-                snprintf(head, sizeof head, "chunk %lld: ", (long long)k);
-                st[(size_t)i] = cst[(size_t)i][k], why[(size_t)i] = std::string(head) + cwhy[(size_t)i][k];
-                break;
-            }
-    }
-    c->err = before;
-    for (int i = 0; i < n; i++)
-        if (st[(size_t)i] != ZS_OK) {
-            char head[48];
-            snprintf(head, sizeof head, "array %d: ", i);
-            c->err = std::string(head) + why[(size_t)i];
-            return finish(st[(size_t)i]);
-        }
-    return finish(ZS_OK);
+    return gate.finish(pc.roll_up("array", "chunk", chunk_status, before, &c->err));
 }
 
 // zs_chunks_encode_filters_batch_device; filters null: zs_chunks_encode_batch_device
@@ -515,18 +477,10 @@ int chunks_encode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
         if (!chunk_items_ok(c, items)) return ZS_STREAM_ERROR;
     }
     const int m = (int)total_chunks;
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    std::vector<int> st((size_t)n, ZS_OK);
-    for (int i = 0; i < n; i++) out_len[i] = 0;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
+    CallGate gate(n, status);
+    if (!gate.open(c, hip_stream, out_len)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
+    std::vector<int> &st = gate.st;
     // chunk q of the call: its array, its number there, what becomes of it
     struct Cut {
         int array;
@@ -552,7 +506,7 @@ int chunks_encode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
         ChunkSet set;
         for (const Cut &t : cuts) add(set, t, nullptr, 0);
         std::vector<uint8_t> same;
-        if (!chunk_run(c, set, kChunkSurvey, s, &no_memory, &ms_survey, &same)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+        if (!chunk_run(c, set, kChunkSurvey, s, &no_memory, &ms_survey, &same)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
         for (size_t q = 0; q < (size_t)m; q++)
             if (same[q]) cuts[q].flags = kChunkAbsent;
         std::fill(geom_of.begin(), geom_of.end(), -1);
@@ -561,10 +515,10 @@ int chunks_encode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
     size_t data_total = 0, zs_total = 0;
     for (Cut &t : cuts) {
         if (t.flags & kChunkAbsent) continue;
-        t.data = data_total, data_total += ((size_t)dims[(size_t)t.array].chunk_bytes + 255) & ~(size_t)255;
-        t.zs = zs_total, zs_total += ((size_t)zs_wrap_bound(dims[(size_t)t.array].chunk_bytes, grids[t.array].wrap) + 255) & ~(size_t)255;
+        t.data = data_total, data_total += pad256((size_t)dims[(size_t)t.array].chunk_bytes);
+        t.zs = zs_total, zs_total += pad256((size_t)zs_wrap_bound(dims[(size_t)t.array].chunk_bytes, grids[t.array].wrap));
     }
-    if (!ensure(c, c->png[kBufChunkData], data_total + 256) || !ensure(c, c->png[kBufChunkZs], zs_total + 256)) return fail_all(ZS_MEM_ERROR);
+    if (!ensure(c, c->png[kBufChunkData], data_total + 256) || !ensure(c, c->png[kBufChunkZs], zs_total + 256)) return gate.fail_all(ZS_MEM_ERROR);
     uint8_t *d_data = (uint8_t *)c->png[kBufChunkData].p, *d_zs = (uint8_t *)c->png[kBufChunkZs].p;
     {
         // (a chunk with delta is gathered plain and little-endian: KI writes the byte order and the planes)
@@ -575,12 +529,12 @@ int chunks_encode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
             if (t.flags & kChunkAbsent) continue;
             const bool swap = filt(t.array).byte_order && grids[t.array].elem_size > 1;
             t.src = d_data + t.data;
-            if (filt(t.array).delta) add(set, t, d_data + t.data, kJobPlain), delta_total += ((size_t)dims[(size_t)t.array].chunk_bytes + 255) & ~(size_t)255;
+            if (filt(t.array).delta) add(set, t, d_data + t.data, kJobPlain), delta_total += pad256((size_t)dims[(size_t)t.array].chunk_bytes);
             else add(set, t, d_data + t.data, (chunk_plain(grids[t.array], 0) ? kJobPlain : 0) | (swap ? kJobSwap : 0));
         }
-        if (!chunk_run(c, set, kChunkGather, s, &no_memory, &ms_gather)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+        if (!chunk_run(c, set, kChunkGather, s, &no_memory, &ms_gather)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
         if (delta_total) {
-            if (!ensure(c, c->png[kBufChunkDelta], delta_total + 256)) return fail_all(ZS_MEM_ERROR);
+            if (!ensure(c, c->png[kBufChunkDelta], delta_total + 256)) return gate.fail_all(ZS_MEM_ERROR);
             uint8_t *d_delta = (uint8_t *)c->png[kBufChunkDelta].p;
             std::vector<DeltaJob> jobs;
             size_t at = 0;
@@ -590,10 +544,10 @@ int chunks_encode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
                 const int64_t cb = dims[(size_t)t.array].chunk_bytes;
                 const bool swap = filt(t.array).byte_order && g.elem_size > 1;
                 jobs.push_back(DeltaJob{t.src, d_delta + at, cb / g.elem_size, g.elem_size, (chunk_plain(g, 0) ? 0 : kDeltaShuffled) | (swap ? kDeltaSwap : 0), 0, 0});
-                t.src = d_delta + at, at += ((size_t)cb + 255) & ~(size_t)255;
+                t.src = d_delta + at, at += pad256((size_t)cb);
             }
             double ms_delta = 0;
-            if (!delta_run(c, jobs, false, s, &no_memory, &ms_delta)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+            if (!delta_run(c, jobs, false, s, &no_memory, &ms_delta)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
             ms_gather += ms_delta;
         }
     }
@@ -614,7 +568,7 @@ int chunks_encode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
             zout[(size_t)j] = d_zs + t.zs, zcap[(size_t)j] = zs_wrap_bound(zin_len[(size_t)j], wrap);
         }
         const int zrc = zs_deflate_wrap_batch_device(c, mz, zin.data(), zin_len.data(), zout.data(), zcap.data(), zlen.data(), zst.data(), level, strategy, hash_variant, wrap, (void *)s);
-        if (zrc != ZS_OK) return fail_all(zrc);
+        if (zrc != ZS_OK) return gate.fail_all(zrc);
         for (int j = 0; j < mz; j++) cuts[idx[(size_t)j]].zlen = zlen[(size_t)j];
     }
     if (c->profiling) c->stage_ms[kStChunk] = ms_survey + ms_gather;
@@ -635,21 +589,15 @@ int chunks_encode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
             if (chunk_flags && chunk_flags[i]) chunk_flags[i][k] = t.flags;
         }
         out_len[i] = at;
-        if (out_cap[i] < at) {
-            st[(size_t)i] = ZS_BUF_ERROR;
-            if (rc == ZS_OK) rc = ZS_BUF_ERROR, c->err = "buffer error";
-        } else {
-            for (int64_t k = 0; k < dims[(size_t)i].n_chunks; k++) n_spans += chunk_len[i][k] > 0;
-        }
     }
-    if (n_spans == 0) return finish(rc);
+    (void)mark_fit(st, out_len, out_cap, &rc, &c->err);
+    for (int i = 0; i < n; i++)
+        if (st[(size_t)i] == ZS_OK)
+            for (int64_t k = 0; k < dims[(size_t)i].n_chunks; k++) n_spans += chunk_len[i][k] > 0;
+    if (n_spans == 0) return gate.finish(rc);
     // ---- one KC job: every chunk of an array that fits copied into its place
     Crc32Job job;
-    if (!crc32_begin(c, n_spans, 0, &job, &no_memory)) {
-        for (int i = 0; i < n; i++)
-            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
-        return finish(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
-    }
+    if (!crc32_begin(c, n_spans, 0, &job, &no_memory)) return gate.fail_live(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
     int sp = 0;
     std::vector<FletSpan> sums;  // the placed chunks that get a checksum behind them
     for (int i = 0; i < n; i++) {
@@ -664,24 +612,16 @@ int chunks_encode(zs_ctx *c, int n, const zs_chunk_grid *grids, const zs_chunk_f
             if (tail) sums.push_back(FletSpan{dst, dst + chunk_len[i][k] - tail, chunk_len[i][k] - tail});
         }
     }
-    if (!crc32_run(c, &job, s)) {
-        for (int i = 0; i < n; i++)
-            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = ZS_STREAM_ERROR;
-        return finish(ZS_STREAM_ERROR);
-    }
+    if (!crc32_run(c, &job, s)) return gate.fail_live(ZS_STREAM_ERROR);
     if (c->profiling) c->stage_ms[kStCrc32] = job.ms;
     // ---- Fletcher-32: one KL job over the placed chunks, whose fold writes the four bytes behind each
     if (!sums.empty()) {
         std::vector<uint32_t> got(sums.size());
         double ms_sum = 0;
-        if (!fletcher_run(c, sums, s, &no_memory, &ms_sum, got.data())) {
-            for (int i = 0; i < n; i++)
-                if (st[(size_t)i] == ZS_OK) st[(size_t)i] = no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
-            return finish(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
-        }
+        if (!fletcher_run(c, sums, s, &no_memory, &ms_sum, got.data())) return gate.fail_live(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
         if (c->profiling) c->stage_ms[kStChunk] += ms_sum;
     }
-    return finish(rc);
+    return gate.finish(rc);
 }
 }  // namespace
 

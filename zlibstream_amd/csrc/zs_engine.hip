@@ -2134,6 +2134,7 @@ int zs_inflate_batch(zs_ctx *c, int n, const void *const *in, const int64_t *in_
 }  // extern "C"
 
 #include "zs_png_host.inc"
+#include "zs_parts_host.inc"
 #include "zs_wrap_host.inc"
 #include "zs_zip_host.inc"
 #include "zs_tiff_host.inc"

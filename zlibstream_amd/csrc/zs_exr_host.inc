@@ -1,8 +1,9 @@
 // zs_exr_host.inc -- host side of the OpenEXR calls of include/zsgpu.h: whole ZIP / ZIPS files from host memory decoded on the
 // device into channel planes, and files written on the device from planes that lie there.  Part of zs_engine.hip's translation
-// unit, behind zs_tiff_host.inc: raw inflate from an offset (InfWrap::body_off), the Adler-32 launch (device_adlers), the
-// flat-list runner (png_run_list) and the KC job runner (Crc32Job) are the files' before it; the container's rules are
-// zs_exr.h's, the predictor kernels (KE) zs_exr.hip's.
+// unit, behind zs_parts_host.inc and zs_tiff_host.inc: the call's gate, the staging, the zlib header's rules, the raw inflate of
+// sub-streams, the Adler-32 compare, the roll-up of the codes and the one deflate call are zs_parts.h's and
+// zs_parts_host.inc's, the flat-list runner (png_run_list) and the KC job runner (Crc32Job) zs_png_host.inc's; the
+// container's rules are zs_exr.h's, the predictor kernels (KE) zs_exr.hip's.
 
 namespace {
 static_assert(sizeof(zs_exr_info) == sizeof(ExrInfo) && offsetof(zs_exr_info, out_len) == offsetof(ExrInfo, out_len) && offsetof(zs_exr_info, tiled) == offsetof(ExrInfo, tiled) &&
@@ -141,36 +142,18 @@ extern "C" int zs_exr_decode_files_batch(zs_ctx *c, int n, const void *const *fi
     if (!c || n < 0) return ZS_STREAM_ERROR;
     if (n == 0) return ZS_OK;
     if (!file || !file_len || !out || !out_cap || !out_len) return ZS_STREAM_ERROR;
-    size_t total = 0;
-    std::vector<size_t> f_at((size_t)n);
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n; i++)
         if (!file[i] || !out[i] || file_len[i] < 0 || out_cap[i] < 0) {
             c->err = "stream error";
             return ZS_STREAM_ERROR;
         }
-        f_at[(size_t)i] = total;
-        if (file_len[i] <= kExrMaxLen) total += ((size_t)file_len[i] + 255) & ~(size_t)255;  // (a larger file fails below, for itself)
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    std::vector<int> st((size_t)n, ZS_OK);
-    std::vector<std::string> why((size_t)n);
-    for (int i = 0; i < n; i++) out_len[i] = 0;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
-    // ---- the files, one copy (the staging of the ZIP files call)
-    if (!ensure(c, c->png[kBufWrapFiles], total + 256) || !ensure_pinned(c, total + 256)) return fail_all(ZS_MEM_ERROR);
-    for (int i = 0; i < n; i++)
-        if (file_len[i] && file_len[i] <= kExrMaxLen) memcpy((uint8_t *)c->pinned + f_at[(size_t)i], file[i], (size_t)file_len[i]);
-    uint8_t *d_files = (uint8_t *)c->png[kBufWrapFiles].p;
-    if (total && hipMemcpyAsync(d_files, c->pinned, total, hipMemcpyHostToDevice, s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);
-    if (hipStreamSynchronize(s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);  // (the inflate call below takes the pinned buffer)
+    const StageLayout lay(n, file_len, kExrMaxLen);  // (a larger file fails below, for itself)
+    CallGate gate(n, status);
+    if (!gate.open(c, hip_stream, out_len)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
+    PartCodes pc(gate.st);
+    uint8_t *d_files = nullptr;
+    if (const int rc = stage_files(c, lay, file, file_len, s, &d_files)) return gate.fail_all(rc);
     // ---- the walk: every file's header, every chunk's place and route
     struct Ref {
         int file, chunk;
@@ -179,13 +162,11 @@ extern "C" int zs_exr_decode_files_batch(zs_ctx *c, int n, const void *const *fi
     std::vector<ExrInfo> infos((size_t)n);
     std::vector<std::vector<ExrChannel>> chans((size_t)n);
     std::vector<std::vector<ExrChunk>> chunks((size_t)n);
-    std::vector<std::vector<int>> cst((size_t)n);            // per chunk: ZS_OK or its code ...
-    std::vector<std::vector<const char *>> cwhy((size_t)n);  // ... and why
     std::vector<Ref> inflated, plain;
     size_t buf_total = 0;
     for (int i = 0; i < n; i++) {
         if (file_len[i] > kExrMaxLen) {
-            st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = "the file is above 2 GiB - 1 KiB";
+            pc.fail_file(i, ZS_DATA_ERROR, "the file is above 2 GiB - 1 KiB");
             continue;
         }
         const uint8_t *f = (const uint8_t *)file[i];
@@ -193,107 +174,76 @@ extern "C" int zs_exr_decode_files_batch(zs_ctx *c, int n, const void *const *fi
         std::vector<ExrChunk> &C = chunks[(size_t)i];
         int rc = exr_walk(f, file_len[i], &ei, nullptr, 0, nullptr, 0);
         if (rc == kExrOk) {
+            // (the room is checked between the two walks here, behind both in the TIFF call: each call keeps its order)
             out_len[i] = ei.out_len;
             if (out_cap[i] < ei.out_len) {
-                st[(size_t)i] = ZS_BUF_ERROR, why[(size_t)i] = "buffer error";
+                pc.fail_file(i, ZS_BUF_ERROR, "buffer error");
                 continue;
             }
             C.resize((size_t)ei.n_chunks), chans[(size_t)i].resize((size_t)ei.n_channels);
             rc = exr_walk(f, file_len[i], &ei, chans[(size_t)i].data(), ei.n_channels, C.data(), ei.n_chunks);
         }
         if (rc != kExrOk) {
-            st[(size_t)i] = exr_err_status(rc), why[(size_t)i] = exr_err_message(rc);
+            pc.fail_file(i, exr_err_status(rc), exr_err_message(rc));
             C.clear();
             continue;
         }
-        cst[(size_t)i].assign(C.size(), ZS_OK), cwhy[(size_t)i].assign(C.size(), "");
+        pc.open_parts(i, C.size());
         for (size_t k = 0; k < C.size(); k++) {
             if (C[k].status != ZS_OK) {
-                cst[(size_t)i][k] = C[k].status, cwhy[(size_t)i][k] = exr_err_message(C[k].reason);
+                pc.fail_part(i, (int64_t)k, C[k].status, exr_err_message(C[k].reason));
                 continue;
             }
             Ref r{i, (int)k, -1};
             if (C[k].data_len == C[k].raw_len) {
                 plain.push_back(r);
             } else {
-                r.buf = (int64_t)buf_total, buf_total += ((size_t)C[k].raw_len + 255) & ~(size_t)255;
+                r.buf = (int64_t)buf_total, buf_total += pad256((size_t)C[k].raw_len);
                 inflated.push_back(r);
             }
         }
     }
-    auto fail_chunk = [&](const Ref &r, int code, const char *text) { cst[(size_t)r.file][(size_t)r.chunk] = code, cwhy[(size_t)r.file][(size_t)r.chunk] = text; };
-    if (!ensure(c, c->png[kBufExrChunks], buf_total + 256)) return fail_all(ZS_MEM_ERROR);
+    auto fail_chunk = [&](const Ref &r, int code, int msg) { pc.fail_part(r.file, r.chunk, code, inf_message(msg)); };
+    if (!ensure(c, c->png[kBufExrChunks], buf_total + 256)) return gate.fail_all(ZS_MEM_ERROR);
     uint8_t *d_buf = (uint8_t *)c->png[kBufExrChunks].p;
     const std::string before = c->err;
-    // ---- one raw inflate over all zlib chunks: the pointer is the stream's address rounded down to 16 bytes, the offset the
-    // remainder and the two bytes of the zlib header, which the host has checked
+    // ---- one raw inflate over all zlib chunks whose header the host accepts
     const int m = (int)inflated.size();
     std::vector<bool> decoded((size_t)m, false);
-    std::vector<int64_t> sused((size_t)m, 0);
     std::vector<int> live;  // the streams of the launch
+    std::vector<InfPart> parts;
     for (int j = 0; j < m; j++) {
         const Ref &r = inflated[(size_t)j];
         const ExrChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
-        const uint8_t *z = (const uint8_t *)file[r.file] + ch.off;
-        if (ch.data_len < 2) fail_chunk(r, ZS_BUF_ERROR, inf_message(kInfTruncated));
-        else if ((z[0] & 15) != 8) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadMethod));
-        else if ((z[0] >> 4) > 7) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadWindow));
-        else if (((z[0] << 8) | z[1]) % 31) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadHeaderCheck));
-        else if (z[1] & 0x20) fail_chunk(r, ZS_NEED_DICT, inf_message(kInfNeedDict));
-        else live.push_back(j);
+        int code = ZS_OK, msg = 0;
+        if (!zlib_head_check((const uint8_t *)file[r.file] + ch.off, ch.data_len, &code, &msg)) {
+            fail_chunk(r, code, msg);
+            continue;
+        }
+        live.push_back(j);
+        parts.push_back(InfPart{lay.at[(size_t)r.file] + (size_t)ch.off, ch.data_len, d_buf + r.buf, ch.raw_len, 2});
     }
-    const int ml = (int)live.size();
-    if (ml) {
-        std::vector<const void *> sin((size_t)ml);
-        std::vector<void *> sout((size_t)ml);
-        std::vector<int64_t> slen((size_t)ml), scap((size_t)ml), olen((size_t)ml, 0), used((size_t)ml, 0);
-        std::vector<int32_t> body((size_t)ml);
-        std::vector<int> sst((size_t)ml, ZS_STREAM_ERROR), smsg((size_t)ml, 0);
-        for (int q = 0; q < ml; q++) {
-            const Ref &r = inflated[(size_t)live[(size_t)q]];
-            const ExrChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
-            const size_t at = f_at[(size_t)r.file] + (size_t)ch.off;  // (d_files and every f_at are 256-byte aligned)
-            body[(size_t)q] = (int32_t)(at & 15) + 2;
-            sin[(size_t)q] = d_files + (at & ~(size_t)15), slen[(size_t)q] = (int64_t)(at & 15) + ch.data_len;
-            sout[(size_t)q] = d_buf + r.buf, scap[(size_t)q] = ch.raw_len;
-        }
-        InfWrap wr;
-        wr.body_off = body.data(), wr.msg = smsg.data(), wr.in_used = used.data();
-        (void)run_inflate(c, ml, sin.data(), slen.data(), sout.data(), scap.data(), olen.data(), sst.data(), s, nullptr, wr);
-        std::vector<const void *> abuf;
-        std::vector<int64_t> alen;
-        std::vector<int> aidx;
-        for (int q = 0; q < ml; q++) {
-            const int j = live[(size_t)q];
-            const Ref &r = inflated[(size_t)j];
-            const ExrChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
-            if (sst[(size_t)q] == ZS_STREAM_ERROR || sst[(size_t)q] == ZS_OK) return fail_all(ZS_STREAM_ERROR);  // (the inflate call itself failed: its message stands)
-            sused[(size_t)j] = used[(size_t)q] - (body[(size_t)q] - 2);
-            // a chunk must inflate to exactly its raw bytes: one that wants more ran out of the room they gave it
-            if (sst[(size_t)q] != ZS_STREAM_END) {
-                const bool too_long = smsg[(size_t)q] == kInfOutputFull;
-                fail_chunk(r, too_long ? (int)ZS_DATA_ERROR : sst[(size_t)q], inf_message(too_long ? (int)kInfBadLength : smsg[(size_t)q]));
-            } else if (olen[(size_t)q] != ch.raw_len) {
-                fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadLength));
-            } else if (sused[(size_t)j] + 4 > ch.data_len) {  // the chunk ends inside its Adler-32
-                fail_chunk(r, ZS_BUF_ERROR, inf_message(kInfTruncated));
-            } else {
-                abuf.push_back(sout[(size_t)q]), alen.push_back(olen[(size_t)q]), aidx.push_back(j);
-            }
-        }
-        // ---- the Adler-32 of every stream that ended, in one launch, against the four bytes behind its last block
-        if (!abuf.empty()) {
-            std::vector<uint32_t> ads(abuf.size(), 0);
-            if (!device_adlers(c, (int)abuf.size(), abuf.data(), alen.data(), nullptr, ads.data(), nullptr, s)) return fail_all(ZS_STREAM_ERROR);
-            for (size_t a = 0; a < abuf.size(); a++) {
-                const int j = aidx[a];
-                const Ref &r = inflated[(size_t)j];
-                const uint8_t *t = (const uint8_t *)file[r.file] + chunks[(size_t)r.file][(size_t)r.chunk].off + sused[(size_t)j];
-                const uint32_t stored = (uint32_t)t[0] << 24 | (uint32_t)t[1] << 16 | (uint32_t)t[2] << 8 | t[3];
-                if (stored != ads[a]) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadCheck));
-                else decoded[(size_t)j] = true;
-            }
-        }
+    std::vector<InfResult> res;
+    if (!inflate_parts(c, d_files, parts, s, &res)) return gate.fail_all(ZS_STREAM_ERROR);
+    // a chunk must inflate to exactly its raw bytes: one that wants more ran out of the room they gave it
+    std::vector<const void *> abuf;
+    std::vector<int64_t> alen;
+    std::vector<const uint8_t *> atrail;
+    std::vector<int> aidx;
+    for (size_t q = 0; q < live.size(); q++) {
+        const Ref &r = inflated[(size_t)live[q]];
+        const ExrChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
+        const PartVerdict v = part_verdict(res[q].status, res[q].msg, res[q].out_len, res[q].used, ch.data_len, kLenExact, ch.raw_len);
+        if (v.cls == kPartFailed) fail_chunk(r, v.code, v.msg);
+        else if (v.trailer_cut) fail_chunk(r, ZS_BUF_ERROR, kInfTruncated);
+        else abuf.push_back(parts[q].out), alen.push_back(res[q].out_len), atrail.push_back((const uint8_t *)file[r.file] + ch.off + res[q].used), aidx.push_back(live[q]);
+    }
+    // ---- the Adler-32 of every stream that ended, in one launch, against the four bytes behind its last block
+    std::vector<bool> same;
+    if (!check_adlers(c, abuf, alen, atrail, s, &same)) return gate.fail_all(ZS_STREAM_ERROR);
+    for (size_t a = 0; a < aidx.size(); a++) {
+        if (same[a]) decoded[(size_t)aidx[a]] = true;
+        else fail_chunk(inflated[(size_t)aidx[a]], ZS_DATA_ERROR, kInfBadCheck);
     }
     // ---- one KE launch: every inflated chunk from the buffer, and the chunks that lie raw from the uploaded files, both steps off
     ExrSet set;
@@ -309,31 +259,11 @@ extern "C" int zs_exr_decode_files_batch(zs_ctx *c, int n, const void *const *fi
     };
     for (int j = 0; j < m; j++)
         if (decoded[(size_t)j]) undo(inflated[(size_t)j], d_buf + inflated[(size_t)j].buf, false);
-    for (const Ref &r : plain) undo(r, d_files + f_at[(size_t)r.file] + (size_t)chunks[(size_t)r.file][(size_t)r.chunk].off, true);
+    for (const Ref &r : plain) undo(r, d_files + lay.at[(size_t)r.file] + (size_t)chunks[(size_t)r.file][(size_t)r.chunk].off, true);
     bool no_memory = false;
-    if (!exr_run(c, set, false, s, &no_memory)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
-    if (png_done(hip_stream, s) != ZS_OK) return fail_all(ZS_STREAM_ERROR);
-    // ---- the codes: a file's is its first failing chunk's, the call's its first failing file's
-    for (int i = 0; i < n; i++) {
-        if (st[(size_t)i] != ZS_OK) continue;
-        if (chunk_status && chunk_status[i] && !cst[(size_t)i].empty()) memcpy(chunk_status[i], cst[(size_t)i].data(), sizeof(int) * cst[(size_t)i].size());
-        for (size_t k = 0; k < cst[(size_t)i].size(); k++)
-            if (cst[(size_t)i][k] != ZS_OK) {
-                char head[48];
-                snprintf(head, sizeof head, "chunk %d: ", (int)k);
-                st[(size_t)i] = cst[(size_t)i][k], why[(size_t)i] = std::string(head) + cwhy[(size_t)i][k];
-                break;
-            }
-    }
-    c->err = before;
-    for (int i = 0; i < n; i++)
-        if (st[(size_t)i] != ZS_OK) {
-            char head[48];
-            snprintf(head, sizeof head, "file %d: ", i);
-            c->err = std::string(head) + why[(size_t)i];
-            return finish(st[(size_t)i]);
-        }
-    return finish(ZS_OK);
+    if (!exr_run(c, set, false, s, &no_memory)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    if (png_done(hip_stream, s) != ZS_OK) return gate.fail_all(ZS_STREAM_ERROR);
+    return gate.finish(pc.roll_up("file", "chunk", chunk_status, before, &c->err));
 }
 
 extern "C" int64_t zs_exr_bound(const zs_exr_put *put) {
@@ -381,7 +311,6 @@ extern "C" int zs_exr_encode_batch_device(zs_ctx *c, int n, const zs_exr_put *pu
     std::vector<Cut> cuts((size_t)m);
     std::vector<size_t> pred_at((size_t)m);
     std::vector<int64_t> zin_len, zcap;
-    std::vector<size_t> z_at;
     size_t pred_total = 0, z_total = 0;
     for (int i = 0; i < n; i++) {
         const ExrLayout &l = lay[(size_t)i];
@@ -390,29 +319,22 @@ extern "C" int zs_exr_encode_batch_device(zs_ctx *c, int n, const zs_exr_put *pu
             const size_t q = (size_t)(first[(size_t)i] + k);
             Cut &t = cuts[q];
             t.image = i, t.y = k * L, t.h = std::min(L, l.height - t.y), t.bytes = t.h * l.width * l.bpp, t.z = -1;
-            pred_at[q] = pred_total, pred_total += ((size_t)t.bytes + 255) & ~(size_t)255;
+            pred_at[q] = pred_total, pred_total += pad256((size_t)t.bytes);
             if (l.compression != 0) {
                 t.z = (int)zin_len.size();
                 zin_len.push_back(t.bytes), zcap.push_back(zs_deflate_bound(t.bytes));
-                z_at.push_back(z_total), z_total += ((size_t)zcap.back() + 255) & ~(size_t)255;
+                z_total += pad256((size_t)zcap.back());
             }
         }
     }
     const int mz = (int)zin_len.size();
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    std::vector<int> st((size_t)n, ZS_OK);
-    for (int i = 0; i < n; i++) out_len[i] = 0;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
-    if (!ensure(c, c->png[kBufExrChunks], pred_total + 256) || !ensure(c, c->png[kBufExrZs], z_total + 256)) return fail_all(ZS_MEM_ERROR);
-    uint8_t *d_pred = (uint8_t *)c->png[kBufExrChunks].p, *d_zs = (uint8_t *)c->png[kBufExrZs].p;
+    CallGate gate(n, status);
+    if (!gate.open(c, hip_stream, out_len)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
+    std::vector<int> &st = gate.st;
+    // (both buffers in front of the first launch: deflate_parts finds its own in place)
+    if (!ensure(c, c->png[kBufExrChunks], pred_total + 256) || !ensure(c, c->png[kBufExrZs], z_total + 256)) return gate.fail_all(ZS_MEM_ERROR);
+    uint8_t *d_pred = (uint8_t *)c->png[kBufExrChunks].p;
     auto add = [&](ExrSet &set, size_t q, bool raw) {
         const Cut &t = cuts[q];
         const ExrLayout &l = lay[(size_t)t.image];
@@ -420,26 +342,19 @@ extern "C" int zs_exr_encode_batch_device(zs_ctx *c, int n, const zs_exr_put *pu
         set.plane_runs(puts[t.image].planes, planes[(size_t)t.image].off, planes[(size_t)t.image].bytes, l.n_channels, l.width, 0, t.y, l.width, t.h);
     };
     bool no_memory = false;
-    std::vector<int64_t> zlen((size_t)mz, 0);
+    std::vector<void *> zout;
+    std::vector<int64_t> zlen;
     if (mz) {
         // ---- one forward launch: every chunk that is to be deflated gathered, split and differenced
         ExrSet set;
         for (size_t q = 0; q < (size_t)m; q++)
             if (cuts[q].z >= 0) add(set, q, false);
-        if (!exr_run(c, set, true, s, &no_memory)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+        if (!exr_run(c, set, true, s, &no_memory)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
         // ---- one deflate call over all of them, into a buffer of the context
         std::vector<const void *> zin((size_t)mz);
-        std::vector<void *> zout((size_t)mz);
         for (size_t q = 0; q < (size_t)m; q++)
-            if (cuts[q].z >= 0) zin[(size_t)cuts[q].z] = d_pred + pred_at[q], zout[(size_t)cuts[q].z] = d_zs + z_at[(size_t)cuts[q].z];
-        std::vector<int> zst((size_t)mz, ZS_STREAM_ERROR);
-        const int zrc = zs_deflate_batch_device(c, mz, zin.data(), zin_len.data(), zout.data(), zcap.data(), zlen.data(), zst.data(), level, strategy, hash_variant, (void *)s);
-        if (zrc != ZS_OK) return fail_all(zrc);
-        for (int z = 0; z < mz; z++)
-            if (zlen[(size_t)z] < 6) {  // (no zlib stream is that short)
-                c->err = "stream error";
-                return fail_all(ZS_STREAM_ERROR);
-            }
+            if (cuts[q].z >= 0) zin[(size_t)cuts[q].z] = d_pred + pred_at[q];
+        if (const int zrc = deflate_parts(c, c->png[kBufExrZs], mz, zin.data(), zin_len.data(), zcap.data(), level, strategy, hash_variant, s, &zout, &zlen)) return gate.fail_all(zrc);
     }
     // ---- a second, small forward launch with both steps off: the chunks of the uncompressed files, and those that zlib did
     // not shrink, which are stored raw
@@ -447,36 +362,27 @@ extern "C" int zs_exr_encode_batch_device(zs_ctx *c, int n, const zs_exr_put *pu
         ExrSet set;
         for (size_t q = 0; q < (size_t)m; q++)
             if (cuts[q].z < 0 || zlen[(size_t)cuts[q].z] >= cuts[q].bytes) cuts[q].z = -1, add(set, q, true);
-        if (!exr_run(c, set, true, s, &no_memory)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+        if (!exr_run(c, set, true, s, &no_memory)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
     }
     // ---- the layout: every file's head on the host, from the lengths the deflate call returned; which files fit
     std::vector<uint8_t> heads(head_total + 2);
     std::vector<size_t> head_at((size_t)n);
     std::vector<int64_t> chunk_off((size_t)m), body_len((size_t)m);
     for (size_t q = 0; q < (size_t)m; q++) body_len[q] = cuts[q].z >= 0 ? zlen[(size_t)cuts[q].z] : cuts[q].bytes;
-    int rc = ZS_OK, n_fit = 0;
+    int rc = ZS_OK;
     size_t at = 0, fit_spans = 0, fit_blob = 0;
     for (int i = 0; i < n; i++) {
         head_at[(size_t)i] = at;
         out_len[i] = exr_put_head(heads.data() + at, lay[(size_t)i], body_len.data() + first[(size_t)i], chunk_off.data() + first[(size_t)i]);
         at += (size_t)exr_head_bytes(lay[(size_t)i]);
-        if (out_cap[i] < out_len[i]) {
-            st[(size_t)i] = ZS_BUF_ERROR;
-            if (rc == ZS_OK) rc = ZS_BUF_ERROR, c->err = "buffer error";
-        } else {
-            n_fit++, fit_blob += (size_t)exr_head_bytes(lay[(size_t)i]) + 8 * (size_t)lay[(size_t)i].n_chunks;
-            fit_spans += 1 + 2 * (size_t)lay[(size_t)i].n_chunks;
-        }
     }
-    if (n_fit == 0) return finish(rc);
+    if (mark_fit(st, out_len, out_cap, &rc, &c->err) == 0) return gate.finish(rc);
+    for (int i = 0; i < n; i++)
+        if (st[(size_t)i] == ZS_OK) fit_blob += (size_t)exr_head_bytes(lay[(size_t)i]) + 8 * (size_t)lay[(size_t)i].n_chunks, fit_spans += 1 + 2 * (size_t)lay[(size_t)i].n_chunks;
     // ---- one KC job.  Per file: its head (host bytes in the job's blob) copied into place, then per chunk its eight bytes of
     // header, from the blob too, and its data
     Crc32Job job;
-    if (!crc32_begin(c, (int)fit_spans, fit_blob, &job, &no_memory)) {
-        for (int i = 0; i < n; i++)
-            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
-        return finish(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
-    }
+    if (!crc32_begin(c, (int)fit_spans, fit_blob, &job, &no_memory)) return gate.fail_live(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
     uint8_t *hb = job.blob;
     int sp = 0;
     for (int i = 0; i < n; i++) {
@@ -491,15 +397,11 @@ extern "C" int zs_exr_encode_batch_device(zs_ctx *c, int n, const zs_exr_put *pu
             exr_put32(hb, (uint32_t)(lay[(size_t)i].y_min + (int32_t)cuts[q].y)), exr_put32(hb + 4, (uint32_t)body_len[q]);
             job.spans[sp++] = Crc32Span{job.d_blob + (hb - job.blob), o + chunk_off[q], nullptr, 8, 0xFFFFFFFFu, 0, 0, 0};
             hb += 8;
-            const uint8_t *src = cuts[q].z >= 0 ? d_zs + z_at[(size_t)cuts[q].z] : d_pred + pred_at[q];
+            const uint8_t *src = cuts[q].z >= 0 ? (const uint8_t *)zout[(size_t)cuts[q].z] : d_pred + pred_at[q];
             job.spans[sp++] = Crc32Span{src, o + chunk_off[q] + 8, nullptr, body_len[q], 0xFFFFFFFFu, 0, 0, 0};
         }
     }
-    if (!crc32_run(c, &job, s)) {
-        for (int i = 0; i < n; i++)
-            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = ZS_STREAM_ERROR;
-        return finish(ZS_STREAM_ERROR);
-    }
+    if (!crc32_run(c, &job, s)) return gate.fail_live(ZS_STREAM_ERROR);
     if (c->profiling) c->stage_ms[kStCrc32] = job.ms;
-    return finish(rc);
+    return gate.finish(rc);
 }

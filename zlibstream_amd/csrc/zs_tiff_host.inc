@@ -1,8 +1,9 @@
 // zs_tiff_host.inc -- host side of the TIFF calls of include/zsgpu.h: whole files from host memory decoded on the device, and
-// files written on the device from images that lie there.  Part of zs_engine.hip's translation unit, behind zs_zip_host.inc:
-// raw inflate from an offset (InfWrap::body_off), the Adler-32 launch (device_adlers), the flat-list runner (png_run_list)
-// and the KC job runner (Crc32Job) are that file's and zs_png_host.inc's; the container's rules are zs_tiff.h's, the
-// predictor kernels (KT) zs_tiff.hip's.
+// files written on the device from images that lie there.  Part of zs_engine.hip's translation unit, behind zs_parts_host.inc
+// and zs_zip_host.inc: the call's gate, the staging, the zlib header's rules, the raw inflate of sub-streams, the Adler-32
+// compare, the roll-up of the codes and the one deflate call are zs_parts.h's and zs_parts_host.inc's, the flat-list runner
+// (png_run_list) and the KC job runner (Crc32Job) zs_png_host.inc's; the container's rules are zs_tiff.h's, the predictor
+// kernels (KT) zs_tiff.hip's.
 
 namespace {
 static_assert(sizeof(zs_tiff_info) == sizeof(TiffInfo) && offsetof(zs_tiff_info, out_len) == offsetof(TiffInfo, out_len) &&
@@ -150,36 +151,18 @@ extern "C" int zs_tiff_decode_files_batch(zs_ctx *c, int n, const void *const *f
     if (!c || n < 0) return ZS_STREAM_ERROR;
     if (n == 0) return ZS_OK;
     if (!file || !file_len || !out || !out_cap || !out_len) return ZS_STREAM_ERROR;
-    size_t total = 0;
-    std::vector<size_t> f_at((size_t)n);
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n; i++)
         if (!file[i] || !out[i] || file_len[i] < 0 || out_cap[i] < 0 || (page && page[i] < 0)) {
             c->err = "stream error";
             return ZS_STREAM_ERROR;
         }
-        f_at[(size_t)i] = total;
-        if (file_len[i] <= kTiffMaxLen) total += ((size_t)file_len[i] + 255) & ~(size_t)255;  // (a larger file fails below, for itself)
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    std::vector<int> st((size_t)n, ZS_OK);
-    std::vector<std::string> why((size_t)n);
-    for (int i = 0; i < n; i++) out_len[i] = 0;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
-    // ---- the files, one copy (the staging of the ZIP files call)
-    if (!ensure(c, c->png[kBufWrapFiles], total + 256) || !ensure_pinned(c, total + 256)) return fail_all(ZS_MEM_ERROR);
-    for (int i = 0; i < n; i++)
-        if (file_len[i] && file_len[i] <= kTiffMaxLen) memcpy((uint8_t *)c->pinned + f_at[(size_t)i], file[i], (size_t)file_len[i]);
-    uint8_t *d_files = (uint8_t *)c->png[kBufWrapFiles].p;
-    if (total && hipMemcpyAsync(d_files, c->pinned, total, hipMemcpyHostToDevice, s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);
-    if (hipStreamSynchronize(s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);  // (the inflate call below takes the pinned buffer)
+    const StageLayout lay(n, file_len, kTiffMaxLen);  // (a larger file fails below, for itself)
+    CallGate gate(n, status);
+    if (!gate.open(c, hip_stream, out_len)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
+    PartCodes pc(gate.st);
+    uint8_t *d_files = nullptr;
+    if (const int rc = stage_files(c, lay, file, file_len, s, &d_files)) return gate.fail_all(rc);
     // ---- the walk: every file's page, every chunk's place and route
     struct Ref {
         int file, chunk;
@@ -188,13 +171,11 @@ extern "C" int zs_tiff_decode_files_batch(zs_ctx *c, int n, const void *const *f
     };
     std::vector<TiffInfo> infos((size_t)n);
     std::vector<std::vector<TiffChunk>> chunks((size_t)n);
-    std::vector<std::vector<int>> cst((size_t)n);            // per chunk: ZS_OK or its code ...
-    std::vector<std::vector<const char *>> cwhy((size_t)n);  // ... and why
     std::vector<Ref> inflated, plain;
     size_t buf_total = 0;
     for (int i = 0; i < n; i++) {
         if (file_len[i] > kTiffMaxLen) {
-            st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = "the file is above 2 GiB - 1 KiB";
+            pc.fail_file(i, ZS_DATA_ERROR, "the file is above 2 GiB - 1 KiB");
             continue;
         }
         const uint8_t *f = (const uint8_t *)file[i];
@@ -205,115 +186,80 @@ extern "C" int zs_tiff_decode_files_batch(zs_ctx *c, int n, const void *const *f
             C.resize((size_t)ti.n_chunks);
             rc = tiff_walk(f, file_len[i], page ? page[i] : 0, &ti, C.data(), ti.n_chunks);
         }
-        if (rc != kTiffOk) {
-            st[(size_t)i] = tiff_err_status(rc), why[(size_t)i] = tiff_err_message(rc);
+        // (the room is checked behind both walks here, between the two in the OpenEXR call: a file that the second walk refuses
+        // and that has no room either gets the walk's code here and ZS_BUF_ERROR there; each call keeps its order)
+        if (rc == kTiffOk) out_len[i] = ti.out_len;
+        if (rc != kTiffOk) pc.fail_file(i, tiff_err_status(rc), tiff_err_message(rc));
+        else if (out_cap[i] < ti.out_len) pc.fail_file(i, ZS_BUF_ERROR, "buffer error");
+        if (gate.st[(size_t)i] != ZS_OK) {
             C.clear();
             continue;
         }
-        out_len[i] = ti.out_len;
-        if (out_cap[i] < ti.out_len) {
-            st[(size_t)i] = ZS_BUF_ERROR, why[(size_t)i] = "buffer error";
-            C.clear();
-            continue;
-        }
-        cst[(size_t)i].assign(C.size(), ZS_OK), cwhy[(size_t)i].assign(C.size(), "");
+        pc.open_parts(i, C.size());
         const int64_t crb = tiff_row_bytes(ti.chunk_w, ti.spp, ti.bits);
         // strips of a file that needs neither sums nor swaps are the image's own bytes
         const bool own_bytes = !ti.tiled && ti.predictor == 1 && !(ti.big_endian && ti.bits > 8);
         for (size_t k = 0; k < C.size(); k++) {
             if (C[k].status != ZS_OK) {
-                cst[(size_t)i][k] = C[k].status, cwhy[(size_t)i][k] = tiff_err_message(kTiffTruncated);
+                pc.fail_part(i, (int64_t)k, C[k].status, tiff_err_message(kTiffTruncated));
                 continue;
             }
             Ref r{i, (int)k, C[k].h * crb, ti.chunk_h * crb, -1};
             if (ti.compression == 1) {
                 plain.push_back(r);
             } else {
-                if (!(own_bytes && r.need == r.full)) r.buf = (int64_t)buf_total, buf_total += ((size_t)r.full + 255) & ~(size_t)255;
+                if (!(own_bytes && r.need == r.full)) r.buf = (int64_t)buf_total, buf_total += pad256((size_t)r.full);
                 inflated.push_back(r);
             }
         }
     }
-    auto fail_chunk = [&](const Ref &r, int code, const char *text) { cst[(size_t)r.file][(size_t)r.chunk] = code, cwhy[(size_t)r.file][(size_t)r.chunk] = text; };
+    auto fail_chunk = [&](const Ref &r, int code, int msg) { pc.fail_part(r.file, r.chunk, code, inf_message(msg)); };
     auto place = [&](const Ref &r) {
         const TiffInfo &ti = infos[(size_t)r.file];
         const TiffChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
         return (uint8_t *)out[r.file] + ch.y * ti.row_bytes + ch.x * ti.spp * ti.bits / 8;  // (a tile's x is a multiple of 16: whole bytes)
     };
-    if (!ensure(c, c->png[kBufTiffChunks], buf_total + 256)) return fail_all(ZS_MEM_ERROR);
+    if (!ensure(c, c->png[kBufTiffChunks], buf_total + 256)) return gate.fail_all(ZS_MEM_ERROR);
     uint8_t *d_buf = (uint8_t *)c->png[kBufTiffChunks].p;
     const std::string before = c->err;
-    // ---- one raw inflate over all deflated chunks: the pointer is the stream's address rounded down to 16 bytes, the offset
-    // the remainder and the two bytes of the zlib header, which the host has checked (Inflate.cs:211-250)
+    // ---- one raw inflate over all deflated chunks whose zlib header the host accepts (Inflate.cs:211-250)
     const int m = (int)inflated.size();
     std::vector<bool> decoded((size_t)m, false);
-    std::vector<int64_t> solen((size_t)m, 0), sused((size_t)m, 0);
     std::vector<int> live;  // the streams of the launch
+    std::vector<InfPart> parts;
     for (int j = 0; j < m; j++) {
         const Ref &r = inflated[(size_t)j];
         const TiffChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
-        const uint8_t *z = (const uint8_t *)file[r.file] + ch.off;
-        if (ch.comp_len < 2) fail_chunk(r, ZS_BUF_ERROR, inf_message(kInfTruncated));
-        else if ((z[0] & 15) != 8) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadMethod));
-        else if ((z[0] >> 4) > 7) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadWindow));
-        else if (((z[0] << 8) | z[1]) % 31) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadHeaderCheck));
-        else if (z[1] & 0x20) fail_chunk(r, ZS_NEED_DICT, inf_message(kInfNeedDict));
-        else live.push_back(j);
+        int code = ZS_OK, msg = 0;
+        if (!zlib_head_check((const uint8_t *)file[r.file] + ch.off, ch.comp_len, &code, &msg)) {
+            fail_chunk(r, code, msg);
+            continue;
+        }
+        live.push_back(j);
+        parts.push_back(InfPart{lay.at[(size_t)r.file] + (size_t)ch.off, ch.comp_len, r.buf < 0 ? place(r) : d_buf + r.buf, r.buf < 0 ? r.need : r.full, 2});
     }
-    const int ml = (int)live.size();
-    if (ml) {
-        std::vector<const void *> sin((size_t)ml);
-        std::vector<void *> sout((size_t)ml);
-        std::vector<int64_t> slen((size_t)ml), scap((size_t)ml), olen((size_t)ml, 0), used((size_t)ml, 0);
-        std::vector<int32_t> body((size_t)ml);
-        std::vector<int> sst((size_t)ml, ZS_STREAM_ERROR), smsg((size_t)ml, 0);
-        for (int q = 0; q < ml; q++) {
-            const Ref &r = inflated[(size_t)live[(size_t)q]];
-            const TiffChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
-            const size_t at = f_at[(size_t)r.file] + (size_t)ch.off;  // (d_files and every f_at are 256-byte aligned)
-            body[(size_t)q] = (int32_t)(at & 15) + 2;
-            sin[(size_t)q] = d_files + (at & ~(size_t)15), slen[(size_t)q] = (int64_t)(at & 15) + ch.comp_len;
-            sout[(size_t)q] = r.buf < 0 ? place(r) : d_buf + r.buf, scap[(size_t)q] = r.buf < 0 ? r.need : r.full;
-        }
-        InfWrap wr;
-        wr.body_off = body.data(), wr.msg = smsg.data(), wr.in_used = used.data();
-        (void)run_inflate(c, ml, sin.data(), slen.data(), sout.data(), scap.data(), olen.data(), sst.data(), s, nullptr, wr);
-        std::vector<const void *> abuf;
-        std::vector<int64_t> alen;
-        std::vector<int> aidx;
-        for (int q = 0; q < ml; q++) {
-            const int j = live[(size_t)q];
-            const Ref &r = inflated[(size_t)j];
-            const TiffInfo &ti = infos[(size_t)r.file];
-            const TiffChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
-            if (sst[(size_t)q] == ZS_STREAM_ERROR || sst[(size_t)q] == ZS_OK) return fail_all(ZS_STREAM_ERROR);  // (the inflate call itself failed: its message stands)
-            solen[(size_t)j] = olen[(size_t)q], sused[(size_t)j] = used[(size_t)q] - (body[(size_t)q] - 2);
-            // a chunk longer than its rows ran out of the room they gave it; a strip must hold its rows inside the image (a last
-            // strip may hold all of RowsPerStrip), a tile all of itself
-            if (sst[(size_t)q] != ZS_STREAM_END) {
-                const bool too_long = smsg[(size_t)q] == kInfOutputFull;
-                fail_chunk(r, too_long ? (int)ZS_DATA_ERROR : sst[(size_t)q], inf_message(too_long ? (int)kInfBadLength : smsg[(size_t)q]));
-            } else if (olen[(size_t)q] < (ti.tiled ? r.full : r.need)) {
-                fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadLength));
-            } else if (sused[(size_t)j] + 4 > ch.comp_len) {  // the chunk ends inside its Adler-32
-                fail_chunk(r, ZS_BUF_ERROR, inf_message(kInfTruncated));
-            } else {
-                abuf.push_back(sout[(size_t)q]), alen.push_back(olen[(size_t)q]), aidx.push_back(j);
-            }
-        }
-        // ---- the Adler-32 of every stream that ended, in one launch, against the four bytes behind its last block
-        if (!abuf.empty()) {
-            std::vector<uint32_t> ads(abuf.size(), 0);
-            if (!device_adlers(c, (int)abuf.size(), abuf.data(), alen.data(), nullptr, ads.data(), nullptr, s)) return fail_all(ZS_STREAM_ERROR);
-            for (size_t a = 0; a < abuf.size(); a++) {
-                const int j = aidx[a];
-                const Ref &r = inflated[(size_t)j];
-                const uint8_t *t = (const uint8_t *)file[r.file] + chunks[(size_t)r.file][(size_t)r.chunk].off + sused[(size_t)j];
-                const uint32_t stored = (uint32_t)t[0] << 24 | (uint32_t)t[1] << 16 | (uint32_t)t[2] << 8 | t[3];
-                if (stored != ads[a]) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadCheck));
-                else decoded[(size_t)j] = true;
-            }
-        }
+    std::vector<InfResult> res;
+    if (!inflate_parts(c, d_files, parts, s, &res)) return gate.fail_all(ZS_STREAM_ERROR);
+    // a chunk longer than its rows ran out of the room they gave it; a strip must hold its rows inside the image (a last strip
+    // may hold all of RowsPerStrip), a tile all of itself
+    std::vector<const void *> abuf;
+    std::vector<int64_t> alen;
+    std::vector<const uint8_t *> atrail;
+    std::vector<int> aidx;
+    for (size_t q = 0; q < live.size(); q++) {
+        const Ref &r = inflated[(size_t)live[q]];
+        const TiffChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
+        const PartVerdict v = part_verdict(res[q].status, res[q].msg, res[q].out_len, res[q].used, ch.comp_len, kLenAtLeast, infos[(size_t)r.file].tiled ? r.full : r.need);
+        if (v.cls == kPartFailed) fail_chunk(r, v.code, v.msg);
+        else if (v.trailer_cut) fail_chunk(r, ZS_BUF_ERROR, kInfTruncated);
+        else abuf.push_back(parts[q].out), alen.push_back(res[q].out_len), atrail.push_back((const uint8_t *)file[r.file] + ch.off + res[q].used), aidx.push_back(live[q]);
+    }
+    // ---- the Adler-32 of every stream that ended, in one launch, against the four bytes behind its last block
+    std::vector<bool> same;
+    if (!check_adlers(c, abuf, alen, atrail, s, &same)) return gate.fail_all(ZS_STREAM_ERROR);
+    for (size_t a = 0; a < aidx.size(); a++) {
+        if (same[a]) decoded[(size_t)aidx[a]] = true;
+        else fail_chunk(inflated[(size_t)aidx[a]], ZS_DATA_ERROR, kInfBadCheck);
     }
     // ---- one KT launch: every chunk that went through the buffer, and the uncompressed ones from the uploaded files
     TiffRun run;
@@ -326,33 +272,13 @@ extern "C" int zs_tiff_decode_files_batch(zs_ctx *c, int n, const void *const *f
         if (decoded[(size_t)j] && inflated[(size_t)j].buf >= 0) undo(inflated[(size_t)j], d_buf + inflated[(size_t)j].buf);
     for (const Ref &r : plain) {
         const TiffChunk &ch = chunks[(size_t)r.file][(size_t)r.chunk];
-        if (ch.comp_len < (infos[(size_t)r.file].tiled ? r.full : r.need)) fail_chunk(r, ZS_DATA_ERROR, inf_message(kInfBadLength));
-        else undo(r, d_files + f_at[(size_t)r.file] + (size_t)ch.off);
+        if (ch.comp_len < (infos[(size_t)r.file].tiled ? r.full : r.need)) fail_chunk(r, ZS_DATA_ERROR, kInfBadLength);
+        else undo(r, d_files + lay.at[(size_t)r.file] + (size_t)ch.off);
     }
     bool no_memory = false;
-    if (!tiff_run(c, run, false, s, &no_memory)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
-    if (png_done(hip_stream, s) != ZS_OK) return fail_all(ZS_STREAM_ERROR);
-    // ---- the codes: a file's is its first failing chunk's, the call's its first failing file's
-    for (int i = 0; i < n; i++) {
-        if (st[(size_t)i] != ZS_OK) continue;
-        if (chunk_status && chunk_status[i] && !cst[(size_t)i].empty()) memcpy(chunk_status[i], cst[(size_t)i].data(), sizeof(int) * cst[(size_t)i].size());
-        for (size_t k = 0; k < cst[(size_t)i].size(); k++)
-            if (cst[(size_t)i][k] != ZS_OK) {
-                char head[48];
-                snprintf(head, sizeof head, "chunk %d: ", (int)k);
-                st[(size_t)i] = cst[(size_t)i][k], why[(size_t)i] = std::string(head) + cwhy[(size_t)i][k];
-                break;
-            }
-    }
-    c->err = before;
-    for (int i = 0; i < n; i++)
-        if (st[(size_t)i] != ZS_OK) {
-            char head[48];
-            snprintf(head, sizeof head, "file %d: ", i);
-            c->err = std::string(head) + why[(size_t)i];
-            return finish(st[(size_t)i]);
-        }
-    return finish(ZS_OK);
+    if (!tiff_run(c, run, false, s, &no_memory)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    if (png_done(hip_stream, s) != ZS_OK) return gate.fail_all(ZS_STREAM_ERROR);
+    return gate.finish(pc.roll_up("file", "chunk", chunk_status, before, &c->err));
 }
 
 extern "C" int64_t zs_tiff_bound(const zs_tiff_put *put) {
@@ -370,7 +296,7 @@ extern "C" int zs_tiff_encode_batch_device(zs_ctx *c, int n, const zs_tiff_put *
     if (!puts || !out || !out_cap || !out_len) return ZS_STREAM_ERROR;
     std::vector<TiffLayout> lay((size_t)n);
     std::vector<int64_t> first((size_t)n + 1, 0);  // image i's chunks in the call's list
-    size_t pred_total = 0, z_total = 0, head_total = 0;
+    size_t pred_total = 0, z_total = 0, head_total = 0;  // (z_total: the room that deflate_parts lays the streams out in)
     for (int i = 0; i < n; i++) {
         if (!out[i] || out_cap[i] < 0 || zs_tiff_bound(puts + i) < 0 || !tiff_layout(puts[i], &lay[(size_t)i])) {
             c->err = "stream error";
@@ -383,31 +309,23 @@ extern "C" int zs_tiff_encode_batch_device(zs_ctx *c, int n, const zs_tiff_put *
         return ZS_STREAM_ERROR;
     }
     const int m = (int)first[(size_t)n];
-    std::vector<int64_t> zin_len((size_t)m), zcap((size_t)m), zlen((size_t)m, 0);
-    std::vector<size_t> pred_at((size_t)m), z_at((size_t)m);
+    std::vector<int64_t> zin_len((size_t)m), zcap((size_t)m);
+    std::vector<size_t> pred_at((size_t)m);
     for (int i = 0; i < n; i++) {
         for (int64_t k = 0; k < lay[(size_t)i].n_chunks; k++) {
             const size_t q = (size_t)(first[(size_t)i] + k);
             zin_len[q] = tiff_cut(lay[(size_t)i], k).bytes, zcap[q] = zs_deflate_bound(zin_len[q]);
-            pred_at[q] = pred_total, z_at[q] = z_total;
-            pred_total += ((size_t)zin_len[q] + 255) & ~(size_t)255, z_total += ((size_t)zcap[q] + 255) & ~(size_t)255;
+            pred_at[q] = pred_total, pred_total += pad256((size_t)zin_len[q]), z_total += pad256((size_t)zcap[q]);
         }
         head_total += (size_t)tiff_head_bytes(lay[(size_t)i]);
     }
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    std::vector<int> st((size_t)n, ZS_OK);
-    for (int i = 0; i < n; i++) out_len[i] = 0;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
-    if (!ensure(c, c->png[kBufTiffChunks], pred_total + 256) || !ensure(c, c->png[kBufTiffZs], z_total + 256)) return fail_all(ZS_MEM_ERROR);
-    uint8_t *d_pred = (uint8_t *)c->png[kBufTiffChunks].p, *d_zs = (uint8_t *)c->png[kBufTiffZs].p;
+    CallGate gate(n, status);
+    if (!gate.open(c, hip_stream, out_len)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
+    std::vector<int> &st = gate.st;
+    // (both buffers in front of the first launch: deflate_parts finds its own in place)
+    if (!ensure(c, c->png[kBufTiffChunks], pred_total + 256) || !ensure(c, c->png[kBufTiffZs], z_total + 256)) return gate.fail_all(ZS_MEM_ERROR);
+    uint8_t *d_pred = (uint8_t *)c->png[kBufTiffChunks].p;
     // ---- one forward launch: every chunk of every image cut, padded and predicted
     TiffRun run;
     for (int i = 0; i < n; i++) {
@@ -420,46 +338,31 @@ extern "C" int zs_tiff_encode_batch_device(zs_ctx *c, int n, const zs_tiff_put *
         }
     }
     bool no_memory = false;
-    if (!tiff_run(c, run, true, s, &no_memory)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+    if (!tiff_run(c, run, true, s, &no_memory)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
     // ---- one deflate call over all of them, into a buffer of the context
     std::vector<const void *> zin((size_t)m);
-    std::vector<void *> zout((size_t)m);
-    for (int q = 0; q < m; q++) zin[(size_t)q] = d_pred + pred_at[(size_t)q], zout[(size_t)q] = d_zs + z_at[(size_t)q];
-    std::vector<int> zst((size_t)m, ZS_STREAM_ERROR);
-    const int zrc = zs_deflate_batch_device(c, m, zin.data(), zin_len.data(), zout.data(), zcap.data(), zlen.data(), zst.data(), level, strategy, hash_variant, (void *)s);
-    if (zrc != ZS_OK) return fail_all(zrc);
-    for (int q = 0; q < m; q++)
-        if (zlen[(size_t)q] < 6) {  // (no zlib stream is that short)
-            c->err = "stream error";
-            return fail_all(ZS_STREAM_ERROR);
-        }
+    std::vector<void *> zout;
+    std::vector<int64_t> zlen;
+    for (int q = 0; q < m; q++) zin[(size_t)q] = d_pred + pred_at[(size_t)q];
+    if (const int zrc = deflate_parts(c, c->png[kBufTiffZs], m, zin.data(), zin_len.data(), zcap.data(), level, strategy, hash_variant, s, &zout, &zlen)) return gate.fail_all(zrc);
     // ---- the layout: every file's head on the host, from the lengths the deflate call returned; which files fit
     std::vector<uint8_t> heads(head_total + 2);
     std::vector<size_t> head_at((size_t)n);
     std::vector<int64_t> chunk_off((size_t)m);
-    int rc = ZS_OK, n_fit = 0;
+    int rc = ZS_OK;
     size_t at = 0, fit_spans = 0, fit_heads = 0;
     for (int i = 0; i < n; i++) {
         head_at[(size_t)i] = at;
         out_len[i] = tiff_put_head(heads.data() + at, lay[(size_t)i], zlen.data() + first[(size_t)i], chunk_off.data() + first[(size_t)i]);
         at += (size_t)tiff_head_bytes(lay[(size_t)i]);
-        if (out_cap[i] < out_len[i]) {
-            st[(size_t)i] = ZS_BUF_ERROR;
-            if (rc == ZS_OK) rc = ZS_BUF_ERROR, c->err = "buffer error";
-        } else {
-            n_fit++, fit_heads += (size_t)tiff_head_bytes(lay[(size_t)i]);
-            fit_spans += 1 + 2 * (size_t)lay[(size_t)i].n_chunks;
-        }
     }
-    if (n_fit == 0) return finish(rc);
+    if (mark_fit(st, out_len, out_cap, &rc, &c->err) == 0) return gate.finish(rc);
+    for (int i = 0; i < n; i++)
+        if (st[(size_t)i] == ZS_OK) fit_heads += (size_t)tiff_head_bytes(lay[(size_t)i]), fit_spans += 1 + 2 * (size_t)lay[(size_t)i].n_chunks;
     // ---- one KC job.  Per file: its head (host bytes in the job's blob) copied into place, then every chunk's stream, and behind
     // a stream of odd length one zero byte, so that the next one begins at an even offset
     Crc32Job job;
-    if (!crc32_begin(c, (int)fit_spans, 16 + fit_heads, &job, &no_memory)) {
-        for (int i = 0; i < n; i++)
-            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
-        return finish(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
-    }
+    if (!crc32_begin(c, (int)fit_spans, 16 + fit_heads, &job, &no_memory)) return gate.fail_live(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
     memset(job.blob, 0, 16);  // the zero byte
     uint8_t *hb = job.blob + 16;
     int sp = 0;
@@ -472,16 +375,12 @@ extern "C" int zs_tiff_encode_batch_device(zs_ctx *c, int n, const zs_tiff_put *
         hb += hbytes;
         for (int64_t k = 0; k < lay[(size_t)i].n_chunks; k++) {
             const size_t q = (size_t)(first[(size_t)i] + k);
-            job.spans[sp++] = Crc32Span{d_zs + z_at[q], o + chunk_off[q], nullptr, zlen[q], 0xFFFFFFFFu, 0, 0, 0};
+            job.spans[sp++] = Crc32Span{(const uint8_t *)zout[q], o + chunk_off[q], nullptr, zlen[q], 0xFFFFFFFFu, 0, 0, 0};
             const int64_t odd = zlen[q] & 1;  // (a span without bytes where the length is even)
             job.spans[sp++] = Crc32Span{job.d_blob, odd ? o + chunk_off[q] + zlen[q] : nullptr, nullptr, odd, 0xFFFFFFFFu, 0, 0, 0};
         }
     }
-    if (!crc32_run(c, &job, s)) {
-        for (int i = 0; i < n; i++)
-            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = ZS_STREAM_ERROR;
-        return finish(ZS_STREAM_ERROR);
-    }
+    if (!crc32_run(c, &job, s)) return gate.fail_live(ZS_STREAM_ERROR);
     if (c->profiling) c->stage_ms[kStCrc32] = job.ms;
-    return finish(rc);
+    return gate.finish(rc);
 }

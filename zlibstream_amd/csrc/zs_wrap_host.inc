@@ -1,7 +1,9 @@
 // zs_wrap_host.inc -- host side of the container calls of include/zsgpu.h (raw deflate and gzip beside zlib): gzip members
 // through the inflate paths, the framing launch behind a deflate call, and gzip files from host memory.  Part of
-// zs_engine.hip's translation unit, behind zs_png_host.inc, whose KC job runner (Crc32Job) it uses; the rules of a gzip
-// header are zs_gzip.h's, the two small kernels zs_gzip.hip's.
+// zs_engine.hip's translation unit, behind zs_png_host.inc, whose KC job runner (Crc32Job) it uses, and zs_parts_host.inc,
+// whose gate, staging and file codes the gzip files call takes; the rules of a gzip header are zs_gzip.h's, the two small
+// kernels zs_gzip.hip's.  zs_deflate_wrap_batch_device keeps its own deflate call and layout: a stream of its that comes out
+// too short fails for itself, where deflate_parts fails the call.
 
 namespace {
 
@@ -134,7 +136,7 @@ extern "C" int zs_deflate_wrap_batch_device(zs_ctx *c, int n, const void *const 
             return ZS_STREAM_ERROR;
         }
         zcap[(size_t)i] = zs_deflate_bound(in_len[i]);
-        z_total += ((size_t)zcap[(size_t)i] + 255) & ~(size_t)255;
+        z_total += pad256((size_t)zcap[(size_t)i]);
     }
     if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -151,7 +153,7 @@ extern "C" int zs_deflate_wrap_batch_device(zs_ctx *c, int n, const void *const 
     size_t at = 0;
     for (int i = 0; i < n; i++) {
         zs_out[(size_t)i] = (uint8_t *)c->png[kBufWrapZs].p + at;
-        at += ((size_t)zcap[(size_t)i] + 255) & ~(size_t)255;
+        at += pad256((size_t)zcap[(size_t)i]);
     }
     const int zrc = zs_deflate_batch_device(c, n, in, in_len, zs_out.data(), zcap.data(), zlen.data(), st.data(), level, strategy, hash_variant, (void *)s);
     if (zrc != ZS_OK) {
@@ -273,42 +275,21 @@ extern "C" int zs_gzip_decode_files_batch(zs_ctx *c, int n, const void *const *f
     if (!c || n < 0) return ZS_STREAM_ERROR;
     if (n == 0) return ZS_OK;
     if (!file || !file_len || !out || !out_cap || !out_len) return ZS_STREAM_ERROR;
-    size_t total = 0;
-    std::vector<size_t> f_at((size_t)n);
-    for (int i = 0; i < n; i++) {
+    // (a file above the limit is refused for the whole call, as the header says: elsewhere such a file fails for itself)
+    for (int i = 0; i < n; i++)
         if (!file[i] || !out[i] || file_len[i] < 0 || file_len[i] > kCrcMaxLen || out_cap[i] < 0 || out_cap[i] > kCrcMaxLen) {
             c->err = "stream error";
             return ZS_STREAM_ERROR;
         }
-        f_at[(size_t)i] = total;
-        total += ((size_t)file_len[i] + 255) & ~(size_t)255;
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    std::vector<int> st((size_t)n, ZS_OK), cnt((size_t)n, 0);
-    std::vector<std::string> why((size_t)n);
-    for (int i = 0; i < n; i++) out_len[i] = 0;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        if (n_members) memcpy(n_members, cnt.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
-    // ---- the files, one copy
-    if (!ensure(c, c->png[kBufWrapFiles], total + 256) || !ensure_pinned(c, total + 256)) return fail_all(ZS_MEM_ERROR);
-    for (int i = 0; i < n; i++)
-        if (file_len[i]) memcpy((uint8_t *)c->pinned + f_at[(size_t)i], file[i], (size_t)file_len[i]);
-    uint8_t *d_files = (uint8_t *)c->png[kBufWrapFiles].p;
-    if (total && hipMemcpyAsync(d_files, c->pinned, total, hipMemcpyHostToDevice, s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);
-    if (hipStreamSynchronize(s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);  // (the inflate calls below take the pinned buffer)
-    auto fail_file = [&](int i, int code, const char *text) {
-        if (st[(size_t)i] != ZS_OK) return;
-        st[(size_t)i] = code;
-        why[(size_t)i] = text;
-    };
+    const StageLayout lay(n, file_len, kCrcMaxLen);
+    std::vector<int> cnt((size_t)n, 0);
+    CallGate gate(n, status);
+    gate.also_out = n_members, gate.also = &cnt;
+    if (!gate.open(c, hip_stream, out_len)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
+    PartCodes pc(gate.st);
+    uint8_t *d_files = nullptr;
+    if (const int rc = stage_files(c, lay, file, file_len, s, &d_files)) return gate.fail_all(rc);
     // ---- BGZF files: every member of every file is one stream of one launch
     std::vector<bool> plain((size_t)n, true);
     {
@@ -327,17 +308,17 @@ extern "C" int zs_gzip_decode_files_batch(zs_ctx *c, int n, const void *const *f
             if (rc != ZS_OK) {
                 if (gz_err != kGzOk) gz_err_code(gz_err, &wst, &wmsg);
                 else wst = rc, wmsg = rc == ZS_BUF_ERROR ? (int)kInfTruncated : (int)kInfBadHeaderCheck;
-                fail_file(i, wst, inf_message(wmsg));
+                pc.fail_file(i, wst, inf_message(wmsg));
             }
             int64_t sum = 0;
             for (const GzFileMember &m : members) sum += m.isize;
             if (sum > out_cap[i]) {
-                fail_file(i, ZS_BUF_ERROR, inf_message(kInfOutputFull));
+                pc.fail_file(i, ZS_BUF_ERROR, inf_message(kInfOutputFull));
                 continue;
             }
             int64_t pos = 0;
             for (const GzFileMember &m : members) {
-                in.push_back(d_files + f_at[(size_t)i] + m.off), ilen.push_back(m.size);
+                in.push_back(d_files + lay.at[(size_t)i] + m.off), ilen.push_back(m.size);
                 o.push_back((uint8_t *)out[i] + pos), ocap.push_back((int64_t)m.isize), owner.push_back(i);
                 pos += m.isize;
             }
@@ -351,18 +332,18 @@ extern "C" int zs_gzip_decode_files_batch(zs_ctx *c, int n, const void *const *f
             std::vector<bool> closed((size_t)n, false);  // a member of the file has failed: what lies behind it does not count
             for (int j = 0; j < m; j++) {  // (a file's members stand in the file's order)
                 const int i = owner[(size_t)j];
-                if (mst[(size_t)j] == ZS_STREAM_ERROR) return fail_all(ZS_STREAM_ERROR);  // (the call itself failed: its message stands)
+                if (mst[(size_t)j] == ZS_STREAM_ERROR) return gate.fail_all(ZS_STREAM_ERROR);  // (the call itself failed: its message stands)
                 if (closed[(size_t)i]) continue;
                 if (mst[(size_t)j] == ZS_STREAM_END) {
                     cnt[(size_t)i]++, out_len[i] += olen[(size_t)j];
                     continue;
                 }
-                // (it lies in front of whatever the walk stopped at: its reason is the file's.)  A body longer than its ISIZE
-                // ran out of the room the ISIZE gave it
-                const bool too_long = mmsg[(size_t)j] == kInfOutputFull;
+                // (it lies in front of whatever the walk stopped at: its reason is the file's, over the walk's.)  A body longer
+                // than its ISIZE ran out of the room the ISIZE gave it (part_failure)
+                int why = 0;
                 closed[(size_t)i] = true;
-                st[(size_t)i] = too_long ? (int)ZS_DATA_ERROR : mst[(size_t)j];
-                why[(size_t)i] = inf_message(too_long ? (int)kInfBadLength : mmsg[(size_t)j]);
+                part_failure(mst[(size_t)j], mmsg[(size_t)j], &gate.st[(size_t)i], &why);
+                pc.why[(size_t)i] = inf_message(why);
             }
             if (ok) c->err = before;
         }
@@ -380,16 +361,16 @@ extern "C" int zs_gzip_decode_files_batch(zs_ctx *c, int n, const void *const *f
         std::vector<int> mst((size_t)m, ZS_STREAM_ERROR), mmsg((size_t)m, 0);
         for (int j = 0; j < m; j++) {
             const int i = live[(size_t)j];
-            in[(size_t)j] = d_files + f_at[(size_t)i] + pos[(size_t)i], ilen[(size_t)j] = file_len[i] - pos[(size_t)i];
+            in[(size_t)j] = d_files + lay.at[(size_t)i] + pos[(size_t)i], ilen[(size_t)j] = file_len[i] - pos[(size_t)i];
             o[(size_t)j] = (uint8_t *)out[i] + out_len[i], ocap[(size_t)j] = out_cap[i] - out_len[i];
         }
         (void)inflate_gzip_members(c, m, in.data(), ilen.data(), o.data(), ocap.data(), olen.data(), used.data(), mst.data(), mmsg.data(), s);
         std::vector<int> next;
         for (int j = 0; j < m; j++) {
             const int i = live[(size_t)j];
-            if (mst[(size_t)j] == ZS_STREAM_ERROR) return fail_all(ZS_STREAM_ERROR);
+            if (mst[(size_t)j] == ZS_STREAM_ERROR) return gate.fail_all(ZS_STREAM_ERROR);
             if (mst[(size_t)j] != ZS_STREAM_END) {
-                fail_file(i, mst[(size_t)j], inf_message(mmsg[(size_t)j]));
+                pc.fail_file(i, mst[(size_t)j], inf_message(mmsg[(size_t)j]));
                 continue;
             }
             cnt[(size_t)i]++, out_len[i] += olen[(size_t)j], pos[(size_t)i] += used[(size_t)j];
@@ -397,12 +378,5 @@ extern "C" int zs_gzip_decode_files_batch(zs_ctx *c, int n, const void *const *f
         }
         live.swap(next);
     }
-    for (int i = 0; i < n; i++)
-        if (st[(size_t)i] != ZS_OK) {
-            char head[48];
-            snprintf(head, sizeof head, "file %d: ", i);
-            c->err = std::string(head) + why[(size_t)i];
-            return finish(st[(size_t)i]);
-        }
-    return finish(ZS_OK);
+    return gate.finish(pc.first_file("file", &c->err));
 }

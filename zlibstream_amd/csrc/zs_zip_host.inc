@@ -1,7 +1,8 @@
 // zs_zip_host.inc -- host side of the ZIP calls of include/zsgpu.h: whole archives from host memory decoded on the device,
 // and archives written on the device from entries that lie there.  Part of zs_engine.hip's translation unit, behind
-// zs_wrap_host.inc: raw inflate from an offset (InfWrap::body_off), the KC job runner (Crc32Job) and the raw deflate body
-// are that file's and zs_png_host.inc's; the container's rules are zs_zip.h's, the closing kernel zs_zip.hip's.
+// zs_parts_host.inc and zs_wrap_host.inc: the call's gate, the staging, the raw inflate of sub-streams, the roll-up of the
+// codes and the one deflate call are zs_parts.h's and zs_parts_host.inc's, the KC job runner (Crc32Job) zs_png_host.inc's;
+// the container's rules are zs_zip.h's, the closing kernel zs_zip.hip's.
 
 namespace {
 static_assert(sizeof(zs_zip_info) == sizeof(ZipInfo) && offsetof(zs_zip_info, zip64) == offsetof(ZipInfo, zip64), "zs_zip_info mirrors ZipInfo");
@@ -31,47 +32,27 @@ extern "C" int zs_zip_decode_files_batch(zs_ctx *c, int n, const void *const *fi
     if (!c || n < 0) return ZS_STREAM_ERROR;
     if (n == 0) return ZS_OK;
     if (!file || !file_len || !out || !out_cap || !out_len) return ZS_STREAM_ERROR;
-    size_t total = 0;
-    std::vector<size_t> f_at((size_t)n);
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n; i++)
         if (!file[i] || !out[i] || file_len[i] < 0 || out_cap[i] < 0) {
             c->err = "stream error";
             return ZS_STREAM_ERROR;
         }
-        f_at[(size_t)i] = total;
-        if (file_len[i] <= kZipMaxLen) total += ((size_t)file_len[i] + 255) & ~(size_t)255;  // (a larger file fails below, for itself)
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    std::vector<int> st((size_t)n, ZS_OK);
-    std::vector<std::string> why((size_t)n);
-    for (int i = 0; i < n; i++) out_len[i] = 0;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
-    // ---- the files, one copy (the staging of the gzip files call)
-    if (!ensure(c, c->png[kBufWrapFiles], total + 256) || !ensure_pinned(c, total + 256)) return fail_all(ZS_MEM_ERROR);
-    for (int i = 0; i < n; i++)
-        if (file_len[i] && file_len[i] <= kZipMaxLen) memcpy((uint8_t *)c->pinned + f_at[(size_t)i], file[i], (size_t)file_len[i]);
-    uint8_t *d_files = (uint8_t *)c->png[kBufWrapFiles].p;
-    if (total && hipMemcpyAsync(d_files, c->pinned, total, hipMemcpyHostToDevice, s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);
-    if (hipStreamSynchronize(s) != hipSuccess) return fail_all(ZS_STREAM_ERROR);  // (the inflate call below takes the pinned buffer)
+    const StageLayout lay(n, file_len, kZipMaxLen);  // (a larger file fails below, for itself)
+    CallGate gate(n, status);
+    if (!gate.open(c, hip_stream, out_len)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
+    PartCodes pc(gate.st);
+    uint8_t *d_files = nullptr;
+    if (const int rc = stage_files(c, lay, file, file_len, s, &d_files)) return gate.fail_all(rc);
     // ---- the walk: every file's directory, every entry's place
     struct Ref {
         int file, entry;
     };
     std::vector<std::vector<ZipEntry>> ents((size_t)n);
-    std::vector<std::vector<int>> est((size_t)n);      // per entry: ZS_OK or its code ...
-    std::vector<std::vector<const char *>> ewhy((size_t)n);  // ... and why
     std::vector<Ref> inflated, stored;
     for (int i = 0; i < n; i++) {
         if (file_len[i] > kZipMaxLen) {
-            st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = "the file is above 2 GiB - 1 KiB";
+            pc.fail_file(i, ZS_DATA_ERROR, "the file is above 2 GiB - 1 KiB");
             continue;
         }
         const uint8_t *f = (const uint8_t *)file[i];
@@ -83,116 +64,58 @@ extern "C" int zs_zip_decode_files_batch(zs_ctx *c, int n, const void *const *fi
             E.resize((size_t)zi.n_entries), errs.resize((size_t)zi.n_entries);
             rc = zip_walk(f, file_len[i], &zi, E.data(), zi.n_entries, errs.data());
         }
-        if (rc != kZipOk) {
-            st[(size_t)i] = zip_err_status(rc), why[(size_t)i] = zip_err_message(rc);
+        if (rc == kZipOk) out_len[i] = zi.total_len;
+        if (rc != kZipOk) pc.fail_file(i, zip_err_status(rc), zip_err_message(rc));
+        else if (zi.total_len > kZipMaxLen) pc.fail_file(i, ZS_DATA_ERROR, "the entries are above 2 GiB - 1 KiB");
+        else if (out_cap[i] < zi.total_len) pc.fail_file(i, ZS_BUF_ERROR, "buffer error");
+        if (gate.st[(size_t)i] != ZS_OK) {
             E.clear();
             continue;
         }
-        out_len[i] = zi.total_len;
-        if (zi.total_len > kZipMaxLen) {
-            st[(size_t)i] = ZS_DATA_ERROR, why[(size_t)i] = "the entries are above 2 GiB - 1 KiB";
-            E.clear();
-            continue;
-        }
-        if (out_cap[i] < zi.total_len) {
-            st[(size_t)i] = ZS_BUF_ERROR, why[(size_t)i] = "buffer error";
-            E.clear();
-            continue;
-        }
-        est[(size_t)i].assign(E.size(), ZS_OK), ewhy[(size_t)i].assign(E.size(), "");
+        pc.open_parts(i, E.size());
         for (size_t e = 0; e < E.size(); e++) {
-            if (E[e].status != ZS_OK) est[(size_t)i][e] = E[e].status, ewhy[(size_t)i][e] = zip_err_message(errs[e]);
+            if (E[e].status != ZS_OK) pc.fail_part(i, (int64_t)e, E[e].status, zip_err_message(errs[e]));
             else (E[e].method == kZipDeflated ? inflated : stored).push_back(Ref{i, (int)e});
         }
     }
-    auto fail_entry = [&](const Ref &r, int code, const char *text) { est[(size_t)r.file][(size_t)r.entry] = code, ewhy[(size_t)r.file][(size_t)r.entry] = text; };
     const std::string before = c->err;
-    // ---- one raw inflate over all deflated entries: the pointer is the body's address rounded down to 16 bytes and the
-    // offset the remainder, so that an entry keeps the 16-byte load paths wherever it lies in its file
-    const int m = (int)inflated.size();
-    std::vector<int64_t> solen((size_t)m, 0);
-    std::vector<bool> decoded((size_t)m, false);
-    if (m) {
-        std::vector<const void *> sin((size_t)m);
-        std::vector<void *> sout((size_t)m);
-        std::vector<int64_t> slen((size_t)m), scap((size_t)m);
-        std::vector<int32_t> body((size_t)m);
-        std::vector<int> sst((size_t)m, ZS_STREAM_ERROR), smsg((size_t)m, 0);
-        for (int j = 0; j < m; j++) {
-            const Ref &r = inflated[(size_t)j];
-            const ZipEntry &e = ents[(size_t)r.file][(size_t)r.entry];
-            const size_t at = f_at[(size_t)r.file] + (size_t)e.body_off;  // (d_files and every f_at are 256-byte aligned)
-            body[(size_t)j] = (int32_t)(at & 15);
-            sin[(size_t)j] = d_files + (at & ~(size_t)15), slen[(size_t)j] = (int64_t)(at & 15) + e.comp_len;
-            sout[(size_t)j] = (uint8_t *)out[r.file] + e.out_off, scap[(size_t)j] = e.len;
-        }
-        InfWrap wr;
-        wr.body_off = body.data(), wr.msg = smsg.data();
-        (void)run_inflate(c, m, sin.data(), slen.data(), sout.data(), scap.data(), solen.data(), sst.data(), s, nullptr, wr);
-        for (int j = 0; j < m; j++) {
-            const Ref &r = inflated[(size_t)j];
-            const ZipEntry &e = ents[(size_t)r.file][(size_t)r.entry];
-            if (sst[(size_t)j] == ZS_STREAM_ERROR || sst[(size_t)j] == ZS_OK) {
-                return fail_all(ZS_STREAM_ERROR);  // (the inflate call itself failed: its message stands)
-            }
-            // a body longer than the directory's length ran out of the room that length gave it; a shorter one ended early.
-            // A stream that ends in front of comp_len is accepted (what lies behind it is nobody's)
-            if (sst[(size_t)j] != ZS_STREAM_END) {
-                const bool too_long = smsg[(size_t)j] == kInfOutputFull;
-                fail_entry(r, too_long ? (int)ZS_DATA_ERROR : sst[(size_t)j], inf_message(too_long ? (int)kInfBadLength : smsg[(size_t)j]));
-            } else if (solen[(size_t)j] != e.len) {
-                fail_entry(r, ZS_DATA_ERROR, inf_message(kInfBadLength));
-            } else {
-                decoded[(size_t)j] = true;
-            }
-        }
+    // ---- one raw inflate over all deflated entries, each into exactly the room that the directory's length gives it.  A
+    // stream that ends in front of comp_len is accepted (what lies behind it is nobody's)
+    std::vector<InfPart> parts;
+    for (const Ref &r : inflated) {
+        const ZipEntry &e = ents[(size_t)r.file][(size_t)r.entry];
+        parts.push_back(InfPart{lay.at[(size_t)r.file] + (size_t)e.body_off, e.comp_len, (uint8_t *)out[r.file] + e.out_off, e.len, 0});
     }
+    std::vector<InfResult> res;
+    if (!inflate_parts(c, d_files, parts, s, &res)) return gate.fail_all(ZS_STREAM_ERROR);
     // ---- one KC job: a stored entry's body copied into place under its CRC-32, an inflated entry's output under its own
-    std::vector<Ref> checked;
-    for (const Ref &r : stored) checked.push_back(r);
+    std::vector<Ref> checked = stored;
     const size_t n_stored = checked.size();
-    for (int j = 0; j < m; j++)
-        if (decoded[(size_t)j]) checked.push_back(inflated[(size_t)j]);
+    for (size_t j = 0; j < inflated.size(); j++) {
+        const Ref &r = inflated[j];
+        const PartVerdict v = part_verdict(res[j].status, res[j].msg, res[j].out_len, 0, 0, kLenExact, parts[j].out_cap);
+        if (v.cls == kPartFailed) pc.fail_part(r.file, r.entry, v.code, inf_message(v.msg));
+        else checked.push_back(r);
+    }
     if (!checked.empty()) {
         Crc32Job job;
         bool no_memory = false;
-        if (!crc32_begin(c, (int)checked.size(), 0, &job, &no_memory)) return fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
+        if (!crc32_begin(c, (int)checked.size(), 0, &job, &no_memory)) return gate.fail_all(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
         for (size_t k = 0; k < checked.size(); k++) {
             const Ref &r = checked[k];
             const ZipEntry &e = ents[(size_t)r.file][(size_t)r.entry];
             uint8_t *place = (uint8_t *)out[r.file] + e.out_off;
-            if (k < n_stored) job.spans[k] = Crc32Span{d_files + f_at[(size_t)r.file] + (size_t)e.body_off, e.len ? place : nullptr, nullptr, e.len, 0xFFFFFFFFu, 0, 0, 0};
+            if (k < n_stored) job.spans[k] = Crc32Span{d_files + lay.at[(size_t)r.file] + (size_t)e.body_off, e.len ? place : nullptr, nullptr, e.len, 0xFFFFFFFFu, 0, 0, 0};
             else job.spans[k] = Crc32Span{place, nullptr, nullptr, e.len, 0xFFFFFFFFu, 0, 0, 0};
         }
-        if (!crc32_run(c, &job, s)) return fail_all(ZS_STREAM_ERROR);
+        if (!crc32_run(c, &job, s)) return gate.fail_all(ZS_STREAM_ERROR);
         png_set_stage(c, kStCrc32, job.ms);
         for (size_t k = 0; k < checked.size(); k++) {
             const Ref &r = checked[k];
-            if (job.crc[k] != ents[(size_t)r.file][(size_t)r.entry].crc32) fail_entry(r, ZS_DATA_ERROR, inf_message(kInfBadCheck));
+            if (job.crc[k] != ents[(size_t)r.file][(size_t)r.entry].crc32) pc.fail_part(r.file, r.entry, ZS_DATA_ERROR, inf_message(kInfBadCheck));
         }
     }
-    // ---- the codes: a file's is its first failing entry's, the call's its first failing file's
-    for (int i = 0; i < n; i++) {
-        if (st[(size_t)i] == ZS_OK) {
-            if (entry_status && entry_status[i] && !est[(size_t)i].empty()) memcpy(entry_status[i], est[(size_t)i].data(), sizeof(int) * est[(size_t)i].size());
-            for (size_t e = 0; e < est[(size_t)i].size(); e++)
-                if (est[(size_t)i][e] != ZS_OK) {
-                    char head[48];
-                    snprintf(head, sizeof head, "entry %d: ", (int)e);
-                    st[(size_t)i] = est[(size_t)i][e], why[(size_t)i] = std::string(head) + ewhy[(size_t)i][e];
-                    break;
-                }
-        }
-    }
-    c->err = before;
-    for (int i = 0; i < n; i++)
-        if (st[(size_t)i] != ZS_OK) {
-            char head[48];
-            snprintf(head, sizeof head, "file %d: ", i);
-            c->err = std::string(head) + why[(size_t)i];
-            return finish(st[(size_t)i]);
-        }
-    return finish(ZS_OK);
+    return gate.finish(pc.roll_up("file", "entry", entry_status, before, &c->err));
 }
 
 extern "C" int64_t zs_zip_bound(const zs_zip_put *entries, int n_entries) {
@@ -222,7 +145,6 @@ extern "C" int zs_zip_encode_batch_device(zs_ctx *c, int n, const zs_zip_put *co
     std::vector<Item> items;
     std::vector<const void *> zin;
     std::vector<int64_t> zin_len, zcap;
-    size_t z_total = 0;
     for (int i = 0; i < n; i++) {
         if (!out[i] || out_cap[i] < 0 || zs_zip_bound(entries[i], n_entries[i]) < 0) {
             c->err = "stream error";
@@ -234,43 +156,19 @@ extern "C" int zs_zip_encode_batch_device(zs_ctx *c, int n, const zs_zip_put *co
             if (p->method != ZS_ZIP_STORED && p->len > 0) {
                 it.z = (int)zin.size();
                 zin.push_back(p->data), zin_len.push_back(p->len), zcap.push_back(zs_deflate_bound(p->len));
-                z_total += ((size_t)zcap.back() + 255) & ~(size_t)255;
             }
             items.push_back(it);
         }
     }
-    if (hipSetDevice(c->device) != hipSuccess) return ZS_STREAM_ERROR;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    std::vector<int> st((size_t)n, ZS_OK);
-    for (int i = 0; i < n; i++) out_len[i] = 0;
-    auto finish = [&](int rc) {
-        if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
-        return rc;
-    };
-    auto fail_all = [&](int rc) {
-        std::fill(st.begin(), st.end(), rc);
-        return finish(rc);
-    };
+    CallGate gate(n, status);
+    if (!gate.open(c, hip_stream, out_len)) return ZS_STREAM_ERROR;
+    hipStream_t s = gate.s;
+    std::vector<int> &st = gate.st;
     // ---- one deflate call over every entry that may be written deflated, into a buffer of the context
-    const int mz = (int)zin.size();
-    std::vector<void *> zs_out((size_t)mz);
-    std::vector<int64_t> zlen((size_t)mz, 0);
-    if (mz) {
-        if (!ensure(c, c->png[kBufZipZs], z_total + 256)) return fail_all(ZS_MEM_ERROR);
-        size_t at = 0;
-        for (int k = 0; k < mz; k++) {
-            zs_out[(size_t)k] = (uint8_t *)c->png[kBufZipZs].p + at;
-            at += ((size_t)zcap[(size_t)k] + 255) & ~(size_t)255;
-        }
-        std::vector<int> zst((size_t)mz, ZS_STREAM_ERROR);
-        const int zrc = zs_deflate_batch_device(c, mz, zin.data(), zin_len.data(), zs_out.data(), zcap.data(), zlen.data(), zst.data(), level, strategy, hash_variant, (void *)s);
-        if (zrc != ZS_OK) return fail_all(zrc);
-        for (int k = 0; k < mz; k++)
-            if (zlen[(size_t)k] < 6) {  // (no zlib stream is that short)
-                c->err = "stream error";
-                return fail_all(ZS_STREAM_ERROR);
-            }
-    }
+    std::vector<void *> zs_out;
+    std::vector<int64_t> zlen;
+    if (const int zrc = deflate_parts(c, c->png[kBufZipZs], (int)zin.size(), zin.data(), zin_len.data(), zcap.data(), level, strategy, hash_variant, s, &zs_out, &zlen))
+        return gate.fail_all(zrc);
     // ---- the layout: stored or deflated per entry, every archive's length, which archives fit
     std::vector<int64_t> cd_off((size_t)n, 0), cd_len((size_t)n, 0);
     for (Item &it : items) {
@@ -283,18 +181,12 @@ extern "C" int zs_zip_encode_batch_device(zs_ctx *c, int n, const zs_zip_put *co
         cd_off[(size_t)it.archive] += kZipLocalBytes + p.name_len + it.comp_len;
         cd_len[(size_t)it.archive] += kZipCentralBytes + p.name_len;
     }
-    int rc = ZS_OK, n_fit = 0;
+    int rc = ZS_OK;
     size_t fit_items = 0, fit_spans = 0, head_bytes = 0;
-    for (int i = 0; i < n; i++) {
-        out_len[i] = cd_off[(size_t)i] + cd_len[(size_t)i] + kZipEndBytes;
-        if (out_cap[i] < out_len[i]) {
-            st[(size_t)i] = ZS_BUF_ERROR;
-            if (rc == ZS_OK) rc = ZS_BUF_ERROR, c->err = "buffer error";
-        } else {
-            n_fit++, head_bytes += (size_t)cd_len[(size_t)i] + kZipEndBytes, fit_spans++;
-        }
-    }
-    if (n_fit == 0) return finish(rc);
+    for (int i = 0; i < n; i++) out_len[i] = cd_off[(size_t)i] + cd_len[(size_t)i] + kZipEndBytes;
+    if (mark_fit(st, out_len, out_cap, &rc, &c->err) == 0) return gate.finish(rc);
+    for (int i = 0; i < n; i++)
+        if (st[(size_t)i] == ZS_OK) head_bytes += (size_t)cd_len[(size_t)i] + kZipEndBytes, fit_spans++;
     for (const Item &it : items)
         if (st[(size_t)it.archive] == ZS_OK) fit_items++, fit_spans += it.method == ZS_ZIP_DEFLATED ? 3 : 2, head_bytes += (size_t)kZipLocalBytes + (size_t)it.put->name_len;
     // ---- one KC job.  Per entry: the local header and name (host bytes in the job's blob) copied into place; the body --
@@ -304,11 +196,7 @@ extern "C" int zs_zip_encode_batch_device(zs_ctx *c, int n, const zs_zip_put *co
     const size_t b_close = sizeof(ZipClose) * fit_items;
     Crc32Job job;
     bool no_memory = false;
-    if (!crc32_begin(c, (int)fit_spans, b_close + head_bytes, &job, &no_memory)) {
-        for (int i = 0; i < n; i++)
-            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR;
-        return finish(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
-    }
+    if (!crc32_begin(c, (int)fit_spans, b_close + head_bytes, &job, &no_memory)) return gate.fail_live(no_memory ? ZS_MEM_ERROR : ZS_STREAM_ERROR);
     ZipClose *closes = (ZipClose *)job.blob;
     uint8_t *hb = job.blob + b_close;  // the next host bytes
     int sp = 0;
@@ -355,11 +243,7 @@ extern "C" int zs_zip_encode_batch_device(zs_ctx *c, int n, const zs_zip_put *co
         hipLaunchKernelGGL(zs_zip_close_kernel, dim3((unsigned)((n_close + 63) / 64)), dim3(64), 0, s, (const ZipClose *)job.d_blob, n_close, d_crc);
         return hipGetLastError() == hipSuccess;
     };
-    if (!crc32_run(c, &job, s, n_close ? &close : nullptr)) {
-        for (int i = 0; i < n; i++)
-            if (st[(size_t)i] == ZS_OK) st[(size_t)i] = ZS_STREAM_ERROR;
-        return finish(ZS_STREAM_ERROR);
-    }
+    if (!crc32_run(c, &job, s, n_close ? &close : nullptr)) return gate.fail_live(ZS_STREAM_ERROR);
     if (c->profiling) c->stage_ms[kStCrc32] = job.ms;
-    return finish(rc);
+    return gate.finish(rc);
 }
