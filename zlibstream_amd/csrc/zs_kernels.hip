@@ -68,6 +68,13 @@ __device__ __forceinline__ uint64_t lds0_u64(int idx) {
     const uint32_t a = q[0], b = q[1], c = q[2];
     return (uint64_t)__builtin_amdgcn_alignbyte(b, a, (uint32_t)idx) | ((uint64_t)__builtin_amdgcn_alignbyte(c, b, (uint32_t)idx) << 32);
 }
+// 16 bytes: five aligned dwords (readable up to idx + 19)
+__device__ __forceinline__ void lds0_u128(int idx, uint32_t &o0, uint32_t &o1, uint32_t &o2, uint32_t &o3) {
+    lds_cu32 q = (lds_cu32)(uintptr_t)(uint32_t)(idx & ~3);
+    const uint32_t a = q[0], b = q[1], c = q[2], d = q[3], e = q[4];
+    o0 = __builtin_amdgcn_alignbyte(b, a, (uint32_t)idx), o1 = __builtin_amdgcn_alignbyte(c, b, (uint32_t)idx);
+    o2 = __builtin_amdgcn_alignbyte(d, c, (uint32_t)idx), o3 = __builtin_amdgcn_alignbyte(e, d, (uint32_t)idx);
+}
 __device__ __forceinline__ int lds0_link(int idx) { return *(lds_cu16)(uintptr_t)(uint32_t)(kMatchLdsBytes + 2 * idx); }
 
 // Match records in `mm` (uint2 per position): x = record for budget K, y = for budget K >> 2, each dist | (len-3) << 16
@@ -314,7 +321,9 @@ __global__ __launch_bounds__(1024) void zs_links_kernel(const StreamDesc *sd, co
 
 // Every lane owns one walk at a time, in one of four states:
 //   1 stepping   at a candidate that has not been looked at yet
-//   2 comparing  the candidate passed the 4-byte prefilter and needs a real compare (cl bytes done so far)
+//   2 comparing  the candidate passed the 4-byte prefilter and needs a real compare (cl bytes done so far: 0 before the
+//                first compare, which takes 16 bytes against the cached sc0 .. sc3 on the text walk and 8 against sc0, sc1
+//                on the RUNS walk; then a multiple of 8, the extension loop's grid)
 //   3 finished   result to be stored, then the lane pulls the next position from the wave cursor
 //   0 idle       the cursor is exhausted
 // The kernel is bound by vector-instruction issue (a wave64 instruction holds its SIMD for 4 cycles), and a wave
@@ -335,6 +344,16 @@ __global__ __launch_bounds__(1024) void zs_links_kernel(const StreamDesc *sd, co
 #ifndef ZS_STEP_UNROLL
 #define ZS_STEP_UNROLL 4
 #endif
+// Width of the first compare of the text walk (RUNS == false): 1 = 16 bytes against sc0 .. sc3, 0 = 8 bytes against sc0, sc1.
+// On text a third of all compares pass 8 equal bytes and next to none pass 16; with the 8-byte compare nearly every
+// visit of the compare phase (it serves some 24 lanes) has such a lane and runs a round of the extension loop for three or
+// four lanes of 64.  Sixteen bytes at once end those compares in the block every waiting lane runs anyway, and the
+// extension loop is entered for real long matches only.  A lane's own walk is the same either way (same candidates, same
+// order, same lengths): the records do not depend on the switch.  The RUNS walk keeps the 8-byte compare: long matches
+// are its rule, and its hint relies on the 8-byte grid.  (tests/cpp/test_match_sched.cpp: the schedule on the host.)
+#ifndef ZS_CMP16
+#define ZS_CMP16 1
+#endif
 // The walk of one tile by one wave's lanes (zs_match_kernel below).  RUNS: positions are handed out in runs of ZS_RUN
 // per lane instead of one at a time, and the match found at p bounds what the same distance gives at p + 1 (the hint).
 template <bool RUNS>
@@ -342,12 +361,16 @@ __device__ __forceinline__ void match_walk(const uint8_t *wb, const uint16_t *wl
                                            int K, int K4, int nice, int lane) {
     constexpr int kWaitNum = ZS_WQ, kWaitDen = ZS_WD;
     constexpr int kRun = RUNS ? ZS_RUN : 1;
+    constexpr bool kCmp16 = ZS_CMP16 && !RUNS;
+    // lds0_u128 at the last position of a tile reads up to 19 bytes behind it; the extension loop up to kMaxMatch + 9
+    static_assert(kMatchFwd >= 20 && kMatchFwd >= kMaxMatch + 10, "the staged bytes must cover the walk's reads behind the last position");
     int st = 3, p = -1, c = 8, best = 2, bdist = 0, n_eval = 0, cl = 0;
     uint32_t snap = 0;       // record for the K>>2 budget once it is known to differ from the final one, else 0
     int snapped = 0;
     uint32_t scan_end = 0, mask = 0;  // scan_end = bytes p+best-3 .. p+best; mask drops the byte before p when best == 2
     uint32_t fmask = 0;               // the candidate's first bytes must match too: 3 of them while best == 2, then 4
     uint32_t sc0 = 0, sc1 = 0;        // bytes p .. p+7 (the first 8 bytes of every compare)
+    uint32_t sc2 = 0, sc3 = 0;        // bytes p+8 .. p+15 (kCmp16: the first compare is 16 bytes wide)
     int run_next = 0, run_end = 0;    // the lane's run of positions: next one to take, end
     int hint_l = 0, hint_d = 0;       // match found at the position just before p (0: none, or p does not follow it)
     // after a finished compare of `len` bytes against candidate c: take the improvement, count the candidate, move on
@@ -394,20 +417,29 @@ __device__ __forceinline__ void match_walk(const uint8_t *wb, const uint16_t *wl
                 const bool take = st == 3 && mine < wendi, dry = st == 3 && mine >= wendi;
                 const int q = take ? mine : 8;  // lanes that take nothing read an in-range dummy
                 const int l = lds0_link(q);
-                const uint64_t first8 = lds0_u64(q);
+                // bytes q .. q+15 (kCmp16) or q .. q+7: the staged bytes reach kMatchFwd = 272 past the last position and the
+                // reads end at q + 19 (the dummy's at 27)
+                uint32_t h0, h1, h2 = 0, h3 = 0;
+                if constexpr (kCmp16) {
+                    lds0_u128(q, h0, h1, h2, h3);
+                } else {
+                    const uint64_t first8 = lds0_u64(q);
+                    h0 = (uint32_t)first8, h1 = (uint32_t)(first8 >> 32);
+                }
                 const bool has = l != 0xFFFF;  // link distances are already <= kMaxDist
                 // a position without a usable link is done at once; its lane takes its next one at the next visit (an
                 // immediate second pull cost more than the idle lane)
-                if (take && !has) om[(int64_t)mine + lo] = make_uint2((uint32_t)first8 << 24, kNoMatch);
+                if (take && !has) om[(int64_t)mine + lo] = make_uint2(h0 << 24, kNoMatch);
                 p = take && has ? mine : p;
                 c = take ? mine - (has ? l : 0) : c;
                 st = take ? (has ? 1 : 3) : (dry ? 0 : st);
                 best = take ? 2 : best, bdist = take ? 0 : bdist, n_eval = take ? 0 : n_eval, snapped = take ? 0 : snapped;
                 cl = take ? 0 : cl;
-                scan_end = take ? (uint32_t)first8 << 8 : scan_end;  // bytes p-1 .. p+2; the mask drops the byte before p
+                scan_end = take ? h0 << 8 : scan_end;  // bytes p-1 .. p+2; the mask drops the byte before p
                 mask = take ? 0xFFFFFF00u : mask;
                 fmask = take ? 0x00FFFFFFu : fmask;
-                sc0 = take ? (uint32_t)first8 : sc0, sc1 = take ? (uint32_t)(first8 >> 32) : sc1;
+                sc0 = take ? h0 : sc0, sc1 = take ? h1 : sc1;
+                if constexpr (kCmp16) sc2 = take ? h2 : sc2, sc3 = take ? h3 : sc3;
             }
         } else if (__ballot(st == 3)) {
             const bool cont = st == 3 && run_next < run_end;  // the next position of the lane's own run
@@ -467,8 +499,19 @@ __device__ __forceinline__ void match_walk(const uint8_t *wb, const uint16_t *wl
                 }
             }
         }
-        // ---- compare phase.  First 8 bytes of every compare against the cached bytes of p (most end here) ...
-        if (st == 2 && cl == 0) {
+        // ---- compare phase.  First 16 (text walk) or 8 bytes of every compare against the cached bytes of p (most end
+        // here: on text practically all of them with 16 bytes, two thirds with 8) ...
+        if constexpr (kCmp16) {
+            if (st == 2 && cl == 0) {
+                uint32_t x0, x1, x2, x3;
+                lds0_u128(c, x0, x1, x2, x3);
+                x0 ^= sc0, x1 ^= sc1, x2 ^= sc2, x3 ^= sc3;
+                const uint32_t lo8 = x0 | x1;
+                const uint64_t x = lo8 ? ((uint64_t)x0 | ((uint64_t)x1 << 32)) : ((uint64_t)x2 | ((uint64_t)x3 << 32));
+                if (x) after_compare((int)(__builtin_ctzll(x) >> 3) + (lo8 ? 0 : 8));
+                else cl = 16;
+            }
+        } else if (st == 2 && cl == 0) {
             if (RUNS && hint_l > 16 && p - c == hint_d) {
                 cl = (hint_l - 1) & ~7;  // the same distance matched hint_l bytes one position earlier
             } else {
@@ -550,8 +593,9 @@ __global__ __launch_bounds__(1024) void zs_resume_check_kernel(const LitPersist 
 // of links are staged in LDS once, then every lane walks hash chains for one
 // position at a time, pulling the next position from a per-wave cursor as soon
 // as its walk ends (lanes of a wave have very different chain lengths).
-// Per main-loop iteration a lane does one unit of work: test a candidate and
-// compare its first 8 bytes, or compare 8 more bytes of a long match.
+// Per main-loop iteration a lane does one unit of work: test a candidate,
+// compare its first 16 bytes (8 on the RUNS walk), or compare 8 more bytes of a
+// long match.
 __global__ __launch_bounds__(1024) void zs_match_kernel(const StreamDesc *sd, const uint2 *work, const uint16_t *link,
                                                         uint2 *mm, LevelCfg lv, int strategy, StreamState *st) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
